@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- EM iterations/s of TrackDLO's registration loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the K steps, writes the outputs of the last timed step
+if --dump-outputs is given, and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step and the workload that was
+timed).  Everything else this script measures or checks -- the other configurations, the f64 figure, the loop-only rate, the per-kernel and
+roofline figures with their rocprofv3 passes, the sysfs clock sampler, the CPU baseline with its in-run parity gate, the multi-rank agreement
+figures and bench_detail.json -- runs with --full only, as described below.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its LAST step (rank 0), one DIR/<name>.npy per array in float64:
+Y (the nodes: M x 3, or frames x M x 3 for a batch), sigma2, iters and n_kept (one entry per frame).  The inputs are synthetic
+and seeded (trackdlo_amd/synth.py), so that the same arguments give the same inputs in every run.
 
 Workloads (BASELINE.json configs; launch/trackdlo.launch parameter values, tol = 0 so that exactly 50 iterations run):
   c2 (default; the configuration the metric is quoted on)  ONE frame per GPU, N = 50 000 points, M = 50 nodes, fp32 E-step + fp64 M-step
@@ -17,16 +27,16 @@ between two resident (cloud, Y0) pairs -- frames f and f+1 of the synthetic scen
 it.  `prune_dispatches_per_call` on the line is counted from tdlo_stats.sort_reused of the timed calls (1.0 = every call pruned).  Only the
 tracking_step leg keeps the reuse on, where the reference's own data flow makes it legitimate (trackdlo.cpp:913-927 / :998).
 
-OUTPUT: the LAST line of stdout is ONE compact JSON object (< 4 KB: the driver's capture holds 8 KB): the contract's keys, `roofline`,
-`cpu_baseline`, and the other configurations as scalars under `configs`.  Everything else (both per-iteration kernels with notes and
-sources, the full legs, `sustained`, `preproc`) is written to bench_detail.json next to this script (path on the line as `detail`).
+OUTPUT: the LAST line of stdout is ONE compact JSON object (< 4 KB: the driver's capture holds 8 KB): the contract's keys and, with --full,
+`roofline`, `cpu_baseline`, and the other configurations as scalars under `configs`.  With --full everything else (both per-iteration kernels
+with notes and sources, the full legs, `sustained`, `preproc`) is written to bench_detail.json next to this script (path on the line as `detail`).
 
 --gpus N > 1 without a torch.distributed environment: this script launches itself as N ranks
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N, one rank per GPU, RCCL).  With WORLD_SIZE already set (the
 driver's launch) it must agree with --gpus.  Frames are independent (c2 / c3 / c5): no data-path collective, "weak" scaling;
 RCCL carries only the closing barrier and the max-over-ranks of the time.
 
-The default run (--gpus 1, config c2) also carries, after the headline measurement (none of it inside the timed region):
+With --full the default run (--gpus 1, config c2) also carries, after the headline measurement (none of it inside the timed region):
   configs           short legs of the other BASELINE configurations on this GPU: c3 (32-frame batch), c4 (N = 2 000 000 on one rank through the
                     split driver), c5 (M = 300, fp64) -- each {value, ms_per_step, roofline, roofline_kernels, cpu_baseline}
   sustained         >= 3 s of back-to-back C2 calls (sustained_iters_per_s): the same quantity as `value` over a span a GPU-activity sampler sees
@@ -38,19 +48,19 @@ The default run (--gpus 1, config c2) also carries, after the headline measureme
                     its per-iteration kernels (the banded LLE M-step k_mstep_band among them) and tracking_step's ms per frame
 (--no-legs switches them off.)
 
---gpus N > 1 (the driver's scaling run), config c2: behind the frame-sharded headline the SAME process group runs, outside the headline's timed region,
+--gpus N > 1 --full, config c2: behind the frame-sharded headline the SAME process group runs, outside the headline's timed region,
   configs.c3        BASELINE configs[2] as written: 32 frames per GPU in one tdlo_cpd_lle_batch call per rank (weak; no data-path collective)
   configs.c4        BASELINE configs[3]: ONE frame of 2 000 000 points split over the N ranks (strong) with the ONE-SHOT EXCHANGE -- value, us_per_iteration,
                     form, ranks_agree (every rank's nodes and sigma2 hash to the same bits), y_sha1, xch_can_access (peer-access matrix), rccl_size per rank
   configs.c4_rccl   the same split with the library's RCCL all-reduces (TDLO_BENCH_FORCE_RCCL=1): the collective path of north_star, measured beside it
 so that a scaling run exercises the N-split's exchange over xGMI and not only N independent frames.
 
-Clocks: a background thread (outside the timed path: it only reads sysfs) samples the GPU's shader clock, memory clock, socket power and busy percentage
+Clocks (--full): a background thread (outside the timed path: it only reads sysfs) samples the GPU's shader clock, memory clock, socket power and busy percentage
 from /sys/class/drm/card*/device (hwmon freq1_input / power1_input / power1_cap, pp_dpm_mclk, gpu_busy_percent) during every timed region; the line carries
 sclk_mhz_mean / sclk_mhz_min / power_w_mean / power_cap_w for the headline and under configs.* for the legs -- a slow box and a regression are then
 told apart by what the line itself says.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline          the per-iteration kernel with the LARGER share of GPU time in this run; roofline_kernels holds both
                     (E-step: algorithmic bytes 3 * s * N per launch against 8 TB/s HBM; `algorithmic_valu_ratio` = SURVEY.md 8(d)'s flop
                     count / time / vector peak -- NOT an achieved fraction: the kernel skips the exactly-zero memberships outside a wave's node
@@ -68,6 +78,7 @@ Extra objects on the JSON line:
                     here) timed on this box's host on a bounded sample of the same workload, single thread like the reference
 """
 import argparse
+import contextlib
 import json
 import os
 import subprocess
@@ -345,6 +356,21 @@ def _pmc_traffic_live(args, cfg, mstep_name):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs in all
+
+
+def _dump_outputs(dirname, **arrays):
+    """--dump-outputs: what the timed path returned in its last step, one <dirname>/<name>.npy per array, float64 (so that two builds can be
+    compared output for output on the same seeded inputs)."""
+    arrs = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def _flush_c_stdio():
     import ctypes
     try:
@@ -382,7 +408,7 @@ def _compact_cpu(c):
     return o
 
 
-def _compact(full):
+def _compact(full, detail=True):
     """The headline the driver parses: the contract's keys with `roofline` and `cpu_baseline` cut down to their figures, the other
     configurations as scalars.  Notes, sources, both kernels' full objects and the legs stay in the detail file."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
@@ -392,14 +418,17 @@ def _compact(full):
               "self_exchange_iters_per_s"):
         if k in full:
             o[k] = full[k]
-    for k in ("sclk_mhz_mean", "sclk_mhz_min", "power_w_mean", "power_cap_w", "host_load_1m"):      # the GPU's clocks and power while the timed region ran (_ClockSampler); the host's load per CPU
-        o[k] = (full.get("clocks") or {}).get(k)
+    if "clocks" in full:        # (--full only, as are roofline and cpu_baseline: a plain run's line carries the headline alone)
+        for k in ("sclk_mhz_mean", "sclk_mhz_min", "power_w_mean", "power_cap_w", "host_load_1m"):      # the GPU's clocks and power while the timed region ran (_ClockSampler); the host's load per CPU
+            o[k] = (full.get("clocks") or {}).get(k)
     if full.get("stub"):
         o["stub"] = full["stub"]
-    o["roofline"] = _compact_roofline(full.get("roofline"))
+    if "roofline" in full:
+        o["roofline"] = _compact_roofline(full.get("roofline"))
     if full.get("roofline_kernels"):
         o["roofline_kernels"] = [{k: r[k] for k in ("kernel", "bound", "frac", "avg_launch_us", "traffic") if k in r} for r in full["roofline_kernels"]]
-    o["cpu_baseline"] = _compact_cpu(full.get("cpu_baseline"))
+    if "cpu_baseline" in full:
+        o["cpu_baseline"] = _compact_cpu(full.get("cpu_baseline"))
     par = (full.get("cpu_baseline") or {}).get("parity")
     if par:         # the in-run parity figure (fatal outside the gate: _parity): max |dY| GPU vs CPU oracle on the workload's own inputs
         o["parity"] = dict(max_abs_dY_m=float(f"{par['max_abs_dY_m']:.3e}"), rel_dsigma2=float(f"{par['rel_dsigma2']:.3e}"), gate_m=par["gate_m"],
@@ -443,7 +472,8 @@ def _compact(full):
         if "1280x720" in ffd:
             o["frame_from_depth_720p_ms"] = ffd["1280x720"].get("frame_from_depth_ms_pinned")
     o["ranks"] = full.get("ranks")
-    o["detail"] = DETAIL_FILE
+    if detail:
+        o["detail"] = DETAIL_FILE
     # the line must stay under the limit whatever a future leg adds: optional parts go first
     for drop in ("roofline_kernels", "em_loop_only_iters_per_s", "frames_per_s", "ranks", "configs"):
         if len(json.dumps(o)) < LINE_LIMIT:
@@ -452,15 +482,17 @@ def _compact(full):
     return o
 
 
-def _emit(full):
-    """The full object goes to bench_detail.json; the compact JSON line is the LAST thing on stdout: RCCL prints its version banner through
+def _emit(full, detail=True):
+    """The full object goes to bench_detail.json (--full); the compact JSON line is the LAST thing on stdout: RCCL prints its version banner through
     C stdio, which is block-buffered on a pipe and would otherwise come out at process exit, behind the line."""
-    try:
-        with open(os.path.join(ROOT, DETAIL_FILE), "w") as fh:
-            json.dump(full, fh, indent=1)
-    except OSError as e:
-        print(f"[bench] could not write {DETAIL_FILE}: {e}", file=sys.stderr)
-    line = json.dumps(_compact(full))
+    if detail:
+        try:
+            with open(os.path.join(ROOT, DETAIL_FILE), "w") as fh:
+                json.dump(full, fh, indent=1)
+        except OSError as e:
+            print(f"[bench] could not write {DETAIL_FILE}: {e}", file=sys.stderr)
+            detail = False
+    line = json.dumps(_compact(full, detail))
     assert len(line) < LINE_LIMIT, len(line)
     _flush_c_stdio()
     print(line, flush=True)
@@ -500,12 +532,20 @@ def main():
     ap.add_argument("--cpu-repeats", type=int, default=None, help="runs of the oracle's loop behind cpu_baseline.value (default per config; the median is reported)")
     ap.add_argument("--no-legs", action="store_true", help="default run (1 GPU, c2): skip the c3 / c4 / c5 legs, the sustained leg and the pre-processing leg")
     ap.add_argument("--pmc", choices=["auto", "off", "child"], default="auto",
-                    help="auto: at N = 1 collect roofline.traffic in two rocprofv3 --pmc child passes; child: the pass itself (the calls only, no output)")
+                    help="auto: at N = 1 collect roofline.traffic in two rocprofv3 --pmc child passes (--full); child: the pass itself (the calls only, no output)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other configurations, f64, loop-only, roofline / PMC, clocks, CPU baseline + parity, bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.mode == "nsplit":
         args.config = "c4"
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must be >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_self_launch(args))
@@ -543,13 +583,13 @@ def main():
             dist.init_process_group(backend)
     env = dict(rank=rank, world=world, dev_index=dev_index, dist=dist, torch=torch, backend=backend)
     res = bench_nsplit(args, cfg, env) if args.config == "c4" else bench_frames(args, cfg, env)
-    if res is not None and world == 1 and args.config == "c2" and not args.frames and not args.no_legs and args.pmc != "child":
+    if res is not None and args.full and world == 1 and args.config == "c2" and not args.frames and not args.no_legs and args.pmc != "child":
         # the other BASELINE configurations, short: the headline above stays what the driver parses
         import copy
         res["configs"] = {}
         for name in ("c3", "c4", "c5"):
             a = copy.copy(args)
-            a.config, a.frames = name, None
+            a.config, a.frames, a.dump_outputs = name, None, None
             lcfg = dict(CONFIGS[name], leg=True, **LEGS[name])
             try:
                 t0 = time.perf_counter()
@@ -561,7 +601,7 @@ def main():
                 raise
             except Exception as e:          # a leg must not take the headline down
                 res["configs"][name] = dict(error=f"{type(e).__name__}: {e}")
-    if world > 1 and args.config == "c2" and not args.frames and not args.no_legs and args.pmc != "child":
+    if args.full and world > 1 and args.config == "c2" and not args.frames and not args.no_legs and args.pmc != "child":
         # the scaling run (the driver's --gpus N): behind the frame-sharded headline the same process group registers BASELINE configs[2] (32 frames per
         # GPU) and configs[3] (ONE 2 000 000-point frame split over the ranks) -- the latter with the one-shot exchange and again with the library's RCCL
         # all-reduces --, so that the run exercises the N-split's exchange over xGMI.  Every rank walks the same legs in the same
@@ -570,7 +610,7 @@ def main():
         legs = {}
         for name, cname, force_rccl in (("c3", "c3", False), ("c4", "c4", False), ("c4_rccl", "c4", True)):
             a = copy.copy(args)
-            a.config, a.frames = cname, None
+            a.config, a.frames, a.dump_outputs = cname, None, None
             lcfg = dict(CONFIGS[cname], leg=True, **LEGS[cname])
             if force_rccl:
                 os.environ["TDLO_BENCH_FORCE_RCCL"] = "1"
@@ -597,7 +637,7 @@ def main():
         if rank == 0:
             time.sleep(0.5)         # the other ranks' exit-time output, if any, first
     if res is not None:
-        _emit(res)
+        _emit(res, detail=args.full)
 
 
 def _rank_table(env):
@@ -938,13 +978,17 @@ def bench_frames(args, cfg, env):
         step()
     barrier()
     timed = []
-    with _ClockSampler(ctx) as clk:       # (a thread that reads sysfs beside the timed region, nothing on its path)
+    with (_ClockSampler(ctx) if args.full else contextlib.nullcontext()) as clk:       # (--full: a thread that reads sysfs beside the timed region, nothing on its path)
         t0 = time.perf_counter()
         for _ in range(cfg["steps"]):
             timed.append(step())
         barrier()
         dt_local = time.perf_counter() - t0
     dt = _max_over_ranks(env, dt_local)
+    if args.dump_outputs and rank == 0:
+        last = timed[-1]
+        st = [last] if F == 1 else list(last["stats"])
+        _dump_outputs(args.dump_outputs, Y=last["Y"], sigma2=last["sigma2"], iters=[s_["iters"] for s_ in st], n_kept=[s_["n_kept"] for s_ in st])
     if args.pmc == "child":     # a PMC pass of _pmc_traffic_live: the calls above are all it is for
         ctx.close()
         return
@@ -953,7 +997,22 @@ def bench_frames(args, cfg, env):
     del timed
     n_ranks, ranks = _rank_table(env)
     value = cfg["steps"] * F * EM_ITERS * n_ranks / dt
-    # outside the timed region: the same calls with the timing events on, for the stream time of the loop alone
+    out = None
+    if rank == 0:
+        out = dict(metric=cfg["metric"], value=round(value, 2), unit="EM iterations/s", n_gpus=n_ranks, ranks=ranks,
+                   steps=cfg["steps"], warmup=cfg["warmup"], ms_per_step=round(dt * 1e3 / cfg["steps"], 4),
+                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype=cfg["prec"], data="synthetic",
+                   config=dict(workload=f"{args.config.upper()}: {F} frame(s) per GPU, N={N} points, M={M} nodes, {EM_ITERS} EM iterations per cpd_lle call, tol=0, "
+                                        f"trackdlo.launch parameters, {'fp32 E-step + fp64 M-step' if cfg['prec'] == 'f32' else 'fp64 everywhere'}; whole calls "
+                                        "(prune + sort + setup + loop + read-back), sorted-cloud reuse OFF"
+                                        + (f", calls alternate between {NP} resident (cloud, Y0) pairs" if F == 1 else ""),
+                               frames_per_gpu=F, parallelism=f"frames sharded, {n_ranks} rank(s), no data-path collective"),
+                   timed_region_s=round(dt, 3), frames_per_s=round(cfg["steps"] * F * n_ranks / dt, 2),
+                   prune_dispatches_per_call=round(pruned / max(1, cfg["steps"]), 3))
+    if not args.full:           # a plain run: the headline is all it measures
+        ctx.close()
+        return out
+    # ---- --full, outside the timed region: the same calls with the timing events on, for the stream time of the loop alone
     ctx.set_timing(True)
     loop_steps, loop_ms = max(20, cfg["steps"] // 10), 0.0
     for _ in range(loop_steps):
@@ -975,17 +1034,7 @@ def bench_frames(args, cfg, env):
         roof["iteration_us"] = round(loop_ms * 1e3 / (loop_steps * EM_ITERS), 3)
         live = _pmc_traffic_live(args, cfg, mname) if n_ranks == 1 else None
         _apply_live_traffic(live, roof, roof_all)
-        out = dict(metric=cfg["metric"], value=round(value, 2), unit="EM iterations/s", n_gpus=n_ranks, ranks=ranks,
-                   steps=cfg["steps"], warmup=cfg["warmup"], ms_per_step=round(dt * 1e3 / cfg["steps"], 4),
-                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype=cfg["prec"], data="synthetic",
-                   config=dict(workload=f"{args.config.upper()}: {F} frame(s) per GPU, N={N} points, M={M} nodes, {EM_ITERS} EM iterations per cpd_lle call, tol=0, "
-                                        f"trackdlo.launch parameters, {'fp32 E-step + fp64 M-step' if cfg['prec'] == 'f32' else 'fp64 everywhere'}; whole calls "
-                                        "(prune + sort + setup + loop + read-back), sorted-cloud reuse OFF"
-                                        + (f", calls alternate between {NP} resident (cloud, Y0) pairs" if F == 1 else ""),
-                               frames_per_gpu=F, parallelism=f"frames sharded, {n_ranks} rank(s), no data-path collective"),
-                   timed_region_s=round(dt, 3), frames_per_s=round(cfg["steps"] * F * n_ranks / dt, 2),
-                   prune_dispatches_per_call=round(pruned / max(1, cfg["steps"]), 3),
-                   em_loop_only_iters_per_s=round(loop_steps * F * EM_ITERS / (loop_ms * 1e-3), 2),
+        out.update(em_loop_only_iters_per_s=round(loop_steps * F * EM_ITERS / (loop_ms * 1e-3), 2),
                    roofline=roof, roofline_kernels=roof_all, clocks=clk.summary())
         if args.config == "c2" and F == 1 and not cfg.get("leg"):
             # the reference's arithmetic is fp64 throughout: the same workload with TDLO_PREC_F64 (not the headline: BASELINE C2 names fp32)
@@ -1114,18 +1163,34 @@ def bench_nsplit(args, cfg, env):
     for _ in range(cfg["warmup"]):
         step()
     barrier()
-    with _ClockSampler(ctx) as clk:
+    with (_ClockSampler(ctx) if args.full else contextlib.nullcontext()) as clk:
         t0 = time.perf_counter()
         for _ in range(cfg["steps"]):
             out = step()
         barrier()
         dt_local = time.perf_counter() - t0
     dt = _max_over_ranks(env, dt_local)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, Y=out["Y"], sigma2=out["sigma2"], iters=[out["iters"]], n_kept=[out["n_kept"]])
     if args.pmc == "child":     # a PMC pass of _pmc_traffic_live: the calls above are all it is for
         ctx.close()
         return
     n_ranks, ranks = _rank_table(env)
-    # every rank solves the same system from the same reduced sums: the nodes and sigma2 must be the same BITS on all of them (first contact with a
+    line = None
+    if rank == 0:
+        line = dict(metric=cfg["metric"], value=round(cfg["steps"] * EM_ITERS / dt, 2), unit="EM iterations/s", n_gpus=n_ranks, ranks=ranks,
+                    steps=cfg["steps"], warmup=cfg["warmup"], ms_per_step=round(dt * 1e3 / cfg["steps"], 4),
+                    higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32", data="synthetic",
+                    config=dict(workload=f"C4: one frame, N={NT} points split over {n_ranks} rank(s) ({hi - lo} per rank), M={M} nodes, {EM_ITERS} EM iterations per cpd_lle call, tol=0, fp32 E-step + fp64 M-step; "
+                                         "whole calls (prune + sort + setup + loop + read-back), every call prunes",
+                                parallelism=f"points sharded over {n_ranks} rank(s); per iteration: {form}; identical M-step on every rank"
+                                            + ("; ONE rank: no peer, the per-iteration exchange is skipped" if n_ranks == 1 and comm is None else "")
+                                            + (" (self_exchange_iters_per_s: with it, against the own inbox)" if n_ranks == 1 and comm is None and args.full else "")),
+                    timed_region_s=round(dt, 3), us_per_iteration=round(dt * 1e6 / (cfg["steps"] * EM_ITERS), 2), iters=out["iters"], form=form)
+    if not args.full:           # a plain run: the headline is all it measures
+        ctx.close()
+        return line
+    # ---- --full: every rank solves the same system from the same reduced sums: the nodes and sigma2 must be the same BITS on all of them (first contact with a
     # multi-GPU box: scripts/gpu_multi_first_contact.sh reads these)
     import hashlib
     import struct
@@ -1155,16 +1220,7 @@ def bench_nsplit(args, cfg, env):
         live = _pmc_traffic_live(args, dict(cfg, N=hi - lo, frames=1), mname) if n_ranks == 1 else None
         _apply_live_traffic(live, roof, roof_all)
         roof["note_durations"] = "back-to-back launches on the shard's state (in the split loop the M-step kernel also waits for the peers' sums, so its in-situ duration is not a kernel cost)"
-        line = dict(metric=cfg["metric"], value=round(cfg["steps"] * EM_ITERS / dt, 2), unit="EM iterations/s", n_gpus=n_ranks, ranks=ranks,
-                    steps=cfg["steps"], warmup=cfg["warmup"], ms_per_step=round(dt * 1e3 / cfg["steps"], 4),
-                    higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32", data="synthetic",
-                    config=dict(workload=f"C4: one frame, N={NT} points split over {n_ranks} rank(s) ({hi - lo} per rank), M={M} nodes, {EM_ITERS} EM iterations per cpd_lle call, tol=0, fp32 E-step + fp64 M-step; "
-                                         "whole calls (prune + sort + setup + loop + read-back), every call prunes",
-                                parallelism=f"points sharded over {n_ranks} rank(s); per iteration: {form}; identical M-step on every rank"
-                                            + ("; ONE rank: no peer, the per-iteration exchange is skipped (self_exchange_iters_per_s: with it, against the own inbox)" if n_ranks == 1 and comm is None else "")),
-                    timed_region_s=round(dt, 3), us_per_iteration=round(dt * 1e6 / (cfg["steps"] * EM_ITERS), 2), iters=out["iters"],
-                    ranks_agree=len(set(hashes)) == 1, xch_can_access=access, form=form, y_sha1=hashes[0],
-                    roofline=roof, roofline_kernels=roof_all, clocks=clk.summary())
+        line.update(ranks_agree=len(set(hashes)) == 1, xch_can_access=access, y_sha1=hashes[0], roofline=roof, roofline_kernels=roof_all, clocks=clk.summary())
         cpu = None
         if n_ranks == 1 and comm is None:
             # a lone rank skips the per-iteration exchange (nobody to exchange with); what the exchange itself costs on this GPU -- every rank of a

@@ -4,9 +4,9 @@
 #   usage: bash scripts/gpu_multi_first_contact.sh [max_gpus]          (default: all visible, at most 8)
 # What it runs, each step logged under gpurun_out/first_contact/ and summarised at the end:
 #   1. the C++ N-split driver (tests/cpp/split_run_test): two ranks on devices 0 / 1 -- the one-shot exchange's peer stores cross xGMI
-#   2. bench.py --config c3 (frames sharded, barrier only) on 2, 4, 8 GPUs
-#      (the driver's own scaling command, `bench.py --gpus N` with the default config, runs c3 and both c4 forms as legs behind its headline as well: configs.c3 / c4 / c4_rccl)
-#   3. bench.py --config c4 (N = 2 000 000 split; per iteration the 4M+2 sums exchanged) on 2, 4, 8 GPUs in BOTH exchange forms:
+#   2. bench.py --config c3 --full (frames sharded, barrier only) on 2, 4, 8 GPUs
+#      (`bench.py --gpus N --full` with the default config runs c3 and both c4 forms as legs behind its headline as well: configs.c3 / c4 / c4_rccl)
+#   3. bench.py --config c4 --full (N = 2 000 000 split; per iteration the 4M+2 sums exchanged) on 2, 4, 8 GPUs in BOTH exchange forms:
 #      default (one-shot exchange: peer-written inboxes, IPC handles) and TDLO_BENCH_FORCE_RCCL=1 (the library's ncclAllReduce calls)
 #   From every line: n_gpus, value, us_per_iteration, the form that ran, ranks[].rccl_size, xch_can_access (rank x rank peer-mapping matrix),
 #   ranks_agree and ranks[].y_sha1 (every rank's nodes + sigma2 hashed: the N-split solves the same system on every rank -- same bits or it is wrong).
@@ -38,7 +38,7 @@ for cfgname in c3 c4; do
       tag=${cfgname}_${n}gpu_${form}
       echo "== bench.py --config $cfgname --gpus $n ($form)" | tee -a $O/summary.txt
       if [ $form = rccl ]; then export TDLO_BENCH_FORCE_RCCL=1; else unset TDLO_BENCH_FORCE_RCCL; fi
-      TDLO_BENCH_PORT=$port timeout 1800 python bench.py --config $cfgname --gpus $n --no-cpu-baseline $STEPS > $O/$tag.log 2> $O/$tag.err
+      TDLO_BENCH_PORT=$port timeout 1800 python bench.py --config $cfgname --gpus $n --no-cpu-baseline --full $STEPS > $O/$tag.log 2> $O/$tag.err
       rc=$?
       python - "$O/$tag.log" $rc <<'PY' | tee -a $O/summary.txt
 import json, sys

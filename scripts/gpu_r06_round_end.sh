@@ -24,10 +24,10 @@ run build_phases $O/build_phases.log bash scripts/build_variant.sh phases -DTDLO
 run build_cstamps $O/build_cstamps.log bash scripts/build_variant.sh cstamps -DTDLO_CLOUD_STAMPS
 g++ -O2 -std=c++17 scripts/ubench/track_cpp.cpp -o scripts/ubench/track_cpp -Ltrackdlo_amd -ltrackdlo_hip -Wl,-rpath,$R/trackdlo_amd || FAILED="$FAILED build_track_cpp"
 # 1. the driver's command: C2 headline + c3 / c4 / c5 legs + sustained + pre-processing + frame-from-depth legs; then every configuration on its own
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_line_default.json 2> $O/bench_stderr.log || FAILED="$FAILED bench_default"
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_line_default.json 2> $O/bench_stderr.log || FAILED="$FAILED bench_default"
 cp bench_detail.json $O/bench_detail_default.json
-timeout 600 python bench.py --no-legs > $O/bench_line_c2.json 2>> $O/bench_stderr.log || FAILED="$FAILED bench_c2"; cp bench_detail.json $O/bench_detail_c2.json
-for c in c3 c4 c5; do timeout 600 python bench.py --config $c > $O/bench_line_$c.json 2>> $O/bench_stderr.log || FAILED="$FAILED bench_$c"; cp bench_detail.json $O/bench_detail_$c.json; done
+timeout 600 python bench.py --no-legs --full > $O/bench_line_c2.json 2>> $O/bench_stderr.log || FAILED="$FAILED bench_c2"; cp bench_detail.json $O/bench_detail_c2.json
+for c in c3 c4 c5; do timeout 600 python bench.py --config $c --full > $O/bench_line_$c.json 2>> $O/bench_stderr.log || FAILED="$FAILED bench_$c"; cp bench_detail.json $O/bench_detail_$c.json; done
 # 2. kernel-trace stats of the same workloads (no PMC child passes, no legs under the tracer)
 cd /tmp
 for c in c2 c3 c4 c5; do

@@ -63,7 +63,7 @@ class StubContext:
 
     def cpd_lle_batch(self, Ys, sigma2s, params, **_):
         time.sleep(0.001)
-        return dict(Y=list(Ys), sigma2=np.asarray(sigma2s), stats=[dict(loop_ms=1.0, iters=params.max_iter, sort_reused=int(getattr(self, "sort_reuse", True))) for _ in Ys])
+        return dict(Y=list(Ys), sigma2=np.asarray(sigma2s), stats=[dict(loop_ms=1.0, iters=params.max_iter, n_kept=0, sort_reused=int(getattr(self, "sort_reuse", True))) for _ in Ys])
 
     def profile_iteration(self, reps=200):
         return 7.0, 17.0, 28.0, "k_mstep_fast<MFMA>"

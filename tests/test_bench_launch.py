@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +39,7 @@ def _detail():
 @pytest.mark.parametrize("config,frames", [("c2", 1), ("c3", 32)])
 def test_gpus_2_self_launches_two_ranks(config, frames):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--config", config,
-                        "--no-cpu-baseline"], env=_env(TDLO_BENCH_PORT="29631"), capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], env=_env(TDLO_BENCH_PORT="29631"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["ranks"] == [dict(rank=0, device=0), dict(rank=1, device=1)]
@@ -86,7 +87,7 @@ def test_driver_style_launch_and_world_size_mismatch():
 
 
 def test_single_rank_line_schema():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env=_env(),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], env=_env(),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -101,9 +102,9 @@ def test_single_rank_line_schema():
 
 
 def test_default_run_with_legs_stays_under_the_line_limit():
-    """The driver's command (no --no-legs): the headline plus the c3 / c4 / c5 legs, `sustained` and `preproc` -- the line carries them as
+    """The full run (--full, no --no-legs): the headline plus the c3 / c4 / c5 legs, `sustained` and `preproc` -- the line carries them as
     scalars, the full objects are in bench_detail.json."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"],
                        env=_env(TDLO_BENCH_STUB_LEGS="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -115,12 +116,48 @@ def test_default_run_with_legs_stays_under_the_line_limit():
     assert "roofline_kernels" in d["configs"]["c3"] and d["configs"]["c4"]["scaling"] == "strong"
 
 
+def test_plain_run_is_the_headline_only():
+    """A plain run (no --full) sets up, warms up, times exactly --steps calls and prints the headline: the contract's keys with ms_per_step the
+    time of one timed step, and nothing of what --full adds (roofline, CPU baseline and parity, clocks, the other configurations, the detail file)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2"], env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["metric"] == "EM iterations/sec at N=50k cloud pts, M=50 nodes" and line["unit"] == "EM iterations/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["n_gpus"] == 1
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 50 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    assert 1.0 <= line["ms_per_step"] and abs(line["timed_region_s"] - 7 * line["ms_per_step"] * 1e-3) <= 1e-3      # (the stand-in sleeps 1 ms per call)
+    for k in ("roofline", "roofline_kernels", "cpu_baseline", "parity", "configs", "em_iters_per_s_f64", "em_loop_only_iters_per_s", "sclk_mhz_mean",
+              "sustained_iters_per_s", "detail"):
+        assert k not in line, k
+
+
+@pytest.mark.parametrize("config,shape", [("c2", (50, 3)), ("c3", (32, 50, 3)), ("c4", (50, 3))])
+def test_dump_outputs(tmp_path, config, shape):
+    """--dump-outputs DIR writes what the last timed step returned as float64 .npy files, and the same arguments give the same inputs (the
+    stand-in context hands its input nodes back as its result, so equal dumps of two runs mean equal inputs)."""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--config", config, "--dump-outputs", str(d)],
+                           env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert _json_line(r.stdout)["steps"] == 3
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("Y", "sigma2", "iters", "n_kept")})
+    a, b = dumps
+    assert a["Y"].shape == shape and all(v.dtype == np.float64 for v in a.values())
+    assert np.all(np.isfinite(a["Y"])) and np.all(a["iters"] == 50)
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
 @pytest.mark.parametrize("fail", ["", "can_access:1", "create:0", "open:1"])
 def test_c4_exchange_negotiation_and_rccl_fallback(fail):
     """bench.py --config c4 --gpus 2: the ranks set the one-shot exchange up step by step -- peer-access probe, inbox, IPC handles
     gathered by EVERY rank, peer inboxes opened -- and agree by a MIN all-reduce; one rank that cannot takes both to the RCCL form (the library's
     own communicator), and the line says which form ran and what RCCL reports as the group size."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c4", "--no-cpu-baseline", "--full"],
                        env=_env(TDLO_BENCH_PORT="29641", TDLO_STUB_FAIL=fail), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = _json_line(r.stdout)
@@ -139,7 +176,7 @@ def test_in_run_parity_figure_is_on_the_line_and_fatal():
     C2 cloud (4.5 cm) and nothing looked at it.  Now bench.py stages the oracle's inputs again before the comparison, puts the figure on the line and
     exits non-zero outside the stated gate.  The stand-in context registers with the oracle here (TDLO_STUB_COMPUTE), so the good case is 0 m; with
     TDLO_STUB_WRONG_CLOUD the slot holds a cloud 4 mm away from the staged one and the run must fail without a JSON line."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--no-legs", "--pmc", "off", "--cpu-repeats", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--no-legs", "--pmc", "off", "--cpu-repeats", "1", "--full"]
     r = subprocess.run(cmd, env=_env(TDLO_STUB_COMPUTE="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)

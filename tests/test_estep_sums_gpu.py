@@ -1,0 +1,590 @@
+"""Each E-step kernel's sums against the extended-precision reference (tests/estep_ref.py), element by element.
+
+The N-split step API (trackdlo_amd.nsplit.HipShard on one context, no exchange) returns one E-step's sums
+[P1 | R = PX - P1 y | Q | N_kept] and the per-node minimum distances from any (Y, sigma2).  Every element must lie within a gate
+DERIVED from the kernels' arithmetic, written out in `gate`:
+
+  * fixed point: the number of shares converted into the element x 2^-(shift + 1) -- one share per (wave x 64-point batch) and node
+    for P1 and R (128-point batches in k_estep2), one per point plus one per batch and node for Q; the shifts restated from
+    prepare_frame (ln, ld, shP), k_estep2's grain (estep2_geometry: one binary digit less) and fp64 mode's sh_boost (set_iter_consts);
+  * arithmetic: u (K0 mass + K1 wmass), u = 2^-24 (fp32 mode) or 2^-53: K0 = 32 covers a membership's own roundings (distance, exp2,
+    reciprocal, product: <= 8) plus the tile's column sum (16-point slices in sequence, then two folds: <= 17) and the wave-origin
+    residual; wmass weights every term by the size of its exponent (the exponent's relative rounding, K1 = 4); distances are taken
+    from an origin up to rho = 0.25 m away (the kernels sum relative to a wave-local origin); plus one fp64 rounding of the read-out;
+  * node window: what memberships below 2^-(E - 1) of their point's largest can amount to (E = win_e32 / win_e64, one bit of margin
+    for the window test's own rounding); with TDLO_WINDOW=exact this term is M 2^-E of the mass;
+  * fp32 mode: points whose discrete decisions (nearest node, second node) are within 2^-20 of a tie count twice their terms.
+
+Every case also asserts, on the reference alone, that each kept point with a membership >= 0.05 moves its node's P1 by more than
+10 x the gate: a gate that cannot see one point would not count.  Every case names the route it asserted (k_estep2 frames, the
+forcing switch and a bitwise difference, the route counters)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import estep_ref as R
+
+pytestmark = pytest.mark.gpu
+LD = np.longdouble
+U = {0: 2.0 ** -24, 1: 2.0 ** -53}
+K0, K1 = 32.0, 4.0
+WIN = {0: 36.0, 1: 66.0}
+WIN_EXACT = {0: 154.0, 1: 1100.0}
+TIE = {0: 2.0 ** -20, 1: None}
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+# ---- scenes -----------------------------------------------------------------------------------------------------------------
+def scene(N0, M, cfg, occ=None, outliers=5, gap=False, off=0):
+    """synth.scene moved so that the nodes' centroid is exactly 0 (coordinates on a 2^-20 grid -- fp32 values -- summing to zero in any
+    order): the kernels' centring offset is then 0 and the fp32 mode's coordinates are the fp32 values the reference is given."""
+    from trackdlo_amd import synth
+    X, Y0, v = synth.scene(N0, M, config=cfg, occlude=occ, outliers=outliers)
+    X = np.array(X, dtype=np.float64); Y0 = np.array(Y0, dtype=np.float64)
+    if gap:                       # the chain's tips folded back (tests/test_estep_wide_gpu.py::test_end_node_gap_inside_a_wide_batch)
+        rng = np.random.default_rng(5)
+        Y0[1] += (0.0, 0.0, 0.09); Y0[M - 2] += (0.0, 0.0, 0.09)
+        k = min(400, N0 // 8)
+        X[:k] = Y0[0] + rng.normal(0, 0.004, (k, 3)); X[k:2 * k] = Y0[M - 1] + rng.normal(0, 0.004, (k, 3))
+    if off:                       # points 6 cm off the chain: every Euclidean membership underflows in fp64 at sigma2 = 1e-6
+        idx = np.arange(off) % (M - 8) + 4
+        X[-off:] = Y0[idx] + (0.0, 0.0, 0.06)
+    c = Y0.mean(axis=0)
+    g = 2.0 ** 20
+    Y0 = np.round((Y0 - c) * g) / g
+    Y0[M // 2] -= np.round(Y0.sum(axis=0) * g) / g
+    assert (Y0.sum(axis=0) == 0).all() and (Y0.astype(np.float32) == Y0).all()
+    X = np.asfortranarray((X - c).astype(np.float32).astype(np.float64))
+    vext = None
+    if occ is not None:
+        vext = np.asarray(synth.extend_visible(v, M, synth.geodesic_coord(Y0)), dtype=np.int32)
+    return X, Y0, vext
+
+
+def params(prec, vis=False, max_iter=10):
+    from trackdlo_amd import binding as B, synth
+    P = synth.LAUNCH_PARAMS
+    return B.make_params(P["beta"], P["lambda_"], P["lle_weight"], P["mu"], max_iter, 0.0, False, 0.0, P["k_vis"] if vis else 0.0,
+                         P["visibility_threshold"], prec)
+
+
+# ---- the gate ---------------------------------------------------------------------------------------------------------------
+def shifts(N0, Y0, prec, sigma2, estep2, boost_off=False):
+    """The exponents of the fixed-point sums (prepare_frame: ln, ld, shP; estep2_geometry: -1; set_iter_consts: sh_boost)."""
+    ln = 0
+    while (1 << ln) < N0 + 1:
+        ln += 1
+    seg = np.sqrt(((Y0[1:] - Y0[:-1]) ** 2).sum(axis=1))
+    length = 0.0
+    for s in seg:
+        length += s
+    ld = 0
+    while 2.0 ** ld < 2.0 * (length + 0.2) and ld < 20:
+        ld += 1
+    shP = min(60 - ln, 44)
+    sh = [shP, shP - ld, shP - 2 * ld]
+    if estep2:
+        sh = [s - 1 for s in sh]
+    boost = 0
+    if prec == 1 and not boost_off and sigma2 > 0:
+        deff = 2.0 * (0.4 + 2.0 * np.sqrt(sigma2))
+        lde = 0
+        while lde < ld and 2.0 ** lde < deff:
+            lde += 1
+        boost = ld - lde
+    return sh[0], sh[1] + boost, sh[2] + 2 * boost
+
+
+def gate(r, prec, N0, Y0, estep2=False, exact_window=False):
+    M = len(Y0); N = r["N"]
+    sP, sR, sQ = shifts(N0, Y0, prec, r["sigma2"], estep2)
+    nb = -(-N // (128 if estep2 else 64))
+    fixed = np.concatenate([np.full(M, nb * 2.0 ** -(sP + 1)), np.full(3 * M, nb * 2.0 ** -(sR + 1)), [(N + M * nb) * 2.0 ** -(sQ + 1)]])
+    mass = r["mass"].astype(np.float64); wmass = r["wmass"].astype(np.float64)
+    arith = U[prec] * (K0 * mass + K1 * wmass) + 2.0 ** -53 * mass
+    win = M * 2.0 ** -WIN_EXACT[prec] * mass if exact_window else r["win"].astype(np.float64)
+    return fixed + arith + win + 2.0 * r["amb"].astype(np.float64)
+
+
+def reference(X, Y0, Y, sigma2, prec, vis=None, dq=None):
+    from trackdlo_amd import synth
+    P = synth.LAUNCH_PARAMS
+    return R.estep(X, Y0, Y, sigma2, mu=P["mu"], k_vis=P["k_vis"] if vis is not None else 0.0, visibility_threshold=P["visibility_threshold"],
+                   visible_nodes=vis, dmin_sq_global=dq, fp32=prec == 0, win_e=WIN[prec] - 1, tie_rel=TIE[prec])
+
+
+def assert_gate_sees_one_point(r, g, label):
+    """Removing any one kept point with a membership >= 0.05 moves its node's P1 or Q by more than 10 gates.  Where the memberships are spread
+    over the whole chain (no membership reaches 0.05: a large sigma2) every kept point is held to it."""
+    M = len(r["P1"])
+    sel = r["pmax"] >= 0.05
+    if not sel.any():
+        sel = np.ones_like(sel)
+    ratio = np.maximum(r["pmax"] / g[:M][r["parg"]], r["qn"] / g[4 * M])[sel]
+    assert ratio.min() > 10.0, (label, "the gate cannot see one point", float(ratio.min()))
+
+
+def compare(got, r, g, label):
+    M = len(r["P1"])
+    assert got[4 * M + 1] == r["N"], (label, got[4 * M + 1], r["N"])
+    err = np.abs(got[:4 * M + 1].astype(LD) - r["sums"][:4 * M + 1]).astype(np.float64)
+    q = err / g
+    i = int(q.argmax())
+    assert q[i] <= 1.0, f"{label}: element {i} of {4 * M + 1} off by {q[i]:.3g} gates (kernel {got[i]!r}, reference {float(r['sums'][i])!r}, gate {g[i]:.3g})"
+    return float(q[i])
+
+
+def check_dmin(got, ref_dq, prec, label):
+    if prec == 1:
+        ok = np.abs(got - ref_dq) <= 2 * np.spacing(ref_dq)
+    else:
+        ok = np.abs(got - ref_dq.astype(np.float64)) <= 8 * 2.0 ** -24 * ref_dq.astype(np.float64) + 1e-38
+    assert ok.all(), (label, "dmin^2", int(np.argmin(ok)))
+
+
+# ---- driving the kernels --------------------------------------------------------------------------------------------------------
+def make_ctx(env=None, **kw):
+    from trackdlo_amd import binding as B
+    env = env or {}
+    old = {k: os.environ.get(k) for k in env}
+    try:
+        for k, v in env.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = str(v)
+        return B.Context(device=0, timing=False, **kw)
+    finally:
+        for k, v in old.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+
+
+def kernel_steps(ctx, X, Y0, s2, prec, vis=None, dq_scale=None, esteps=1):
+    """begin -> set_global -> [dmin] -> estep, then (esteps > 1) mstep on the kernel's own sums -> estep ...  Returns the list of sums, the
+    shard's dmin^2 (visibility cases) and the global dmin^2 handed in."""
+    from trackdlo_amd import nsplit
+    sh = nsplit.HipShard(ctx, X)
+    init = sh.begin(Y0, s2, params(prec, vis is not None), None, vis, None)
+    sh.set_global(init[0], init[1])
+    out, dmins, dqs = [], [], []
+    try:
+        for k in range(esteps):
+            dq = None
+            if vis is not None:
+                d = sh.dmin(); dmins.append(d)
+                dq = d * dq_scale if dq_scale else d
+                dqs.append(dq)
+            out.append(sh.estep(dq))
+            if k + 1 < esteps:
+                assert not sh.mstep(out[-1])
+    finally:
+        sh.abort()
+    return out, dmins, dqs
+
+
+def end_state(ctx, X, Y0, s2, prec, msteps):
+    """Run A: begin -> (estep -> mstep) x msteps -> end: the nodes and sigma2 the next E-step starts from."""
+    from trackdlo_amd import nsplit
+    sh = nsplit.HipShard(ctx, X)
+    init = sh.begin(Y0, s2, params(prec), None, None, None)
+    sh.set_global(init[0], init[1])
+    for _ in range(msteps):
+        sh.mstep(sh.estep(None))
+    o = sh.end()
+    return np.asarray(o["Y"]), o["sigma2"]
+
+
+def estep2_count(ctx):
+    return int(ctx.estep2_frames())
+
+
+# ---- the matrix -------------------------------------------------------------------------------------------------------------------
+MS = [4, 8, 45, 64, 65, 128, 129, 256, 257, 512, 513, 1024]
+RES = [0, 1, 63, 65, 127]
+
+
+def base_cases():
+    cs = []
+    for i, M in enumerate(MS):
+        for prec in (0, 1):
+            r = RES[(i + prec) % len(RES)]
+            N0 = max(2048, 20 * M) // 128 * 128 + r
+            cs.append(dict(N0=N0, M=M, cfg=100 + M, prec=prec, s2=0.0))
+    cs.append(dict(N0=37, M=8, cfg=7, prec=0, s2=0.0))            # a cloud smaller than one batch
+    cs.append(dict(N0=37, M=8, cfg=7, prec=1, s2=0.0))
+    return cs
+
+
+def window_nodes(Y0, s2, prec):
+    """Nodes inside the E-step's window at sigma2: an arc of 2 sqrt(E 2 ln2 sigma2) (set_iter_consts: rwin = E 2 ln2 sigma2, a squared arc length,
+    on either side of the nearest pair) over the scene's mean node spacing."""
+    h = float(np.sqrt(((Y0[1:] - Y0[:-1]) ** 2).sum(axis=1)).mean())
+    return 2.0 * np.sqrt(WIN[prec] * 2 * np.log(2) * s2) / h
+
+
+def window_sigma2(M, cfg, prec, nodes):
+    from trackdlo_amd import synth
+    _, Y0, _ = synth.scene(64, M, config=cfg)
+    h = float(np.sqrt(((Y0[1:] - Y0[:-1]) ** 2).sum(axis=1)).mean())
+    return float((nodes * h / 2.0) ** 2 / (WIN[prec] * 2 * np.log(2)))
+
+
+def regime_cases():
+    cs = []
+    for prec in (0, 1):
+        for M in (45, 257):
+            cs.append(dict(N0=8000 + 63, M=M, cfg=300 + M, prec=prec, s2=0.5))          # the window is the whole chain
+            for nodes in (16, 24):                                                       # windows around kTileRows32 / kTileRows
+                cs.append(dict(N0=8000 + 1, M=M, cfg=310 + M + nodes, prec=prec, s2=window_sigma2(M, 310 + M + nodes, prec, nodes), win=nodes))
+            cs.append(dict(N0=6000 + 127, M=M, cfg=320 + M, prec=prec, s2=1e-6, off=64))  # rows where every membership underflows
+        cs.append(dict(N0=6000 + 65, M=45, cfg=330, prec=prec, s2=0.0, occ=(0.4, 0.6), dq_scale=0.81))   # visibility, a global dmin handed in
+        cs.append(dict(N0=9000, M=257, cfg=331, prec=prec, s2=2e-4, occ=(0.3, 0.5), dq_scale=0.81))
+        cs.append(dict(N0=6000, M=60, cfg=777, prec=prec, s2=0.0, gap=True))                                 # the end-node gap
+        cs.append(dict(N0=6000, M=200, cfg=777, prec=prec, s2=0.0, gap=True))
+    return cs
+
+
+def cid(c):
+    return "-".join(f"{k}{v}" for k, v in c.items() if k not in ("cfg",))
+
+
+def ckey(c):
+    return tuple(sorted((k, str(v)) for k, v in c.items()))
+
+
+_REF = {}
+
+
+def case_ref(c, Y=None, s2=None, dq=None, key=None):
+    X, Y0, vis = scene(c["N0"], c["M"], c["cfg"], occ=c.get("occ"), gap=c.get("gap", False), off=c.get("off", 0))
+    k = (ckey(c), key, None if dq is None else np.asarray(dq).tobytes())
+    if k not in _REF:
+        _REF[k] = reference(X, Y0, Y0 if Y is None else Y, c["s2"] if s2 is None else s2, c["prec"], vis, dq)
+    return X, Y0, vis, _REF[k]
+
+
+def run_and_check(ctx, c, label, estep2=False, exact_window=False):
+    X, Y0, vis = scene(c["N0"], c["M"], c["cfg"], occ=c.get("occ"), gap=c.get("gap", False), off=c.get("off", 0))
+    sums, dmins, dqs = kernel_steps(ctx, X, Y0, c["s2"], c["prec"], vis, c.get("dq_scale"))
+    dq = None
+    if vis is not None:
+        keep = R.prune(X, Y0)
+        rd = R.dmin_sq(X[keep], Y0, fp32=c["prec"] == 0)
+        check_dmin(dmins[0], rd, c["prec"], label)
+        dq = dqs[0]
+    _, _, _, r = case_ref(c, dq=dq)
+    g = gate(r, c["prec"], c["N0"], Y0, estep2=estep2, exact_window=exact_window)
+    assert_gate_sees_one_point(r, g, label)
+    w = compare(sums[0], r, g, label)
+    return sums[0], w, r
+
+
+@pytest.fixture(scope="module")
+def big_ctx():
+    ctx = make_ctx(max_points=140000, max_nodes=1024)
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.parametrize("c", base_cases() + regime_cases(), ids=cid)
+def test_estep_sums_against_the_reference(big_ctx, c):
+    n2 = estep2_count(big_ctx)
+    _, w, r = run_and_check(big_ctx, c, cid(c))
+    assert estep2_count(big_ctx) == n2                  # route: k_estep (one frame below 2048 batches, or fp64 / beyond 64 nodes)
+    if c.get("gap"):
+        assert r["gap_quirk"] > 100
+    if c.get("off"):
+        assert r["n_underflow"] >= c["off"]
+    if c.get("win"):                                    # the window really is 15-17 / 23-25 nodes wide
+        X, Y0, _ = scene(c["N0"], c["M"], c["cfg"])
+        w = window_nodes(Y0, c["s2"], c["prec"])
+        assert c["win"] - 1 <= w <= c["win"] + 1, (c["win"], w)
+    print(f"{cid(c)}: k_estep, worst {w:.3f} of the gate")
+
+
+@pytest.mark.parametrize("rows", [8, 16])
+@pytest.mark.parametrize("N0,M,s2", [(2048 + 65, 8, 0.0), (4096 + 127, 45, 0.0), (3000 + 1, 64, 1e-4), (5000 + 63, 45, 5e-4), (37, 20, 0.0)])
+def test_k_estep2_forced(N0, M, s2, rows):
+    c = dict(N0=N0, M=M, cfg=500 + M, prec=0, s2=s2)
+    ctx = make_ctx({"TDLO_ESTEP2": 1, "TDLO_ESTEP2_ROWS": rows}, max_points=8192, max_nodes=64)
+    try:
+        n2 = estep2_count(ctx)
+        _, w, _ = run_and_check(ctx, c, cid(c), estep2=True)
+        assert estep2_count(ctx) == n2 + 1               # route: k_estep2
+    finally:
+        ctx.close()
+    print(f"{cid(c)} rows {rows}: k_estep2 (TDLO_ESTEP2=1), worst {w:.3f}")
+
+
+def test_k_estep2_default_choice_for_a_cloud_that_fills_the_gpu(big_ctx):
+    c = dict(N0=131072 + 65, M=64, cfg=510, prec=0, s2=0.0)
+    n2 = estep2_count(big_ctx)
+    _, w, _ = run_and_check(big_ctx, c, cid(c), estep2=True)
+    assert estep2_count(big_ctx) == n2 + 1
+    print(f"{cid(c)}: k_estep2 by default, worst {w:.3f}")
+
+
+def test_lane_per_node_form_against_thread_per_point(big_ctx):
+    """fp64, a window that is the whole chain, more than 128 nodes: the lane = node form by default, TDLO_ESTEP_WIDE=0 the thread = point form --
+    different bits (the route was taken), both within the gate."""
+    c = dict(N0=9000 + 63, M=257, cfg=520, prec=1, s2=0.5)
+    other = make_ctx({"TDLO_ESTEP_WIDE": 0}, max_points=16384, max_nodes=257)
+    try:
+        a, wa, _ = run_and_check(big_ctx, c, cid(c) + "-wide")
+        b, wb, _ = run_and_check(other, c, cid(c) + "-thread")
+    finally:
+        other.close()
+    assert not np.array_equal(a, b)
+    print(f"{cid(c)}: lane = node {wa:.3f}, thread = point {wb:.3f}, bits differ")
+
+
+@pytest.mark.parametrize("prec", [0, 1])
+def test_launch_geometry_does_not_change_the_bits(prec):
+    c = dict(N0=12000 + 63, M=45, cfg=530, prec=prec, s2=0.0)
+    got = []
+    for nb in (0, 7, 131):
+        ctx = make_ctx(max_points=16384, max_nodes=64, estep_blocks=nb)
+        try:
+            s, w, _ = run_and_check(ctx, c, f"{cid(c)}-blocks{nb}")
+        finally:
+            ctx.close()
+        got.append(s)
+    assert np.array_equal(got[0], got[1]) and np.array_equal(got[0], got[2])
+
+
+@pytest.mark.parametrize("prec,M", [(0, 45), (1, 45), (1, 257), (0, 129)])
+def test_second_and_third_esteps_read_the_other_parity(big_ctx, prec, M):
+    """Run A: begin -> (estep -> mstep) x k -> end gives (Y_k, sigma2_k).  Run B continues with estep after each mstep: its k-th E-step reads and
+    clears the other parity's accumulator rows, and must match the reference at (Y_k, sigma2_k) (runs are bitwise repeatable)."""
+    c = dict(N0=7000 + 65, M=M, cfg=540 + M, prec=prec, s2=0.0)
+    X, Y0, _ = scene(c["N0"], M, c["cfg"])
+    sums, _, _ = kernel_steps(big_ctx, X, Y0, 0.0, prec, esteps=3)
+    for k in (1, 2):
+        Yk, s2k = end_state(big_ctx, X, Y0, 0.0, prec, k)
+        r = reference(X, Y0, Yk, s2k, prec)
+        g = gate(r, prec, c["N0"], Y0)
+        assert_gate_sees_one_point(r, g, f"{cid(c)}-it{k + 1}")
+        w = compare(sums[k], r, g, f"{cid(c)}-it{k + 1}")
+        print(f"{cid(c)} E-step {k + 1}: worst {w:.3f}")
+
+
+def test_one_context_across_shapes(big_ctx):
+    """M = 64 -> 8 -> 257 -> 45 and N large -> small -> large on one context: nothing of the previous shape may be left over."""
+    for c in (dict(N0=60000 + 1, M=64, cfg=550, prec=0, s2=0.0), dict(N0=300 + 63, M=8, cfg=551, prec=0, s2=0.0),
+              dict(N0=50000 + 127, M=257, cfg=552, prec=1, s2=0.0), dict(N0=900, M=45, cfg=553, prec=1, s2=0.0),
+              dict(N0=40000 + 65, M=45, cfg=554, prec=0, s2=1e-4)):
+        run_and_check(big_ctx, c, "reuse-" + cid(c))
+
+
+# ---- switches read once per process: in a child process ---------------------------------------------------------------------------
+CHILD_CASES = {
+    "window": [c for c in base_cases() + regime_cases() if c["prec"] == 0],
+    "eb512": [c for c in base_cases() + regime_cases() if c["prec"] == 0 and c["M"] <= 64],
+}
+
+
+def _child(which, out):
+    ctx = make_ctx(max_points=140000, max_nodes=1024)
+    res = {}
+    try:
+        for i, c in enumerate(CHILD_CASES[which]):
+            X, Y0, vis = scene(c["N0"], c["M"], c["cfg"], occ=c.get("occ"), gap=c.get("gap", False), off=c.get("off", 0))
+            sums, _, dqs = kernel_steps(ctx, X, Y0, c["s2"], c["prec"], vis, c.get("dq_scale"))
+            res[f"s{i}"] = sums[0]
+            if dqs:
+                res[f"d{i}"] = dqs[0]
+    finally:
+        ctx.close()
+    np.savez(out, **res)
+
+
+@pytest.mark.parametrize("which,env", [("window", {"TDLO_WINDOW": "exact"}), ("eb512", {"TDLO_ESTEP_EB": "512"})])
+def test_process_wide_switches(tmp_path, big_ctx, which, env):
+    """TDLO_WINDOW=exact (every fp32 case again, the window term of the gate is then M 2^-E of the mass) and TDLO_ESTEP_EB=512 (8-wave
+    workgroups; the sums are integers from one wave x one batch on: the default's bits)."""
+    out = str(tmp_path / "sums.npz")
+    e = dict(os.environ, **env)
+    code = f"import sys; sys.path[:0] = [{HERE!r}, {os.path.dirname(HERE)!r}]; import test_estep_sums_gpu as t; t._child({which!r}, {out!r})"
+    p = subprocess.run([sys.executable, "-c", code], env=e, cwd=os.path.dirname(HERE), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    z = np.load(out)
+    worst = 0.0
+    for i, c in enumerate(CHILD_CASES[which]):
+        got = z[f"s{i}"]
+        dq = z[f"d{i}"] if f"d{i}" in z.files else None
+        X, Y0, vis = scene(c["N0"], c["M"], c["cfg"], occ=c.get("occ"), gap=c.get("gap", False), off=c.get("off", 0))
+        _, _, _, r = case_ref(c, dq=dq)
+        g = gate(r, 0, c["N0"], Y0, exact_window=which == "window")
+        worst = max(worst, compare(got, r, g, f"{which}-{cid(c)}"))
+        if which == "eb512":
+            same, _, _ = kernel_steps(big_ctx, X, Y0, c["s2"], 0, vis, c.get("dq_scale"))
+            assert np.array_equal(same[0], got), cid(c)
+    print(f"{which}: {len(CHILD_CASES[which])} cases, worst {worst:.3f}")
+
+
+# ---- entry points the step API does not reach: one iteration of cpd_lle / cpd_lle_batch against the oracle ---------------------------
+def mstep_ref(sums, Y0, sigma2):
+    from oracle import ref_cpu
+    from trackdlo_amd import synth
+    P = synth.LAUNCH_PARAMS
+    return R.mstep(sums, Y0, Y0, sigma2, beta=P["beta"], lambda_=P["lambda_"], solve=ref_cpu.solve_extended)
+
+
+def propagated_gate(r, g, Y0, draws=4):
+    """The E-step's gate carried through one extended-precision M-step: the sums moved by +- their gates (all +, then random signs), 4 x the
+    largest change of Y and of sigma2, floored at 1e-12 m (and 1e-12 relative)."""
+    M = len(Y0)
+    Yb, sb = mstep_ref(r["sums"], Y0, r["sigma2"])
+    rng = np.random.default_rng(7)
+    dy = ds = 0.0
+    for k in range(draws):
+        sg = np.ones(4 * M + 1) if k == 0 else rng.choice([-1.0, 1.0], 4 * M + 1)
+        s = r["sums"].copy()
+        s[:4 * M + 1] += (sg * g).astype(LD)
+        Yk, sk = mstep_ref(s, Y0, r["sigma2"])
+        dy = max(dy, float(np.abs(Yk - Yb).max())); ds = max(ds, abs(sk - sb))
+    return max(4 * dy, 1e-12), max(4 * ds, 1e-12 * sb)
+
+
+def oracle_one_iteration(X, Y0, s2):
+    from oracle import ref_cpu
+    from trackdlo_amd import synth
+    P = synth.LAUNCH_PARAMS
+    return ref_cpu.cpd_lle(X, Y0, s2, beta=P["beta"], lambda_=P["lambda_"], lle_weight=P["lle_weight"], mu=P["mu"], max_iter=1, tol=0.0,
+                           include_lle=False, alpha=0.0, k_vis=0.0, visibility_threshold=P["visibility_threshold"])
+
+
+def check_one_iteration(Y, s2, X, Y0, s2_in, prec, estep2, label):
+    r = reference(X, Y0, Y0, s2_in, prec)
+    g = gate(r, prec, len(X), Y0, estep2=estep2)
+    gy, gs = propagated_gate(r, g, Y0)
+    o = oracle_one_iteration(X, Y0, s2_in)
+    dy = float(np.abs(np.asarray(Y) - o["Y"]).max()); ds = abs(s2 - o["sigma2"])
+    assert dy <= gy and ds <= gs, f"{label}: |dY| {dy:.3g} m against a gate of {gy:.3g}, |d sigma2| {ds:.3g} against {gs:.3g}"
+    return dy / gy, ds / gs
+
+
+FRAME_N = [40000 + 1, 40000 + 63, 40000 + 65, 40000 + 127, 40000, 40000 + 64, 40000 + 33, 40000 + 100]
+FRAME_S2 = [0.0, 1e-4, 3e-4, 0.0, 1e-3, 2e-4, 0.0, 5e-4]
+
+
+@pytest.mark.parametrize("prec", [0, 1])
+def test_one_iteration_of_the_single_call_against_the_oracle(prec):
+    """cpd_lle (fused prologue, default route), max_iter = 1 from a given (Y, sigma2): Y and sigma2 within the E-step's gate carried through the M-step."""
+    from trackdlo_amd import binding as B
+    ctx = make_ctx(max_points=40200, max_nodes=64)
+    try:
+        for f in (0, 1, 4):
+            X, Y0, _ = scene(FRAME_N[f], 50, 600 + f)
+            g = ctx.cpd_lle(X, Y0, FRAME_S2[f], params(prec, max_iter=1))
+            assert g["rc"] == 0 and g["iters"] == 1
+            qy, qs = check_one_iteration(g["Y"], g["sigma2"], X, Y0, FRAME_S2[f], prec, False, f"single-{prec}-{f}")
+            print(f"cpd_lle frame {f} prec {prec}: |dY| {qy:.3f}, |d sigma2| {qs:.3f} of the gates")
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("F,N,two_rows", [(3, FRAME_N, False), (8, FRAME_N, False), (6, [12000 + k * 37 for k in range(6)], True)],
+                         ids=["3x40k-k_estep", "8x40k-merged-k_estep2", "6x12k-two-replica-rows"])
+def test_one_iteration_of_a_batch_against_the_oracle(F, N, two_rows):
+    """cpd_lle_batch, max_iter = 1, ragged N and a different sigma2 per frame, on both sides of the 2048-wave threshold: 3 x 40 000 points take
+    k_estep, 8 x 40 000 the merged k_estep2; 6 frames of at most 64 E-step workgroups each spread their atomics over two replica rows.  Each frame
+    within its gate of the oracle -- and the first frame of the GPU-filling batch is also run alone (k_estep): both within the
+    gate of the same reference."""
+    from trackdlo_amd import binding as B
+    ctx = make_ctx(max_frames=8, max_points=40200, max_nodes=64)
+    try:
+        scenes = [scene(N[f], 50, 610 + f) for f in range(F)]
+        for f, (X, _, _) in enumerate(scenes):
+            ctx.set_cloud(f, X)
+        s2s = FRAME_S2[:F]
+        n2 = estep2_count(ctx)
+        out = ctx.cpd_lle_batch([y for _, y, _ in scenes], s2s, params(0, max_iter=1))
+        merged = estep2_count(ctx) - n2
+        waves = sum(-(-n // 64) for n in N[:F])
+        assert merged == (F if waves >= 2048 else 0), (merged, waves)
+        for f, (X, Y0, _) in enumerate(scenes):
+            assert out["stats"][f]["status"] == 0
+            qy, qs = check_one_iteration(out["Y"][f], out["sigma2"][f], X, Y0, s2s[f], 0, merged > 0, f"batch{F}-frame{f}")
+            print(f"batch of {F} ({'k_estep2' if merged else 'k_estep'}) frame {f}: |dY| {qy:.3f}, |d sigma2| {qs:.3f} of the gates")
+        if merged:
+            X, Y0, _ = scenes[0]
+            n2 = estep2_count(ctx)
+            g = ctx.cpd_lle(X, Y0, s2s[0], params(0, max_iter=1))
+            assert estep2_count(ctx) == n2                  # alone: k_estep
+            check_one_iteration(g["Y"], g["sigma2"], X, Y0, s2s[0], 0, True, "frame 0 alone")
+    finally:
+        ctx.close()
+
+
+# ---- the fixed-point range at its edges (fp64 mode: limits that follow sigma) ---------------------------------------------------------
+def limits(N0, Y0, sigma2, boosted):
+    """Per-share limits of the E-step's range check (prepare_frame: acc_lim; k_estep: scaled by the boost): P1, R, and one point's Q."""
+    ln = 0
+    while (1 << ln) < N0 + 1:
+        ln += 1
+    sP, sR, sQ = shifts(N0, Y0, 1, sigma2, False, boost_off=not boosted)
+    lshare = min(51, 67 - max(ln, 6)); lpoint = min(51, 61 - ln)
+    return 2.0 ** (lshare - sP), 2.0 ** (lshare - sR), 2.0 ** (lpoint - sQ)
+
+
+def fabricated_move(M, n, shift, s2_target):
+    """Sums whose M-step moves every node by `shift` (lambda sigma2 is small against P1) and leaves sigma2 at about s2_target:
+    R = P1 shift, Q = Np (|shift|^2 + 3 s2_target)."""
+    P1 = np.full(M, n / M)
+    Rm = P1[:, None] * np.asarray(shift)[None, :]
+    Q = P1.sum() * (float(np.dot(shift, shift)) + 3 * s2_target)
+    return np.concatenate([P1, Rm.T.reshape(-1), [Q, float(n)]])
+
+
+@pytest.mark.parametrize("zone,shift,s2t", [("succeed", 0.0, 0.01), ("between", 5.0, 0.005), ("refuse", 20.0, 0.005)])
+def test_fixed_point_range_zones(zone, shift, s2t):
+    """Nodes moved 0 / 5 / 20 m by an M-step on fabricated sums, then one E-step at a small sigma2 (moved: every point's membership of the gap node is 1).  From the reference's
+    per-point contributions: if 64 x the largest point contribution per class is below the BOOSTED limit the E-step must succeed (and match the
+    reference); if one point's Q contribution alone exceeds the COARSE limit it must refuse (TDLO_E_NUMERIC); in between it may do either, and if
+    it succeeds it must match."""
+    from trackdlo_amd import binding as B, nsplit
+    N0, M = 6000, 45
+    X, Y0, _ = scene(N0, M, 700)
+    u = (Y0[2] - Y0[1]) / np.linalg.norm(Y0[2] - Y0[1])
+    sv = -shift * u             # against the chain's first link: node 2 nearer than node 1 to every point, so once every Euclidean membership
+    ctx = make_ctx(max_points=8192, max_nodes=64)         # underflows (node 0, :298-310) node 1 takes the gap's exp(0) = 1 (:313-350), metres away
+    try:
+        def run(second_estep):
+            sh = nsplit.HipShard(ctx, X)
+            init = sh.begin(Y0, 1e-6, params(1), None, None, None)
+            sh.set_global(init[0], init[1])
+            sh.estep(None)
+            assert not sh.mstep(fabricated_move(M, init[0], sv, s2t))
+            sums = sh.estep(None) if second_estep else None
+            try:
+                o = sh.end()
+                return 0, sums, o
+            except B.TdloError as e:
+                return e.code, sums, None
+        rc, _, a = run(False)
+        assert rc == 0
+        Y1, s21 = np.asarray(a["Y"]), a["sigma2"]
+        assert np.abs((Y1 - Y0).mean(axis=0) - sv).max() < 0.05 * max(shift, 1.0) and abs(s21 - s2t) < 0.5 * s2t, ((Y1 - Y0).mean(axis=0), s21)
+        r = reference(X, Y0, Y1, s21, 1)
+        lp_b, lr_b, lq_b = limits(N0, Y0, s21, True)
+        lp_c, lr_c, lq_c = limits(N0, Y0, s21, False)
+        below_boosted = 64 * 1.0 < lp_b and 64 * r["rmax"].max() < lr_b and r["qn"].max() < lq_b
+        beyond_coarse = r["qn"].max() > lq_c
+        got = {"succeed": below_boosted and not beyond_coarse, "refuse": beyond_coarse, "between": not below_boosted and not beyond_coarse}
+        assert got[zone], (zone, 64 * r["rmax"].max(), lr_b, lr_c, r["qn"].max(), lq_b, lq_c)      # the input lands in its zone
+        rc, sums, _ = run(True)
+        if zone == "refuse":
+            assert rc == B.TDLO_E_NUMERIC, rc
+        elif zone == "succeed" or rc == 0:
+            assert rc == 0, rc
+            g = gate(r, 1, N0, Y0)
+            w = compare(sums, r, g, f"zone {zone}")
+            print(f"zone {zone}: succeeded, worst {w:.3f} of the gate")
+        else:
+            assert rc == B.TDLO_E_NUMERIC, rc
+            print(f"zone {zone}: refused under the boosted limits")
+    finally:
+        ctx.close()

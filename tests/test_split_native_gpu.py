@@ -349,3 +349,75 @@ def test_one_shot_exchange_a_failing_shard_takes_its_peers_along(tmp_path, lle):
     assert [int(v) for v in z[:, 0]] == [B.TDLO_E_NUMERIC] * 3, z
     assert z[:, 1].max() < 1.5, z            # nobody waited for the 2 s time limit of the exchange
     assert [int(v) for v in z[:, 2]] == [0, 0, 0]
+
+
+_BOOST_SCRIPT = r"""
+import sys, threading, queue
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+from trackdlo_amd import binding as B, synth
+P = synth.LAUNCH_PARAMS
+M, N = 45, 12000
+X, Y0, v = synth.scene(N, M, config=82, occlude=(0.4, 0.6), outliers=5)
+vext = synth.extend_visible(v, M, synth.geodesic_coord(Y0))
+pr = B.make_params(P["beta"], P["lambda_"], P["lle_weight"], P["mu"], 12, 0.0, False, 0.0, P["k_vis"], P["visibility_threshold"], precision=1)
+res = {}
+def put(key, ctxs, outs):
+    res[key + "_Y"] = np.stack([o.get("Y", np.zeros((M, 3))) for o in outs])
+    res[key + "_s"] = np.array([[o.get("sigma2", 0.0), o["rc"], int(c.lib.tdlo_debug_route_count(c.h, 10))] for c, o in zip(ctxs, outs)])
+# one rank, one-shot exchange
+c = B.Context(device=0, max_points=N, max_nodes=64)
+c.xch_bind(0, [c.xch_create(1, 64)]); c.set_cloud(0, X)
+put("one", [c], [c.split_run(Y0, 0.0, pr, visible_nodes=vext, check=False)])
+c.close()
+# one rank, RCCL
+import os
+os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")
+c = B.Context(device=0, max_points=N, max_nodes=64)
+comm = c.rccl_comm_init(1, 0, B.rccl_unique_id())
+c.set_cloud(0, X)
+put("rccl", [c], [c.split_run(Y0, 0.0, pr, comm=comm, visible_nodes=vext, check=False)])
+c.close()
+# two shards on this GPU, one-shot exchange (one thread per rank)
+ctxs = [B.Context(device=0, max_points=N, max_nodes=64) for _ in range(2)]
+inb = [k.xch_create(2, 64) for k in ctxs]
+out = queue.Queue()
+def work(r):
+    try:
+        ctxs[r].xch_bind(r, inb); ctxs[r].set_cloud(0, X[r * N // 2:(r + 1) * N // 2])
+        out.put((r, ctxs[r].split_run(Y0, 0.0, pr, visible_nodes=vext, check=False)))
+    except Exception as e:
+        out.put((r, dict(rc=-99, err=repr(e))))
+th = [threading.Thread(target=work, args=(r,)) for r in range(2)]
+[t.start() for t in th]; [t.join() for t in th]
+o = dict(out.get() for _ in range(2))
+put("two", ctxs, [o[0], o[1]])
+for k in ctxs: k.close()
+np.savez(sys.argv[2], **res)
+"""
+
+
+def test_split_run_repeats_a_refusal_under_the_boosted_limits(tmp_path, oracle):
+    """ADVICE r06 item 2: fp64 mode's E-step checks its shares against limits that follow sigma (IterState::sh_boost); a share refused there
+    would pass the coarse limits, and run_frames repeats such a call once without the boost -- tdlo_split_run now does the same, decided on the
+    common status so that every rank repeats together.  TDLO_TEST_BOOST_FAIL=1 treats every fp64 first attempt as such a refusal: one rank
+    (one-shot exchange and RCCL) and two shards on this GPU must return rc 0 within the fp64 gate of the oracle, one retry counted per rank."""
+    import subprocess, sys
+    from trackdlo_amd import synth
+    P = synth.LAUNCH_PARAMS
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", TDLO_TEST_BOOST_FAIL="1")
+    out = tmp_path / "boost.npz"
+    r = subprocess.run([sys.executable, "-c", _BOOST_SCRIPT, root, str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    z = np.load(out)
+    M = 45
+    X, Y0, v = synth.scene(12000, M, config=82, occlude=(0.4, 0.6), outliers=5)
+    vext = synth.extend_visible(v, M, synth.geodesic_coord(Y0))
+    o = oracle.cpd_lle(X, Y0, 0.0, beta=P["beta"], lambda_=P["lambda_"], lle_weight=P["lle_weight"], mu=P["mu"], max_iter=12, tol=0.0,
+                       include_lle=False, k_vis=P["k_vis"], visibility_threshold=P["visibility_threshold"], visible_nodes=vext)
+    ty, ts = TOL[1]
+    for key in ("one", "rccl", "two"):
+        for Y, (s2, rc, retries) in zip(z[key + "_Y"], z[key + "_s"]):
+            assert rc == 0 and retries == 1, (key, rc, retries)
+            assert np.abs(Y - o["Y"]).max() <= ty and abs(s2 - o["sigma2"]) <= ts * o["sigma2"], (key, np.abs(Y - o["Y"]).max())

@@ -276,7 +276,7 @@ struct tdlo_ctx {
     bool xch_self = getenv("TDLO_XCH_SELF") && atoi(getenv("TDLO_XCH_SELF")) != 0;      // a lone rank of the one-shot exchange exchanges with its own inbox (tdlo_set_xch_self)
     bool boost_off_once = false;          // run_frames' retry: an fp64-mode E-step refused a share under the sigma-following (finer) limits -- this call repeats with the coarse ones
     long long boost_retries = 0;          // how often that happened (tdlo_debug_route_count 10)
-    bool test_boost_fail = getenv("TDLO_TEST_BOOST_FAIL") && atoi(getenv("TDLO_TEST_BOOST_FAIL")) != 0;   // test hook: every fp64-mode call's first attempt is treated as such a refusal
+    bool test_boost_fail = getenv("TDLO_TEST_BOOST_FAIL") && atoi(getenv("TDLO_TEST_BOOST_FAIL")) != 0;   // test hook: every fp64-mode call's first attempt has its shares refused under the boosted limits (set_iter_consts)
     // Round 6 experiment, OFF by default: one frame's fixed-length loop as a spin-ahead loop -- E-steps on the second stream, M-steps on
     // the first, the kernels parked on device words instead of the streams' dependent dispatches (FrameDev::spin_on).  TDLO_SPIN_AHEAD=1 switches it on.
     bool spin_ahead_on = getenv("TDLO_SPIN_AHEAD") && atoi(getenv("TDLO_SPIN_AHEAD")) != 0;
@@ -834,7 +834,7 @@ int prepare_frame(tdlo_ctx *c, int slot, const double *Y, int M, double sigma2, 
         const int lshare = std::min(51, 67 - std::max(ln, 6)), lpoint = std::min(51, 61 - ln);
         f.acc_lim[0] = std::ldexp(1.0, lshare - f.acc_sh[0]); f.acc_lim[1] = std::ldexp(1.0, lshare - f.acc_sh[1]); f.acc_lim[2] = std::ldexp(1.0, lpoint - f.acc_sh[2]);
     }
-    f.acc_boost_off = c->boost_off_once ? 1 : 0;
+    f.acc_boost_off = c->boost_off_once ? 1 : (c->test_boost_fail ? -1 : 0);      // (-1: the test hook of set_iter_consts)
     f.estep_wide_min = c->estep_wide_min;
     // (acc_rows: choose_acc_rows, once the E-step's geometry is final)
     // one frame whose cloud fills the GPU alone (2048 waves of 64 points: from there on two points per lane win, scripts/gpu_estep2_check.py /
@@ -988,7 +988,9 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
             f.wide_tile = 0;
             // batches fill the GPU: half the workgroups per frame, every wave takes two 64-point batches -- the per-workgroup prologue (nodes
             // to LDS) and epilogue (wave sums, atomics) are paid half as often (32 frames: 879 k -> 991 k it/s in the loop).  The sums do
-            // not depend on how batches are dealt out (integer accumulation), so the results are those of the single call, bit for bit.
+            // not depend on how batches are dealt out (integer accumulation): with k_estep on both sides the results are those of the single
+            // call, bit for bit.  A batch that fills the GPU takes k_estep2 below (128-point grain, one binary digit less) where the frame
+            // alone takes k_estep: then each frame's sums are the single call's within the E-step's own rounding, not bit for bit.
             if (c->cfg.estep_blocks <= 0 && f.nblkE >= 64) f.nblkE = (f.nblkE + 1) / 2;
             double *bu = c->xfer + (size_t)i * up, *br = c->xfer + (size_t)F * up + fdd + (size_t)i * nc.readback;
             f.Yin = bu + nc.Yin; f.aJ = bu + nc.aJ; f.aYd = bu + nc.aYd;
@@ -1477,7 +1479,7 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
     // small -- would have passed under the coarse limits.  It is not failed for the boost: the call is repeated ONCE without it (inputs, Y, sigma2
     // untouched so far), and only that verdict is reported.
     if (p->precision == TDLO_PREC_F64 && !c->boost_off_once && p->max_iter > 0) {
-        bool numeric = c->test_boost_fail;
+        bool numeric = false;
         for (int i = 0; i < F && !numeric; ++i) {
             IterState is;
             std::memcpy(&is, c->pin + (size_t)i * rstride + (nc.st - nc.Yout), sizeof is);
@@ -2158,6 +2160,18 @@ int tdlo_split_run(tdlo_ctx *c, void *nccl_comm, double *Y, int M, double *sigma
         const int rr = tdlo_split_run(c, nccl_comm, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
         c->lle_dense_once = false;
         if (stats) stats->band_retry = 1;
+        return rr;
+    }
+    // fp64 mode: a share refused under the limits that follow sigma (IterState::sh_boost) would have passed the coarse ones.  As in run_frames, the
+    // status does not say which check failed, so EVERY fp64 TDLO_E_NUMERIC repeats the call ONCE with the coarse limits (Y and sigma2 are untouched
+    // so far; a failure of another kind -- non-finite sigma2, a singular system -- fails again and costs a second run).  The status is common to the
+    // ranks (RCCL form: the MIN all-reduce above; one-shot form: a rank whose own shard failed has told its peers, kXchErrMark), so every rank
+    // repeats or none does.  tdlo_debug_route_count 10 counts the repeats.
+    if (p->precision == TDLO_PREC_F64 && !c->boost_off_once && p->max_iter > 0 && is.status == TDLO_E_NUMERIC) {
+        c->boost_off_once = true;
+        ++c->boost_retries;
+        const int rr = tdlo_split_run(c, nccl_comm, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
+        c->boost_off_once = false;
         return rr;
     }
     if ((is.status == 0 || is.status == TDLO_E_NUMERIC) && is.it > 0) { std::memcpy(Y, c->pin, sizeof(double) * 3 * M); }

@@ -305,12 +305,15 @@ __device__ __forceinline__ void set_iter_consts(const FrameDev &f, IterState *st
     // E-step still CHECKS every share against the (finer) limit.  With lambda sigma2 ~ 1e-5 (lambda = 1 without the LLE term) the coarse resolution, 2^-39 m
     // per share on a chain of 460 nodes, had put nodes 1e-8 m from the oracle's (profiles/r05_fuzz.log); fp32 mode's tile sums carry 1e-7 relative anyway.
     int boost = 0;
-    if (f.precision == TDLO_PREC_F64 && !f.acc_boost_off && sigma2 > 0.0) {
+    if (f.precision == TDLO_PREC_F64 && f.acc_boost_off <= 0 && sigma2 > 0.0) {
         const int ld = f.acc_sh[0] - f.acc_sh[1];
         const double deff = 2.0 * (0.4 + 2.0 * ::sqrt(sigma2));
         int lde = 0;                                   // (D_eff >= 0.8: 2^0 is the smallest extent there is)
         while (lde < ld && ::ldexp(1.0, lde) < deff) ++lde;
         boost = ld - lde;
+        // test hook (TDLO_TEST_BOOST_FAIL, acc_boost_off < 0): 40 digits more than the boost, so that the E-step's range check REFUSES the R and Q shares
+        // under the boosted limits -- a real refusal, which the repeat with the coarse limits (acc_boost_off = 1, no boost at all) must clear
+        if (f.acc_boost_off < 0) boost += 40;
     }
     st->sh_boost = boost;
 }

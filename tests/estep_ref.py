@@ -47,6 +47,23 @@ def chain_coord(Y0):
     return c
 
 
+def chain_gaps_exact(Y0):
+    """|coord_i - coord_j| for every pair, to a few longdouble ulp RELATIVE to the distance itself: the segment lengths in longdouble, their
+    running sum carried as an unevaluated pair hi + lo (two-sum at every step), the difference of two entries formed from both parts.  The
+    fp64 running sum of chain_coord is off by ~1e-16 m absolute, which the dense form G W amplifies by |G| |W| / |V| (up to 1e6 with the
+    pre-processing parameters): tests/mstep_ref.py's reference must not carry that."""
+    Y0 = np.asarray(Y0, dtype=np.float64).astype(LD)
+    seg = np.sqrt(((Y0[1:] - Y0[:-1]) ** 2).sum(axis=1))
+    hi = np.zeros(len(Y0), dtype=LD); lo = np.zeros(len(Y0), dtype=LD)
+    h = LD(0); l = LD(0)
+    for i, sg in enumerate(seg):
+        t = h + sg
+        l += (h - t) + sg if abs(h) >= abs(sg) else (sg - t) + h
+        h = t
+        hi[i + 1] = h; lo[i + 1] = l
+    return np.abs((hi[:, None] - hi[None, :]) + (lo[:, None] - lo[None, :]))
+
+
 def sum_d2(X, Y0):
     """The sigma2 initialisation's sum over kept points and nodes (trackdlo.cpp:263-273), in longdouble."""
     X = np.asarray(X, dtype=LD); Y0 = np.asarray(Y0, dtype=LD)
@@ -229,31 +246,44 @@ def sums_vector(r):
     return np.concatenate([r["P1"], r["R"].T.reshape(-1), [r["Q"], LD(r["N"])]])
 
 
-def mstep(sums, Y0, Y, sigma2, *, beta, lambda_, solve, alpha=0.0, priors=None, lle_weight=0.0, H=None):
+def mstep(sums, Y0, Y, sigma2, *, beta, lambda_, solve, alpha=0.0, priors=None, lle_weight=0.0, H=None, exact=False):
     """The M-step of trackdlo.cpp:392-422 from sums in the kernels' layout, as tests/numpy_shard.py builds it: R is converted
     back to PX = R + P1 y and the system is solved by `solve(A, B)` (oracle.solve_extended).  sigma2 in the residual form
-    sum P |x - T|^2 = Q - 2 sum_m d_m . R_m + sum_m P1_m |d_m|^2, d = T - y, evaluated in longdouble."""
+    sum P |x - T|^2 = Q - 2 sum_m d_m . R_m + sum_m P1_m |d_m|^2, d = T - y, evaluated in longdouble.
+    exact=True (tests/mstep_ref.py): the distances along the chain are those of chain_gaps_exact (relative error ~1e-19, not the fp64
+    running sum's absolute 1e-16 m), G, A and B = R + P1 (y - Y0) are formed in longdouble from them and the fp64 inputs and handed to
+    `solve` as longdouble, T = Y0 + G W stays in longdouble, and T and sigma2 are returned in longdouble."""
     Y0 = np.asarray(Y0, dtype=np.float64); Y = np.asarray(Y, dtype=np.float64)
     M = len(Y0)
+    F = LD if exact else np.float64
     s = np.asarray(sums, dtype=LD)
     P1L = s[:M]; RL = s[M:4 * M].reshape(3, M).T; QL = s[4 * M]
-    P1 = P1L.astype(np.float64)
-    PX = (RL + P1L[:, None] * Y.astype(LD)).astype(np.float64)
-    coord = chain_coord(Y0)
-    dd = np.abs(coord[:, None] - coord[None, :])
-    G = 1 / (2 * beta * 2 * beta) * np.exp(-np.sqrt(2) * dd / beta) * (2 * dd + np.sqrt(2) * beta)       # :233
-    A = P1[:, None] * G + lambda_ * sigma2 * np.eye(M)
-    Bm = PX - P1[:, None] * Y0
+    P1 = P1L.astype(F)
+    if exact:
+        dd = chain_gaps_exact(Y0)
+    else:
+        coord = chain_coord(Y0)
+        dd = np.abs(coord[:, None] - coord[None, :])
+    b = F(beta); r2 = np.sqrt(F(2))
+    G = 1 / (2 * b * 2 * b) * np.exp(-r2 * dd / b) * (2 * dd + r2 * b)       # :233
+    A = P1[:, None] * G + F(lambda_) * F(sigma2) * np.eye(M, dtype=F)
+    if exact:
+        Bm = RL + P1L[:, None] * (Y.astype(LD) - Y0.astype(LD))
+    else:
+        PX = (RL + P1L[:, None] * Y.astype(LD)).astype(np.float64)
+        Bm = PX - P1[:, None] * Y0
+    Y0F = Y0.astype(F)
     if H is not None:
-        A = A + sigma2 * lle_weight * H @ G; Bm = Bm - sigma2 * lle_weight * H @ Y0
+        HF = np.asarray(H, dtype=np.float64).astype(F); g = F(sigma2) * F(lle_weight)
+        A = A + g * HF @ G; Bm = Bm - g * HF @ Y0F
     if priors is not None and len(priors):
-        J = np.zeros(M); Yext = Y0.copy()
+        J = np.zeros(M, dtype=F); Yext = Y0F.copy()
         for r in np.asarray(priors, dtype=np.float64).reshape(-1, 4):
             J[int(r[0])] = 1.0; Yext[int(r[0])] = r[1:]
-        A = A + alpha * J[:, None] * G; Bm = Bm + alpha * (Yext - Y0)
+        A = A + F(alpha) * J[:, None] * G; Bm = Bm + F(alpha) * (Yext - Y0F)
     W = solve(A, Bm)
-    T = Y0 + G @ W
+    T = Y0F + G @ np.asarray(W, dtype=F)
     d = T.astype(LD) - Y.astype(LD)
     num = QL - LD(2) * (d * RL).sum() + (P1L[:, None] * d * d).sum()
-    s2 = float(num / (P1L.sum() * LD(3)))
-    return T, s2
+    s2 = num / (P1L.sum() * LD(3))
+    return (T, s2) if exact else (T, float(s2))

@@ -1,0 +1,457 @@
+"""Each M-step kernel from given sums against the quad-precision solve (tests/mstep_ref.py), node by node.
+
+The N-split step API (trackdlo_amd.nsplit.HipShard on one context) runs begin -> set_global -> estep -> mstep(sums) -> end, and mstep copies any
+sums [P1 | R | Q | N_kept] into the frame (from_sums = 1): that reaches every M-step kernel.  The sums are the extended-precision E-step's
+(tests/estep_ref.py) of a synth scene, then edited: P1 (with R) zeroed at the chain's ends and at the smoother's junction nodes, a single observed
+node, priors there, lambda sigma2 over eleven decades, an LLE regulariser whose rows do not sum to zero on a scene 12 m from the origin.  T and
+sigma2 must lie within `mstep_ref.gate`, and done / iters / converged must be the reference's decisions exactly.  Every case names the kernel it
+reached (Context.profile_iteration: mstep_kernel_name).
+
+After a successful M-step the next E-step must start from it: its sums match the E-step reference at the kernel's own (T, sigma2), and in fp64 mode
+their resolution follows the new sigma2 (IterState::sh_boost, set_iter_consts) -- every R x 2^sR an integer, not all of them even."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+import chain_numpy as cn  # noqa: E402
+import estep_ref as R  # noqa: E402
+import mstep_ref as MR  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+LD = np.longdouble
+SHIFT = np.array([10.0, -7.0, 3.0])
+
+
+# ---- the matrix ---------------------------------------------------------------------------------------------------------------------
+def _direct_edge():
+    """The chain lengths on both sides of nQ = kDirectMax = 21 steps per direction (ChainCarve): the backward pass walked step by step or in strides."""
+    Ms = [M for M in range(40, 120) if cn.carve(M)[4] == 21]
+    return Ms[-1], Ms[-1] + 1
+
+
+DE = _direct_edge()
+CHAIN_M = [4, 5, 7, 9, 13, 24, DE[0], DE[1], 255, 256, 257, 319, 320, 511, 512]
+LONG_M = [513, 777, 1024]
+BAND_M = [4, 5, 6, 7, 12, 13, 14, 19, 20, 26, 27, 45, 128, 129, 256, 257, 480, 512]
+DENSE_M = [8, 45, 60, 61, 64, 65, 129, 300, 512, 513]
+LLE_DENSE_M = [8, 45, 64, 65, 128, 129, 300, 512, 513]
+
+
+def _c(family, route, M, regime, prec=1, **kw):
+    return dict(family=family, route=route, M=M, regime=regime, prec=prec, **kw)
+
+
+def cases():
+    cs = []
+    for M in CHAIN_M:
+        cs.append(_c("chain", "chain", M, "typical"))
+        if M >= 7:
+            cs.append(_c("chain", "chain", M, "p1zero"))
+            cs.append(_c("chain", "chain", M, "priors"))
+    for M in (45, 256):
+        cs.append(_c("chain", "chain", M, "single"))
+        cs.append(_c("chain", "chain", M, "tiny_c"))
+        cs.append(_c("chain", "chain", M, "big_c"))
+        cs.append(_c("chain", "chain", M, "typical", prec=0))
+        cs.append(_c("chain", "chain", M, "coincident"))
+    for M in LONG_M:
+        cs.append(_c("chain", "long", M, "typical"))          # (M >= 513: a quad solve of 10 - 20 s each on the CPU -- typical sums only, and one p1zero)
+    cs.append(_c("chain", "long", 777, "p1zero"))
+    for M in BAND_M:
+        cs.append(_c("band", "band", M, "typical"))
+        if M >= 12:
+            cs.append(_c("band", "band", M, "p1zero"))
+    for M in (45, 257):
+        cs.append(_c("band", "band", M, "shifted_h"))
+        cs.append(_c("band", "band", M, "priors"))
+        cs.append(_c("band", "band", M, "typical", prec=0))
+    for M in DENSE_M:
+        cs.append(_c("dense", "dense", M, "typical"))
+        cs.append(_c("dense", "dense", M, "p1zero"))
+    for M in (45, 129):
+        cs.append(_c("dense", "dense", M, "priors"))
+        cs.append(_c("dense", "dense", M, "dense_c"))
+        cs.append(_c("dense", "dense", M, "typical", prec=0))
+        cs.append(_c("dense", "lambda0", M, "lambda0"))
+    for M in LLE_DENSE_M:
+        cs.append(_c("dense", "lle_dense", M, "typical"))
+    for M in (45, 129):
+        cs.append(_c("dense", "lle_dense", M, "shifted_h"))
+        cs.append(_c("dense", "lle_dense", M, "coincident"))
+    return cs
+
+
+# Cells dropped, each for what tests/test_mstep_ref.py shows on the CPU (restatement / sharpness ratios from that run):
+#   * band, 256+ nodes (pre-processing parameters, beta = 3): the banded solve's own fp64 error grows with the chain (its restatement is 3e-12 m off at
+#     257 nodes) and the gate that contains it is wider than an fp32 slip of the sums (gate / slip 1.3 at 257, 3e5 at 480); at 512 nodes the restatement
+#     is 8 - 160 gates out: the gate's state-precision term does not model the band there.  The band is held to the reference up to 129 nodes.
+#   * dense eliminations without the LLE term from 129 nodes on (k_mstep_mcu at 129 / 300 / 512, k_mstep<1wg> at 513) and at lambda sigma2 = 1e-7: the
+#     dense gate carries |G| |A^-1| |A| |W| and the fp64 chain coordinate's worst-case running-sum error through G W; it is 0.2 - 5 (129 - 513 nodes),
+#     3e4 - 6e5 (lambda sigma2 = 1e-7) of an fp32 slip.  k_mstep_mcu is held at 61 - 65 nodes, k_mstep_fast<MFMA> up to 60.
+#   * every dense LLE cell (k_mstep_fast<pivoted>, k_mstep<LDS>, k_mstep_pivot_mcu, k_mstep<1wg> with the LLE term; the TDLO_MSTEP_LLE=1wg comparator
+#     for the same reason): W is 1e5 - 1e9 times larger than V = G W, and the gate is 3e5 - 7e21 of an fp32 slip.  Their routes are still asserted
+#     (the hand-over tests below) and the band's hand-over cases are held to the dense gate, which contains their restatement.
+DROPPED = {
+    "band-M256-typical-f64", "band-M256-p1zero-f64", "band-M257-typical-f64", "band-M257-p1zero-f64", "band-M480-typical-f64",
+    "band-M480-p1zero-f64", "band-M512-typical-f64", "band-M512-p1zero-f64", "band-M257-shifted_h-f64", "band-M257-priors-f64",
+    "band-M257-typical-f32",
+    "dense-M129-typical-f64", "dense-M129-p1zero-f64", "dense-M300-typical-f64", "dense-M300-p1zero-f64", "dense-M512-typical-f64",
+    "dense-M512-p1zero-f64", "dense-M513-typical-f64", "dense-M513-p1zero-f64", "dense-M45-dense_c-f64", "dense-M129-priors-f64",
+    "dense-M129-dense_c-f64", "dense-M129-typical-f32",
+    "lle_dense-M8-typical-f64", "lle_dense-M45-typical-f64", "lle_dense-M64-typical-f64", "lle_dense-M65-typical-f64", "lle_dense-M128-typical-f64",
+    "lle_dense-M129-typical-f64", "lle_dense-M300-typical-f64", "lle_dense-M512-typical-f64", "lle_dense-M513-typical-f64",
+    "lle_dense-M45-shifted_h-f64", "lle_dense-M45-coincident-f64", "lle_dense-M129-shifted_h-f64", "lle_dense-M129-coincident-f64",
+}
+ALL_CASES = cases()
+CASES = [c for c in ALL_CASES if f"{c['route']}-M{c['M']}-{c['regime']}-{'f64' if c['prec'] else 'f32'}" not in DROPPED]
+
+
+def cid(c):
+    return f"{c['route']}-M{c['M']}-{c['regime']}-{'f64' if c['prec'] else 'f32'}"
+
+
+def expected_kernel(route, M):
+    """mstep_kernel_name (tdlo_device.hip) for the route a case forces."""
+    if route == "chain":
+        return "k_mstep_chain"
+    if route == "long":
+        return "k_mstep_chain_long"
+    if route == "band":
+        return "k_mstep_band"
+    if route in ("dense", "lambda0"):
+        return "k_mstep_fast<MFMA>" if M <= 60 else ("k_mstep<1wg>" if M > 512 else "k_mstep_mcu")
+    return "k_mstep_fast<pivoted>" if M <= 64 else ("k_mstep<LDS>" if M <= 128 else ("k_mstep<1wg>" if M > 512 else "k_mstep_pivot_mcu"))
+
+
+# ---- scenes and sums ----------------------------------------------------------------------------------------------------------------------
+def scene(M, cfg, scale=1.0, coincident=False):
+    """synth.scene on a 2^-20 m grid with the nodes' centroid exactly 0 (fp32 mode reads the fp32 node copy: the centring and the coordinates are
+    then exact in fp32 and the test does not measure their rounding).  scale stretches the chain (the resolution check wants >= 3 m)."""
+    from trackdlo_amd import synth
+    N0 = max(600, 16 * M)
+    X, Y0, _ = synth.scene(N0, M, config=cfg)
+    X = np.array(X, dtype=np.float64) * scale; Y0 = np.array(Y0, dtype=np.float64) * scale
+    if coincident:
+        Y0[M // 3 + 1] = Y0[M // 3]
+    c = Y0.mean(axis=0)
+    g = 2.0 ** 20
+    Y0 = np.round((Y0 - c) * g) / g
+    k = M // 2 if not coincident or M // 2 not in (M // 3, M // 3 + 1) else M - 1
+    Y0[k] -= np.round(Y0.sum(axis=0) * g) / g
+    assert (Y0.sum(axis=0) == 0).all() and (Y0.astype(np.float32) == Y0).all()
+    X = np.asfortranarray((X - c).astype(np.float32).astype(np.float64))
+    return X, Y0
+
+
+def params_of(case):
+    from trackdlo_amd import synth
+    P = synth.LAUNCH_PARAMS
+    lle = case["route"] in ("band", "lle_dense")
+    lam = {"tiny_c": 1e-4, "dense_c": 0.1, "big_c": 5e4, "lambda0": 0.0}.get(case["regime"], P["lambda_pre_proc"] if lle else P["lambda_"])
+    beta = P["beta_pre_proc"] if lle else P["beta"]
+    s2 = {"tiny_c": 1e-6, "dense_c": 1e-6, "big_c": 2e-4}.get(case["regime"], 2e-5 if lle else 1e-4)
+    return dict(beta=beta, lambda_=lam, alpha=P["alpha"], lle_weight=P["lle_weight"], mu=P["mu"], lle=lle, s2=s2)
+
+
+def junctions(M):
+    j1, j2, j3, _, _ = cn.carve(M)
+    return sorted({0, j1, max(j2 - 1, 0), j2, j3, M - 1})
+
+
+def lle_H(Y0, regime):
+    from oracle import ref_cpu
+    M = len(Y0)
+    L = ref_cpu.calc_lle_weights(Y0, 6)
+    H = (np.eye(M) - L).T @ (np.eye(M) - L)
+    if regime == "shifted_h":
+        H = H + 0.05 * np.eye(M) + 0.01 * (np.eye(M, k=1) + np.eye(M, k=-1))      # rows no longer sum to zero (still banded and symmetric)
+    return H
+
+
+_BUILT = {}
+
+
+def build_case(case, with_scene=False):
+    """(mstep_ref.Case, X, Y0 handed to the library, priors handed to the library)."""
+    key = cid(case)
+    if key not in _BUILT:
+        M = case["M"]; p = params_of(case)
+        X, Y0 = scene(M, 800 + M + (1000 if case["prec"] == 0 else 0), coincident=case["regime"] == "coincident")
+        r = R.estep(X, Y0, Y0, 1e-4, mu=p["mu"])
+        s = r["sums"].copy()
+        P1 = s[:M]; Rm = s[M:4 * M].reshape(3, M).T.copy()
+        reg = case["regime"]
+        if reg == "p1zero":
+            z = junctions(M)
+            j2 = cn.carve(M)[1]
+            if M >= 12:                                                                  # (shorter chains: the junctions alone leave few nodes observed)
+                z += list(range(max(j2 - 2, 0), min(j2 + 3, M)))                        # a run of unobserved nodes across j2
+            P1[z] = 0; Rm[z] = 0
+        elif reg == "single":
+            keep = M // 3
+            m = np.ones(M, dtype=bool); m[keep] = False
+            P1[m] = 0; Rm[m] = 0
+        elif reg == "lambda0":
+            P1[M // 2] = 0; Rm[M // 2] = 0                                               # one unobserved node: A's row is exactly zero
+        if reg in ("typical", "p1zero", "priors") and M >= 8 and case["family"] == "chain" and M % 3 == 0:
+            P1[: M // 4] *= LD(1e-10); Rm[: M // 4] *= LD(1e-10)                         # P1 over fourteen decades on one chain
+        s[:M] = P1; s[M:4 * M] = Rm.T.reshape(-1)
+        priors = None
+        if reg == "priors":
+            idx = junctions(M)
+            rows = [[i, *(Y0[i] + 0.003)] for i in idx] + [[idx[1], *(Y0[idx[1]] - 0.002)]]      # two priors on one node: the last one wins
+            priors = np.array(rows, dtype=np.float64)
+            if M >= 7:
+                P1[idx[1]] = 0; Rm[idx[1]] = 0                                         # a prior where no point is
+                s[:M] = P1; s[M:4 * M] = Rm.T.reshape(-1)
+        H = lle_H(Y0, reg) if p["lle"] else None
+        Yl = Y0 + SHIFT if reg == "shifted_h" else Y0                                     # the sums are translation-invariant
+        Xl = X + SHIFT if reg == "shifted_h" else X
+        c = MR.Case(s, Yl, Yl, p["s2"], beta=p["beta"], lambda_=p["lambda_"], alpha=p["alpha"] if priors is not None else 0.0, priors=None
+                    if priors is None else np.column_stack([priors[:, 0], priors[:, 1:] + (SHIFT if reg == "shifted_h" else 0)]),
+                    lle_weight=p["lle_weight"] if p["lle"] else 0.0, H=H)
+        _BUILT[key] = (c, np.asfortranarray(Xl), Yl, c.priors)
+    c, X, Y0, pr = _BUILT[key]
+    return (c, X, Y0, pr) if with_scene else c
+
+
+# ---- driving the kernels ----------------------------------------------------------------------------------------------------------------------
+def make_params(case, max_iter=10, tol=0.0):
+    from trackdlo_amd import binding as B
+    p = params_of(case)
+    return B.make_params(p["beta"], p["lambda_"], p["lle_weight"], p["mu"], max_iter, tol, p["lle"], p["alpha"], 0.0, 0.008, case["prec"])
+
+
+def run_mstep(ctx, X, Y0, s2, prm, sums, priors=None, H=None, then_estep=False):
+    """begin -> set_global -> estep -> mstep(sums) [-> estep] -> end: (rc, done flag, end() dict or None, next E-step's sums or None)."""
+    from trackdlo_amd import binding as B, nsplit
+    sh = nsplit.HipShard(ctx, X)
+    init = sh.begin(Y0, s2, prm, priors, None, H)
+    sh.set_global(init[0], init[1])
+    sh.estep(None)
+    done = sh.mstep(np.asarray(sums, dtype=np.float64))
+    nxt = sh.estep(None) if then_estep and not done else None
+    try:
+        o = sh.end()
+        return 0, done, o, nxt
+    except B.TdloError as e:
+        return e.code, done, None, nxt
+
+
+def set_route(route):
+    from trackdlo_amd import binding as B
+    B.mstep_dense(route in ("dense",))
+    B.mstep_lle_dense(route in ("lle_dense",))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from trackdlo_amd import binding as B
+    c = B.Context(device=0, timing=False, max_points=16 * 1024, max_nodes=1024)
+    yield c
+    B.mstep_dense(False); B.mstep_lle_dense(False)
+    c.close()
+
+
+WORST = {}
+
+
+def _report():
+    for k, (qt, qs) in sorted(WORST.items()):
+        print(f"  {k}: worst |dT| / gate {qt:.3g}, |d sigma2| / gate {qs:.3g}")
+
+
+@pytest.mark.parametrize("case", CASES, ids=cid)
+def test_mstep_from_sums_against_the_quad_solve(ctx, case):
+    from trackdlo_amd import binding as B
+    c, X, Y0, priors = build_case(case, with_scene=True)
+    set_route(case["route"])
+    rc, done, o, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), c.sums, priors, c.H)
+    name = ctx.profile_iteration(1)[3]
+    assert name == expected_kernel(case["route"], case["M"]), (cid(case), name)
+    if case["route"] == "lambda0":
+        # one unobserved node with lambda = 0: A's row is exactly zero -- no fp64 answer; every dense kernel refuses
+        assert rc == B.TDLO_E_NUMERIC, (cid(case), rc, name)
+        return
+    assert rc == 0 and done, (cid(case), rc, done)
+    assert o["iters"] == 1 and o["converged"] is False                  # max_iter = 1: done, not converged
+    T, s2, _ = MR.reference(c)
+    gT, gS, _ = MR.gate(c, case["family"], T)
+    dT = np.abs(np.asarray(o["Y"]) - T.astype(np.float64))
+    qt = float((dT / gT).max()); qs = abs(o["sigma2"] - float(s2)) / gS
+    k = f"{name} {'f64' if case['prec'] else 'f32'}"
+    a, b = WORST.get(k, (0.0, 0.0)); WORST[k] = (max(a, qt), max(b, qs))
+    print(f"{cid(case)} -> {name}: |dT| / gate {qt:.3g} (max |dT| {dT.max():.3g} m), |d sigma2| / gate {qs:.3g}")
+    assert qt <= 1.0, (cid(case), qt)
+    assert qs <= 1.0, (cid(case), qs)
+
+
+def test_zz_worst_per_kernel():
+    _report()
+
+
+# ---- decisions --------------------------------------------------------------------------------------------------------------------------------
+DEC = [_c("chain", "chain", 45, "typical"), _c("chain", "long", 513, "typical"), _c("band", "band", 45, "typical"), _c("dense", "dense", 45, "typical")]
+# (the dense LLE eliminations are not here: their gate on crit is half of crit itself -- see DROPPED)
+
+
+@pytest.mark.parametrize("case", DEC, ids=cid)
+def test_stopping_decision_and_refusals(ctx, case):
+    """tol at crit* (1 +- 1e-6) -- far above crit's gate -- gives done exactly as the reference; an exact sigma2 < 0 (Q lowered) and N_p = 0 (every P1
+    zero) end in TDLO_E_NUMERIC from end()."""
+    from trackdlo_amd import binding as B
+    c, X, Y0, priors = build_case(case, with_scene=True)
+    set_route(case["route"])
+    T, s2, crit = MR.reference(c)
+    _, _, gC = MR.gate(c, case["family"], T)
+    assert gC < 1e-7 * float(crit)
+    for f, want in ((1 + 1e-6, True), (1 - 1e-6, False)):
+        tol = float(crit) * f
+        rc, done, o, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=10, tol=tol), c.sums, priors, c.H)
+        assert MR.decision(float(crit), 1, tol, 10) == (want, True)
+        assert done == want, (cid(case), f, done)
+        if want:
+            assert rc == 0 and o["iters"] == 1 and o["converged"] is True
+    # sigma2 < 0: Q below what the residual form subtracts
+    M = c.M
+    d = T - c.y.astype(LD)
+    Rm = c.sums[M:4 * M].reshape(3, M).T; P1 = c.sums[:M]
+    q0 = LD(2) * (d * Rm).sum() - (P1[:, None] * d * d).sum()                          # Q at which sigma2 = 0
+    bad = c.sums.copy(); bad[4 * M] = q0 - LD(0.5) * abs(c.sums[4 * M] - q0)
+    rc, _, _, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), bad, priors, c.H)
+    assert rc == B.TDLO_E_NUMERIC, (cid(case), "sigma2 < 0", rc)
+    empty = c.sums.copy(); empty[:4 * M] = 0
+    rc, _, _, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), empty, priors, c.H)
+    assert rc == B.TDLO_E_NUMERIC, (cid(case), "N_p = 0", rc)
+
+
+HANDOVER_BAND = ["big_s2", "close"]
+
+
+def band_handover_case(regime):
+    """(case, mstep_ref.Case, X, Y0, priors): the band's M = 45 scene with sigma2 = 50 m2 (above band_s2_max) or two nodes 10 um apart (below the gap bound)."""
+    M = 45
+    case = _c("dense", "band", M, "typical")
+    c, X, Y0, priors = build_case(case, with_scene=True)
+    if regime == "big_s2":
+        c = MR.Case(c.sums, c.Y0, c.y, 50.0, **c.kw())
+    else:
+        Y0 = Y0.copy(); Y0[M // 2 + 1] = Y0[M // 2] + 1e-5
+        c = MR.Case(c.sums, Y0, Y0, c.s2, **dict(c.kw(), H=lle_H(Y0, "typical")))
+    return case, c, X, Y0, priors
+
+
+@pytest.mark.parametrize("regime", HANDOVER_BAND)
+def test_band_hands_over_to_the_dense_kernels(ctx, regime):
+    """A registration whose sigma2 is above band_s2_max (prepare_frame, fp64) or whose nodes are closer than the gap bound takes the dense pivoted
+    kernels -- and is held to the dense gate there (tests/test_mstep_ref.py: the restatement inside it; the dense LLE gate is not sharp, see DROPPED)."""
+    case, c, X, Y0, priors = band_handover_case(regime)
+    set_route("band")
+    rc, done, o, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), c.sums, priors, c.H)
+    name = ctx.profile_iteration(1)[3]
+    assert name == "k_mstep_fast<pivoted>", (regime, name)
+    assert rc == 0
+    T, s2, _ = MR.reference(c)
+    gT, gS, _ = MR.gate(c, "dense", T)
+    q = float((np.abs(np.asarray(o["Y"]) - T.astype(np.float64)) / gT).max())
+    print(f"band {regime}: {name}, |dT| / gate {q:.3g}")
+    assert q <= 1.0, (regime, q)
+
+
+# ---- the hand-over to the next E-step, and its resolution (IterState::sh_boost) ----------------------------------------------------------------
+HANDOVER = [("chain", 200, 1), ("chain", 300, 1), ("chain", 200, 0), ("long", 600, 1), ("band", 200, 1), ("band", 300, 1), ("band", 200, 0),
+            ("dense", 200, 1), ("dense", 300, 0), ("lle_dense", 200, 1)]
+
+
+@pytest.mark.parametrize("route,M,prec", HANDOVER, ids=[f"{r}-M{m}-{'f64' if p else 'f32'}" for r, m, p in HANDOVER])
+def test_next_estep_starts_from_the_mstep(ctx, route, M, prec):
+    """sigma2 = 1 m2 at the start on a chain of >= 3 m (the set-up grants no extra resolution), sums fabricated so that the M-step leaves sigma2 at 1e-4 m2:
+    the next E-step's sums must match the reference at the kernel's own (T, sigma2) and, in fp64 mode, carry the resolution set_iter_consts grants at
+    that sigma2 -- R x 2^sR integers, not all even (P1 is the control)."""
+    import test_estep_sums_gpu as ES
+    from trackdlo_amd import binding as B
+    case = _c("band" if route in ("band", "lle_dense") else ("dense" if route == "dense" else "chain"), route, M, "typical", prec=prec)
+    p = params_of(case)
+    X, Y0 = scene(M, 1700 + M)
+    assert R.chain_coord(Y0)[-1] >= 3.0
+    N0 = len(X)
+    r = R.estep(X, Y0, Y0, 1e-4, mu=p["mu"])
+    H = lle_H(Y0, "typical") if p["lle"] else None
+    c = MR.Case(r["sums"], Y0, Y0, 1.0, beta=p["beta"], lambda_=p["lambda_"], lle_weight=p["lle_weight"] if p["lle"] else 0.0, H=H)
+    T, _, _ = MR.reference(c)
+    d = T - c.y.astype(LD)
+    P1 = c.sums[:M]; Rm = c.sums[M:4 * M].reshape(3, M).T
+    s = c.sums.copy()
+    s[4 * M] = LD(3) * P1.sum() * LD(1e-4) + LD(2) * (d * Rm).sum() - (P1[:, None] * d * d).sum()        # sigma2_new = 1e-4 (fabricated_move's identity)
+    set_route(route)
+    prm = make_params(case, max_iter=10)
+    rc, done, o, _ = run_mstep(ctx, X, Y0, 1.0, prm, s, None, H)
+    assert rc == 0 and not done
+    name = ctx.profile_iteration(1)[3]
+    assert name == expected_kernel(route, M), name          # (the band: sigma2 = 1 is below band_s2_max for these chains)
+    Yk, s2k = np.asarray(o["Y"]), o["sigma2"]
+    assert abs(s2k - 1e-4) < 1e-6
+    _, _, _, nxt = run_mstep(ctx, X, Y0, 1.0, prm, s, None, H, then_estep=True)
+    if prec == 1:       # the resolution sigma2 = 1e-4 is granted is finer than the set-up's at sigma2 = 1: a boost left at the set-up's value shows
+        assert ES.shifts(N0, Y0, 1, s2k, False)[1] > ES.shifts(N0, Y0, 1, 1.0, False)[1]
+    re = ES.reference(X, Y0, Yk, s2k, prec)
+    g = ES.gate(re, prec, N0, Y0)
+    w = ES.compare(nxt, re, g, f"{route}-M{M}")
+    msg = f"{route} M {M} ({name}) prec {prec}: next E-step worst {w:.3f} of the gate"
+    if prec == 1:
+        sP, sR, _ = ES.shifts(N0, Y0, 1, s2k, False)
+        for lab, v, sh in (("P1", nxt[:M], sP), ("R", nxt[M:4 * M], sR)):
+            k = np.ldexp(v, sh)
+            assert (k == np.round(k)).all(), (lab, "not integers at 2^-%d" % sh)
+            nz = k[k != 0]
+            odd = np.mod(nz, 2) != 0
+            assert odd.any(), f"{msg}: every {lab} x 2^{sh} is even -- the sums are coarser than the resolution sigma2 = {s2k:.3g} is granted"
+        msg += f", R resolved to 2^-{sR}"
+    print(msg)
+
+
+# ---- process-wide switches: in a child process ----------------------------------------------------------------------------------------------------
+CHILD = {"big": ("TDLO_MSTEP_BIG", "1wg", [_c("dense", "dense", 61, "typical"), _c("dense", "dense", 129, "typical")], "k_mstep_big")}
+
+
+def _child(which, out):
+    from trackdlo_amd import binding as B
+    ctx = B.Context(device=0, timing=False, max_points=16 * 1024, max_nodes=1024)
+    res = {}
+    try:
+        for i, case in enumerate(CHILD[which][2]):
+            c, X, Y0, priors = build_case(case, with_scene=True)
+            set_route(case["route"])
+            rc, done, o, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), c.sums, priors, c.H)
+            res[f"rc{i}"] = np.array([rc]); res[f"name{i}"] = np.array([ctx.profile_iteration(1)[3]])
+            if rc == 0:
+                res[f"Y{i}"] = np.asarray(o["Y"]); res[f"s{i}"] = np.array([o["sigma2"]])
+    finally:
+        ctx.close()
+    np.savez(out, **res)
+
+
+@pytest.mark.parametrize("which", sorted(CHILD))
+def test_process_wide_switches(tmp_path, which):
+    env_key, env_val, cs, kname = CHILD[which]
+    out = str(tmp_path / "m.npz")
+    e = dict(os.environ, **{env_key: env_val})
+    code = f"import sys; sys.path[:0] = [{HERE!r}, {os.path.dirname(HERE)!r}]; import test_mstep_sums_gpu as t; t._child({which!r}, {out!r})"
+    p = subprocess.run([sys.executable, "-c", code], env=e, cwd=os.path.dirname(HERE), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    z = np.load(out)
+    for i, case in enumerate(cs):
+        assert int(z[f"rc{i}"][0]) == 0, (which, cid(case))
+        assert str(z[f"name{i}"][0]) == kname, (which, cid(case), z[f"name{i}"][0])
+        c = build_case(case)
+        T, s2, _ = MR.reference(c)
+        gT, gS, _ = MR.gate(c, "dense", T)
+        q = float((np.abs(z[f"Y{i}"] - T.astype(np.float64)) / gT).max()); qs = abs(float(z[f"s{i}"][0]) - float(s2)) / gS
+        print(f"{which} {cid(case)} ({z[f'name{i}'][0]}): |dT| / gate {q:.3g}, |d sigma2| / gate {qs:.3g}")
+        assert q <= 1.0 and qs <= 1.0, (which, cid(case), q, qs)

@@ -286,18 +286,10 @@ template <int NT> __device__ __forceinline__ void acc_clear_other(const FrameDev
     for (int i = t; i < n; i += NT) z[i] = 0;
 }
 
-__device__ __forceinline__ void set_iter_consts(const FrameDev &f, IterState *st, double sigma2, double Nc) {
-    // c of trackdlo.cpp:300 (or c' of :378 when visibility weighting is active)
-    const double tp = 2.0 * M_PI * sigma2, rtp = ::sqrt(tp);
-    double c = tp * rtp * f.mu / (1.0 - f.mu);                 // (2 pi sigma2)^(3/2): one square root instead of pow() at the end of every M-step
-    c = f.vis_branch ? c / Nc : c * (double)f.M / Nc;
-    st->sigma2 = sigma2;
-    st->Nc = Nc;
-    st->k2 = -1.4426950408889634 / (2.0 * sigma2);
-    st->c_norm = c;
-    // the E-step's node window (FrameDev::win_e32): E / |k2| = E 2 ln2 sigma2
-    st->rwin32 = f.win_e32 * 1.3862943611198906 * sigma2;
-    st->rwin64 = f.win_e64 * 1.3862943611198906 * sigma2;
+// fp64 mode: the extra binary digits (IterState::sh_boost) of the fixed-point sums of the E-step that follows an iteration at sigma2.  Every M-step that
+// publishes a new sigma2 calls this -- set_iter_consts and the inline tails of k_mstep_chain (and k_batch_loop, which runs its body), k_mstep_chain_long and
+// k_mstep_band -- so that the resolution follows sigma on every route.
+__device__ __forceinline__ int acc_boost(const FrameDev &f, double sigma2) {
     // fp64 mode: the resolution of the fixed-point sums follows sigma.  FrameDev::acc_sh is sized for point-node distances up to twice the chain's
     // length (a wave's share of R_m = sum p (x - y_m) is bounded by 64 D); but a normalised membership times its distance is at most about
     // d_nearest + 0.61 sigma (p <= exp(-arc^2 / 2 sigma2), |x - y_m| <= d_nearest + arc), so once sigma is centimetres the shares are a hundredth of that
@@ -315,7 +307,22 @@ __device__ __forceinline__ void set_iter_consts(const FrameDev &f, IterState *st
         // under the boosted limits -- a real refusal, which the repeat with the coarse limits (acc_boost_off = 1, no boost at all) must clear
         if (f.acc_boost_off < 0) boost += 40;
     }
-    st->sh_boost = boost;
+    return boost;
+}
+
+__device__ __forceinline__ void set_iter_consts(const FrameDev &f, IterState *st, double sigma2, double Nc) {
+    // c of trackdlo.cpp:300 (or c' of :378 when visibility weighting is active)
+    const double tp = 2.0 * M_PI * sigma2, rtp = ::sqrt(tp);
+    double c = tp * rtp * f.mu / (1.0 - f.mu);                 // (2 pi sigma2)^(3/2): one square root instead of pow() at the end of every M-step
+    c = f.vis_branch ? c / Nc : c * (double)f.M / Nc;
+    st->sigma2 = sigma2;
+    st->Nc = Nc;
+    st->k2 = -1.4426950408889634 / (2.0 * sigma2);
+    st->c_norm = c;
+    // the E-step's node window (FrameDev::win_e32): E / |k2| = E 2 ln2 sigma2
+    st->rwin32 = f.win_e32 * 1.3862943611198906 * sigma2;
+    st->rwin64 = f.win_e64 * 1.3862943611198906 * sigma2;
+    st->sh_boost = acc_boost(f, sigma2);
 }
 
 

@@ -2366,10 +2366,10 @@ const char *mstep_kernel_name(const FrameDev *fh, int F) {
     if (any_lle && fh[0].lle_band) return "k_mstep_band";
     if (M <= 60 && !any_lle) return "k_mstep_fast<MFMA>";
     if (M > kChainLdsMaxNodes) return "k_mstep<1wg>";
-    if (!any_lle) return "k_mstep_mcu";
+    if (!any_lle) return mstep_mcu_enabled() ? "k_mstep_mcu" : "k_mstep_big";
     if (M <= 64) return "k_mstep_fast<pivoted>";
     if (M <= kLdsSolveMaxM) return "k_mstep<LDS>";
-    return "k_mstep_pivot_mcu";
+    return mstep_pivot_mcu_enabled() ? "k_mstep_pivot_mcu" : "k_mstep<1wg>";
 }
 
 // kind: 0 E-step, 1 dmin, 2 M-step (from the E-step's accumulators), 3 M-step export-only (split), 4 M-step from global sums (split),

@@ -269,6 +269,7 @@ size_t mstep_big_scratch_doubles(int M);
 // M-step with the LLE term for M > kLdsSolveMaxM: 16 rows per workgroup, partial pivoting across the workgroups
 hipError_t launch_mstep_pivot_mcu(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);
 bool mstep_pivot_mcu_enabled();
+bool mstep_mcu_enabled();          // TDLO_MSTEP_BIG=1wg: false (the dense M-step without the LLE term in one workgroup, k_mstep_big)
 // tdlo_mstep_chain.hip: M-step without the LLE term as a Kalman / Rauch-Tung-Striebel smoother along the chain, any M
 hipError_t launch_mstep_chain(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);
 void mstep_parity_hint(int iteration);          // (tdlo_mstep_chain.hip) the iteration this thread's next chain M-step launches belong to; -1: unknown

@@ -1039,7 +1039,7 @@ size_t mstep_big_scratch_doubles(int M) { const size_t Mp = ((size_t)M + 15) & ~
 
 // TDLO_MSTEP_BIG=1wg keeps the whole elimination in one workgroup (k_mstep_big, the comparator of the tests and of
 // scripts/gpu_c5.py); the export-only form of the N-split interface (from_sums == 2) has no elimination and stays there.
-static bool mcu_enabled() {
+bool mstep_mcu_enabled() {
     static const int on = [] { const char *e = getenv("TDLO_MSTEP_BIG"); return (e && e[0] == '1') ? 0 : 1; }();
     return on != 0;
 }
@@ -1071,7 +1071,7 @@ hipError_t launch_mstep_pivot_mcu(const FrameDev *fd, const FrameDev *fh, int F,
 hipError_t launch_mstep_big(const FrameDev *fd, const FrameDev *fh, int F, int from_sums, bool f64, hipStream_t s) {
     const int M = fh[0].M;
     hipError_t e;
-    if (from_sums != 2 && mcu_enabled()) {
+    if (from_sums != 2 && mstep_mcu_enabled()) {
         const size_t lds = mcu_lds_bytes(M);
         const dim3 grid((unsigned)((M + 15) >> 4), (unsigned)F);
         if (f64) {

@@ -14,6 +14,7 @@ cd $S
 /opt/rocm/bin/hipcc $F -c tdlo_estep2.hip -o $B/tdlo_estep2.o &
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-mfma-vgpr-form -c tdlo_mstep_big.hip -o $B/tdlo_mstep_big.o &
 /opt/rocm/bin/hipcc $F -c tdlo_mstep_chain.hip -o $B/tdlo_mstep_chain.o &
+/opt/rocm/bin/hipcc $F -c tdlo_iter_fused.hip -o $B/tdlo_iter_fused.o &
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-mfma-vgpr-form -c tdlo_mstep_band.hip -o $B/tdlo_mstep_band.o &
 /opt/rocm/bin/hipcc $F -c tdlo_cloud.hip -o $B/tdlo_cloud.o &
 /opt/rocm/bin/hipcc $F -c tdlo_reg.hip -o $B/tdlo_reg.o &

@@ -76,6 +76,7 @@ struct NodeCarve {
     size_t fdev, Yin, aJ, aYd, Hb, H, upload;      // fdev: the frame's descriptor travels at the head of the upload block (one frame per call)
     size_t Yout, st, readback;
     size_t ctr, Y, Y0, nodes, coord, G, chain, HG, HY0, dmin, sums, dbg, Ascr, acc, band, total;
+    size_t Yout2, st2, Y2, nodes2;                 // the second copies of result, state, Y and nodes of the loop with one launch per iteration (tdlo_iter_fused.hip)
     explicit NodeCarve(int M) {
         const size_t m = (size_t)M, mm = m * m;
         size_t o = 0;
@@ -86,8 +87,11 @@ struct NodeCarve {
         ctr = take(4); Y = take(3 * m); Y0 = take(3 * m); nodes = take(4 * m); coord = take(m);
         G = take(mm); chain = take(8 * (m + 1)); HG = take(mm); HY0 = take(3 * m); dmin = take(m); sums = take(4 * m + 2); dbg = take(64);
         Ascr = take(std::max((size_t)(M | 1) * (m + 3), mstep_big_scratch_doubles(M)));
-        acc = take((size_t)2 * kAccRows * (4 * m + 2));       // the E-step's fixed-point accumulators, two iteration parities
+        acc = take((size_t)3 * kAccRows * (4 * m + 2));       // the E-step's fixed-point accumulators: two iteration parities; the loop with one launch per iteration
+                                                              // (tdlo_iter_fused.hip) rotates over three buffers
         band = take(band_record_doubles(M));                  // column records of the banded LLE M-step
+        Yout2 = take(3 * m); st2 = take((sizeof(IterState) + 7) / 8);      // ([Yout | IterState] laid out as the read-back block is: host_publish)
+        Y2 = take(3 * m); nodes2 = take(4 * m);
         total = o;
     }
 };
@@ -283,6 +287,10 @@ struct tdlo_ctx {
     // fp64 E-step of chains beyond 64 nodes: batches whose node window is wide go lane = node (tdlo_estep_wide.h); TDLO_ESTEP_WIDE=0: thread = point throughout (comparator)
     int estep_wide_min = getenv("TDLO_ESTEP_WIDE") ? (atoi(getenv("TDLO_ESTEP_WIDE")) > 0 ? atoi(getenv("TDLO_ESTEP_WIDE")) : (1 << 30)) : kEstepWideMin;
     long long spin_calls = 0;             // registrations run that way (tdlo_debug_route_count 11)
+    // One launch per iteration (tdlo_iter_fused.hip: k_iter_fused = M-step ; next E-step) for the registrations fused_iter_eligible names.  TDLO_FUSED_ITER=0: never
+    // (the two-launch loop, the comparator); =1: also beyond the point count up to which it is the default; unset: by eligibility.
+    int fused_iter_mode = getenv("TDLO_FUSED_ITER") ? (atoi(getenv("TDLO_FUSED_ITER")) != 0 ? 1 : 0) : -1;
+    long long fused_calls = 0;            // registrations run that way (tdlo_debug_route_count 14)
     // A batch's whole fixed-length loop in ONE launch (k_batch_loop, tdlo_estep2.hip): tickets (iteration, frame, chunk) drawn by resident workgroups, the workgroup
     // that completes a frame's E-step runs its M-step.  Round 6 EXPERIMENT, OFF by default (TDLO_BATCH_PERSIST=1 switches it on): the same bits, but 5.1 ms
     // against 1.27 ms per C3 call.  A call whose loop kernel gives a wait up is repeated on the launch-per-step loop.
@@ -639,6 +647,18 @@ static void choose_acc_rows(const tdlo_ctx *c, FrameDev &f, bool merged) {
     if (!merged && !f.include_lle && !f.mstep_dense && f.M > kChunk && f.M <= kChainLdsMaxNodes && f.precision == TDLO_PREC_F64) r = 2;
     if (env == 2 || env == 4 || env == 8) r = env;
     f.acc_rows = r;
+}
+
+// The loop with one launch per iteration (tdlo_iter_fused.hip): ONE frame in fp32 mode on the chain M-step (no LLE term, TDLO_MSTEP not dense), 8 .. 64 nodes, no
+// visibility term (k_dmin would sit between the two halves), k_estep with the one-frame tile (not k_estep2), results through the mailbox, none of tracking_step's
+// short cuts -- and a cloud whose E-step has fewer waves than the GPU has SIMDs (65 536 points): there the E-step is a chain of latencies, and every workgroup
+// repeating the M-step costs no time; beyond, the E-step's workgroups take several batches each and the M-step in front of each is issue time (TDLO_FUSED_ITER=1
+// takes those too).  What run_frames adds: not a batch, not a paired / ahead / late-priors registration, not the spin-ahead experiment.
+constexpr int kFusedIterMaxPoints = 65536;
+static bool fused_iter_eligible(const tdlo_ctx *c, const FrameDev &f) {
+    return c->fused_iter_mode != 0 && f.precision == TDLO_PREC_F32 && !f.include_lle && !f.mstep_dense && f.M >= 8 && f.M <= kChunk && !f.vis_branch &&
+           f.estep2 == 0 && f.wide_tile != 0 && f.eb == 256 && f.max_iter > 0 && f.host_prog != nullptr && f.lle_next == nullptr && f.spec_flag == nullptr &&
+           f.late_aJ == nullptr && f.pair_sums == nullptr && f.xch_nranks == 0 && (c->fused_iter_mode == 1 || f.N0 <= kFusedIterMaxPoints);
 }
 
 static bool estep2_eligible(const tdlo_ctx *c, const FrameDev &f) {
@@ -1168,9 +1188,26 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         HIPCHK(c, hipStreamWaitEvent(c->stream2[0], c->evx[0], 0));
         ++c->spin_calls;
     }
+    // one launch per iteration (tdlo_iter_fused.hip): iteration k of the call is `M-step (k) ; E-step (k + 1)` in one kernel, behind a plain k_estep for
+    // iteration 0; the registration's last M-step is a k_mstep_chain on its own.  Launch k reads copy k & 1 of state / Y / Yout / nodes and writes the other one.
+    const bool fused_mode = !merged && F == 1 && !paired && !ahead && late == nullptr && c->pair.state == 0 && use_mbox && !spin_mode && !sums_first && !ahead_first &&
+                            fused_iter_eligible(c, c->fh[0]);
+    if (fused_mode) ++c->fused_calls;
+    auto fused_copy = [&](int k) {
+        FrameDev fc = c->fh[0];           // (as it stands now: host_report_it changes from chunk to chunk)
+        if (k & 1) { double *blk = nodeblk_used; fc.Yout = blk + nc.Yout2; fc.st = (IterState *)(blk + nc.st2); fc.Y = blk + nc.Y2; fc.nodes = blk + nc.nodes2; }
+        return fc;
+    };
     auto iterate = [&](int n) -> hipError_t {
         for (int it = 0; it < n; ++it) {
             ++enqueued;
+            if (fused_mode) {
+                const int k = enqueued - 1;
+                if (k == 0) TDLO_RET(launch_estep_only(fdp, c->fh.data(), 1, 0, s));
+                if (k + 1 < p->max_iter) TDLO_RET(launch_iter_fused(fused_copy(k), fused_copy(k + 1), k, s));
+                else TDLO_RET(launch_mstep_chain_close(fused_copy(k), k, s));
+                continue;
+            }
             if (spin_mode) {
                 Slot &sl = c->slots[slots[0]];
                 TDLO_RET(launch_iteration_spin(fdp, c->fh.data(), c->stream2[0], s, enqueued == 1, &sl.spin_ecount, &sl.spin_mtag));
@@ -2698,7 +2735,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 13) return -1;
+    if (!c || which < 0 || which > 14) return -1;
+    if (which == 14) return c->fused_calls;
     if (which == 13) return c->batch_loop_fallbacks;
     if (which == 12) return c->batch_loop_calls;
     if (which == 11) return c->spin_calls;

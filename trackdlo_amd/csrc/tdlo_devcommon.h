@@ -431,7 +431,9 @@ typedef double mfma_d4 __attribute__((ext_vector_type(4)));     // accumulator o
 // loads), stored to the host with plain stores, fenced at system scope, then the progress word goes out.
 static_assert(offsetof(IterState, N) == 72 && offsetof(IterState, it) == 76 && offsetof(IterState, done) == 80 && offsetof(IterState, status) == 88 &&
               sizeof(IterState) <= 13 * 8, "host_publish reads {N, it}, {done, converged}, {status, retry_pending} as 64-bit words");
-__device__ __forceinline__ void host_publish(const FrameDev &f, IterState *st, int lane, bool fresh) {
+// (ALT: the result block the state sits behind is Yalt -- the copy of FrameDev::Yout that the one-launch iteration's workgroup 0 has just written)
+template <bool ALT>
+__device__ __forceinline__ void host_publish_from(const FrameDev &f, const double *Yalt, IterState *st, int lane, bool fresh) {
     if (!f.host_prog) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // lane 0's stores to *st have been performed
     const unsigned long long *sw = (const unsigned long long *)st;
@@ -445,8 +447,8 @@ __device__ __forceinline__ void host_publish(const FrameDev &f, IterState *st, i
     it = __builtin_amdgcn_readfirstlane(it); done = __builtin_amdgcn_readfirstlane(done); status = __builtin_amdgcn_readfirstlane(status);
     if (!fresh && status == 0) return;
     if (done) {
-        const int n = 3 * f.M, so = (int)((const double *)st - f.Yout);
-        const unsigned long long *yo = (const unsigned long long *)f.Yout;
+        const int n = 3 * f.M, so = (int)((const double *)st - (ALT ? Yalt : f.Yout));
+        const unsigned long long *yo = (const unsigned long long *)(ALT ? Yalt : f.Yout);
         unsigned long long *ho = (unsigned long long *)f.host_out;
         for (int i = lane; i < n; i += 64) ho[i] = __hip_atomic_load(yo + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         constexpr int nst = (int)((sizeof(IterState) + 7) / 8);
@@ -457,6 +459,9 @@ __device__ __forceinline__ void host_publish(const FrameDev &f, IterState *st, i
         __hip_atomic_store(f.host_prog, ((unsigned long long)f.host_epoch << 32) | ((unsigned long long)(done ? 1u : 0u) << 31) | (unsigned)(it & 0x7fffffff),
                            __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+__device__ __forceinline__ void host_publish(const FrameDev &f, IterState *st, int lane, bool fresh) { host_publish_from<false>(f, nullptr, st, lane, fresh); }
+__device__ __forceinline__ void host_publish_at(const FrameDev &f, const double *Yout, IterState *st, int lane, bool fresh) { host_publish_from<true>(f, Yout, st, lane, fresh); }
 
 // ---- spin-ahead loop (FrameDev::spin_on): bounded wait of ONE thread for a word of `sync` to take a value (agent scope); false: 2 s passed
 __device__ __forceinline__ bool spin_wait_word(const unsigned *word, unsigned want) {

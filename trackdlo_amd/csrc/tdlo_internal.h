@@ -182,6 +182,11 @@ struct FrameDev {
     int acc_rows;
 };
 constexpr int kSpinWordM = 110, kSpinWordE = 111;
+// The loop with one launch per iteration (k_iter_fused): an E-step half that refuses a contribution (TDLO_E_NUMERIC) stores the registration's mailbox epoch in
+// a word of `sync` -- the state's copies are being written by its launch's workgroup 0 at that time, so the state itself is not the place -- and the M-step of
+// the NEXT launch, finding its own epoch there, ends the registration with that error, as the M-step behind a refusing k_estep does.  Two words, 112 and 113:
+// launch j writes word j & 1 and reads the other one, so that no workgroup reads a word that a workgroup of the same launch may be writing.
+constexpr int kFusedErrWord = 112;
 
 // Inbox layout in 64-bit words (R ranks, node capacity Mc); rank r writes the [r] entries of every peer's inbox:
 //   flags: init [R] | dmin [2][R] | sums [2][R]      (parity = iteration & 1)
@@ -272,6 +277,11 @@ bool mstep_pivot_mcu_enabled();
 bool mstep_mcu_enabled();          // TDLO_MSTEP_BIG=1wg: false (the dense M-step without the LLE term in one workgroup, k_mstep_big)
 // tdlo_mstep_chain.hip: M-step without the LLE term as a Kalman / Rauch-Tung-Striebel smoother along the chain, any M
 hipError_t launch_mstep_chain(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);
+// tdlo_iter_fused.hip: M-step (iteration) and E-step (iteration + 1) of one frame in ONE launch; fr / fw: the descriptor with the copies of state, Y, Yout and
+// nodes the launch reads / its workgroup 0 writes.  launch_mstep_chain_close: the k_mstep_chain that closes that loop, in place on f's copies
+hipError_t launch_iter_fused(const FrameDev &fr, const FrameDev &fw, int iteration, hipStream_t s);
+size_t iter_fused_lds_bytes(int M);
+hipError_t launch_mstep_chain_close(const FrameDev &f, int iteration, hipStream_t s);
 void mstep_parity_hint(int iteration);          // (tdlo_mstep_chain.hip) the iteration this thread's next chain M-step launches belong to; -1: unknown
 hipError_t launch_lle_band_debug(const double *Y_dev, int M, double *Hb_dev, hipStream_t s);      // test aid: the device form of lle_regulariser_band (tdlo_lle_dev.h), M <= 256
 bool mstep_chain_enabled();

@@ -1,0 +1,88 @@
+// tdlo_iter_fused.hip -- one launch per EM iteration of ONE frame: k_iter_fused = M-step (k) ; E-step (k + 1).
+//
+// The two-launch iteration (k_estep, then k_mstep_chain) is two chains of latency with a kernel boundary behind each: the M-step is one workgroup that waits a
+// memory round trip for the sums and one for its records, walks its recursion, and publishes nodes and state to memory so that the next launch's ~200 workgroups
+// can read them back -- behind a dependent dispatch.  Here EVERY workgroup of the E-step's grid runs the M-step itself: it is a deterministic function of integer
+// sums (64-bit fixed point), so all of them get the same bits, at one workgroup's latency, and then hold the new nodes and the E-step's constants in LDS when
+// their E-step part starts.  No workgroup waits for another one: the kernel boundary stays the only synchronisation, there is one per iteration instead of two,
+// and the workgroup's points are requested at the top of the kernel and arrive behind the whole M-step.
+//
+// Nothing a launch reads is written in that launch (its workgroups start at different times):
+//   * the iteration number comes with the launch (the host counts), never from the state;
+//   * state, Y, Yout and the nodes exist twice (the node block's `alt` copies): launch j reads copy j & 1, its workgroup 0 writes copy (j + 1) & 1;
+//   * the accumulators rotate over three buffers: launch j reads j % 3, adds into (j + 1) % 3, its workgroup 0 clears (j + 2) % 3 (the buffer launch j - 1 read);
+//   * an E-step half that refuses a contribution reports it in one of two words of `sync` (kFusedErrWord), the next launch reads that one.
+// The loop: k_estep (iteration 0, from the set-up's nodes) -> k_iter_fused x (iterations - 1) -> k_mstep_chain<.., CLOSE> (the last M-step; run_frames).
+// Both halves are the statements of the two-launch kernels (tdlo_mstep_chain_body.h with FUSE = 1, tdlo_estep_body.inc with FUSED): the same arithmetic in the
+// same order, so a registration's Y, sigma2 and iteration count are those of the two-launch loop bit for bit (tests/test_fused_iter_gpu.py).
+#include "tdlo_mstep_chain_body.h"
+#include "tdlo_estep_body.h"
+#include <hip/hip_ext.h>
+#include <type_traits>
+
+namespace tdlo {
+
+// what changes from launch to launch (the descriptor names the copies the launch READS)
+struct FusedLaunch {
+    IterState *st_w;            // the copies workgroup 0 writes
+    double *Y_w, *Yout_w;
+    void *nodes_w;
+    long long *acc_clr;         // the accumulator buffer workgroup 0 clears
+    int iteration;              // the M-step's iteration (0 = the registration's first)
+    int acc_r;                  // the buffer the M-step's sums are in; the E-step half adds into the next one
+    int err_r;                  // the error word the M-step half reads; the E-step half writes the other one
+};
+
+constexpr size_t kFusedStateBytes = 128;        // the LDS copy of the state between the two halves' regions
+static_assert(sizeof(IterState) <= kFusedStateBytes, "IterState outgrew its LDS slot");
+static size_t fused_estep_bytes(int M) { return (estep_lds_bytes<float, kCB>(M, true) + 15) & ~(size_t)15; }
+
+// LDS: [ the E-step's carve | state | the M-step's carve ] -- side by side, so that the M-step's tail can put the nodes where the E-step reads them
+// (a template on the E-step's precision, instantiated for float alone: the E-step's statements discard their fp64 parts as a template's `if constexpr` does)
+template <typename T>
+__global__ __launch_bounds__(kCB) void k_iter_fused(const FrameDev f0, const FusedLaunch a, const unsigned estep_bytes) {
+    constexpr int NCH = 1, EB = kCB;
+    constexpr bool VIS = false, SINGLE = true, FUSED = true;
+    const FrameDev &f = f0;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    EstepHand<T> h;
+    {
+        // this lane's first point: on its way while the M-step runs
+        h.x = 0; h.y = 0; h.z = 0;
+        const auto xs = TDLO_AS_GLOBAL(T, f.Xs);
+        const size_t ld = f.ldx;
+        const int n = ((int)blockIdx.x * (EB / 64) + (int)(threadIdx.x >> 6)) * 64 + (int)(threadIdx.x & 63);
+        if (n < f.N0) { h.x = xs[n]; h.y = xs[ld + n]; h.z = xs[2 * ld + n]; }     // N <= N0: always in bounds
+        ChainFused z;
+        z.iteration = a.iteration; z.err_r = a.err_r;
+        z.st_w = a.st_w; z.Y_w = a.Y_w; z.Yout_w = a.Yout_w; z.nodes_w = a.nodes_w; z.acc_clr = a.acc_clr;
+        z.stL = (IterState *)(smem + estep_bytes);
+        z.nodesL = smem;                        // (the head of the E-step's carve: nodesL)
+        z.go = false;
+        mstep_chain_run<T, true, false, false, false, kAccRows, true, 1>(f, 0, smem + estep_bytes + kFusedStateBytes, a.acc_r, &z);
+        if (!z.go) return;                      // (the registration is over: workgroup 0 has said so where it has to be said)
+        h.st = z.stL;
+        h.acc_buf = a.acc_r == 2 ? 0 : a.acc_r + 1;
+        h.err_w = a.err_r ^ 1;
+    }
+    const EstepHand<T> *const hand = &h;
+#include "tdlo_estep_body.inc"
+}
+
+size_t iter_fused_lds_bytes(int M) { return fused_estep_bytes(M) + kFusedStateBytes + ChainCarve(M).total * sizeof(double); }
+
+// fr: the descriptor with the copies launch `iteration` reads; fw: the one with the copies it writes
+hipError_t launch_iter_fused(const FrameDev &fr, const FrameDev &fw, int iteration, hipStream_t s) {
+    const int M = fr.M;
+    if (M > kChunk || fr.precision != TDLO_PREC_F32 || fr.vis_branch || fr.eb != kCB || !fr.wide_tile || fr.estep2) return hipErrorInvalidValue;
+    const size_t lds = iter_fused_lds_bytes(M);
+    if (lds > 64 * 1024) { const hipError_t e = hipFuncSetAttribute((const void *)k_iter_fused<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; }
+    FusedLaunch a;
+    a.st_w = fw.st; a.Y_w = fw.Y; a.Yout_w = fw.Yout; a.nodes_w = fw.nodes;
+    a.acc_clr = fr.acc + (size_t)((iteration + 2) % 3) * kAccRows * acc_stride(M);
+    a.iteration = iteration; a.acc_r = iteration % 3; a.err_r = (iteration + 1) & 1;
+    hipLaunchKernelGGL(k_iter_fused<float>, dim3(fr.nblkE), dim3(kCB), lds, s, fr, a, (unsigned)fused_estep_bytes(M));
+    return hipGetLastError();
+}
+
+}  // namespace tdlo

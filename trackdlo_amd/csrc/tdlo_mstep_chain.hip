@@ -60,13 +60,20 @@ namespace tdlo {
 extern thread_local hipEvent_t g_mstep_ev[2];       // tdlo_device.hip: start/stop events for the M-step dispatch (tdlo_profile_iteration)
 
 // (the body: tdlo_mstep_chain_body.h, mstep_chain_run)
-template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false>
+// CLOSE: the M-step that closes the loop with one launch per iteration (k_iter_fused; mstep_chain_run's FUSE 2): bits 8-9 of from_sums_in name the accumulator
+// buffer (0 .. 2), bit 10 the error word it reads
+template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false, bool CLOSE = false>
 __global__ __launch_bounds__(kCB) void k_mstep_chain(const FrameDev *__restrict__ frames, const FrameDev f0, int from_sums_in) {
-    const int from_sums = from_sums_in & 0xff, par_hint = (from_sums_in >> 8) & 1;          // (HINT: bit 8 carries the iteration's parity)
+    const int from_sums = from_sums_in & 0xff, par_hint = (from_sums_in >> 8) & (CLOSE ? 3 : 1);          // (HINT: bit 8 carries the iteration's parity)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // One wave walks a chain of dependent instructions.  In a batch the other stream groups' E-steps fill the same SIMDs with waves that always have
     // something to issue: at the default priority this wave takes its turn among them (C3: 10.0 us per M-step against 7.4 us with the GPU to itself)
     if (!SINGLE) __builtin_amdgcn_s_setprio(3);
+    if constexpr (CLOSE) {
+        ChainFused z;
+        z.err_r = (from_sums_in >> 10) & 1;
+        mstep_chain_run<T, SINGLE, XCH, TRK, SPIN, ROWS, HINT, 2>(f0, from_sums, smem, par_hint, &z);
+    } else
     mstep_chain_run<T, SINGLE, XCH, TRK, SPIN, ROWS, HINT>(SINGLE ? f0 : frames[blockIdx.x], from_sums, smem, par_hint);
 }
 
@@ -326,6 +333,17 @@ __global__ __launch_bounds__(kCB) void k_lle_band_debug(const double *__restrict
 hipError_t launch_lle_band_debug(const double *Y, int M, double *Hb, hipStream_t s) {
     if (M < 1 || M > 256) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_lle_band_debug, dim3(1), dim3(kCB), 0, s, Y, M, Hb);
+    return hipGetLastError();
+}
+
+// the M-step that closes the loop with one launch per iteration (tdlo_iter_fused.hip): f names the copies the loop's last launch wrote, iteration is its own
+hipError_t launch_mstep_chain_close(const FrameDev &f, int iteration, hipStream_t s) {
+    if (f.M > kChunk || f.precision != TDLO_PREC_F32) return hipErrorInvalidValue;
+    const size_t lds = mstep_chain_lds_bytes(f.M);
+    const hipError_t e = set_lds_c(k_mstep_chain<float, true, false, false, false, kAccRows, true, true>, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_mstep_chain<float, true, false, false, false, kAccRows, true, true>), dim3(1), dim3(kCB), lds, s, (const FrameDev *)nullptr, f,
+                       ((iteration % 3) << 8) | (((iteration + 1) & 1) << 10));
     return hipGetLastError();
 }
 

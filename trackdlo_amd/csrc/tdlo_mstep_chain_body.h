@@ -28,16 +28,16 @@ __device__ __forceinline__ double swap_add16(double x, double y) {      // rows 
     const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
     return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
+template <int CTRL> __device__ __forceinline__ double dpp_f64c(double v) {      // (tdlo_estep_wide.h has a dpp_f64 of its own: both bodies meet in tdlo_iter_fused.hip)
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_sum4(double a, double b, double c, double d) {
     double z = swap_add16(swap_add32(a, b), swap_add32(c, d));
-    z += dpp_f64<0x128>(z);      // row_ror:8
-    z += dpp_f64<0x124>(z);      // row_ror:4
-    z += dpp_f64<0x122>(z);      // row_ror:2
-    z += dpp_f64<0x121>(z);      // row_ror:1
+    z += dpp_f64c<0x128>(z);      // row_ror:8
+    z += dpp_f64c<0x124>(z);      // row_ror:4
+    z += dpp_f64c<0x122>(z);      // row_ror:2
+    z += dpp_f64c<0x121>(z);      // row_ror:1
     return z;
 }
 
@@ -101,8 +101,28 @@ struct ChainCarve {
 // runs on another stream -- everything but the sums is requested, then the kernel waits for the E-step's workgroups to have counted themselves in.
 // ROWS: how many replica rows of the accumulators the E-step in front used (FrameDev::acc_rows; the launcher instantiates 2 / 4 for the plain one-frame kernel)
 // HINT: the launch carries the iteration's parity (par_hint, 0 / 1): the sums are requested from that parity's rows alone, without waiting for the device's counter
-template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false>
-__device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums, char *smem, int par_hint = 0) {
+// FUSE: the loop with ONE launch per iteration (tdlo_iter_fused.hip; run_frames).  "Where the results go" is this policy, the arithmetic is the same statements:
+//   1  the M-step half of k_iter_fused.  EVERY workgroup of the launch runs it (the sums are integers: the same bits everywhere).  The iteration number
+//      comes with the launch (ChainFused::iteration), the sums from accumulator buffer par_hint (0 .. 2); the descriptor's st / Y / Yout / nodes are the copies
+//      the launch READS.  The new nodes go to the E-step's LDS copy, the new state to LDS (the E-step half reads both there); workgroup 0 alone writes memory
+//      -- the OTHER copies (st_w, Y_w, Yout_w, nodes_w), the accumulator buffer after next (acc_clr) and the mailbox: nothing a launch reads is written in it.
+//   2  the k_mstep_chain that closes that loop (one workgroup, in place on the copies its descriptor names): sums from buffer par_hint (0 .. 2), nothing cleared
+//      (the set-up kernel clears the buffers a registration starts with, the loop the third one).
+//   Both honour the loop's sticky error word (kFusedErrWord).
+struct ChainFused {
+    int iteration;                  // the M-step's iteration, counted by the host from the registration's first
+    int err_r;                      // which of the loop's two error words this launch READS (its E-step half writes the other one: kFusedErrWord); FUSE 2 sets this alone
+    IterState *st_w;                // workgroup 0: the copies the NEXT launch reads
+    double *Y_w, *Yout_w;
+    void *nodes_w;
+    long long *acc_clr;             // workgroup 0: the accumulator buffer the next launch's E-step half adds into, cleared here
+    IterState *stL;                 // LDS: the state this M-step leaves (every workgroup)
+    void *nodesL;                   // LDS: the E-step half's node copy (every workgroup)
+    bool go;                        // out: the registration goes on -- the E-step half runs
+};
+template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false, int FUSE = 0>
+__device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums, char *smem, int par_hint = 0, ChainFused *fz = nullptr) {
+    static_assert(FUSE == 0 || (SINGLE && HINT && !XCH && !TRK && !SPIN), "the one-launch iteration: one frame, told its accumulator buffer, no exchange / tracker extras");
     constexpr int MB = kCB;
     // One wave walks a chain of dependent instructions.  In a batch the other stream groups' E-steps fill the same SIMDs with waves that always have
     // something to issue: at the default priority this wave takes its turn among them (C3: 10.0 us per M-step against 7.4 us with the GPU to itself)
@@ -133,7 +153,9 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         asm volatile("" :: "s"(p0), "s"(p1), "s"(p2), "s"(p3), "s"(p4), "s"(p5), "s"(p6));
     }
     const auto stg = TDLO_AS_GLOBAL(IterState, st);
-    const int done = stg->done;
+    // (FUSE: an E-step half that refused a contribution has left the registration's epoch in the loop's error word)
+    const bool err_w = FUSE != 0 && TDLO_AS_GLOBAL(unsigned, f.sync)[kFusedErrWord + (FUSE != 0 ? fz->err_r : 0)] == f.host_epoch;
+    const int done = FUSE != 0 ? (stg->done | (err_w ? 1 : 0)) : stg->done;
     const double sigma2 = stg->sigma2;
     const int pri = f.has_priors;
     const double ctr0 = f.ctr[0], ctr1 = f.ctr[1], ctr2 = f.ctr[2];
@@ -182,7 +204,10 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     // for the iteration counter (M <= 512: at most 9 elements per thread).  Requested before the slot: its index arithmetic
     // runs while these are in flight.
     const bool spec_wait = TRK && f.spec_flag != nullptr;      // launched ahead of its priors (FrameDev::spec_flag): the wait sits behind the requests below
-    const int itn = stg->it;
+    const int itn = FUSE == 1 ? fz->iteration : stg->it;
+    if constexpr (FUSE == 1) {      // the state this launch reads, whole, into the LDS copy: the tail below replaces what an M-step sets, the rest is carried
+        if (t < (int)((sizeof(IterState) + 7) / 8)) ((unsigned long long *)fz->stL)[t] = TDLO_AS_GLOBAL(unsigned long long, st)[t];
+    }
     double sq[9];
     SlotQ q0;
     bool spin_lost = false;
@@ -314,6 +339,30 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
 #ifdef TDLO_TIMELINE      // wall-clock (100 MHz) begin / end of iterations 20..27, scripts/gpu_timeline.py
     if (t == 0 && itn >= 20 && itn < 28) f.dbg[4 * (itn - 20) + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
+    if constexpr (FUSE == 1) {
+        if (done) {
+            // a finished registration: the launch is a no-op but for workgroup 0, which passes state and result on to the copies the next launch reads
+            // (the error word's verdict written into them) and reports a registration that ended on an error, as the two-launch M-step does
+            fz->go = false;
+            if (blockIdx.x != 0) return;
+            for (int i = t; i < 3 * M; i += MB) fz->Yout_w[i] = f.Yout[i];
+            __syncthreads();
+            if (t < 64) {
+                constexpr int nst = (int)((sizeof(IterState) + 7) / 8);
+                if (lane < nst) ((unsigned long long *)fz->st_w)[lane] = TDLO_AS_GLOBAL(unsigned long long, st)[lane];
+                const bool err_new = err_w && stg->done == 0;
+                if (err_new && lane == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); fz->st_w->status = TDLO_E_NUMERIC; fz->st_w->converged = 0; fz->st_w->done = 1; }
+                if (stg->status != 0 || err_new) host_publish_at(f, fz->Yout_w, fz->st_w, lane, false);
+            }
+            return;
+        }
+        fz->go = true;
+    }
+    if (FUSE == 2 && err_w && stg->done == 0) {
+        if (t == 0) { st->status = TDLO_E_NUMERIC; st->converged = 0; st->done = 1; }
+        if (t < 64) host_publish(f, st, lane, false);
+        return;
+    }
     if (done) {
         if (XCH && from_sums == 3) xch_post_error(f, st, t);
         spin_report();
@@ -321,7 +370,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         return;
     }
     CSTAMP(1);
-    if (HINT && from_sums != 1 && (itn & 1) != par_hint) {
+    if (HINT && FUSE == 0 && from_sums != 1 && (itn & 1) != par_hint) {
         // the host's count of the iterations it has enqueued and the device's counter disagree (a registration continued by a caller that did not say so):
         // the sums are read again, the ordinary way.  Never seen in the tests' routes; kept so that the hint can only cost time, never a result.
 #pragma unroll
@@ -523,6 +572,10 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (wr) *(dbl2 *)(red + 32 + 2 * (dir * 5 + hl)) = dbl2{acc0, acc1};
     } else {
         // waves 2 and 3 have nothing to do in this phase: they clear the other parity's accumulator rows for the next E-step
+        if constexpr (FUSE == 1) {
+            if (blockIdx.x == 0) { const int n = kAccRows * acc_stride(M); for (int i = t - 128; i < n; i += MB - 128) fz->acc_clr[i] = 0; }
+        } else if constexpr (FUSE == 2) {
+        } else
         if (from_sums != 1) acc_clear_other<MB - 128>(f, itn, t - 128);
         if (wv == 2) {
             // ... and wave 2 prepares what the junction solve (4., below) needs of the covariances alone, while the means finish:
@@ -795,10 +848,20 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         }
         s_np += p1; s_dr += dr; s_pd += p1 * pd2; s_cr += ::sqrt(cr2);
         V4<T> w; w.x = (T)Td[0]; w.y = (T)Td[1]; w.z = (T)Td[2]; w.w = (T)q.w;      // .w = chain coordinate, unchanged
+        if constexpr (FUSE == 1) {
+            ((V4<T> *)fz->nodesL)[m] = w;
+            if (blockIdx.x == 0) {
+                ((V4<T> *)fz->nodes_w)[m] = w;
+                f.dminbits[m] = ~0ull;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) { fz->Y_w[d * M + m] = Td[d]; fz->Yout_w[d * M + m] = Td[d] + (d == 0 ? ctr0 : (d == 1 ? ctr1 : ctr2)); }
+            }
+        } else {
         nodes_w[m] = w;
         f.dminbits[m] = ~0ull;
 #pragma unroll
         for (int d = 0; d < 3; ++d) { f.Y[d * M + m] = Td[d]; f.Yout[d * M + m] = Td[d] + (d == 0 ? ctr0 : (d == 1 ? ctr1 : ctr2)); }
+        }
     }
     // the wave's four sums at once (wave_sum4: 21 instructions, no LDS round trips); rows 0..3 of the wave end up with sums 0, 2, 1, 3
     // (waves without slots contribute zeros)
@@ -810,6 +873,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     }
     __syncthreads();
     CSTAMP(7);
+    IterState *const sto = FUSE == 1 ? fz->stL : st;      // (FUSE 1: every workgroup forms the new state, in LDS; workgroup 0 stores it below)
     int pub = 0;        // lane 0: this M-step has something to tell the host (results mailbox, FrameDev::host_prog)
     if (t == 0) {
         const double t_np = ((red[0] + red[4]) + red[8]) + red[12], t_dr = ((red[1] + red[5]) + red[9]) + red[13];
@@ -817,22 +881,32 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         const double new_sigma2 = (S[4 * M] - 2.0 * t_dr + t_pd) * fast_rcp(t_np * 3.0);
         const double crit = t_cr / (double)M;
         const int it = itn + 1;
-        st->it = it; st->crit = crit; st->Np = t_np;
+        sto->it = it; sto->crit = crit; sto->Np = t_np;
         const bool finite_ok = (new_sigma2 == new_sigma2) && (fabs(new_sigma2) < 1e300) && (new_sigma2 > 0) && (crit == crit);
-        st->sigma2 = new_sigma2;
+        sto->sigma2 = new_sigma2;
         if (finite_ok) {        // set_iter_consts with the sigma2-independent factor formed up front
             const double tp = 2.0 * M_PI * new_sigma2, rtp = ::sqrt(tp);
-            st->k2 = -1.4426950408889634 * 0.5 * fast_rcp(new_sigma2);
-            st->c_norm = tp * rtp * kc;
-            st->rwin32 = f.win_e32 * 1.3862943611198906 * new_sigma2; st->rwin64 = f.win_e64 * 1.3862943611198906 * new_sigma2;      // the E-step's node window (set_iter_consts)
-            st->sh_boost = acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts)
-        } else { st->status = TDLO_E_NUMERIC; st->done = 1; st->converged = 0; pub = 1; }
-        if (crit < f.tol) { st->done = 1; pub = 1; }                                   // :424-428
-        else if (it >= f.max_iter) { st->converged = 0; st->done = 1; pub = 1; }      // :433-437
+            sto->k2 = -1.4426950408889634 * 0.5 * fast_rcp(new_sigma2);
+            sto->c_norm = tp * rtp * kc;
+            sto->rwin32 = f.win_e32 * 1.3862943611198906 * new_sigma2; sto->rwin64 = f.win_e64 * 1.3862943611198906 * new_sigma2;      // the E-step's node window (set_iter_consts)
+            sto->sh_boost = acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts)
+        } else { sto->status = TDLO_E_NUMERIC; sto->done = 1; sto->converged = 0; pub = 1; }
+        if (crit < f.tol) { sto->done = 1; pub = 1; }                                   // :424-428
+        else if (it >= f.max_iter) { sto->converged = 0; sto->done = 1; pub = 1; }      // :433-437
         if (it == f.host_report_it) pub = 1;      // the host looks at the progress word after this iteration (the last one of an early-exit polling chunk)
 #ifdef TDLO_TIMELINE
         if (itn >= 20 && itn < 28) f.dbg[4 * (itn - 20) + 3] = __builtin_amdgcn_s_memrealtime();
 #endif
+    }
+    if constexpr (FUSE == 1) {
+        __syncthreads();          // the state in LDS is whole: the E-step half reads it, workgroup 0 sends it to memory -- and the registration may have ended here
+        fz->go = fz->stL->done == 0;
+        if (blockIdx.x == 0 && t < 64) {
+            constexpr int nst = (int)((sizeof(IterState) + 7) / 8);
+            if (lane < nst) ((unsigned long long *)fz->st_w)[lane] = ((const unsigned long long *)fz->stL)[lane];
+            if (__builtin_amdgcn_readfirstlane(pub)) host_publish_at(f, fz->Yout_w, fz->st_w, lane, true);
+        }
+        return;
     }
     spin_report();
     if (!XCH && t < 64 && __builtin_amdgcn_readfirstlane(pub)) host_publish(f, st, lane, true);      // progress (and, from the M-step that finishes the registration, the results) into pinned host memory

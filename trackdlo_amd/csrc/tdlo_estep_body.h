@@ -16,6 +16,7 @@ template <typename T> struct EstepHand {
     const IterState *st;        // LDS: the state the M-step half has just formed (N, k2, c_norm, sh_boost, rwin32); the nodes are in the E-step's LDS copy already
     int acc_buf;                // which of the accumulator buffers this E-step adds into
     int err_w;                  // which of the loop's two error words (kFusedErrWord) a refused contribution is reported in
+    int acc_rows;               // acc_rows_used(f), taken from the kernel's first batch of arguments (k_iter_fused)
 };
 
 // dynamic LDS of the E-step's statements (the carve at their head)

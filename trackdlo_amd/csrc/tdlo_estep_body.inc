@@ -609,7 +609,7 @@
     }
     __syncthreads();
     ESTAMP(6);
-    long long *arow = f.acc + ((size_t)(EARLY ? par_e : (TDLO_AS_GLOBAL(IterState, f.st)->it & 1)) * kAccRows + (blockIdx.x & (acc_rows_used(f) - 1))) * acc_stride(M);
+    long long *arow = f.acc + ((size_t)(EARLY ? par_e : (TDLO_AS_GLOBAL(IterState, f.st)->it & 1)) * kAccRows + (blockIdx.x & ((FUSED ? hand->acc_rows : acc_rows_used(f)) - 1))) * acc_stride(M);
     {
         const long long *accAll = (const long long *)(scratch + 16);
         for (int i = tid; i < 4 * M; i += EB) {

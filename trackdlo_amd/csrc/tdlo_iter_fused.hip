@@ -47,6 +47,17 @@ __global__ __launch_bounds__(kCB) void k_iter_fused(const FrameDev f0, const Fus
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EstepHand<T> h;
     {
+        // Every kernel-argument word that an address of the M-step half's prologue is formed from, asked for HERE, in the kernel's first scalar batch (the
+        // descriptor is 0x2d8 bytes of kernel arguments: left to the compiler the words come in six batches, each waited for where it is first used --
+        // between the requests for the state, the sums and the slot)
+        const void *p0 = f.Xs, *p1 = f.st, *p2 = f.chain, *p3 = f.nodes, *p4 = f.Y, *p5 = f.Y0, *p6 = f.aJ, *p7 = f.aYd, *p8 = f.acc, *p9 = f.sync, *p10 = f.ctr;
+        asm volatile("" :: "s"(p0), "s"(p1), "s"(p2), "s"(p3), "s"(p4), "s"(p5), "s"(p6), "s"(p7), "s"(p8), "s"(p9), "s"(p10),
+                     "s"(f.N0), "s"(f.M), "s"(f.ldx), "s"(f.has_priors), "s"(f.host_epoch), "s"(f.acc_sh[0]), "s"(f.acc_sh[1]), "s"(f.acc_sh[2]),
+                     "s"(a.acc_r), "s"(a.err_r), "s"(estep_bytes));
+        // (the one word the E-step half alone needs that the compiler otherwise fetches, waits for and sets aside in the middle of the M-step's requests:
+        //  as a value it has to keep)
+        h.acc_rows = acc_rows_used(f);
+        asm volatile("" : "+s"(h.acc_rows));
         // this lane's first point: on its way while the M-step runs
         h.x = 0; h.y = 0; h.z = 0;
         const auto xs = TDLO_AS_GLOBAL(T, f.Xs);
@@ -61,6 +72,7 @@ __global__ __launch_bounds__(kCB) void k_iter_fused(const FrameDev f0, const Fus
         z.go = false;
         mstep_chain_run<T, true, false, false, false, kAccRows, true, 1>(f, 0, smem + estep_bytes + kFusedStateBytes, a.acc_r, &z);
         if (!z.go) return;                      // (the registration is over: workgroup 0 has said so where it has to be said)
+        asm volatile("" :: "s"(__builtin_amdgcn_kernarg_segment_ptr()));
         h.st = z.stL;
         h.acc_buf = a.acc_r == 2 ? 0 : a.acc_r + 1;
         h.err_w = a.err_r ^ 1;

@@ -138,9 +138,10 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     double *S = (double *)smem + cv.S, *red = (double *)smem + cv.red, *dump = (double *)smem + cv.dump, *slots = (double *)smem + cv.slots;
 
     // phase stamps (scripts/gpu_stamps.py, tdlo_debug_stamps) only in a -DTDLO_CHAIN_STAMPS build (scripts/build_variant.sh stamps ...): each one is an
-    // s_memtime behind a full lgkmcnt wait plus a store behind an exec branch, eight of them per launch
+    // s_memtime behind a full lgkmcnt wait plus a store behind an exec branch, eight of them per launch.  The M-step half of k_iter_fused (FUSE 1) stamps in
+    // workgroup 0 alone and into words 56 .. 63, which the k_mstep_chain that closes its loop does not overwrite (scripts/gpu_fused_stamps.py)
 #ifdef TDLO_CHAIN_STAMPS
-#define CSTAMP(i) do { if (t == 0) f.dbg[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#define CSTAMP(i) do { if (t == 0 && (FUSE != 1 || blockIdx.x == 0)) f.dbg[(FUSE == 1 ? 56 : 0) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CSTAMP(i) do { } while (0)
 #endif
@@ -157,7 +158,10 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     const bool err_w = FUSE != 0 && TDLO_AS_GLOBAL(unsigned, f.sync)[kFusedErrWord + (FUSE != 0 ? fz->err_r : 0)] == f.host_epoch;
     const int done = FUSE != 0 ? (stg->done | (err_w ? 1 : 0)) : stg->done;
     const double sigma2 = stg->sigma2;
-    const int pri = f.has_priors;
+    int pri = f.has_priors;
+    // (FUSE 1: the word as a value the compiler has to KEEP -- a kernel argument it would rather fetch again where the slot's requests branch on it, with a
+    //  wait of its own in the middle of them: the kernel is short of scalar registers)
+    if constexpr (FUSE == 1) asm volatile("" : "+s"(pri));
     const double ctr0 = f.ctr[0], ctr1 = f.ctr[1], ctr2 = f.ctr[2];
     const auto ndg = TDLO_AS_GLOBAL(V4<T>, f.nodes);
     const auto Yg = TDLO_AS_GLOBAL(double, f.Y);
@@ -205,11 +209,20 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     // runs while these are in flight.
     const bool spec_wait = TRK && f.spec_flag != nullptr;      // launched ahead of its priors (FrameDev::spec_flag): the wait sits behind the requests below
     const int itn = FUSE == 1 ? fz->iteration : stg->it;
-    if constexpr (FUSE == 1) {      // the state this launch reads, whole, into the LDS copy: the tail below replaces what an M-step sets, the rest is carried
-        if (t < (int)((sizeof(IterState) + 7) / 8)) ((unsigned long long *)fz->stL)[t] = TDLO_AS_GLOBAL(unsigned long long, st)[t];
-    }
+    // FUSE 1: the state this launch reads, whole, for the LDS copy (the tail below replaces what an M-step sets, the rest is carried).  Requested here into a
+    // register -- index clamped, no branch -- and stored to LDS behind the last request below: a store inside `if (t < 13)` at this place is a full wait for
+    // wave 0's loads so far, one memory round trip before the sums have even been asked for.
+    constexpr int kStWords = (int)((sizeof(IterState) + 7) / 8);
+    unsigned long long st_word = 0;
+    if constexpr (FUSE == 1) st_word = TDLO_AS_GLOBAL(unsigned long long, st)[t < kStWords ? t : kStWords - 1];
     double sq[9];
     SlotQ q0;
+    // FUSE 1: the sums' rows as the integers they are, converted behind the last request (fused_sum below).  acc_read_par converts on the spot, and its shift
+    // reads IterState::sh_boost: a load whose value the compiler wants in a scalar register, i.e. a wait in front of the slot's requests.  The word is not
+    // read here at all: the one-launch loop runs in fp32 mode only (launch_iter_fused refuses anything else), where acc_boost() is 0 by construction in
+    // every kernel that sets it (k_setup's set_iter_consts, every M-step's tail) -- the shift is FrameDev::acc_sh alone, the same bits.
+    long long fr0[ROWS], fr1[ROWS];
+    const int fi0 = t < nS ? t : nS - 1, fi1 = t + MB < nS ? t + MB : nS - 1;
     bool spin_lost = false;
     if (SPIN) {
         // (up to 63 nodes: one element per thread.)  The slot -- links, the node, Y0, Y -- is requested first: nothing of it comes from this iteration's
@@ -225,6 +238,21 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     } else {
     // (the first element without a branch -- index clamped, the accumulators exist in every mode: inside a conditional block the compiler sums the
     //  16 rows on the spot, i.e. waits for them BEFORE it requests the slot below: two memory round trips in a row instead of one)
+    if constexpr (FUSE == 1) {
+        const auto rows = TDLO_AS_GLOBAL(long long, f.acc) + (size_t)par_hint * kAccRows * acc_stride(M);
+        const int stride = acc_stride(M);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) fr0[r] = rows[(size_t)r * stride + fi0];
+        // (chains of 64 nodes: a second element per thread, its rows in the same batch -- a uniform branch around requests alone, nothing is summed in it)
+        if (nS > MB) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) fr1[r] = rows[(size_t)r * stride + fi1];
+        } else {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) fr1[r] = 0;
+        }
+        sq[0] = 0.0;
+    } else
     sq[0] = HINT ? acc_read_par<ROWS>(f, t < nS ? t : nS - 1, par_hint) : acc_read_both<ROWS>(f, t < nS ? t : nS - 1, itn);
 #pragma unroll
     for (int u = 1; u < 9; ++u) sq[u] = 0.0;
@@ -241,7 +269,9 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (t < 64) host_publish(f, st, lane, false);
         return;
     }
-    if (SPIN) {
+    if constexpr (FUSE == 1) {         // (at most 64 nodes, launch_iter_fused: every slot is a thread's first one)
+        q0 = load_slot(t, true);
+    } else if (SPIN) {
     } else if (nS <= MB) {             // up to 63 nodes: the slot's loads follow the sums' in the same basic block (nothing is waited for in between)
         q0 = load_slot(t, !spec_wait);
     } else {                    // longer chains: the further elements first (with the slot's forty registers live the compiler requests their
@@ -329,12 +359,34 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
 #pragma unroll
         for (int u = 0; u < 4; ++u) { const int i = t + u * MB, ic = i < 4 * M ? i : 4 * M - 1; kq[u] = ic < M ? aJg[ic] : aYg[ic - M]; }
     }
-    const double pinf0 = chg[0].x, pinf1 = chg[0].y;  // sf2, s^2 sf2
+    dbl2 ch0 = dbl2{0.0, 0.0}, ch1 = dbl2{0.0, 0.0};
+    double Nc_f = 0.0;
+    if constexpr (FUSE == 1) {
+        ch0 = chg[0]; ch1 = chg[1]; Nc_f = stg->Nc;      // (the last three requests: below they are made where they are first used)
+        // Everything this half reads before its first barrier has been requested: ONE memory round trip.  The marker is a compiler barrier for memory
+        // operations (no request moves behind it, the LDS stores below do not move in front of it) and the line tests/test_fused_prologue_isa.py looks for:
+        // no s_waitcnt vmcnt stands between the kernel's first vector load and this line.
+        asm volatile("; TDLO_FUSED_PROLOGUE_REQUESTED" ::: "memory");
+        asm volatile("" :: "s"(__builtin_amdgcn_kernarg_segment_ptr()));
+        auto fused_sum = [&](const long long (&rw)[ROWS], int i) __attribute__((always_inline)) {
+            long long a = 0;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) a += rw[r];
+            // (the element's exponent by two independent selects against zero: a select chain over f.acc_sh[...] itself becomes a vector load from the
+            //  kernel-argument block at a selected address, or a table in scratch memory)
+            const int sh = f.acc_sh[0] + (i >= M ? f.acc_sh[1] - f.acc_sh[0] : 0) + (i >= 4 * M ? f.acc_sh[2] - f.acc_sh[1] : 0);
+            return ::ldexp((double)a, -sh);
+        };
+        sq[0] = fused_sum(fr0, fi0);
+        if (t + MB < nS) sq[1] = fused_sum(fr1, fi1);
+        if (t < kStWords) ((unsigned long long *)fz->stL)[t] = st_word;
+    }
+    const double pinf0 = FUSE == 1 ? ch0.x : chg[0].x, pinf1 = FUSE == 1 ? ch0.y : chg[0].y;  // sf2, s^2 sf2
     const double c2 = f.lambda * sigma2, rc2 = fast_rcp(c2);
-    const double cp0 = c2 * chg[1].x, cp1 = c2 * chg[1].y;  // Pinf^-1 in the units of the filter (P = covariance / c); reciprocals from k_setup
+    const double cp0 = c2 * (FUSE == 1 ? ch1.x : chg[1].x), cp1 = c2 * (FUSE == 1 ? ch1.y : chg[1].y);  // Pinf^-1 in the units of the filter (P = covariance / c); reciprocals from k_setup
     // what the kernel's last thread needs of set_iter_consts, formed while the loads are in flight: c of :300 / c' of :378 is
     // (2 pi sigma2)^(3/2) times this factor
-    const double Nc = stg->Nc;
+    const double Nc = FUSE == 1 ? Nc_f : stg->Nc;
     const double kc = f.mu / (1.0 - f.mu) * (f.vis_branch ? 1.0 / Nc : (double)M / Nc);
 #ifdef TDLO_TIMELINE      // wall-clock (100 MHz) begin / end of iterations 20..27, scripts/gpu_timeline.py
     if (t == 0 && itn >= 20 && itn < 28) f.dbg[4 * (itn - 20) + 2] = __builtin_amdgcn_s_memrealtime();
@@ -377,8 +429,9 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         for (int u = 0; u < 9; ++u) { const int i = t + u * MB; if (i < nS) sq[u] = acc_read_both<ROWS>(f, i, itn); }
     }
     if (from_sums != 1) {
+        constexpr int nU = FUSE == 1 ? 2 : 9;       // (FUSE 1: at most 64 nodes, two elements per thread)
 #pragma unroll
-        for (int u = 0; u < 9; ++u) { const int i = t + u * MB; if (i < nS) S[i] = sq[u]; }
+        for (int u = 0; u < nU; ++u) { const int i = t + u * MB; if (i < nS) S[i] = sq[u]; }
     } else {
         const auto sums = TDLO_AS_GLOBAL(double, f.sums);
         if (TRK) {
@@ -889,7 +942,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
             sto->k2 = -1.4426950408889634 * 0.5 * fast_rcp(new_sigma2);
             sto->c_norm = tp * rtp * kc;
             sto->rwin32 = f.win_e32 * 1.3862943611198906 * new_sigma2; sto->rwin64 = f.win_e64 * 1.3862943611198906 * new_sigma2;      // the E-step's node window (set_iter_consts)
-            sto->sh_boost = acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts)
+            sto->sh_boost = FUSE == 1 ? 0 : acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts; FUSE 1 is fp32 mode: 0, see the prologue)
         } else { sto->status = TDLO_E_NUMERIC; sto->done = 1; sto->converged = 0; pub = 1; }
         if (crit < f.tol) { sto->done = 1; pub = 1; }                                   // :424-428
         else if (it >= f.max_iter) { sto->converged = 0; sto->done = 1; pub = 1; }      // :433-437

@@ -525,9 +525,30 @@ int tdlo_set_xch_self(tdlo_ctx *ctx, int on);
 /* The PCI bus id of the context's GPU ("0000:c1:00.0"; out needs >= 16 bytes): which /sys/bus/pci/devices/<id> node -- clocks, power, busy percentage --
  * belongs to it (bench.py's clock sampler: the container's /sys/class/drm lists every card of the host, not only the visible one). */
 int tdlo_pci_bus_id(tdlo_ctx *ctx, char *out, int len);
-/* Development aid: copies the pruned, centred, node-sorted cloud of the last call (N x 3 column-major, widened to
- * double) and the centring offset; returns N. */
-int tdlo_debug_read_cloud(tdlo_ctx *ctx, int slot, double *out, int max_points, double *ctr);
+/* Development aid: copies the pruned, centred, node-sorted cloud of FRAME `frame` OF THE LAST CALL (N x 3 column-major, widened to
+ * double) and that frame's centring offset; returns N.  The last call's frame list has one entry per frame of that call: frame i of a
+ * tdlo_cpd_lle_batch, and exactly frame 0 of a single registration whatever slot it ran on.  TDLO_E_INVALID beyond the list (or N > max_points). */
+int tdlo_debug_read_cloud(tdlo_ctx *ctx, int frame, double *out, int max_points, double *ctr);
+/* Development aid: what the set-up stage (prune / sort / centring / chain links) left in device memory for frame `frame` of the last call
+ * (frames counted as for tdlo_debug_read_cloud), copied to out (capacity cap doubles); returns the number of doubles, or TDLO_E_INVALID.
+ *   TDLO_SETUP_COORD   M       the chain coordinate (trackdlo.cpp:214-223)
+ *   TDLO_SETUP_CHAIN   8 M     row 0 {Pinf11, Pinf22, 1/Pinf11, 1/Pinf22, 0 ...}, row i {Phi11, Phi12, Phi21, Phi22, Q11, Q12, Q22, 0} of the gap (i - 1, i)
+ *   TDLO_SETUP_HY0     3 M     H Y0, column-major (registrations with the LLE term only: TDLO_E_INVALID otherwise)
+ *   TDLO_SETUP_Y0      3 M     the incoming nodes less the centring offset, fp64, column-major
+ *   TDLO_SETUP_NODES   4 M     the node block of the E-step {x, y, z, coord} in compute precision, widened: x, y, z are the CURRENT nodes -- the
+ *                              incoming ones only until the first M-step has run (after tdlo_split_begin, say); coord stays
+ *   TDLO_SETUP_KEEP    4       {kept points, sum of d2} as kept with the slot's sorted cloud (not written by tdlo_split_begin), then the same two
+ *                              numbers from the registration's state
+ *   TDLO_SETUP_SIGMA2  1       the state's sigma2 as it stands: every M-step overwrites it, so it is the iteration-0 value only before the first
+ *                              one (after tdlo_split_begin + tdlo_split_set_global); elsewhere sigma2_0 = sum / (3 M kept) from TDLO_SETUP_KEEP */
+#define TDLO_SETUP_COORD 0
+#define TDLO_SETUP_CHAIN 1
+#define TDLO_SETUP_HY0 2
+#define TDLO_SETUP_Y0 3
+#define TDLO_SETUP_NODES 4
+#define TDLO_SETUP_KEEP 5
+#define TDLO_SETUP_SIGMA2 6
+int tdlo_debug_read_setup(tdlo_ctx *ctx, int frame, int what, double *out, int cap);
 
 #ifdef __cplusplus
 }

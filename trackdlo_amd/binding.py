@@ -56,7 +56,7 @@ SYMBOLS = [
     "tdlo_tracker_initialize_nodes", "tdlo_tracker_initialize_geodesic_coord", "tdlo_tracker_copy_state", "tdlo_tracker_get_sigma2",
     "tdlo_tracker_set_sigma2", "tdlo_tracker_get_tracking_result", "tdlo_tracker_get_guide_nodes",
     "tdlo_tracker_get_correspondence_pairs", "tdlo_tracker_tracking_step", "tdlo_calc_lle_weights", "tdlo_calc_lle_regulariser",
-    "tdlo_line_sphere_intersection", "tdlo_traverse_euclidean", "tdlo_profile_kernel", "tdlo_profile_iteration", "tdlo_debug_stamps", "tdlo_debug_exp2", "tdlo_debug_mstep_dense", "tdlo_debug_mstep_lle_dense", "tdlo_debug_band_retries", "tdlo_debug_lle_band_device", "tdlo_debug_route_count", "tdlo_debug_fail_hip", "tdlo_set_timing", "tdlo_set_sort_reuse", "tdlo_set_xch_self", "tdlo_pci_bus_id", "tdlo_debug_read_cloud", "tdlo_image_buffers", "tdlo_debug_cloud_stamps", "tdlo_visibility_prepass", "tdlo_depth_to_cloud_visibility", "tdlo_tracker_frame_from_depth", "tdlo_piecewise_error", "tdlo_compute_error",
+    "tdlo_line_sphere_intersection", "tdlo_traverse_euclidean", "tdlo_profile_kernel", "tdlo_profile_iteration", "tdlo_debug_stamps", "tdlo_debug_exp2", "tdlo_debug_mstep_dense", "tdlo_debug_mstep_lle_dense", "tdlo_debug_band_retries", "tdlo_debug_lle_band_device", "tdlo_debug_route_count", "tdlo_debug_fail_hip", "tdlo_set_timing", "tdlo_set_sort_reuse", "tdlo_set_xch_self", "tdlo_pci_bus_id", "tdlo_debug_read_cloud", "tdlo_debug_read_setup", "tdlo_image_buffers", "tdlo_debug_cloud_stamps", "tdlo_visibility_prepass", "tdlo_depth_to_cloud_visibility", "tdlo_tracker_frame_from_depth", "tdlo_piecewise_error", "tdlo_compute_error",
     "tdlo_depth_to_cloud", "tdlo_reg", "tdlo_self_occlusion_visible", "tdlo_extend_visible_nodes", "tdlo_tracker_set_self_occlusion",
 ]
 
@@ -191,6 +191,7 @@ def load_library(path: str | None = None):
     lib.tdlo_set_xch_self.argtypes = [vp, ci]
     lib.tdlo_set_xch_self.restype = ci
     lib.tdlo_debug_read_cloud.argtypes = [vp, ci, vp, ci, vp]
+    lib.tdlo_debug_read_setup.argtypes = [vp, ci, ci, vp, ci]
     lib.tdlo_piecewise_error.restype = cd
     lib.tdlo_piecewise_error.argtypes = [vp, ci, vp, ci]
     lib.tdlo_compute_error.restype = cd
@@ -536,12 +537,32 @@ class Context:
                                                           _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
 
-    def debug_read_cloud(self, max_points, slot=0):
-        out = np.zeros((3, max_points)); ctr = np.zeros(3)
-        n = self.lib.tdlo_debug_read_cloud(self.h, slot, _ptr(out), max_points, _ptr(ctr))
+    def debug_read_cloud(self, max_points, frame=0):
+        """The pruned, centred, node-sorted cloud [n x 3] and the centring offset of frame `frame` of the last call (tdlo_debug_read_cloud)."""
+        out = np.zeros((3, max(max_points, 1))); ctr = np.zeros(3)
+        n = self.lib.tdlo_debug_read_cloud(self.h, frame, _ptr(out), max_points, _ptr(ctr))
         if n < 0:
             raise TdloError(n, "tdlo_debug_read_cloud")
         return out.reshape(-1)[:3 * n].reshape(3, n).T.copy(), ctr
+
+    SETUP = dict(coord=0, chain=1, HY0=2, Y0=3, nodes=4, keep=5, sigma2=6)
+
+    def debug_read_setup(self, what, M, frame=0):
+        """What the set-up stage left for frame `frame` of the last call (tdlo_debug_read_setup): coord [M], chain [M x 8], HY0 [M x 3], Y0 [M x 3],
+        nodes [M x 4], keep [4], sigma2 (a float)."""
+        cap = 8 * max(int(M), 1)
+        out = np.zeros(cap)
+        n = self.lib.tdlo_debug_read_setup(self.h, int(frame), self.SETUP[what], _ptr(out), cap)
+        if n < 0:
+            raise TdloError(n, f"tdlo_debug_read_setup({what})")
+        out = out[:n].copy()
+        if what in ("HY0", "Y0"):
+            return out.reshape(3, M).T.copy()
+        if what == "chain":
+            return out.reshape(M, 8)
+        if what == "nodes":
+            return out.reshape(M, 4)
+        return float(out[0]) if what == "sigma2" else out
 
     def debug_exp2(self, x):
         """2^x as the fp64 E-step computes it (test aid)."""

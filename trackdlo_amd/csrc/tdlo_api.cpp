@@ -2713,9 +2713,9 @@ int tdlo_profile_iteration(tdlo_ctx *c, int reps, float *estep_us, float *mstep_
     return TDLO_OK;
 }
 
-int tdlo_debug_read_cloud(tdlo_ctx *c, int slot, double *out, int max_points, double *ctr) {
-    if (!c || slot < 0 || slot >= (int)c->slots.size() || !out || c->fh.empty()) return TDLO_E_INVALID;
-    const FrameDev &f = c->fh[0];
+int tdlo_debug_read_cloud(tdlo_ctx *c, int frame, double *out, int max_points, double *ctr) {
+    if (!c || frame < 0 || frame >= (int)c->fh.size() || !out) return TDLO_E_INVALID;
+    const FrameDev &f = c->fh[frame];
     IterState is;
     HIPCHK(c, hipMemcpy(&is, f.st, sizeof is, hipMemcpyDeviceToHost));
     const int N = is.N;
@@ -2728,6 +2728,51 @@ int tdlo_debug_read_cloud(tdlo_ctx *c, int slot, double *out, int max_points, do
     }
     if (ctr) HIPCHK(c, hipMemcpy(ctr, f.ctr, 3 * sizeof(double), hipMemcpyDeviceToHost));
     return N;
+}
+
+int tdlo_debug_read_setup(tdlo_ctx *c, int frame, int what, double *out, int cap) {
+    if (!c || frame < 0 || frame >= (int)c->fh.size() || !out) return TDLO_E_INVALID;
+    const FrameDev &f = c->fh[frame];
+    const int M = f.M;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double *src = nullptr;
+    int n = 0;
+    switch (what) {
+    case TDLO_SETUP_COORD: src = f.coord; n = M; break;
+    case TDLO_SETUP_CHAIN: src = f.chain; n = 8 * M; break;
+    case TDLO_SETUP_HY0: src = f.include_lle ? f.HY0 : nullptr; n = 3 * M; break;
+    case TDLO_SETUP_Y0: src = f.Y0; n = 3 * M; break;
+    case TDLO_SETUP_NODES: {
+        n = 4 * M;
+        if (n > cap || !f.nodes) return TDLO_E_INVALID;
+        if (f.precision == TDLO_PREC_F64) { HIPCHK(c, hipMemcpy(out, f.nodes, sizeof(double) * n, hipMemcpyDeviceToHost)); return n; }
+        std::vector<float> buf((size_t)n);
+        HIPCHK(c, hipMemcpy(buf.data(), f.nodes, sizeof(float) * n, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) out[i] = (double)buf[i];
+        return n;
+    }
+    case TDLO_SETUP_KEEP: {
+        n = 4;
+        if (n > cap || !f.keep || !f.st) return TDLO_E_INVALID;
+        IterState is;
+        HIPCHK(c, hipMemcpy(out, f.keep, 2 * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&is, f.st, sizeof is, hipMemcpyDeviceToHost));
+        out[2] = (double)is.N; out[3] = is.sum_d2;
+        return n;
+    }
+    case TDLO_SETUP_SIGMA2: {
+        n = 1;
+        if (n > cap || !f.st) return TDLO_E_INVALID;
+        IterState is;
+        HIPCHK(c, hipMemcpy(&is, f.st, sizeof is, hipMemcpyDeviceToHost));
+        out[0] = is.sigma2;
+        return n;
+    }
+    default: return TDLO_E_INVALID;
+    }
+    if (!src || n > cap) return TDLO_E_INVALID;
+    HIPCHK(c, hipMemcpy(out, src, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return n;
 }
 
 int tdlo_debug_mstep_dense(int on) { return mstep_set_dense(on); }

@@ -498,8 +498,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * the reference at the mode's tolerance, but a frame registered alone (k_estep) and the same frame inside a GPU-filling batch (k_estep2) agree
  * to about 1e-8 m, not to the bit.  10: fp64-mode calls repeated without the sigma-following resolution of the E-step's sums because a share was
  * refused under its finer range limits (the repeat runs under the coarse limits of every other mode; only its verdict is reported).
- * 11: calls served by the spin-ahead loop (TDLO_SPIN_AHEAD=1, a round-6 experiment, off by default); 12 / 13: batches whose whole loop ran as one launch
- * (TDLO_BATCH_PERSIST=1, a round-6 experiment, off by default) / such calls repeated on the launch-per-step loop because a wait inside the launch gave up.
+ * 11, 12, 13: always 0 -- these indices belonged to experiments that were measured slower and removed (the spin-ahead loop TDLO_SPIN_AHEAD, a batch's loop
+ * in one launch TDLO_BATCH_PERSIST and its repeats; docs/HISTORY.md has the numbers); the indices are not reused.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

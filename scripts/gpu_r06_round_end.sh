@@ -65,8 +65,6 @@ sec() { echo "== $1"; shift; "$@" 2>&1 | grep -v amdgpu.ids; local rc=${PIPESTAT
   sec "E-step phases at N = 2 000 000, k_estep2 (clocks of one wave; the stamps wait for the prefetch, so 'x loads' is an artefact of the instrumentation)" env TDLO_ESTEP2=1 timeout 200 python scripts/gpu_ephases.py 2000000 50
   sec "E-step phases at N = 2 000 000, k_estep (TDLO_ESTEP2=0)" env TDLO_ESTEP2=0 timeout 200 python scripts/gpu_ephases.py 2000000 50
   sec "k_estep2 over workgroup counts at C4 (TDLO_ESTEP2_BLOCKS)" bash scripts/gpu_estep2_sweep.sh "8" "782 977 1024 1280 1536 1954"
-  sec "C3 over stream groups and TDLO_BATCH_CHAIN" bash scripts/gpu_c3_ns.sh "2 3 4" "0 1 2"
-  sec "spin-ahead loop of one frame against the ordinary loop (TDLO_SPIN_AHEAD)" timeout 300 python scripts/gpu_spin_ab.py 3
   sec "stamps (C2: E-step / chain M-step phases and the iteration's timeline)" timeout 200 python scripts/gpu_stamps.py
   sec "chain stamps (k_mstep_chain phases over chain lengths; instrumented build)" env TDLO_ALT_LIB=scripts/tmp/libtrackdlo_stamps.so timeout 200 python scripts/gpu_chain_stamps.py
   sec "band stamps (k_mstep_band phases, shader clocks; instrumented build)" timeout 200 python scripts/gpu_band_stamps.py
@@ -83,7 +81,6 @@ sec() { echo "== $1"; shift; "$@" 2>&1 | grep -v amdgpu.ids; local rc=${PIPESTAT
   sec "pcie" timeout 200 python scripts/gpu_pcie.py
   sec "fp64 E-step of long chains: wide windows lane = node (default) against thread = point (TDLO_ESTEP_WIDE=0), C5" env MODES=0,129 timeout 400 python scripts/gpu_estep_wide_ab.py 200000 300 3
   sec "the same, per-iteration E-step durations of one call (rocprofv3 kernel trace)" env ITERS=50 CASES=1 timeout 400 bash scripts/gpu_estep_wide_trace.sh gpurun_out/$tag/wide_trace
-  sec "a batch's loop as one launch (TDLO_BATCH_PERSIST=1, experiment) against the launch-per-step loop, C3" timeout 300 python scripts/gpu_batch_loop_ab.py 32 50000 2 50
   sec "loop timeline under the profiler: C2" bash scripts/gpu_loop_timeline.sh 50000 50 0
   sec "loop timeline under the profiler: C4" bash scripts/gpu_loop_timeline.sh 2000000 50 0
   sec "loop timeline under the profiler: C5" bash scripts/gpu_loop_timeline.sh 200000 300 1

@@ -17,7 +17,6 @@
 #include <mutex>
 #include <string>
 #include <thread>
-#include <atomic>
 #include <vector>
 
 using namespace tdlo;
@@ -35,7 +34,6 @@ constexpr int kChunkIters = 4;          // EM iterations per early-exit polling 
                                         // a tracker in steady state converges in one or two iterations
 
 struct Slot {
-    unsigned spin_ecount = 0, spin_mtag = 0;      // the spin-ahead loop's running counts (FrameDev::spin_wait / spin_signal): E-step workgroups reported, M-steps tagged
     // cloud-sized
     int cap_points = 0;
     int N0 = 0;
@@ -157,17 +155,6 @@ struct tdlo_ctx {
     size_t xfer_doubles = 0;
     hipStream_t stream2[kBatchStreams - 1] = {};   // further groups of a batch: their E-steps overlap another group's one-workgroup-per-frame M-step
     hipEvent_t evx[kBatchStreams] = {}, evj[kBatchStreams] = {};   // fork / join of the batch groups
-    // chained E-steps of a batch's stream groups (run_frames): group g's E-step of iteration k goes out behind group g-1's (an event per group and
-    // iteration, a ring of kChainRing): the groups' E-steps then run ONE AFTER THE OTHER, each with the GPU to itself, beside the other groups' M-steps.
-    // Left to themselves the groups lock into whatever phase the first iteration gave them -- E-steps on top of each other, then a stretch with
-    // nothing but M-steps (scripts/gpu_c3_timeline.sh).  Round 6 experiment, TDLO_BATCH_CHAIN=1 switches it on: the events and the host threads waiting for
-    // each other cost more than the phase is worth.
-    static constexpr int kChainRing = 8;
-    hipEvent_t evc[kBatchStreams][kChainRing] = {};
-    // 0 (default): never.  1: every iteration -- measured SLOWER, 0.90 - 0.96 M against 1.21 - 1.24 M it/s at C3: the events and the enqueueing threads waiting
-    // for each other cost more than the phase is worth.  2: only at four iterations of the call (two groups of equal work that overlap slow each other down
-    // equally, so a phase once set should persist) -- 1.18 - 1.21 M against 1.23 M: no gain either (profiles/r06_measured.log).  Kept as comparators.
-    int batch_chain = getenv("TDLO_BATCH_CHAIN") ? atoi(getenv("TDLO_BATCH_CHAIN")) : 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 0..3 timing, 4..5 early-exit polling
     tdlo_config cfg{};
     std::vector<Slot> slots;
@@ -281,24 +268,12 @@ struct tdlo_ctx {
     bool boost_off_once = false;          // run_frames' retry: an fp64-mode E-step refused a share under the sigma-following (finer) limits -- this call repeats with the coarse ones
     long long boost_retries = 0;          // how often that happened (tdlo_debug_route_count 10)
     bool test_boost_fail = getenv("TDLO_TEST_BOOST_FAIL") && atoi(getenv("TDLO_TEST_BOOST_FAIL")) != 0;   // test hook: every fp64-mode call's first attempt has its shares refused under the boosted limits (set_iter_consts)
-    // Round 6 experiment, OFF by default: one frame's fixed-length loop as a spin-ahead loop -- E-steps on the second stream, M-steps on
-    // the first, the kernels parked on device words instead of the streams' dependent dispatches (FrameDev::spin_on).  TDLO_SPIN_AHEAD=1 switches it on.
-    bool spin_ahead_on = getenv("TDLO_SPIN_AHEAD") && atoi(getenv("TDLO_SPIN_AHEAD")) != 0;
     // fp64 E-step of chains beyond 64 nodes: batches whose node window is wide go lane = node (tdlo_estep_wide.h); TDLO_ESTEP_WIDE=0: thread = point throughout (comparator)
     int estep_wide_min = getenv("TDLO_ESTEP_WIDE") ? (atoi(getenv("TDLO_ESTEP_WIDE")) > 0 ? atoi(getenv("TDLO_ESTEP_WIDE")) : (1 << 30)) : kEstepWideMin;
-    long long spin_calls = 0;             // registrations run that way (tdlo_debug_route_count 11)
     // One launch per iteration (tdlo_iter_fused.hip: k_iter_fused = M-step ; next E-step) for the registrations fused_iter_eligible names.  TDLO_FUSED_ITER=0: never
     // (the two-launch loop, the comparator); =1: also beyond the point count up to which it is the default; unset: by eligibility.
     int fused_iter_mode = getenv("TDLO_FUSED_ITER") ? (atoi(getenv("TDLO_FUSED_ITER")) != 0 ? 1 : 0) : -1;
     long long fused_calls = 0;            // registrations run that way (tdlo_debug_route_count 14)
-    // A batch's whole fixed-length loop in ONE launch (k_batch_loop, tdlo_estep2.hip): tickets (iteration, frame, chunk) drawn by resident workgroups, the workgroup
-    // that completes a frame's E-step runs its M-step.  Round 6 EXPERIMENT, OFF by default (TDLO_BATCH_PERSIST=1 switches it on): the same bits, but 5.1 ms
-    // against 1.27 ms per C3 call.  A call whose loop kernel gives a wait up is repeated on the launch-per-step loop.
-    bool batch_persist_on = getenv("TDLO_BATCH_PERSIST") && atoi(getenv("TDLO_BATCH_PERSIST")) != 0;
-    unsigned *batch_ctl = nullptr;        // device: ticket, abort, per-frame progress counters (batch_loop_ctl_words)
-    size_t batch_ctl_words = 0;
-    long long batch_loop_calls = 0, batch_loop_fallbacks = 0;      // tdlo_debug_route_count 12 / 13
-    bool batch_persist_off_once = false;  // run_frames' repeat of a call whose loop kernel gave a wait up
     long long estep2_frames = 0;          // registrations whose E-step was k_estep2 (tdlo_debug_route_count 9)
     bool timing = false;                  // tdlo_set_timing: record the four events behind tdlo_stats.loop_ms / total_ms (~15 us per call)
     EnqueuePool *pool = nullptr;          // made by the first batch that runs on several streams
@@ -389,37 +364,40 @@ hipError_t drain_for_realloc(tdlo_ctx *c) {
     return hipSuccess;
 }
 
-int ensure_pin(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->pin_doubles) return 0;
-    HIPCHK(c, drain_for_realloc(c));
-    if (c->pin) hipHostFree(c->pin);
-    c->pin = nullptr; c->pin_doubles = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->pin, doubles * sizeof(double), hipHostMallocDefault));
-    c->pin_doubles = doubles;
+// The context's growing staging buffers follow one rule: a buffer is replaced only by a larger one; what may still read or poll the old one is
+// drained first; a failing allocation leaves {nullptr, 0} behind, never a dangling pointer for tdlo_destroy.
+enum class Staging {
+    Pinned,            // pinned host memory, contents left as they come
+    PinnedZeroed,      // ... cleared (flags and epochs that kernels compare with start at 0)
+    DeviceZeroed       // device memory, cleared on the context's stream; only that stream is drained
+};
+static int grow_staging(tdlo_ctx *c, double *&buf, size_t &have, size_t doubles, Staging kind) {
+    if (doubles <= have) return 0;
+    const bool dev = kind == Staging::DeviceZeroed;
+    HIPCHK(c, dev ? hipStreamSynchronize(c->stream) : drain_for_realloc(c));
+    if (buf) { if (dev) hipFree(buf); else hipHostFree(buf); }
+    buf = nullptr; have = 0;
+    if (dev) {
+        HIPCHK(c, hipMalloc((void **)&buf, doubles * sizeof(double)));
+        HIPCHK(c, hipMemsetAsync(buf, 0, doubles * sizeof(double), c->stream));
+    } else {
+        HIPCHK(c, hipHostMalloc((void **)&buf, doubles * sizeof(double), hipHostMallocDefault));
+        if (kind == Staging::PinnedZeroed) std::memset(buf, 0, doubles * sizeof(double));
+    }
+    have = doubles;
     return 0;
 }
-
-int ensure_late(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->late_doubles) return 0;
-    HIPCHK(c, drain_for_realloc(c));
-    if (c->late_buf) hipHostFree(c->late_buf);
-    c->late_buf = nullptr; c->late_doubles = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->late_buf, doubles * sizeof(double), hipHostMallocDefault));
-    std::memset(c->late_buf, 0, doubles * sizeof(double));        // (its last word is the spec flag a kernel launched ahead compares with its epoch)
-    c->late_doubles = doubles;
-    return 0;
+int ensure_pin(tdlo_ctx *c, size_t doubles) { return grow_staging(c, c->pin, c->pin_doubles, doubles, Staging::Pinned); }
+int ensure_pin2(tdlo_ctx *c, size_t doubles) { return grow_staging(c, c->pin2, c->pin2_doubles, doubles, Staging::Pinned); }
+// (its last word is the spec flag a kernel launched ahead compares with its epoch)
+int ensure_late(tdlo_ctx *c, size_t doubles) { return grow_staging(c, c->late_buf, c->late_doubles, doubles, Staging::PinnedZeroed); }
+// (kernels of an earlier call may still report their progress into the old one: hence the drain)
+int ensure_mbox(tdlo_ctx *c, size_t doubles) { return grow_staging(c, c->mbox, c->mbox_doubles, doubles, Staging::PinnedZeroed); }
+int ensure_cloud_pin(tdlo_ctx *c, size_t doubles) {
+    if (doubles <= c->cloud_pin_doubles) return 0;
+    return grow_staging(c, c->cloud_pin, c->cloud_pin_doubles, (doubles + 4095) & ~(size_t)4095, Staging::Pinned);
 }
-
-int ensure_mbox(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->mbox_doubles) return 0;
-    HIPCHK(c, drain_for_realloc(c));         // (kernels of an earlier call may still report their progress into the old one)
-    if (c->mbox) hipHostFree(c->mbox);
-    c->mbox = nullptr; c->mbox_doubles = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->mbox, doubles * sizeof(double), hipHostMallocDefault));
-    std::memset(c->mbox, 0, doubles * sizeof(double));
-    c->mbox_doubles = doubles;
-    return 0;
-}
+int ensure_xfer(tdlo_ctx *c, size_t doubles) { return grow_staging(c, c->xfer, c->xfer_doubles, doubles, Staging::DeviceZeroed); }
 
 // Waits until the M-steps of registration `epoch` have reported `min_it` completed iterations, or that the registration is done (need_done:
 // only that).  *word = the progress word seen.  Returns 0; 1 when the stream has drained without that report (the caller falls back on the
@@ -451,17 +429,6 @@ int mbox_wait(tdlo_ctx *c, hipStream_t stream, unsigned epoch, int min_it, bool 
         __builtin_ia32_pause();
 #endif
     }
-}
-
-int ensure_xfer(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->xfer_doubles) return 0;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->xfer) hipFree(c->xfer);
-    c->xfer = nullptr; c->xfer_doubles = 0;
-    HIPCHK(c, hipMalloc((void **)&c->xfer, doubles * sizeof(double)));
-    HIPCHK(c, hipMemsetAsync(c->xfer, 0, doubles * sizeof(double), c->stream));
-    c->xfer_doubles = doubles;
-    return 0;
 }
 
 int ensure_points(tdlo_ctx *c, Slot &s, int n) {
@@ -526,33 +493,12 @@ int ensure_hb_next(tdlo_ctx *c, Slot &s, int M) {
     return 0;
 }
 
-int ensure_cloud_pin(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->cloud_pin_doubles) return 0;
-    HIPCHK(c, drain_for_realloc(c));
-    if (c->cloud_pin) hipHostFree(c->cloud_pin);
-    c->cloud_pin = nullptr; c->cloud_pin_doubles = 0;
-    const size_t cap = (doubles + 4095) & ~(size_t)4095;
-    HIPCHK(c, hipHostMalloc((void **)&c->cloud_pin, cap * sizeof(double), hipHostMallocDefault));
-    c->cloud_pin_doubles = cap;
-    return 0;
-}
-
 // a cloud staged in pinned memory that no prologue has taken to the device goes there by a copy
 int flush_pending_cloud(tdlo_ctx *c) {
     if (c->cloud_pending < 0) return 0;
     Slot &s = c->slots[c->cloud_pending];
     c->cloud_pending = -1;
     HIPCHK(c, hipMemcpyAsync(s.Xraw, c->cloud_pin, 3 * (size_t)s.N0 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
-
-int ensure_pin2(tdlo_ctx *c, size_t doubles) {
-    if (doubles <= c->pin2_doubles) return 0;
-    HIPCHK(c, drain_for_realloc(c));
-    if (c->pin2) hipHostFree(c->pin2);
-    c->pin2 = nullptr; c->pin2_doubles = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->pin2, doubles * sizeof(double), hipHostMallocDefault));
-    c->pin2_doubles = doubles;
     return 0;
 }
 
@@ -653,7 +599,7 @@ static void choose_acc_rows(const tdlo_ctx *c, FrameDev &f, bool merged) {
 // visibility term (k_dmin would sit between the two halves), k_estep with the one-frame tile (not k_estep2), results through the mailbox, none of tracking_step's
 // short cuts -- and a cloud whose E-step has fewer waves than the GPU has SIMDs (65 536 points): there the E-step is a chain of latencies, and every workgroup
 // repeating the M-step costs no time; beyond, the E-step's workgroups take several batches each and the M-step in front of each is issue time (TDLO_FUSED_ITER=1
-// takes those too).  What run_frames adds: not a batch, not a paired / ahead / late-priors registration, not the spin-ahead experiment.
+// takes those too).  What run_frames adds: not a batch, not a paired / ahead / late-priors registration.
 constexpr int kFusedIterMaxPoints = 65536;
 static bool fused_iter_eligible(const tdlo_ctx *c, const FrameDev &f) {
     return c->fused_iter_mode != 0 && f.precision == TDLO_PREC_F32 && !f.include_lle && !f.mstep_dense && f.M >= 8 && f.M <= kChunk && !f.vis_branch &&
@@ -889,11 +835,33 @@ void fill_stats(tdlo_stats *st, const IterState &is) {
 // K x 4 rows, or an error code.
 typedef std::function<int(const double *&, int &)> LatePriors;
 
+// the mailbox epoch of the next registration that reports there (never 0: a cleared mailbox carries 0)
+static unsigned next_mbox_epoch(tdlo_ctx *c) {
+    unsigned e = ++c->mbox_epoch;
+    if (e == 0) e = ++c->mbox_epoch;
+    return e;
+}
+
+// The descriptor of a main registration's first M-step that is launched AHEAD of its priors (FrameDev::spec_flag), from the registration's own
+// descriptor PairNext::f: the priors will come through the late buffer, the results go to the mailbox under `epoch`.  spec_prev: the state of the
+// pre-processing registration whose end it waits for (nullptr: the host's word alone); lle_next: where the M-step that finishes the registration
+// leaves the next frame's LLE regulariser (nullptr: nowhere).
+static FrameDev spec_mstep_descriptor(tdlo_ctx *c, const tdlo_ctx::PairNext &pn, unsigned epoch, const IterState *spec_prev, double *lle_next) {
+    FrameDev fs = pn.f;
+    fs.reuse_sorted = 1; fs.has_priors = 1;
+    fs.late_aJ = c->late_buf; fs.late_aYd = c->late_buf + pn.M;
+    fs.host_out = c->mbox; fs.host_prog = (unsigned long long *)(c->mbox + c->mbox_doubles - 2); fs.host_epoch = epoch;
+    fs.host_report_it = (pn.p.tol <= 0.0 || pn.p.max_iter <= 2 * kChunkIters) ? 0 : std::max(1, std::min(std::min(c->iter_hint_next, kIterHintMax), pn.p.max_iter));
+    fs.spec_flag = spec_flag_word(c); fs.spec_prev = spec_prev; fs.spec_epoch = epoch;
+    if (lle_next) fs.lle_next = lle_next;
+    return fs;
+}
+
 // PairNext::ahead (tracking_step with hidden nodes; called by the pre-processing registration's run_frames once its own first iterations are on the
 // first stream): the main registration's fused prologue, k_dmin and first E-step on the SECOND stream, in the context's twin slot -- they read
 // the frame's cloud from the pinned staging buffer like the pre-processing registration's own prologue -- and its first M-step behind them, waiting
 // for the priors.  Returns 0 whether or not it launched anything (PairNext::state == 2 && ahead says it did); a negative code for a HIP error.
-int launch_ahead(tdlo_ctx *c) {
+static int launch_ahead(tdlo_ctx *c) {
     tdlo_ctx::PairNext &pn = c->pair;
     const int M = pn.M;
     const int N0 = c->slots[pn.slot].N0;
@@ -926,56 +894,137 @@ int launch_ahead(tdlo_ctx *c) {
     const FrameDev *fdb = (const FrameDev *)(tw.nodeblk + nc.fdev);
     if (f.vis_branch) HIPCHK(c, launch_estep_only(fdb, &f, 1, 1, sb));
     HIPCHK(c, launch_estep_only(fdb, &f, 1, 0, sb));
-    unsigned e2 = ++c->mbox_epoch;
-    if (e2 == 0) e2 = ++c->mbox_epoch;
-    FrameDev fs = f;
-    fs.reuse_sorted = 1; fs.has_priors = 1;
-    fs.late_aJ = c->late_buf; fs.late_aYd = c->late_buf + M;
-    fs.host_out = c->mbox; fs.host_prog = (unsigned long long *)(c->mbox + c->mbox_doubles - 2); fs.host_epoch = e2;
-    fs.host_report_it = (pn.p.tol <= 0.0 || pn.p.max_iter <= 2 * kChunkIters) ? 0 : std::max(1, std::min(std::min(c->iter_hint_next, kIterHintMax), pn.p.max_iter));
-    fs.spec_flag = spec_flag_word(c); fs.spec_prev = nullptr; fs.spec_epoch = e2;
+    const unsigned e2 = next_mbox_epoch(c);
+    const FrameDev fs = spec_mstep_descriptor(c, pn, e2, nullptr, nullptr);
     HIPCHK(c, launch_mstep_chain(fdb, &fs, 1, 0, fs.precision == TDLO_PREC_F64, sb));
     pn.has_sums = false; pn.spec = 1; pn.spec_epoch = e2; pn.ahead = true; pn.state = 2;
     return 0;
 }
 
-// Shared driver of tdlo_cpd_lle_resident / _batch.
+// iterations of early-exit chunk number `chunk`: 1, 1, 2, 4, 4, ... and no more than are left
+static int chunk_iters(int chunk, int left) { return std::min(chunk < 2 ? 1 : (chunk == 2 ? 2 : kChunkIters), left); }
+
+// frame i's state in an array of read-back blocks [Yout | IterState] in host memory, `stride` doubles apart
+static IterState readback_state(const double *blocks, size_t stride, const NodeCarve &nc, int i) {
+    IterState is;
+    std::memcpy(&is, blocks + (size_t)i * stride + (nc.st - nc.Yout), sizeof is);
+    return is;
+}
+static bool every_frame_done(const double *blocks, size_t stride, const NodeCarve &nc, int F) {
+    for (int i = 0; i < F; ++i) if (readback_state(blocks, stride, nc, i).done == 0) return false;
+    return true;
+}
+static bool any_frame_ended_with(int status, const double *blocks, size_t stride, const NodeCarve &nc, int F) {
+    for (int i = 0; i < F; ++i) if (readback_state(blocks, stride, nc, i).status == status) return true;
+    return false;
+}
+
 int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
                const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats,
-               const LatePriors *late = nullptr) {
-    const auto t_host0 = std::chrono::steady_clock::now();
-    int rc = check_params(c, M, p);
-    if (rc) return rc;
-    const int iter_hint = c->iter_hint_on ? c->iter_hint : 0;
-    if (!c->iter_hint_on) c->iter_hint_next = 0;
-    c->iter_hint = 0;
-    if (late && F != 1) return fail(c, TDLO_E_INVALID, "late priors: one frame per call");
-    if (F < 1 || F > c->cfg.max_frames) return fail(c, TDLO_E_INVALID, "bad frame count");
-    NodeCarve nc(M);
-    // Batches move their host-supplied blocks and their results with ONE copy each way: every small copy is a 4-5 us blit
-    // kernel on the stream, and 32 frames x (upload + read-back [+ flags per polling chunk]) had grown to 0.3 ms of a 2.3 ms
-    // call.  The frames' [Yin | aJ | aYd | H] and [Yout | IterState] then live in one device buffer instead of the slots'
-    // node blocks (the kernels only see pointers).
-    const bool merged = F > 1;
+               const LatePriors *late = nullptr);
+
+// a paired registration's first M-step may already be waiting on the stream (launched by the previous call): released when the priors are staged,
+// told to leave on every other way out of run_frames
+struct SpecGuard {
+    tdlo_ctx *c; unsigned epoch = 0; bool live = false;
+    void release(bool go) { if (live) { spec_release(c, epoch, go); live = false; } }
+    ~SpecGuard() { release(false); }
+};
+
+// One call of run_frames: its arguments, what it has decided and how far it has come.  The member functions are run_frames' phases, in the order
+// run_frames calls them; each returns 0 or the call's error code.
+struct FramesCall {
+    // the arguments
+    tdlo_ctx *const c; const int F; const int *const slots; double *const Y; const int M; double *const sigma2; const tdlo_params *const p;
+    const double *const priors; const int K; const int *const vis; const int n_vis; const double *const H_override; tdlo_stats *const stats;
+    const LatePriors *const late;
+    const int iter_hint;          // tdlo_ctx::iter_hint as this call found it
+    const bool timing;
+    // layout.  Batches move their host-supplied blocks and their results with ONE copy each way: every small copy is a 4-5 us blit kernel on the
+    // stream, and 32 frames x (upload + read-back [+ flags per polling chunk]) had grown to 0.3 ms of a 2.3 ms call.  The frames' [Yin | aJ | aYd | H]
+    // and [Yout | IterState] then live in one device buffer instead of the slots' node blocks (the kernels only see pointers).
+    const NodeCarve nc;
+    const bool merged;
     // how much of a frame's block travels: without the LLE term up to Hb; with it the 13 diagonals Hb when the banded solve serves the call, else
     // the dense H as well.  A batch is staged at the stride of the banded form first; a frame the banded solve cannot take sends the whole
     // batch to the dense kernels (one M-step kernel per launch), and the frames are staged again at the full stride.
-    bool band_batch = p->include_lle && mstep_band_enabled() && !c->lle_dense_once;
-    size_t up = upload_doubles(nc, p, band_batch);
-    size_t ustride = merged ? up : nc.upload;
+    size_t up, ustride;
     // the frame descriptors ride in the same host-to-device copy: one frame -> at the head of its upload block, a batch -> as an array
     // behind the F upload blocks (every separate small copy is a blit kernel plus a dependent-dispatch gap, ~4 us)
-    const size_t fdd = ((size_t)F * sizeof(FrameDev) + 15) / 16 * 2;      // doubles of the descriptor array of a batch
-    rc = ensure_pin(c, (size_t)F * std::max(nc.upload, nc.readback + 2) + fdd + 2 * (size_t)F * std::max(nc.readback, (sizeof(IterState) + 7) / 8) + 4);
-    if (rc) return rc;
-    if (merged) { rc = ensure_xfer(c, (size_t)F * (upload_doubles(nc, p, false) + nc.readback) + fdd); if (rc) return rc; }
-    // tracking_step's second registration whose node-side set-up the first one's prologue has already done (PairNext): same slot, nodes, sigma2 and
-    // parameters as were set up, on the cloud that was sorted for these nodes -- then nothing is staged and no prologue is launched
-    bool paired = false;
+    const size_t fdd;             // doubles of the descriptor array of a batch
+    // route
+    bool paired = false;          // tracking_step's second registration whose node-side set-up the first one's prologue has already done (PairNext)
     bool ahead = false;           // ... or whose whole first iteration up to the M-step has run beside the previous registration, in the twin slot (PairNext::ahead)
+    bool use_mbox = false;        // the results come back through the pinned mailbox
+    bool fused_mode = false;      // one launch per iteration (tdlo_iter_fused.hip)
+    bool late_async = false;      // the late priors are formed beside the set-up kernel
+    bool lle_next = false;        // the M-step that finishes the registration leaves the next frame's LLE regulariser behind
+    // streams
+    hipStream_t s = nullptr;      // the call's first stream
+    hipStream_t gs[kBatchStreams] = {};
+    int goff[kBatchStreams + 1] = {};
+    int NS = 1;
+    bool forked = false;
+    // progress
+    int enqueued = 0;             // iterations this call has put on the stream (or released)
+    bool sums_first = false;      // the first iteration is its M-step alone, from the sums the previous registration's first M-step left
+    bool ahead_first = false;     // the first iteration is on the second stream already: its M-step waits for the priors staged by this call
+    bool spec_released = false;   // ... and that M-step had been launched ahead and was released by this call
+    unsigned epoch = 0;           // of the mailbox
+    bool have_readback = false;   // the results are already in pinned memory (early exit after the first iteration; the mailbox)
+    const FrameDev *fdp = nullptr;      // this call's descriptors on the device
+    double *nodeblk_used = nullptr;     // one frame: the node block the registration runs out of
+    SpecGuard sg;
+
+    FramesCall(tdlo_ctx *c_, int F_, const int *slots_, double *Y_, int M_, double *sigma2_, const tdlo_params *p_, const double *priors_, int K_,
+               const int *vis_, int n_vis_, const double *H_override_, tdlo_stats *stats_, const LatePriors *late_, int iter_hint_)
+        : c(c_), F(F_), slots(slots_), Y(Y_), M(M_), sigma2(sigma2_), p(p_), priors(priors_), K(K_), vis(vis_), n_vis(n_vis_), H_override(H_override_),
+          stats(stats_), late(late_), iter_hint(iter_hint_), timing(c_->timing), nc(M_), merged(F_ > 1),
+          up(upload_doubles(nc, p_, p_->include_lle && mstep_band_enabled() && !c_->lle_dense_once)), ustride(merged ? up : nc.upload),
+          fdd(((size_t)F_ * sizeof(FrameDev) + 15) / 16 * 2), sg{c_} {}
+
+    Slot &slot0() const { return c->slots[slots[0]]; }
+    size_t rstride() const { return merged ? nc.readback : nc.upload; }      // of the read-back blocks in tdlo_ctx::pin
+    bool fixed_count() const { return p->tol <= 0.0 || p->max_iter <= 2 * kChunkIters; }
+
+    int size_staging();
+    void recognise_pair();
+    int stage_frames();
+    int choose_batch_kernels();
+    int choose_routes();
+    int open_mailbox();
+    int upload_and_prologue();
+    int stage_late_priors();
+    int fork_streams();
+    void choose_loop();
+    int drive_fixed();
+    int drive_mailbox();
+    int drive_polled();
+    int read_back();
+    bool repeat(int *rc);
+    int results_out(std::chrono::steady_clock::time_point t_host0);
+
+    FrameDev fused_copy(int k) const;
+    hipError_t iterate(int n);
+    hipError_t join();
+    int mbox_done(int min_it, bool need_done, bool *done);
+    int take_mbox(bool events_recorded);
+    int launch_paired_mstep_ahead();
+};
+
+int FramesCall::size_staging() {
+    int rc = ensure_pin(c, (size_t)F * std::max(nc.upload, nc.readback + 2) + fdd + 2 * (size_t)F * std::max(nc.readback, (sizeof(IterState) + 7) / 8) + 4);
+    if (rc) return rc;
+    if (merged) rc = ensure_xfer(c, (size_t)F * (upload_doubles(nc, p, false) + nc.readback) + fdd);
+    return rc;
+}
+
+// tracking_step's second registration whose node-side set-up the first one's prologue has already done (PairNext): same slot, nodes, sigma2 and
+// parameters as were set up, on the cloud that was sorted for these nodes -- then nothing is staged and no prologue is launched
+void FramesCall::recognise_pair() {
     if (late && c->pair.state == 2) {
         const tdlo_ctx::PairNext &pn = c->pair;
-        const Slot &sl = c->slots[slots[0]];
+        const Slot &sl = slot0();
         const bool same = F == 1 && !priors && !H_override && pn.slot == slots[0] && pn.M == M && pn.n_vis == n_vis && pn.sigma2 == sigma2[0] && same_params(pn.p, *p) &&
                           std::memcmp(pn.Y.data(), Y, sizeof(double) * 3 * M) == 0 && pn.f.wide_tile != 0;
         if (pn.ahead) paired = ahead = same && c->stream2[0] != nullptr;
@@ -983,13 +1032,6 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
                       sl.sorted_Y.size() == 3 * (size_t)M && std::memcmp(sl.sorted_Y.data(), Y, sizeof(double) * 3 * M) == 0;
         c->pair.state = 0; c->pair.ahead = false;
     }
-    // its first M-step may already be waiting on the stream (launched by the previous call, below): released when the priors are staged, told to
-    // leave on every other way out of this function
-    struct SpecGuard {
-        tdlo_ctx *c; unsigned epoch = 0; bool live = false;
-        void release(bool go) { if (live) { spec_release(c, epoch, go); live = false; } }
-        ~SpecGuard() { release(false); }
-    } sg{c};
     if (late && c->pair.spec) { sg.epoch = c->pair.spec_epoch; sg.live = true; c->pair.spec = 0; }
     if (!paired) sg.release(false);
     c->fh.assign(F, FrameDev{});
@@ -998,65 +1040,79 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         if (ahead) ++c->route_count[4];
         else { ++c->route_count[0]; if (c->pair.has_sums) ++c->route_count[1]; }
     }
+}
+
+// every frame's upload block and descriptor, in up to two passes: banded LLE form first, the dense one if a frame of the batch cannot take it
+int FramesCall::stage_frames() {
     for (int pass = 0; pass < 2 && !paired; ++pass) {
-    for (int i = 0; i < F; ++i) {
-        rc = prepare_frame(c, slots[i], Y + (size_t)i * 3 * M, M, sigma2[i], p, priors, K, vis, n_vis, H_override,
-                           c->pin + (size_t)i * ustride, c->fh[i], false, !merged);
-        if (rc) return rc;
-        if (merged) {
-            FrameDev &f = c->fh[i];
-            f.wide_tile = 0;
-            // batches fill the GPU: half the workgroups per frame, every wave takes two 64-point batches -- the per-workgroup prologue (nodes
-            // to LDS) and epilogue (wave sums, atomics) are paid half as often (32 frames: 879 k -> 991 k it/s in the loop).  The sums do
-            // not depend on how batches are dealt out (integer accumulation): with k_estep on both sides the results are those of the single
-            // call, bit for bit.  A batch that fills the GPU takes k_estep2 below (128-point grain, one binary digit less) where the frame
-            // alone takes k_estep: then each frame's sums are the single call's within the E-step's own rounding, not bit for bit.
-            if (c->cfg.estep_blocks <= 0 && f.nblkE >= 64) f.nblkE = (f.nblkE + 1) / 2;
-            double *bu = c->xfer + (size_t)i * up, *br = c->xfer + (size_t)F * up + fdd + (size_t)i * nc.readback;
-            f.Yin = bu + nc.Yin; f.aJ = bu + nc.aJ; f.aYd = bu + nc.aYd;
-            if (p->include_lle) { f.Hb = bu + nc.Hb; f.H = bu + nc.H; }
-            f.Yout = br; f.st = (IterState *)(br + (nc.st - nc.Yout));
+        for (int i = 0; i < F; ++i) {
+            const int rc = prepare_frame(c, slots[i], Y + (size_t)i * 3 * M, M, sigma2[i], p, priors, K, vis, n_vis, H_override,
+                                         c->pin + (size_t)i * ustride, c->fh[i], false, !merged);
+            if (rc) return rc;
+            if (merged) {
+                FrameDev &f = c->fh[i];
+                f.wide_tile = 0;
+                // batches fill the GPU: half the workgroups per frame, every wave takes two 64-point batches -- the per-workgroup prologue (nodes
+                // to LDS) and epilogue (wave sums, atomics) are paid half as often (32 frames: 879 k -> 991 k it/s in the loop).  The sums do
+                // not depend on how batches are dealt out (integer accumulation): with k_estep on both sides the results are those of the single
+                // call, bit for bit.  A batch that fills the GPU takes k_estep2 below (128-point grain, one binary digit less) where the frame
+                // alone takes k_estep: then each frame's sums are the single call's within the E-step's own rounding, not bit for bit.
+                if (c->cfg.estep_blocks <= 0 && f.nblkE >= 64) f.nblkE = (f.nblkE + 1) / 2;
+                double *bu = c->xfer + (size_t)i * up, *br = c->xfer + (size_t)F * up + fdd + (size_t)i * nc.readback;
+                f.Yin = bu + nc.Yin; f.aJ = bu + nc.aJ; f.aYd = bu + nc.aYd;
+                if (p->include_lle) { f.Hb = bu + nc.Hb; f.H = bu + nc.H; }
+                f.Yout = br; f.st = (IterState *)(br + (nc.st - nc.Yout));
+            }
         }
-    }
-    if (merged) {
-        // a batch whose frames together fill the GPU takes the E-step with two points per lane (one choice for the whole launch)
-        long long waves = 0;
-        bool elig = true;
-        for (int i = 0; i < F; ++i) { waves += (c->fh[i].N0 + 63) / 64; elig = elig && estep2_eligible(c, c->fh[i]); }
-        const bool two = elig && (c->estep2_mode == 1 || waves >= kEstep2MinWaves);
-        for (int i = 0; i < F; ++i) if (two) estep2_geometry(c, c->fh[i], true);      // (a frame prepare_frame had given to k_estep2 on its own size keeps it only if the whole batch does:
-        for (int i = 0; i < F; ++i) choose_acc_rows(c, c->fh[i], true);
-        // a batch of short fp32 chains without the LLE term whose frames have at most 64 E-step workgroups each (C3: 49): two replica rows -- no more atomics
-        // per address than one 50 000-point frame puts on eight -- and a quarter of the sums for every frame's M-step to fetch (one choice for the whole batch)
-        {
-            static const int env = getenv("TDLO_ACC_ROWS") ? atoi(getenv("TDLO_ACC_ROWS")) : 0;
-            bool small = env == 0 && !p->include_lle;
-            for (int i = 0; i < F; ++i) small = small && c->fh[i].nblkE <= 64 && !c->fh[i].mstep_dense && c->fh[i].M <= kChunk;
-            if (small) for (int i = 0; i < F; ++i) c->fh[i].acc_rows = 2;
-        }
-        if (!two) for (int i = 0; i < F; ++i) if (c->fh[i].estep2) return fail(c, TDLO_E_INVALID, "internal: a batch's frames disagree about the E-step kernel");   //  same M, precision and mode -- they cannot)
-    }
-    if (!p->include_lle) break;
-    bool all_band = true;
-    for (int i = 0; i < F; ++i) all_band = all_band && c->fh[i].lle_band;
-    if (all_band) break;
-    if (!merged) { up = upload_doubles(nc, p, false); break; }      // one frame: its block was staged at the full stride anyway
-    if (pass == 0) { c->lle_batch_dense = true; band_batch = false; up = upload_doubles(nc, p, false); ustride = up; }
+        if (merged) { const int rc = choose_batch_kernels(); if (rc) return rc; }
+        if (!p->include_lle) break;
+        bool all_band = true;
+        for (int i = 0; i < F; ++i) all_band = all_band && c->fh[i].lle_band;
+        if (all_band) break;
+        if (!merged) { up = upload_doubles(nc, p, false); break; }      // one frame: its block was staged at the full stride anyway
+        if (pass == 0) { c->lle_batch_dense = true; up = upload_doubles(nc, p, false); ustride = up; }
     }
     c->lle_batch_dense = false;
-    if (!merged && !paired && p->include_lle && c->fh[0].lle_band && c->slots[slots[0]].hb_next != nullptr && c->fh[0].Hb == c->slots[slots[0]].hb_next)
+    return 0;
+}
+
+// what a batch decides once for all its frames: the E-step kernel and the replica rows of the accumulators
+int FramesCall::choose_batch_kernels() {
+    // a batch whose frames together fill the GPU takes the E-step with two points per lane (one choice for the whole launch)
+    long long waves = 0;
+    bool elig = true;
+    for (int i = 0; i < F; ++i) { waves += (c->fh[i].N0 + 63) / 64; elig = elig && estep2_eligible(c, c->fh[i]); }
+    const bool two = elig && (c->estep2_mode == 1 || waves >= kEstep2MinWaves);
+    for (int i = 0; i < F; ++i) if (two) estep2_geometry(c, c->fh[i], true);      // (a frame prepare_frame had given to k_estep2 on its own size keeps it only if the whole batch does:
+    for (int i = 0; i < F; ++i) choose_acc_rows(c, c->fh[i], true);
+    // a batch of short fp32 chains without the LLE term whose frames have at most 64 E-step workgroups each (C3: 49): two replica rows -- no more atomics
+    // per address than one 50 000-point frame puts on eight -- and a quarter of the sums for every frame's M-step to fetch (one choice for the whole batch)
+    {
+        static const int env = getenv("TDLO_ACC_ROWS") ? atoi(getenv("TDLO_ACC_ROWS")) : 0;
+        bool small = env == 0 && !p->include_lle;
+        for (int i = 0; i < F; ++i) small = small && c->fh[i].nblkE <= 64 && !c->fh[i].mstep_dense && c->fh[i].M <= kChunk;
+        if (small) for (int i = 0; i < F; ++i) c->fh[i].acc_rows = 2;
+    }
+    if (!two) for (int i = 0; i < F; ++i) if (c->fh[i].estep2) return fail(c, TDLO_E_INVALID, "internal: a batch's frames disagree about the E-step kernel");   //  same M, precision and mode -- they cannot)
+    return 0;
+}
+
+// what tracking_step's short cuts add to the descriptor, the late priors that cannot ride beside the set-up kernel, the sort reused per launch
+int FramesCall::choose_routes() {
+    if (!merged && !paired && p->include_lle && c->fh[0].lle_band && slot0().hb_next != nullptr && c->fh[0].Hb == slot0().hb_next)
         { up = nc.Hb; ++c->route_count[3]; }      // H's 13 diagonals are on the device already (Slot::hb_next): they do not travel
     // tracking_step's main registration: the M-step that finishes it leaves the next frame's LLE regulariser behind (FrameDev::lle_next; the
     // buffer was sized by tracking_step before anything was launched)
-    const bool lle_next = late != nullptr && !merged && !ahead && c->lle_next_on && !p->include_lle && !c->fh[0].mstep_dense && M <= 256 && p->max_iter > 0 &&
-                          c->slots[slots[0]].hb_next_cap >= M;      // (ahead: its first M-step is on the second stream already, without this job -- and the next frame's
-                                                                    //  pre-processing registration, on the first stream, must not race it)
-    if (lle_next) { c->fh[0].lle_next = c->slots[slots[0]].hb_next; c->slots[slots[0]].hb_next_valid = false; }
+    lle_next = late != nullptr && !merged && !ahead && c->lle_next_on && !p->include_lle && !c->fh[0].mstep_dense && M <= 256 && p->max_iter > 0 &&
+               slot0().hb_next_cap >= M;      // (ahead: its first M-step is on the second stream already, without this job -- and the next frame's
+                                              //  pre-processing registration, on the first stream, must not race it)
+    if (lle_next) { c->fh[0].lle_next = slot0().hb_next; slot0().hb_next_valid = false; }
     // Late priors ride beside the set-up kernel only where the E-step can hand them to the M-step (the one-frame kernel, which takes the frame
     // descriptor by value): otherwise they are formed here, before anything is launched, and staged like ordinary ones.
-    bool late_async = late != nullptr && c->fh[0].wide_tile != 0 && (c->late_on || paired);
+    late_async = late != nullptr && c->fh[0].wide_tile != 0 && (c->late_on || paired);
     if (late && !late_async) {
         const double *lp = nullptr; int lk = 0;
+        int rc;
         if ((rc = (*late)(lp, lk))) return rc;
         if ((rc = stage_priors(c, c->pin + nc.aJ, c->pin + nc.aYd, Y, M, lp, lk, p->alpha))) return rc;
         c->fh[0].has_priors = lk > 0 ? 1 : 0;
@@ -1068,32 +1124,37 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         for (int i = 0; i < F; ++i) all_reuse = all_reuse && c->fh[i].reuse_sorted;
         if (!all_reuse) for (int i = 0; i < F; ++i) c->fh[i].reuse_sorted = 0;
     }
-    // One frame per call on a one-workgroup M-step (the chain smoother, the banded LLE solve): the results come back through the pinned
-    // mailbox -- the M-step that finishes the registration writes them there itself -- instead of a copy and a stream synchronisation
-    const bool use_mbox = !merged && c->mbox_on && p->max_iter > 0 &&
-                          ((!p->include_lle && !c->fh[0].mstep_dense) || (p->include_lle && c->fh[0].lle_band));
-    unsigned epoch = 0;
-    if (!use_mbox) sg.release(false);
-    if (use_mbox) {
-        rc = ensure_mbox(c, nc.readback + 4);
-        if (rc) return rc;
-        if (sg.live) epoch = sg.epoch;         // (the waiting M-step reports under the epoch it was launched with)
-        else { epoch = ++c->mbox_epoch; if (epoch == 0) epoch = ++c->mbox_epoch; }
-        c->fh[0].host_out = c->mbox; c->fh[0].host_prog = (unsigned long long *)(c->mbox + c->mbox_doubles - 2); c->fh[0].host_epoch = epoch;
-    }
-    hipStream_t s = ahead ? c->stream2[0] : c->stream;      // (a registration that began on the second stream stays there: its kernels are ordered by the stream)
-    const bool timing = c->timing;
+    return 0;
+}
+
+// One frame per call on a one-workgroup M-step (the chain smoother, the banded LLE solve): the results come back through the pinned
+// mailbox -- the M-step that finishes the registration writes them there itself -- instead of a copy and a stream synchronisation
+int FramesCall::open_mailbox() {
+    use_mbox = !merged && c->mbox_on && p->max_iter > 0 &&
+               ((!p->include_lle && !c->fh[0].mstep_dense) || (p->include_lle && c->fh[0].lle_band));
+    if (!use_mbox) { sg.release(false); return 0; }
+    const int rc = ensure_mbox(c, nc.readback + 4);
+    if (rc) return rc;
+    epoch = sg.live ? sg.epoch : next_mbox_epoch(c);         // (the waiting M-step reports under the epoch it was launched with)
+    c->fh[0].host_out = c->mbox; c->fh[0].host_prog = (unsigned long long *)(c->mbox + c->mbox_doubles - 2); c->fh[0].host_epoch = epoch;
+    return 0;
+}
+
+// the host-supplied blocks to the device and the prologue (prune, sort, set-up) behind them, on one of three routes: set up by the previous
+// call (paired), one launch that reads the block from pinned host memory, or a copy and the three kernels
+int FramesCall::upload_and_prologue() {
+    int rc;
+    s = ahead ? c->stream2[0] : c->stream;      // (a registration that began on the second stream stays there: its kernels are ordered by the stream)
     if (timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    const FrameDev *fdp;          // this call's descriptors on the device
     if (merged) {
         std::memcpy(c->pin + (size_t)F * up, c->fh.data(), sizeof(FrameDev) * F);
         HIPCHK(c, hipMemcpyAsync(c->xfer, c->pin, ((size_t)F * up + fdd) * sizeof(double), hipMemcpyHostToDevice, s));
         fdp = (const FrameDev *)(c->xfer + (size_t)F * up);
     } else {
         if (!paired) std::memcpy(c->pin + nc.fdev, c->fh.data(), sizeof(FrameDev));
-        fdp = (const FrameDev *)((ahead ? c->twin.nodeblk : (paired ? c->slots[slots[0]].nodeblk2 : c->slots[slots[0]].nodeblk)) + nc.fdev);
+        nodeblk_used = ahead ? c->twin.nodeblk : (paired ? slot0().nodeblk2 : slot0().nodeblk);
+        fdp = (const FrameDev *)(nodeblk_used + nc.fdev);
     }
-    double *const nodeblk_used = merged ? nullptr : (ahead ? c->twin.nodeblk : (paired ? c->slots[slots[0]].nodeblk2 : c->slots[slots[0]].nodeblk));
     if (c->cloud_pending >= 0) {
         // tracking_step staged this frame's cloud in pinned host memory: the fused prologue reads it from there; any other route gets a copy first
         const bool fused = !merged && !paired && c->direct_in && c->fuse_on && c->cloud_pending == slots[0] && !c->fh[0].reuse_sorted && prologue_pair_ok(c->fh[0]);
@@ -1104,7 +1165,7 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         // (set up by the previous call's prologue)
     } else if (!merged && c->direct_in && (c->fuse_on || c->fh[0].reuse_sorted) && prologue_direct_ok(c->fh[0])) {
         // one small frame (or a reused sort): ONE launch reads the block from pinned host memory, puts it in its place and does the whole prologue
-        Slot &sl = c->slots[slots[0]];
+        Slot &sl = slot0();
         const unsigned fep = c->fh[0].reuse_sorted ? 0u : next_fuse_epoch(c, sl);      // (a reused sort: the set-up workgroup alone, no barrier)
         // tracking_step asked for the set-up of its second registration to ride along (PairNext): staged like a frame of its own into the second
         // pinned block / the slot's second node block, one more workgroup of the fused prologue
@@ -1132,7 +1193,7 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         c->fh[0].Xhost = nullptr;          // (the cloud is in Xraw for everything that follows)
         if (f2) pn.state = 2;
     } else {
-        if (!merged) HIPCHK(c, hipMemcpyAsync(c->slots[slots[0]].nodeblk, c->pin, up * sizeof(double), hipMemcpyHostToDevice, s));
+        if (!merged) HIPCHK(c, hipMemcpyAsync(slot0().nodeblk, c->pin, up * sizeof(double), hipMemcpyHostToDevice, s));
         HIPCHK(c, launch_prune_and_setup(fdp, c->fh.data(), F, s));
     }
     g_prof.mark(g_prof.base + 3);
@@ -1140,11 +1201,15 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         Slot &sl = c->slots[slots[i]];
         if (!c->fh[i].reuse_sorted) { sl.sorted_Y.assign(Y + (size_t)i * 3 * M, Y + (size_t)(i + 1) * 3 * M); sl.sorted_prec = p->precision; sl.sorted_valid = true; }
     }
+    return 0;
+}
+
+// the set-up kernel is on its way (it copies the staging block as it is: the priors' part is overwritten by the E-step's copy of what
+// follows); now the host forms the priors and puts them where the first E-step fetches them
+int FramesCall::stage_late_priors() {
     if (late_async) {
-        // the set-up kernel is on its way (it copies the staging block as it is: the priors' part is overwritten by the E-step's copy of what
-        // follows); now the host forms the priors and puts them where the first E-step fetches them
         const double *lp = nullptr; int lk = 0;
-        rc = (*late)(lp, lk);
+        int rc = (*late)(lp, lk);
         if (!rc) rc = ensure_late(c, 4 * (size_t)M);
         if (!rc) rc = stage_priors(c, c->late_buf, c->late_buf + M, Y, M, lp, lk, p->alpha);
         if (rc) { sg.release(false); (void)hipStreamSynchronize(s); return rc; }        // (the set-up kernel reads the pinned staging block: drained before anybody reuses it)
@@ -1154,314 +1219,253 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         g_prof.mark(7);
     }
     if (timing) HIPCHK(c, hipEventRecord(c->ev[1], s));
-    // A batch runs as up to kBatchStreams groups of frames on as many streams, each group one E-step behind the previous
-    // one: a batch's M-step is one workgroup per frame (F of the 256 CUs busy for 17 us), and meanwhile the other groups'
-    // E-steps have the rest of the GPU.  The groups are independent registrations: the results do not depend on the split
-    // (TDLO_BATCH_STREAMS=1 disables it).
+    return 0;
+}
+
+// A batch runs as up to kBatchStreams groups of frames on as many streams, each group one E-step behind the previous
+// one: a batch's M-step is one workgroup per frame (F of the 256 CUs busy for 17 us), and meanwhile the other groups'
+// E-steps have the rest of the GPU.  The groups are independent registrations: the results do not depend on the split
+// (TDLO_BATCH_STREAMS=1 disables it).
+int FramesCall::fork_streams() {
     static const int ns_env = getenv("TDLO_BATCH_STREAMS") ? atoi(getenv("TDLO_BATCH_STREAMS")) : 0;
     // (32 frames: three groups of 11 / 11 / 10 frames -- 1078 workgroups per E-step launch, about what the GPU holds at once -- give 1.155 M it/s against
     // 1.129 M for four groups of 8, three runs each, on one box and 1.124 M against 1.118 M on another; 24 frames: four groups 0.93 M against 0.91 M; 48 frames: three groups 1.26 M against 1.18 M)
-    int NS = ns_env > 0 ? ns_env : (F >= 28 ? 3 : (F >= 16 ? 4 : (F >= 8 ? 2 : 1)));
+    NS = ns_env > 0 ? ns_env : (F >= 28 ? 3 : (F >= 16 ? 4 : (F >= 8 ? 2 : 1)));
     NS = std::max(1, std::min(std::min(NS, kBatchStreams), F));
-    int goff[kBatchStreams + 1];
     for (int g = 0; g <= NS; ++g) goff[g] = (int)(((long long)F * g) / NS);
-    hipStream_t gs[kBatchStreams];
     gs[0] = s;
     for (int g = 1; g < NS; ++g) {            // the further streams are made when a batch first needs them: a context that only ever
         if (!c->stream2[g - 1]) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2[g - 1], hipStreamNonBlocking));   // registers single frames
         gs[g] = c->stream2[g - 1];            // (or a shard) occupies one hardware queue, not four
     }
-    bool forked = false;
-    bool sums_first = paired && !ahead && c->pair.has_sums;      // the first iteration is its M-step alone, from the sums the previous registration's first M-step left
-    bool ahead_first = ahead;                          // the first iteration is on the second stream already: its M-step waits for the priors staged above
-    bool spec_released = false;                        // ... and that M-step had been launched ahead and was released by this call
-    int enqueued = 0;                                  // iterations this call has put on the stream (or released)
-    // test hook: the M-step launched ahead is told to leave instead of being released, as if it had given up waiting (2 s without the host)
-    const bool spec_force_timeout = c->spec_force_timeout;
-    // the spin-ahead loop (experiment): ONE frame, fixed iteration count, fp32 mode, the chain smoother on up to 63 nodes, no visibility term, results through the mailbox
-    const bool spin_mode = c->spin_ahead_on && !merged && F == 1 && !paired && !ahead && late == nullptr && use_mbox && !timing && p->precision == TDLO_PREC_F32 &&
-                           !p->include_lle && !c->fh[0].mstep_dense && !c->fh[0].vis_branch && c->fh[0].wide_tile != 0 && c->fh[0].estep2 == 0 && 4 * M + 1 <= 256 &&
-                           (p->tol <= 0.0 || p->max_iter <= 2 * kChunkIters) && p->max_iter > 0;
-    if (spin_mode) {
-        if (!c->stream2[0]) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2[0], hipStreamNonBlocking));
-        HIPCHK(c, hipEventRecord(c->evx[0], s));                       // the first E-step behind the prologue; every later one behind its M-step's tag
-        HIPCHK(c, hipStreamWaitEvent(c->stream2[0], c->evx[0], 0));
-        ++c->spin_calls;
-    }
-    // one launch per iteration (tdlo_iter_fused.hip): iteration k of the call is `M-step (k) ; E-step (k + 1)` in one kernel, behind a plain k_estep for
-    // iteration 0; the registration's last M-step is a k_mstep_chain on its own.  Launch k reads copy k & 1 of state / Y / Yout / nodes and writes the other one.
-    const bool fused_mode = !merged && F == 1 && !paired && !ahead && late == nullptr && c->pair.state == 0 && use_mbox && !spin_mode && !sums_first && !ahead_first &&
-                            fused_iter_eligible(c, c->fh[0]);
+    return 0;
+}
+
+// how the first iteration starts, and whether the loop is the one with one launch per iteration (tdlo_iter_fused.hip): iteration k of the call is
+// `M-step (k) ; E-step (k + 1)` in one kernel, behind a plain k_estep for iteration 0; the registration's last M-step is a k_mstep_chain on its own.
+// Launch k reads copy k & 1 of state / Y / Yout / nodes and writes the other one.
+void FramesCall::choose_loop() {
+    sums_first = paired && !ahead && c->pair.has_sums;
+    ahead_first = ahead;
+    fused_mode = !merged && F == 1 && !paired && !ahead && late == nullptr && c->pair.state == 0 && use_mbox && !sums_first && !ahead_first &&
+                 fused_iter_eligible(c, c->fh[0]);
     if (fused_mode) ++c->fused_calls;
-    auto fused_copy = [&](int k) {
-        FrameDev fc = c->fh[0];           // (as it stands now: host_report_it changes from chunk to chunk)
-        if (k & 1) { double *blk = nodeblk_used; fc.Yout = blk + nc.Yout2; fc.st = (IterState *)(blk + nc.st2); fc.Y = blk + nc.Y2; fc.nodes = blk + nc.nodes2; }
-        return fc;
-    };
-    auto iterate = [&](int n) -> hipError_t {
-        for (int it = 0; it < n; ++it) {
-            ++enqueued;
-            if (fused_mode) {
-                const int k = enqueued - 1;
-                if (k == 0) TDLO_RET(launch_estep_only(fdp, c->fh.data(), 1, 0, s));
-                if (k + 1 < p->max_iter) TDLO_RET(launch_iter_fused(fused_copy(k), fused_copy(k + 1), k, s));
-                else TDLO_RET(launch_mstep_chain_close(fused_copy(k), k, s));
-                continue;
+}
+
+FrameDev FramesCall::fused_copy(int k) const {
+    FrameDev fc = c->fh[0];           // (as it stands now: host_report_it changes from chunk to chunk)
+    if (k & 1) { double *blk = nodeblk_used; fc.Yout = blk + nc.Yout2; fc.st = (IterState *)(blk + nc.st2); fc.Y = blk + nc.Y2; fc.nodes = blk + nc.nodes2; }
+    return fc;
+}
+
+// the next n iterations onto the stream(s)
+hipError_t FramesCall::iterate(int n) {
+    for (int it = 0; it < n; ++it) {
+        ++enqueued;
+        if (fused_mode) {
+            const int k = enqueued - 1;
+            if (k == 0) TDLO_RET(launch_estep_only(fdp, c->fh.data(), 1, 0, s));
+            if (k + 1 < p->max_iter) TDLO_RET(launch_iter_fused(fused_copy(k), fused_copy(k + 1), k, s));
+            else TDLO_RET(launch_mstep_chain_close(fused_copy(k), k, s));
+            continue;
+        }
+        if (sums_first || ahead_first) {
+            const bool from_given = sums_first;
+            sums_first = false; ahead_first = false;
+            // test hook (tdlo_ctx::spec_force_timeout): the M-step launched ahead is told to leave instead of being released, as if it had given up waiting (2 s without the host)
+            if (sg.live) { sg.release(!c->spec_force_timeout); spec_released = true; if (!ahead) ++c->route_count[2]; }      // it is on the stream already: the priors are staged, off it goes
+            else if (from_given) TDLO_RET(launch_mstep_chain(fdp, c->fh.data(), 1, 1, c->fh[0].precision == TDLO_PREC_F64, s));
+            else {          // (ahead, and the waiting M-step was sent away -- no priors after all --: it has cleared its E-step's sums, an ordinary iteration follows it)
+                c->fh[0].late_mstep = 0;
+                TDLO_RET(launch_iteration(fdp, c->fh.data(), 1, s));
             }
-            if (spin_mode) {
-                Slot &sl = c->slots[slots[0]];
-                TDLO_RET(launch_iteration_spin(fdp, c->fh.data(), c->stream2[0], s, enqueued == 1, &sl.spin_ecount, &sl.spin_mtag));
-                continue;
-            }
-            if (sums_first || ahead_first) {
-                const bool from_given = sums_first;
-                sums_first = false; ahead_first = false;
-                if (sg.live) { sg.release(!spec_force_timeout); spec_released = true; if (!ahead) ++c->route_count[2]; }      // it is on the stream already: the priors are staged, off it goes
-                else if (from_given) TDLO_RET(launch_mstep_chain(fdp, c->fh.data(), 1, 1, c->fh[0].precision == TDLO_PREC_F64, s));
-                else {          // (ahead, and the waiting M-step was sent away -- no priors after all --: it has cleared its E-step's sums, an ordinary iteration follows it)
-                    c->fh[0].late_mstep = 0;
-                    TDLO_RET(launch_iteration(fdp, c->fh.data(), 1, s));
-                }
-                c->fh[0].late_mstep = 0;               // (later M-steps find the priors in the node block, where the first one put them)
-                continue;
-            }
-            for (int g = 0; g < NS; ++g) {
-                const FrameDev *fdg = fdp + goff[g], *fhg = c->fh.data() + goff[g];
-                const int Fg = goff[g + 1] - goff[g];
-                if (NS > 1 && !forked && g + 1 < NS) {
-                    // first iteration, kernel by kernel (same kernels, same order as launch_iteration), so that the next group
-                    // can be released when this group's first E-step has drained
-                    if (fhg[0].vis_branch) TDLO_RET(launch_estep_only(fdg, fhg, Fg, 1, gs[g]));
-                    TDLO_RET(launch_estep_only(fdg, fhg, Fg, 0, gs[g]));
-                    TDLO_RET(hipEventRecord(c->evx[g], gs[g]));
-                    TDLO_RET(hipStreamWaitEvent(gs[g + 1], c->evx[g], 0));
-                    TDLO_RET(launch_estep_only(fdg, fhg, Fg, 2, gs[g]));
-                } else {
-                    TDLO_RET(launch_iteration(fdg, fhg, Fg, gs[g], enqueued - 1));      // (this call's count of the registration's iterations: mstep_parity_hint)
-                }
-            }
-            forked = true;
+            c->fh[0].late_mstep = 0;               // (later M-steps find the priors in the node block, where the first one put them)
+            continue;
         }
-        return hipSuccess;
-    };
-    auto join = [&]() -> hipError_t {          // everything enqueued on the other streams so far precedes what follows on the first
-        if (NS < 2 || !forked) return hipSuccess;
-        for (int g = 1; g < NS; ++g) {
-            TDLO_RET(hipEventRecord(c->evj[g - 1], gs[g]));
-            TDLO_RET(hipStreamWaitEvent(s, c->evj[g - 1], 0));
-        }
-        return hipSuccess;
-    };
-    static const bool pool_on = !(getenv("TDLO_BATCH_THREADS") && atoi(getenv("TDLO_BATCH_THREADS")) == 0);
-    bool have_readback = false;            // the results are already in pinned memory (early exit after the first iteration; the mailbox)
-    auto mbox_done = [&](int min_it, bool need_done, bool *done) -> int {     // 0, or an error code
-        unsigned long long w = 0;
-        int wr = mbox_wait(c, s, epoch, min_it, need_done, &w);
-        if (wr == 1 && spec_released) {
-            // The M-step launched ahead of its priors gave up waiting for them (this thread was held up for more than the kernel's 2 s) and left
-            // without touching anything; what was enqueued behind it ran as a registration that does its own first E-step.  The state on the
-            // device says where that stands: the iterations this call believes to be on the stream are made up, the ordinary way.
-            spec_released = false;
-            IterState is;
-            HIPCHK(c, hipMemcpy(&is, c->fh[0].st, sizeof is, hipMemcpyDeviceToHost));
-            int have = is.it;
-            // (ahead: the M-step that left has cleared its E-step's sums -- ordinary iterations from the start)
-            if (!ahead && !is.done && have == 0 && enqueued > 0) { HIPCHK(c, launch_mstep_chain(fdp, c->fh.data(), 1, 1, c->fh[0].precision == TDLO_PREC_F64, s)); have = 1; }
-            for (; !is.done && have < enqueued; ++have) HIPCHK(c, launch_iteration(fdp, c->fh.data(), 1, s));
-            wr = mbox_wait(c, s, epoch, min_it, need_done, &w);
-        }
-        if (wr < 0) return wr;
-        if (wr == 1) return fail(c, TDLO_E_HIP, "the stream drained, but the M-step did not report the state of the registration");
-        *done = (w >> 31) & 1u;
-        return 0;
-    };
-    auto take_mbox = [&](bool events_recorded) -> int {
-        std::memcpy(c->pin, c->mbox, nc.readback * sizeof(double));
-        have_readback = true;
-        if (timing) {
-            if (!events_recorded) { HIPCHK(c, hipEventRecord(c->ev[2], s)); HIPCHK(c, hipEventRecord(c->ev[3], s)); }
-            HIPCHK(c, hipEventSynchronize(c->ev[3]));
-        }
-        return 0;
-    };
-    // a batch whose frames all take k_estep2 and the chain smoother, fixed iteration count: the whole loop as one launch (k_batch_loop)
-    bool persist = merged && c->batch_persist_on && !c->batch_persist_off_once && (p->tol <= 0.0 || p->max_iter <= 2 * kChunkIters) && p->max_iter > 0 &&
-                   p->precision == TDLO_PREC_F32 && !p->include_lle && M <= 63;
-    for (int i = 0; i < F && persist; ++i) persist = c->fh[i].estep2 != 0 && !c->fh[i].vis_branch && !c->fh[i].mstep_dense;
-    if (persist) {
-        const size_t words = batch_loop_ctl_words(F);
-        if (words > c->batch_ctl_words) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (c->batch_ctl) (void)hipFree(c->batch_ctl);
-            c->batch_ctl = nullptr; c->batch_ctl_words = 0;
-            HIPCHK(c, hipMalloc((void **)&c->batch_ctl, words * sizeof(unsigned)));
-            c->batch_ctl_words = words;
-        }
-        HIPCHK(c, hipMemsetAsync(c->batch_ctl, 0, words * sizeof(unsigned), s));
-        HIPCHK(c, launch_batch_loop(fdp, c->fh.data(), F, p->max_iter, c->batch_ctl, s));
-        ++c->batch_loop_calls;
-    } else
-    if (p->tol <= 0.0 || p->max_iter <= 2 * kChunkIters) {
-        // fixed iteration count: enqueue everything, no host involvement.  Several stream groups and enough iterations: the first
-        // iteration (which releases the groups one after the other) from this thread, the rest of every group from a thread of its own.
-        if (NS > 1 && pool_on && p->max_iter >= 8) {
-            HIPCHK(c, iterate(1));
-            if (!c->pool) { c->pool = new EnqueuePool; c->pool->start(kBatchStreams - 1, c->device); }
-            const int rest = p->max_iter - 1;
-            const bool chain = c->batch_chain != 0 && !c->fh[0].vis_branch;
-            const bool chain_all = c->batch_chain == 1;
-            auto chain_at = [&](int it) { return chain_all || it == 4 || it == 10 || it == 22 || it == 34; };      // (iterations of the enqueueing loop: the call's iteration it + 1)
-            if (chain)
-                for (int g = 0; g < NS; ++g) for (int r = 0; r < tdlo_ctx::kChainRing; ++r)
-                    if (!c->evc[g][r]) HIPCHK(c, hipEventCreateWithFlags(&c->evc[g][r], hipEventDisableTiming));
-            // (chain) how far every group's enqueueing thread has come: recorded[g] = iterations whose E-step event group g has recorded, waited[g] =
-            // iterations whose event of group g-1 group g has put a wait on -- a thread records event it % ring only when the group behind it has
-            // put its wait on the record of iteration it - ring, and waits on an event only when it has been recorded for this iteration
-            std::atomic<int> recorded[kBatchStreams], waited[kBatchStreams];
-            std::atomic<bool> broken{false};
-            for (int g = 0; g < kBatchStreams; ++g) { recorded[g].store(0); waited[g].store(0); }
-            const int prc = c->pool->run([&](int g) -> int {
-                if (g >= NS) return 0;
-                const FrameDev *fdg = fdp + goff[g], *fhg = c->fh.data() + goff[g];
-                const int Fg = goff[g + 1] - goff[g];
-                if (!chain) {
-                    for (int it = 0; it < rest; ++it) { const hipError_t e = launch_iteration(fdg, fhg, Fg, gs[g], 1 + it); if (e != hipSuccess) return (int)e; }
-                    return 0;
-                }
-                auto bail = [&](hipError_t e) { broken.store(true); return (int)e; };
-                for (int it = 0; it < rest; ++it) {
-                    hipError_t e;
-                    if (!chain_at(it)) { if ((e = launch_iteration(fdg, fhg, Fg, gs[g], 1 + it)) != hipSuccess) return bail(e); continue; }
-                    // (the event of a chained iteration: every iteration -> a ring with the hazard check below; the four phase-setting iterations -> one event each)
-                    const int slot = chain_all ? it % tdlo_ctx::kChainRing : (it == 4 ? 0 : (it == 10 ? 1 : (it == 22 ? 2 : 3)));
-                    if (g > 0) {            // behind the E-step of the group in front, same iteration
-                        while (recorded[g - 1].load(std::memory_order_acquire) <= it) { if (broken.load()) return 0; std::this_thread::yield(); }
-                        if ((e = hipStreamWaitEvent(gs[g], c->evc[g - 1][slot], 0)) != hipSuccess) return bail(e);
-                        waited[g].store(it + 1, std::memory_order_release);
-                    }
-                    if ((e = launch_estep_only(fdg, fhg, Fg, 0, gs[g])) != hipSuccess) return bail(e);
-                    if (g + 1 < NS) {
-                        while (chain_all && waited[g + 1].load(std::memory_order_acquire) < it + 1 - tdlo_ctx::kChainRing) { if (broken.load()) return 0; std::this_thread::yield(); }
-                        if ((e = hipEventRecord(c->evc[g][slot], gs[g])) != hipSuccess) return bail(e);
-                        recorded[g].store(it + 1, std::memory_order_release);
-                    }
-                    if ((e = launch_estep_only(fdg, fhg, Fg, 2, gs[g])) != hipSuccess) return bail(e);
-                }
-                return 0;
-            });
-            if (prc) return fail(c, TDLO_E_HIP, std::string("batch enqueue: ") + hipGetErrorString((hipError_t)prc));
-        } else {
-            HIPCHK(c, iterate(p->max_iter));
-        }
-        if (use_mbox) {
-            if (timing) { HIPCHK(c, hipEventRecord(c->ev[2], s)); HIPCHK(c, hipEventRecord(c->ev[3], s)); }      // behind the last iteration, as the read-back path does
-            bool done = false;
-            if ((rc = mbox_done(0, true, &done))) return rc;
-            if ((rc = take_mbox(true))) return rc;
-        }
-    } else if (use_mbox) {
-        // early exit (trackdlo.cpp:424-428), decided on the device and read from the mailbox: the first iteration is checked eagerly (a tracker
-        // in steady state converges in it) -- or the first `iter_hint` iterations, when the caller knows how many the registration took last time
-        // (tdlo_ctx::iter_hint) --; after that iterations go out in chunks of 1, 1, 2, 4, 4, ... and the host looks at the progress
-        // word of the chunk BEFORE the one it has just enqueued, so that the GPU never idles (kernels of a finished registration are no-ops)
-        const int first = std::max(1, std::min(std::min(iter_hint, kIterHintMax), p->max_iter));
-        c->fh[0].host_report_it = first;       // (the frame descriptor travels by value with every launch of the one-frame kernels)
-        HIPCHK(c, iterate(first));
-        if (!late && c->pair.state == 2 && c->pair.has_sums && c->spec_on && c->mbox_on && !timing && c->pair.p.max_iter > 0) {
-            // tracking_step's main registration starts with its M-step (PairNext::has_sums): launched NOW, behind this registration's first
-            // iteration -- a steady-state tracker converges in it -- and ahead of the priors it needs (FrameDev::spec_flag)
-            tdlo_ctx::PairNext &pn = c->pair;
-            Slot &sl = c->slots[slots[0]];
-            const NodeCarve nc2(pn.M);
-            if ((rc = ensure_late(c, 4 * (size_t)pn.M + 2))) return rc;         // (may drain the stream: before anything waits on it)
-            unsigned e2 = ++c->mbox_epoch;
-            if (e2 == 0) e2 = ++c->mbox_epoch;
-            FrameDev fs = pn.f;
-            fs.reuse_sorted = 1; fs.has_priors = 1;
-            fs.late_aJ = c->late_buf; fs.late_aYd = c->late_buf + pn.M;
-            fs.host_out = c->mbox; fs.host_prog = (unsigned long long *)(c->mbox + c->mbox_doubles - 2); fs.host_epoch = e2;
-            fs.host_report_it = (pn.p.tol <= 0.0 || pn.p.max_iter <= 2 * kChunkIters) ? 0 : std::max(1, std::min(std::min(c->iter_hint_next, kIterHintMax), pn.p.max_iter));
-            fs.spec_flag = spec_flag_word(c); fs.spec_prev = c->fh[0].st; fs.spec_epoch = e2;
-            if (c->lle_next_on && pn.M <= 256 && sl.hb_next_cap >= pn.M) fs.lle_next = sl.hb_next;      // (as the registration itself will set it, above)
-            HIPCHK(c, launch_mstep_chain((const FrameDev *)(sl.nodeblk2 + nc2.fdev), &fs, 1, 1, fs.precision == TDLO_PREC_F64, s));
-            pn.spec = 1; pn.spec_epoch = e2;
-        } else if (!late && c->pair.state == 3) {
-            // tracking_step with hidden nodes: the main registration's first iteration goes out NOW, on the second stream, beside this registration
-            c->pair.state = 0; c->pair.ahead = false;
-            if (c->spec_on && c->mbox_on && !timing && c->pair.slot == slots[0] && (rc = launch_ahead(c))) { spec_abort(c); return rc; }
-        }
-        g_prof.mark(g_prof.base + 4);
-        bool stop = false;
-        if ((rc = mbox_done(first, false, &stop))) { spec_abort(c); return rc; }
-        if (!stop && !c->pair.ahead) c->pair.spec = 0;           // (this registration goes on: the waiting M-step has seen that and left; one launched AHEAD keeps waiting)
-        g_prof.mark(g_prof.base + 5);
-        int launched = first, chunk = 0;
-        while (launched < p->max_iter && !stop) {
-            const int n = std::min(chunk < 2 ? 1 : (chunk == 2 ? 2 : kChunkIters), p->max_iter - launched);
-            c->fh[0].host_report_it = launched + n;      // the chunk's last M-step reports (a store to host memory costs an M-step ~1 us: not every one)
-            HIPCHK(c, iterate(n));
-            launched += n;
-            if ((rc = mbox_done(launched - n, false, &stop))) return rc;
-            ++chunk;
-        }
-        if (!stop && (rc = mbox_done(0, true, &stop))) return rc;      // the last chunk reaches max_iter, which ends the registration
-        if ((rc = take_mbox(false))) return rc;
-    } else {
-        // early exit (trackdlo.cpp:424-428) is decided on the device; kernels of finished frames are
-        // no-ops.  To avoid enqueueing up to max_iter of them, iterations go out in chunks and the
-        // `done` flags of chunk i are inspected while chunk i+1 is already running (the GPU never idles).
-        IterState *flags = (IterState *)(c->pin + (size_t)F * nc.upload + fdd);     // pinned, 2 x F entries (one frame) ...
-        double *fl_rb = c->pin + (size_t)F * nc.upload + fdd;                        // ... or 2 x F read-back blocks (batches)
-        // A tracker in steady state converges in its first iteration (launch tolerance 2e-4): the first iteration is followed by the
-        // read-back block itself (results + state) and a host sync; if every frame is done the call is over -- no second chunk of
-        // no-op kernels, no separate flag copies (two no-op kernels and two 4 us copies per registration: 20 us of a 90 us call).
-        HIPCHK(c, iterate(1));
-        HIPCHK(c, join());
-        if (timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        if (merged) HIPCHK(c, hipMemcpyAsync(c->pin, c->xfer + (size_t)F * up + fdd, (size_t)F * nc.readback * sizeof(double), hipMemcpyDeviceToHost, s));
-        else HIPCHK(c, hipMemcpyAsync(c->pin, nodeblk_used + nc.Yout, nc.readback * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (timing) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, wait_stream(s));
-        {
-            bool all = true;
-            for (int i = 0; i < F; ++i) {
-                IterState is;
-                std::memcpy(&is, c->pin + (size_t)i * (merged ? nc.readback : nc.upload) + (nc.st - nc.Yout), sizeof is);
-                all = all && is.done != 0;
-            }
-            have_readback = all;
-        }
-        int launched = 1, chunk = 0;
-        bool stop = have_readback;
-        while (launched < p->max_iter && !stop) {
-            const int n = std::min(chunk < 2 ? 1 : (chunk == 2 ? 2 : kChunkIters), p->max_iter - launched);      // 1, 1, 2, 4, 4, ...
-            HIPCHK(c, iterate(n));
-            launched += n;
-            const int slotp = chunk & 1;
-            if (merged) {           // the whole read-back area (Yout + IterState per frame) in one copy, after the groups have joined
-                HIPCHK(c, join());
-                HIPCHK(c, hipMemcpyAsync(fl_rb + (size_t)slotp * F * nc.readback, c->xfer + (size_t)F * up + fdd, (size_t)F * nc.readback * sizeof(double),
-                                         hipMemcpyDeviceToHost, s));
+        for (int g = 0; g < NS; ++g) {
+            const FrameDev *fdg = fdp + goff[g], *fhg = c->fh.data() + goff[g];
+            const int Fg = goff[g + 1] - goff[g];
+            if (NS > 1 && !forked && g + 1 < NS) {
+                // first iteration, kernel by kernel (same kernels, same order as launch_iteration), so that the next group
+                // can be released when this group's first E-step has drained
+                if (fhg[0].vis_branch) TDLO_RET(launch_estep_only(fdg, fhg, Fg, 1, gs[g]));
+                TDLO_RET(launch_estep_only(fdg, fhg, Fg, 0, gs[g]));
+                TDLO_RET(hipEventRecord(c->evx[g], gs[g]));
+                TDLO_RET(hipStreamWaitEvent(gs[g + 1], c->evx[g], 0));
+                TDLO_RET(launch_estep_only(fdg, fhg, Fg, 2, gs[g]));
             } else {
-                HIPCHK(c, hipMemcpyAsync(&flags[slotp * F], c->fh[0].st, sizeof(IterState), hipMemcpyDeviceToHost, s));
+                TDLO_RET(launch_iteration(fdg, fhg, Fg, gs[g], enqueued - 1));      // (this call's count of the registration's iterations: mstep_parity_hint)
             }
-            HIPCHK(c, hipEventRecord(c->ev[4 + slotp], s));
-            if (chunk > 0) {
-                const int prev = (chunk - 1) & 1;
-                HIPCHK(c, hipEventSynchronize(c->ev[4 + prev]));
-                bool all = true;
-                for (int i = 0; i < F; ++i) {
-                    IterState is;
-                    if (merged) std::memcpy(&is, fl_rb + ((size_t)prev * F + i) * nc.readback + (nc.st - nc.Yout), sizeof is);
-                    else is = flags[prev * F + i];
-                    all = all && is.done != 0;
-                }
-                stop = all;
-            }
-            ++chunk;
+        }
+        forked = true;
+    }
+    return hipSuccess;
+}
+
+// everything enqueued on the other streams so far precedes what follows on the first
+hipError_t FramesCall::join() {
+    if (NS < 2 || !forked) return hipSuccess;
+    for (int g = 1; g < NS; ++g) {
+        TDLO_RET(hipEventRecord(c->evj[g - 1], gs[g]));
+        TDLO_RET(hipStreamWaitEvent(s, c->evj[g - 1], 0));
+    }
+    return hipSuccess;
+}
+
+// waits for the mailbox to report min_it iterations (need_done: the end of the registration); *done: the registration has ended
+int FramesCall::mbox_done(int min_it, bool need_done, bool *done) {
+    unsigned long long w = 0;
+    int wr = mbox_wait(c, s, epoch, min_it, need_done, &w);
+    if (wr == 1 && spec_released) {
+        // The M-step launched ahead of its priors gave up waiting for them (this thread was held up for more than the kernel's 2 s) and left
+        // without touching anything; what was enqueued behind it ran as a registration that does its own first E-step.  The state on the
+        // device says where that stands: the iterations this call believes to be on the stream are made up, the ordinary way.
+        spec_released = false;
+        IterState is;
+        HIPCHK(c, hipMemcpy(&is, c->fh[0].st, sizeof is, hipMemcpyDeviceToHost));
+        int have = is.it;
+        // (ahead: the M-step that left has cleared its E-step's sums -- ordinary iterations from the start)
+        if (!ahead && !is.done && have == 0 && enqueued > 0) { HIPCHK(c, launch_mstep_chain(fdp, c->fh.data(), 1, 1, c->fh[0].precision == TDLO_PREC_F64, s)); have = 1; }
+        for (; !is.done && have < enqueued; ++have) HIPCHK(c, launch_iteration(fdp, c->fh.data(), 1, s));
+        wr = mbox_wait(c, s, epoch, min_it, need_done, &w);
+    }
+    if (wr < 0) return wr;
+    if (wr == 1) return fail(c, TDLO_E_HIP, "the stream drained, but the M-step did not report the state of the registration");
+    *done = (w >> 31) & 1u;
+    return 0;
+}
+
+// the mailbox's read-back block into the staging buffer, where the results are read from
+int FramesCall::take_mbox(bool events_recorded) {
+    std::memcpy(c->pin, c->mbox, nc.readback * sizeof(double));
+    have_readback = true;
+    if (timing) {
+        if (!events_recorded) { HIPCHK(c, hipEventRecord(c->ev[2], s)); HIPCHK(c, hipEventRecord(c->ev[3], s)); }
+        HIPCHK(c, hipEventSynchronize(c->ev[3]));
+    }
+    return 0;
+}
+
+// fixed iteration count: enqueue everything, no host involvement.  Several stream groups and enough iterations: the first
+// iteration (which releases the groups one after the other) from this thread, the rest of every group from a thread of its own.
+int FramesCall::drive_fixed() {
+    static const bool pool_on = !(getenv("TDLO_BATCH_THREADS") && atoi(getenv("TDLO_BATCH_THREADS")) == 0);
+    int rc;
+    if (NS > 1 && pool_on && p->max_iter >= 8) {
+        HIPCHK(c, iterate(1));
+        if (!c->pool) { c->pool = new EnqueuePool; c->pool->start(kBatchStreams - 1, c->device); }
+        const int rest = p->max_iter - 1;
+        const int prc = c->pool->run([&](int g) -> int {
+            if (g >= NS) return 0;
+            const FrameDev *fdg = fdp + goff[g], *fhg = c->fh.data() + goff[g];
+            const int Fg = goff[g + 1] - goff[g];
+            for (int it = 0; it < rest; ++it) { const hipError_t e = launch_iteration(fdg, fhg, Fg, gs[g], 1 + it); if (e != hipSuccess) return (int)e; }
+            return 0;
+        });
+        if (prc) return fail(c, TDLO_E_HIP, std::string("batch enqueue: ") + hipGetErrorString((hipError_t)prc));
+    } else {
+        HIPCHK(c, iterate(p->max_iter));
+    }
+    if (use_mbox) {
+        if (timing) { HIPCHK(c, hipEventRecord(c->ev[2], s)); HIPCHK(c, hipEventRecord(c->ev[3], s)); }      // behind the last iteration, as the read-back path does
+        bool done = false;
+        if ((rc = mbox_done(0, true, &done))) return rc;
+        if ((rc = take_mbox(true))) return rc;
+    }
+    return 0;
+}
+
+// tracking_step's main registration starts with its M-step (PairNext::has_sums): launched NOW, behind the pre-processing registration's first
+// iteration -- a steady-state tracker converges in it -- and ahead of the priors it needs (FrameDev::spec_flag)
+int FramesCall::launch_paired_mstep_ahead() {
+    tdlo_ctx::PairNext &pn = c->pair;
+    Slot &sl = slot0();
+    const NodeCarve nc2(pn.M);
+    const int rc = ensure_late(c, 4 * (size_t)pn.M + 2);         // (may drain the stream: before anything waits on it)
+    if (rc) return rc;
+    const unsigned e2 = next_mbox_epoch(c);
+    const bool leaves_lle = c->lle_next_on && pn.M <= 256 && sl.hb_next_cap >= pn.M;      // (as the registration itself will set it, choose_routes)
+    const FrameDev fs = spec_mstep_descriptor(c, pn, e2, c->fh[0].st, leaves_lle ? sl.hb_next : nullptr);
+    HIPCHK(c, launch_mstep_chain((const FrameDev *)(sl.nodeblk2 + nc2.fdev), &fs, 1, 1, fs.precision == TDLO_PREC_F64, s));
+    pn.spec = 1; pn.spec_epoch = e2;
+    return 0;
+}
+
+// early exit (trackdlo.cpp:424-428), decided on the device and read from the mailbox: the first iteration is checked eagerly (a tracker
+// in steady state converges in it) -- or the first `iter_hint` iterations, when the caller knows how many the registration took last time
+// (tdlo_ctx::iter_hint) --; after that iterations go out in chunks of 1, 1, 2, 4, 4, ... and the host looks at the progress
+// word of the chunk BEFORE the one it has just enqueued, so that the GPU never idles (kernels of a finished registration are no-ops)
+int FramesCall::drive_mailbox() {
+    int rc;
+    const int first = std::max(1, std::min(std::min(iter_hint, kIterHintMax), p->max_iter));
+    c->fh[0].host_report_it = first;       // (the frame descriptor travels by value with every launch of the one-frame kernels)
+    HIPCHK(c, iterate(first));
+    if (!late && c->pair.state == 2 && c->pair.has_sums && c->spec_on && c->mbox_on && !timing && c->pair.p.max_iter > 0) {
+        if ((rc = launch_paired_mstep_ahead())) return rc;
+    } else if (!late && c->pair.state == 3) {
+        // tracking_step with hidden nodes: the main registration's first iteration goes out NOW, on the second stream, beside this registration
+        c->pair.state = 0; c->pair.ahead = false;
+        if (c->spec_on && c->mbox_on && !timing && c->pair.slot == slots[0] && (rc = launch_ahead(c))) { spec_abort(c); return rc; }
+    }
+    g_prof.mark(g_prof.base + 4);
+    bool stop = false;
+    if ((rc = mbox_done(first, false, &stop))) { spec_abort(c); return rc; }
+    if (!stop && !c->pair.ahead) c->pair.spec = 0;           // (this registration goes on: the waiting M-step has seen that and left; one launched AHEAD keeps waiting)
+    g_prof.mark(g_prof.base + 5);
+    int launched = first;
+    for (int chunk = 0; launched < p->max_iter && !stop; ++chunk) {
+        const int n = chunk_iters(chunk, p->max_iter - launched);
+        c->fh[0].host_report_it = launched + n;      // the chunk's last M-step reports (a store to host memory costs an M-step ~1 us: not every one)
+        HIPCHK(c, iterate(n));
+        launched += n;
+        if ((rc = mbox_done(launched - n, false, &stop))) return rc;
+    }
+    if (!stop && (rc = mbox_done(0, true, &stop))) return rc;      // the last chunk reaches max_iter, which ends the registration
+    return take_mbox(false);
+}
+
+// early exit (trackdlo.cpp:424-428) is decided on the device; kernels of finished frames are
+// no-ops.  To avoid enqueueing up to max_iter of them, iterations go out in chunks and the
+// `done` flags of chunk i are inspected while chunk i+1 is already running (the GPU never idles).
+int FramesCall::drive_polled() {
+    IterState *flags = (IterState *)(c->pin + (size_t)F * nc.upload + fdd);     // pinned, 2 x F entries (one frame) ...
+    double *fl_rb = c->pin + (size_t)F * nc.upload + fdd;                        // ... or 2 x F read-back blocks (batches)
+    const double *results_dev = merged ? c->xfer + (size_t)F * up + fdd : nodeblk_used + nc.Yout;
+    // A tracker in steady state converges in its first iteration (launch tolerance 2e-4): the first iteration is followed by the
+    // read-back block itself (results + state) and a host sync; if every frame is done the call is over -- no second chunk of
+    // no-op kernels, no separate flag copies (two no-op kernels and two 4 us copies per registration: 20 us of a 90 us call).
+    HIPCHK(c, iterate(1));
+    HIPCHK(c, join());
+    if (timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
+    HIPCHK(c, hipMemcpyAsync(c->pin, results_dev, (size_t)F * nc.readback * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (timing) HIPCHK(c, hipEventRecord(c->ev[3], s));
+    HIPCHK(c, wait_stream(s));
+    have_readback = every_frame_done(c->pin, rstride(), nc, F);
+    int launched = 1;
+    bool stop = have_readback;
+    for (int chunk = 0; launched < p->max_iter && !stop; ++chunk) {
+        const int n = chunk_iters(chunk, p->max_iter - launched);
+        HIPCHK(c, iterate(n));
+        launched += n;
+        const int slotp = chunk & 1;
+        if (merged) {           // the whole read-back area (Yout + IterState per frame) in one copy, after the groups have joined
+            HIPCHK(c, join());
+            HIPCHK(c, hipMemcpyAsync(fl_rb + (size_t)slotp * F * nc.readback, results_dev, (size_t)F * nc.readback * sizeof(double), hipMemcpyDeviceToHost, s));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(&flags[slotp], c->fh[0].st, sizeof(IterState), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(c, hipEventRecord(c->ev[4 + slotp], s));
+        if (chunk > 0) {
+            const int prev = (chunk - 1) & 1;
+            HIPCHK(c, hipEventSynchronize(c->ev[4 + prev]));
+            stop = merged ? every_frame_done(fl_rb + (size_t)prev * F * nc.readback, nc.readback, nc, F) : flags[prev].done != 0;
         }
     }
-    const size_t rstride = merged ? nc.readback : nc.upload;
+    return 0;
+}
+
+// the results into the staging buffer, unless the loop's driver has them there already
+int FramesCall::read_back() {
     if (!have_readback) {
         HIPCHK(c, join());
         if (timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
@@ -1472,81 +1476,57 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
         HIPCHK(c, wait_stream(s));
     }
     c->last_F = F;
+    return 0;
+}
+
+// The two verdicts after which the call is run again, once, another way -- inputs, Y and sigma2 are untouched so far.  true: *rc is the repeat's result.
+bool FramesCall::repeat(int *rc) {
+    auto drop_what_was_launched_ahead = [&] {
+        if (c->pair.ahead) { spec_abort(c); c->pair.state = 0; c->pair.ahead = false; }      // (the repeat is another call: the main registration takes the ordinary route)
+        else c->pair.spec = 0;             // (a paired M-step launched ahead has seen the error status and left)
+    };
     // The banded L D L^T takes no pivots: a system that is not positive definite in floating point (an indefinite H_override; a chain the gap
     // test let through and rounding did not) ends its registration with TDLO_E_NUMERIC.  The reference's solver is a general one
-    // (trackdlo.cpp:415), so the call is repeated once on the dense pivoted kernels -- inputs, Y and sigma2 are untouched so far -- and only
-    // their verdict is reported.
-    if (p->include_lle && c->fh[0].lle_band && !c->lle_dense_once) {
-        bool numeric = false;
-        for (int i = 0; i < F; ++i) {
-            IterState is;
-            std::memcpy(&is, c->pin + (size_t)i * rstride + (nc.st - nc.Yout), sizeof is);
-            numeric = numeric || is.status == TDLO_E_NUMERIC;
-        }
-        if (numeric) {
-            if (c->pair.ahead) { spec_abort(c); c->pair.state = 0; c->pair.ahead = false; }      // (the repeat is another call: the main registration takes the ordinary route)
-            else c->pair.spec = 0;             // (a paired M-step launched ahead has seen the error status and left)
-            c->lle_dense_once = true;
-            ++c->band_retries;
-            const int rr = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
-            c->lle_dense_once = false;
-            return rr;
-        }
-    }
-    // the loop kernel gave a wait up (2 s; a frame ended with TDLO_E_EXCHANGE): the call is repeated once on the launch-per-step loop -- inputs, Y and sigma2 are untouched so far
-    if (persist) {
-        bool gave_up = false;
-        for (int i = 0; i < F && !gave_up; ++i) {
-            IterState is;
-            std::memcpy(&is, c->pin + (size_t)i * rstride + (nc.st - nc.Yout), sizeof is);
-            gave_up = is.status == TDLO_E_EXCHANGE;
-        }
-        if (gave_up) {
-            ++c->batch_loop_fallbacks;
-            std::fprintf(stderr, "trackdlo_hip: a wait inside the batch loop kernel gave up after 2 s (device %d); the call is repeated with a launch per step\n", c->device);
-            for (int i = 0; i < F; ++i) c->slots[slots[i]].sorted_valid = false;
-            c->batch_persist_off_once = true;
-            const int rr = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late);
-            c->batch_persist_off_once = false;
-            return rr;
-        }
+    // (trackdlo.cpp:415), so the call is repeated once on the dense pivoted kernels and only their verdict is reported.
+    if (p->include_lle && c->fh[0].lle_band && !c->lle_dense_once && any_frame_ended_with(TDLO_E_NUMERIC, c->pin, rstride(), nc, F)) {
+        drop_what_was_launched_ahead();
+        c->lle_dense_once = true;
+        ++c->band_retries;
+        *rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
+        c->lle_dense_once = false;
+        return true;
     }
     // fp64 mode: the E-step's range check runs against limits that follow sigma (IterState::sh_boost: finer sums while sigma is small).  The extent
     // behind them is a heuristic (D_eff = 2 (0.4 m + 2 sigma)): a registration whose shares exceed it -- nodes dragged far by priors while sigma is
-    // small -- would have passed under the coarse limits.  It is not failed for the boost: the call is repeated ONCE without it (inputs, Y, sigma2
-    // untouched so far), and only that verdict is reported.
-    if (p->precision == TDLO_PREC_F64 && !c->boost_off_once && p->max_iter > 0) {
-        bool numeric = false;
-        for (int i = 0; i < F && !numeric; ++i) {
-            IterState is;
-            std::memcpy(&is, c->pin + (size_t)i * rstride + (nc.st - nc.Yout), sizeof is);
-            numeric = is.status == TDLO_E_NUMERIC;
-        }
-        if (numeric) {
-            if (c->pair.ahead) { spec_abort(c); c->pair.state = 0; c->pair.ahead = false; }
-            else c->pair.spec = 0;
-            c->boost_off_once = true;
-            ++c->boost_retries;
-            for (int i = 0; i < F; ++i) c->slots[slots[i]].sorted_valid = false;
-            const int rr = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late);      // (late priors: formed again from the same guide nodes)
-            c->boost_off_once = false;
-            return rr;
-        }
+    // small -- would have passed under the coarse limits.  It is not failed for the boost: the call is repeated ONCE without it, and only that
+    // verdict is reported.
+    if (p->precision == TDLO_PREC_F64 && !c->boost_off_once && p->max_iter > 0 && any_frame_ended_with(TDLO_E_NUMERIC, c->pin, rstride(), nc, F)) {
+        drop_what_was_launched_ahead();
+        c->boost_off_once = true;
+        ++c->boost_retries;
+        for (int i = 0; i < F; ++i) c->slots[slots[i]].sorted_valid = false;
+        *rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late);      // (late priors: formed again from the same guide nodes)
+        c->boost_off_once = false;
+        return true;
     }
+    return false;
+}
+
+// nodes, sigma2 and statistics to the caller; the call's verdict
+int FramesCall::results_out(std::chrono::steady_clock::time_point t_host0) {
     float loop_ms = 0, total_ms = 0;
     if (timing) { hipEventElapsedTime(&loop_ms, c->ev[1], c->ev[2]); hipEventElapsedTime(&total_ms, c->ev[0], c->ev[3]); }
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
     int worst = 0;
     for (int i = 0; i < F; ++i) {
-        const double *rb = c->pin + (size_t)i * rstride;
-        IterState is;
-        std::memcpy(&is, rb + (nc.st - nc.Yout), sizeof is);
+        const double *rb = c->pin + (size_t)i * rstride();
+        IterState is = readback_state(c->pin, rstride(), nc, i);
         if (is.status == 0 || is.status == TDLO_E_NUMERIC) {
             if (p->max_iter > 0 && is.it > 0) std::memcpy(Y + (size_t)i * 3 * M, rb, sizeof(double) * 3 * M);
             sigma2[i] = is.sigma2;
         }
         if (lle_next && i == 0 && is.status == 0 && is.done != 0 && is.it > 0) {      // (the finishing M-step has formed H of exactly these nodes)
-            Slot &sl = c->slots[slots[0]];
+            Slot &sl = slot0();
             sl.hb_next_Y.assign(Y, Y + 3 * (size_t)M);
             sl.hb_next_valid = true;
         }
@@ -1572,6 +1552,37 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
     if (worst == TDLO_E_EMPTY) return fail(c, worst, "every point was pruned (no point within 0.1 m of a node, trackdlo.cpp:190)");
     if (worst == TDLO_E_NUMERIC) return fail(c, worst, "non-finite or non-positive sigma2, or singular M-step system");
     return TDLO_OK;
+}
+
+// Shared driver of tdlo_cpd_lle_resident / _batch.
+int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
+               const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats,
+               const LatePriors *late) {
+    const auto t_host0 = std::chrono::steady_clock::now();
+    int rc = check_params(c, M, p);
+    if (rc) return rc;
+    const int iter_hint = c->iter_hint_on ? c->iter_hint : 0;
+    if (!c->iter_hint_on) c->iter_hint_next = 0;
+    c->iter_hint = 0;
+    if (late && F != 1) return fail(c, TDLO_E_INVALID, "late priors: one frame per call");
+    if (F < 1 || F > c->cfg.max_frames) return fail(c, TDLO_E_INVALID, "bad frame count");
+    FramesCall k(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late, iter_hint);
+    if ((rc = k.size_staging())) return rc;             // the pinned staging buffer, a batch's transfer buffer
+    k.recognise_pair();                                 // tracking_step's second registration, set up (or begun) by the first one's call
+    if ((rc = k.stage_frames())) return rc;             // upload blocks and descriptors; a batch's kernels
+    if ((rc = k.choose_routes())) return rc;            // tracking_step's short cuts; late priors that cannot wait; the sort reused per launch
+    if ((rc = k.open_mailbox())) return rc;             // one frame on a one-workgroup M-step reports through pinned host memory
+    if ((rc = k.upload_and_prologue())) return rc;      // blocks to the device; prune, sort, set-up
+    if ((rc = k.stage_late_priors())) return rc;        // priors formed beside the set-up kernel
+    if ((rc = k.fork_streams())) return rc;             // a batch's stream groups
+    k.choose_loop();                                    // how the first iteration starts; one launch per iteration or two
+    if (k.fixed_count()) rc = k.drive_fixed();          // the EM loop: everything enqueued up front,
+    else if (k.use_mbox) rc = k.drive_mailbox();        // ... early exit read from the mailbox,
+    else rc = k.drive_polled();                         // ... or polled by copies of the frames' state
+    if (rc) return rc;
+    if ((rc = k.read_back())) return rc;                // results into the staging buffer
+    if (k.repeat(&rc)) return rc;                       // banded solve -> dense kernels; fp64 sums without the boost
+    return k.results_out(t_host0);
 }
 
 }  // namespace
@@ -1665,8 +1676,6 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->own_comm) { const RcclApi *r = rccl_api(nullptr, nullptr); if (r) r->CommDestroy(c->own_comm); }
     for (auto &e : c->evx) if (e) hipEventDestroy(e);
     for (auto &e : c->evj) if (e) hipEventDestroy(e);
-    for (auto &row : c->evc) for (auto &e : row) if (e) hipEventDestroy(e);
-    if (c->batch_ctl) (void)hipFree(c->batch_ctl);
     for (auto &q : c->stream2) if (q) hipStreamDestroy(q);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -2782,9 +2791,7 @@ long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
     if (!c || which < 0 || which > 14) return -1;
     if (which == 14) return c->fused_calls;
-    if (which == 13) return c->batch_loop_fallbacks;
-    if (which == 12) return c->batch_loop_calls;
-    if (which == 11) return c->spin_calls;
+    if (which >= 11 && which <= 13) return 0;      // (belonged to experiments that were removed; not reused)
     if (which == 10) return c->boost_retries;
     if (which == 9) return c->estep2_frames;
     if (which == 8) return c->cloud_vis_rides;

@@ -287,7 +287,7 @@ template <int NT> __device__ __forceinline__ void acc_clear_other(const FrameDev
 }
 
 // fp64 mode: the extra binary digits (IterState::sh_boost) of the fixed-point sums of the E-step that follows an iteration at sigma2.  Every M-step that
-// publishes a new sigma2 calls this -- set_iter_consts and the inline tails of k_mstep_chain (and k_batch_loop, which runs its body), k_mstep_chain_long and
+// publishes a new sigma2 calls this -- set_iter_consts and the inline tails of k_mstep_chain, k_mstep_chain_long and
 // k_mstep_band -- so that the resolution follows sigma on every route.
 __device__ __forceinline__ int acc_boost(const FrameDev &f, double sigma2) {
     // fp64 mode: the resolution of the fixed-point sums follows sigma.  FrameDev::acc_sh is sized for point-node distances up to twice the chain's
@@ -462,16 +462,6 @@ __device__ __forceinline__ void host_publish_from(const FrameDev &f, const doubl
 
 __device__ __forceinline__ void host_publish(const FrameDev &f, IterState *st, int lane, bool fresh) { host_publish_from<false>(f, nullptr, st, lane, fresh); }
 __device__ __forceinline__ void host_publish_at(const FrameDev &f, const double *Yout, IterState *st, int lane, bool fresh) { host_publish_from<true>(f, Yout, st, lane, fresh); }
-
-// ---- spin-ahead loop (FrameDev::spin_on): bounded wait of ONE thread for a word of `sync` to take a value (agent scope); false: 2 s passed
-__device__ __forceinline__ bool spin_wait_word(const unsigned *word, unsigned want) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();      // 100 MHz
-    while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) return false;
-    }
-    return true;
-}
 
 // ---- one-shot exchange of the N-split: peer-written inboxes (xGMI peer stores on a multi-GPU node), system scope ---------
 // payload: relaxed system-scope stores -> release fence (system) -> flag store; reader: relaxed poll of the flag ->

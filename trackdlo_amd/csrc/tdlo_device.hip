@@ -1700,18 +1700,6 @@ hipError_t launch_iteration(const FrameDev *fd, const FrameDev *fh, int F, hipSt
     return e;
 }
 
-hipError_t launch_iteration_spin(const FrameDev *fd, FrameDev *fh, hipStream_t s_e, hipStream_t s_m, bool first, unsigned *ecount, unsigned *mtag) {
-    FrameDev &f = fh[0];
-    f.spin_on = 1;
-    f.spin_first = first ? 1 : 0; f.spin_wait = *mtag; f.spin_signal = 0;             // E-step: behind the M-step that stored the tag in front of it
-    TDLO_TRY(launch_estep_T<float>(fd, fh, 1, s_e));
-    *ecount += (unsigned)f.nblkE;
-    f.spin_first = 0; f.spin_wait = *ecount; f.spin_signal = ++*mtag;                  // M-step: behind every workgroup of that E-step
-    TDLO_TRY(launch_mstep_chain(fd, fh, 1, 0, false, s_m));
-    f.spin_on = 0;
-    return hipSuccess;
-}
-
 hipError_t launch_iteration_timed(const FrameDev *fd, const FrameDev *fh, int F, hipStream_t s, hipEvent_t e_start, hipEvent_t e_stop,
                                   hipEvent_t m_start, hipEvent_t m_stop, int iteration) {
     g_estep_ev[0] = e_start; g_estep_ev[1] = e_stop;

@@ -164,15 +164,6 @@ struct FrameDev {
     // fp64 mode: 1 = the sums' resolution does NOT follow sigma (IterState::sh_boost stays 0): the call is the repeat of one whose E-step refused a share
     // under the finer limits (run_frames: a registration that the coarse limits of rounds 1-4 would have served must not fail on the boost)
     int acc_boost_off;
-    // The spin-ahead loop of ONE frame (round 6 experiment, TDLO_SPIN_AHEAD=1; run_frames): the E-steps go to a second stream, the M-steps stay on the
-    // first, everything is enqueued up front, and the kernels order themselves through two words of `sync` -- E-step k+1 is dispatched while M-step k still
-    // runs, requests its first points and parks on word 110 until that M-step stores its tag there; M-step k+1 is dispatched behind M-step k, requests
-    // everything that does not come from the E-step and parks on word 111 until the E-step's workgroups have all added themselves to it.  The tags are
-    // the host's running counts (unsigned, compared for equality: no reset between registrations).  Every wait is bounded (2 s -> TDLO_E_EXCHANGE).
-    // spin_on: 0 off; 1 this launch takes part.  E-step: waits for word 110 == spin_wait unless spin_first; adds 1 per workgroup to word 111.
-    // M-step: waits for word 111 == spin_wait; stores spin_signal to word 110.
-    int spin_on, spin_first;
-    unsigned spin_wait, spin_signal;
     // fp64 E-step, chains beyond 64 nodes: a batch whose node window holds at least this many nodes (and at most 320) goes lane = node (tdlo_estep_wide.h;
     // TDLO_ESTEP_WIDE=0: never -- the comparator; =n: from n nodes on)
     int estep_wide_min;
@@ -181,7 +172,6 @@ struct FrameDev {
     // round trip is on every iteration's critical path, requests only the used ones (choose_acc_rows in tdlo_api.cpp has the measurements)
     int acc_rows;
 };
-constexpr int kSpinWordM = 110, kSpinWordE = 111;
 // The loop with one launch per iteration (k_iter_fused): an E-step half that refuses a contribution (TDLO_E_NUMERIC) stores the registration's mailbox epoch in
 // a word of `sync` -- the state's copies are being written by its launch's workgroup 0 at that time, so the state itself is not the place -- and the M-step of
 // the NEXT launch, finding its own epoch there, ends the registration with that error, as the M-step behind a refusing k_estep does.  Two words, 112 and 113:
@@ -244,18 +234,12 @@ bool prologue_pair_ok(const FrameDev &f);      // the fused form itself (not the
 hipError_t launch_prologue_direct(const FrameDev *fh, const double *host_up, double *dev_up, int up_doubles, int yin_off, unsigned epoch, hipStream_t s,
                                   const FrameDev *f2 = nullptr, const double *host_up2 = nullptr, double *dev_up2 = nullptr, int up_doubles2 = 0);
 hipError_t launch_iteration(const FrameDev *frames_dev, const FrameDev *frames_host, int F, hipStream_t s, int iteration = -1);      // (iteration: mstep_parity_hint)
-// one iteration of the spin-ahead loop (FrameDev::spin_on): the E-step on s_e, the M-step on s_m; fh[0]'s spin fields are set per launch (the one-frame kernels take
-// the descriptor by value).  ecount / mtag: the slot's running counts behind the tags.
-hipError_t launch_iteration_spin(const FrameDev *frames_dev, FrameDev *frames_host, hipStream_t s_e, hipStream_t s_m, bool first, unsigned *ecount, unsigned *mtag);
 hipError_t launch_iteration_timed(const FrameDev *frames_dev, const FrameDev *frames_host, int F, hipStream_t s, hipEvent_t e_start, hipEvent_t e_stop,
                                   hipEvent_t m_start, hipEvent_t m_stop, int iteration = -1);
 const char *mstep_kernel_name(const FrameDev *frames_host, int F);
 // tdlo_estep2.hip: the E-step with two points per lane (FrameDev::estep2)
 hipError_t launch_estep2(const FrameDev *frames_dev, const FrameDev *frames_host, int F, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 size_t estep2_lds_bytes(int M, int tile_rows);
-// tdlo_estep2.hip: a batch's whole loop in one launch (k_batch_loop): tickets (iteration, frame, chunk), per-frame dependency counters in `ctl`
-size_t batch_loop_ctl_words(int F);
-hipError_t launch_batch_loop(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int iters, unsigned *ctl, hipStream_t s);
 hipError_t launch_estep_only(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int kind, hipStream_t s);
 hipError_t launch_split_setup(const FrameDev *frames_dev, const FrameDev *frames_host, hipStream_t s);
 hipError_t launch_split_set_global(const FrameDev *frames_dev, double Nglob, double Sglob, hipStream_t s);

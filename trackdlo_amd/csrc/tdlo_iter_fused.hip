@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kCB) void k_iter_fused(const FrameDev f0, const Fus
         z.stL = (IterState *)(smem + estep_bytes);
         z.nodesL = smem;                        // (the head of the E-step's carve: nodesL)
         z.go = false;
-        mstep_chain_run<T, true, false, false, false, kAccRows, true, 1>(f, 0, smem + estep_bytes + kFusedStateBytes, a.acc_r, &z);
+        mstep_chain_run<T, true, false, false, kAccRows, true, 1>(f, 0, smem + estep_bytes + kFusedStateBytes, a.acc_r, &z);
         if (!z.go) return;                      // (the registration is over: workgroup 0 has said so where it has to be said)
         asm volatile("" :: "s"(__builtin_amdgcn_kernarg_segment_ptr()));
         h.st = z.stL;

@@ -62,7 +62,7 @@ extern thread_local hipEvent_t g_mstep_ev[2];       // tdlo_device.hip: start/st
 // (the body: tdlo_mstep_chain_body.h, mstep_chain_run)
 // CLOSE: the M-step that closes the loop with one launch per iteration (k_iter_fused; mstep_chain_run's FUSE 2): bits 8-9 of from_sums_in name the accumulator
 // buffer (0 .. 2), bit 10 the error word it reads
-template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false, bool CLOSE = false>
+template <typename T, bool SINGLE, bool XCH, bool TRK = false, int ROWS = kAccRows, bool HINT = false, bool CLOSE = false>
 __global__ __launch_bounds__(kCB) void k_mstep_chain(const FrameDev *__restrict__ frames, const FrameDev f0, int from_sums_in) {
     const int from_sums = from_sums_in & 0xff, par_hint = (from_sums_in >> 8) & (CLOSE ? 3 : 1);          // (HINT: bit 8 carries the iteration's parity)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -72,9 +72,9 @@ __global__ __launch_bounds__(kCB) void k_mstep_chain(const FrameDev *__restrict_
     if constexpr (CLOSE) {
         ChainFused z;
         z.err_r = (from_sums_in >> 10) & 1;
-        mstep_chain_run<T, SINGLE, XCH, TRK, SPIN, ROWS, HINT, 2>(f0, from_sums, smem, par_hint, &z);
+        mstep_chain_run<T, SINGLE, XCH, TRK, ROWS, HINT, 2>(f0, from_sums, smem, par_hint, &z);
     } else
-    mstep_chain_run<T, SINGLE, XCH, TRK, SPIN, ROWS, HINT>(SINGLE ? f0 : frames[blockIdx.x], from_sums, smem, par_hint);
+    mstep_chain_run<T, SINGLE, XCH, TRK, ROWS, HINT>(SINGLE ? f0 : frames[blockIdx.x], from_sums, smem, par_hint);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -288,8 +288,8 @@ template <typename T> static hipError_t launch_mstep_chain_T(const FrameDev *fd,
     if (from_sums == 3) {          // one frame (a shard of the split cloud), exchange inside the kernel
         if (F != 1) return hipErrorInvalidValue;
         if (g_par_hint >= 0) {          // (tdlo_split_run counts its iterations as run_frames does: the shard's own sums from that parity's rows alone)
-            if ((e = set_lds_c(k_mstep_chain<T, true, true, false, false, kAccRows, true>, lds)) != hipSuccess) return e;
-            hipLaunchKernelGGL((k_mstep_chain<T, true, true, false, false, kAccRows, true>), dim3(1), dim3(kCB), lds, s, fd, fh[0], from_sums | (g_par_hint << 8));
+            if ((e = set_lds_c(k_mstep_chain<T, true, true, false, kAccRows, true>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((k_mstep_chain<T, true, true, false, kAccRows, true>), dim3(1), dim3(kCB), lds, s, fd, fh[0], from_sums | (g_par_hint << 8));
             return hipGetLastError();
         }
         if ((e = set_lds_c(k_mstep_chain<T, true, true>, lds)) != hipSuccess) return e;
@@ -298,20 +298,15 @@ template <typename T> static hipError_t launch_mstep_chain_T(const FrameDev *fd,
         if ((e = set_lds_c(k_mstep_chain<T, true, false, true>, lds)) != hipSuccess) return e;
         if (g_mstep_ev[0]) hipExtLaunchKernelGGL((k_mstep_chain<T, true, false, true>), dim3(1), dim3(kCB), lds, s, g_mstep_ev[0], g_mstep_ev[1], 0, fd, fh[0], from_sums);
         else hipLaunchKernelGGL((k_mstep_chain<T, true, false, true>), dim3(1), dim3(kCB), lds, s, fd, fh[0], from_sums);
-    } else if (F == 1 && fh[0].spin_on != 0) {          // the spin-ahead loop's M-step (63 nodes at most: launch_iteration_spin's caller has checked)
-        if (4 * fh[0].M + 1 > kCB) return hipErrorInvalidValue;
-        if ((e = set_lds_c(k_mstep_chain<T, true, false, false, true>, lds)) != hipSuccess) return e;
-        if (g_mstep_ev[0]) hipExtLaunchKernelGGL((k_mstep_chain<T, true, false, false, true>), dim3(1), dim3(kCB), lds, s, g_mstep_ev[0], g_mstep_ev[1], 0, fd, fh[0], from_sums);
-        else hipLaunchKernelGGL((k_mstep_chain<T, true, false, false, true>), dim3(1), dim3(kCB), lds, s, fd, fh[0], from_sums);
     } else if (F == 1) {
         // (the plain one-frame kernel exists for 2, 4 and all 8 replica rows of the accumulators: FrameDev::acc_rows says how many the E-step in front used;
         //  every other variant adds up all eight -- the unused ones are zero)
         //  When the caller has said which iteration this is (mstep_parity_hint), the HINT instantiation asks for that parity's rows alone.
         const int hint = from_sums == 0 ? g_par_hint : -1, fsh = from_sums | ((hint > 0 ? 1 : 0) << 8);
 #define TDLO_CHAIN1(SGL, ROWS, HINT, NWG) do { \
-        if ((e = set_lds_c(k_mstep_chain<T, SGL, false, false, false, ROWS, HINT>, lds)) != hipSuccess) return e; \
-        if (g_mstep_ev[0]) hipExtLaunchKernelGGL((k_mstep_chain<T, SGL, false, false, false, ROWS, HINT>), dim3(NWG), dim3(kCB), lds, s, g_mstep_ev[0], g_mstep_ev[1], 0, fd, fh[0], fsh); \
-        else hipLaunchKernelGGL((k_mstep_chain<T, SGL, false, false, false, ROWS, HINT>), dim3(NWG), dim3(kCB), lds, s, fd, fh[0], fsh); } while (0)
+        if ((e = set_lds_c(k_mstep_chain<T, SGL, false, false, ROWS, HINT>, lds)) != hipSuccess) return e; \
+        if (g_mstep_ev[0]) hipExtLaunchKernelGGL((k_mstep_chain<T, SGL, false, false, ROWS, HINT>), dim3(NWG), dim3(kCB), lds, s, g_mstep_ev[0], g_mstep_ev[1], 0, fd, fh[0], fsh); \
+        else hipLaunchKernelGGL((k_mstep_chain<T, SGL, false, false, ROWS, HINT>), dim3(NWG), dim3(kCB), lds, s, fd, fh[0], fsh); } while (0)
         if (hint >= 0) { if (fh[0].acc_rows == 2) TDLO_CHAIN1(true, 2, true, 1); else if (fh[0].acc_rows == 4) TDLO_CHAIN1(true, 4, true, 1); else TDLO_CHAIN1(true, kAccRows, true, 1); }
         else { if (fh[0].acc_rows == 2) TDLO_CHAIN1(true, 2, false, 1); else if (fh[0].acc_rows == 4) TDLO_CHAIN1(true, 4, false, 1); else TDLO_CHAIN1(true, kAccRows, false, 1); }
     } else {
@@ -340,9 +335,9 @@ hipError_t launch_lle_band_debug(const double *Y, int M, double *Hb, hipStream_t
 hipError_t launch_mstep_chain_close(const FrameDev &f, int iteration, hipStream_t s) {
     if (f.M > kChunk || f.precision != TDLO_PREC_F32) return hipErrorInvalidValue;
     const size_t lds = mstep_chain_lds_bytes(f.M);
-    const hipError_t e = set_lds_c(k_mstep_chain<float, true, false, false, false, kAccRows, true, true>, lds);
+    const hipError_t e = set_lds_c(k_mstep_chain<float, true, false, false, kAccRows, true, true>, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mstep_chain<float, true, false, false, false, kAccRows, true, true>), dim3(1), dim3(kCB), lds, s, (const FrameDev *)nullptr, f,
+    hipLaunchKernelGGL((k_mstep_chain<float, true, false, false, kAccRows, true, true>), dim3(1), dim3(kCB), lds, s, (const FrameDev *)nullptr, f,
                        ((iteration % 3) << 8) | (((iteration + 1) & 1) << 10));
     return hipGetLastError();
 }

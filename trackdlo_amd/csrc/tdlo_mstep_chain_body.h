@@ -1,5 +1,5 @@
 // tdlo_mstep_chain_body.h -- the chain smoother of tdlo_mstep_chain.hip (trackdlo.cpp:392-437 without the LLE term) as a DEVICE FUNCTION, so that the kernel
-// k_mstep_chain and the batches' persistent loop (tdlo_estep2.hip, k_batch_loop: the workgroup that finishes a frame's E-step runs the frame's M-step) share one body.
+// k_mstep_chain and the M-step half of the loop with one launch per iteration (tdlo_iter_fused.hip, k_iter_fused) share one body.
 // The derivation, the phases and what bounds it: the head of tdlo_mstep_chain.hip.
 #pragma once
 #include <type_traits>
@@ -97,8 +97,6 @@ struct ChainCarve {
 // TRK: the extras of tracking_step's main registration (one frame, no exchange) -- late priors read from pinned host memory when no E-step has
 // run yet, the launch ahead of its priors (FrameDev::spec_flag), the next frame's LLE regulariser at the end (FrameDev::lle_next).  The plain
 // instantiation is the kernel of the registrations proper, unchanged.
-// SPIN (round 6 experiment, FrameDev::spin_on): the launch was dispatched behind the M-step of the iteration before while THIS iteration's E-step still
-// runs on another stream -- everything but the sums is requested, then the kernel waits for the E-step's workgroups to have counted themselves in.
 // ROWS: how many replica rows of the accumulators the E-step in front used (FrameDev::acc_rows; the launcher instantiates 2 / 4 for the plain one-frame kernel)
 // HINT: the launch carries the iteration's parity (par_hint, 0 / 1): the sums are requested from that parity's rows alone, without waiting for the device's counter
 // FUSE: the loop with ONE launch per iteration (tdlo_iter_fused.hip; run_frames).  "Where the results go" is this policy, the arithmetic is the same statements:
@@ -120,9 +118,9 @@ struct ChainFused {
     void *nodesL;                   // LDS: the E-step half's node copy (every workgroup)
     bool go;                        // out: the registration goes on -- the E-step half runs
 };
-template <typename T, bool SINGLE, bool XCH, bool TRK = false, bool SPIN = false, int ROWS = kAccRows, bool HINT = false, int FUSE = 0>
+template <typename T, bool SINGLE, bool XCH, bool TRK = false, int ROWS = kAccRows, bool HINT = false, int FUSE = 0>
 __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums, char *smem, int par_hint = 0, ChainFused *fz = nullptr) {
-    static_assert(FUSE == 0 || (SINGLE && HINT && !XCH && !TRK && !SPIN), "the one-launch iteration: one frame, told its accumulator buffer, no exchange / tracker extras");
+    static_assert(FUSE == 0 || (SINGLE && HINT && !XCH && !TRK), "the one-launch iteration: one frame, told its accumulator buffer, no exchange / tracker extras");
     constexpr int MB = kCB;
     // One wave walks a chain of dependent instructions.  In a batch the other stream groups' E-steps fill the same SIMDs with waves that always have
     // something to issue: at the default priority this wave takes its turn among them (C3: 10.0 us per M-step against 7.4 us with the GPU to itself)
@@ -223,19 +221,6 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     // every kernel that sets it (k_setup's set_iter_consts, every M-step's tail) -- the shift is FrameDev::acc_sh alone, the same bits.
     long long fr0[ROWS], fr1[ROWS];
     const int fi0 = t < nS ? t : nS - 1, fi1 = t + MB < nS ? t + MB : nS - 1;
-    bool spin_lost = false;
-    if (SPIN) {
-        // (up to 63 nodes: one element per thread.)  The slot -- links, the node, Y0, Y -- is requested first: nothing of it comes from this iteration's
-        // E-step; then the wait for that E-step's workgroups, then the sums
-        q0 = load_slot(t, true);
-        if (t == 0) red[29] = spin_wait_word(f.sync + kSpinWordE, f.spin_wait) ? 1.0 : 0.0;
-        __syncthreads();
-        spin_lost = red[29] == 0.0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        sq[0] = acc_read_both<ROWS>(f, t < nS ? t : nS - 1, itn);
-#pragma unroll
-        for (int u = 1; u < 9; ++u) sq[u] = 0.0;
-    } else {
     // (the first element without a branch -- index clamped, the accumulators exist in every mode: inside a conditional block the compiler sums the
     //  16 rows on the spot, i.e. waits for them BEFORE it requests the slot below: two memory round trips in a row instead of one)
     if constexpr (FUSE == 1) {
@@ -256,22 +241,8 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     sq[0] = HINT ? acc_read_par<ROWS>(f, t < nS ? t : nS - 1, par_hint) : acc_read_both<ROWS>(f, t < nS ? t : nS - 1, itn);
 #pragma unroll
     for (int u = 1; u < 9; ++u) sq[u] = 0.0;
-    }
-    // spin-ahead: this M-step's tag goes out when it is through, whatever way it leaves (the next E-step is parked on it)
-    auto spin_report = [&]() __attribute__((always_inline)) {
-        if (!SPIN) return;
-        __syncthreads();                                           // (every thread's stores to the nodes and to Y have been performed: workgroup-scope release)
-        if (t == 0) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __hip_atomic_store(f.sync + kSpinWordM, f.spin_signal, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
-    };
-    if (SPIN && spin_lost) {      // the E-step never completed (2 s): the registration ends with an error, the tag still goes out
-        if (t == 0) { st->status = TDLO_E_EXCHANGE; st->done = 1; st->converged = 0; }
-        spin_report();
-        if (t < 64) host_publish(f, st, lane, false);
-        return;
-    }
     if constexpr (FUSE == 1) {         // (at most 64 nodes, launch_iter_fused: every slot is a thread's first one)
         q0 = load_slot(t, true);
-    } else if (SPIN) {
     } else if (nS <= MB) {             // up to 63 nodes: the slot's loads follow the sums' in the same basic block (nothing is waited for in between)
         q0 = load_slot(t, !spec_wait);
     } else {                    // longer chains: the further elements first (with the slot's forty registers live the compiler requests their
@@ -417,7 +388,6 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     }
     if (done) {
         if (XCH && from_sums == 3) xch_post_error(f, st, t);
-        spin_report();
         if (!XCH && t < 64 && stg->status != 0) host_publish(f, st, lane, false);      // a registration that ended on an error somewhere else (E-step, setup)
         return;
     }
@@ -961,7 +931,6 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         }
         return;
     }
-    spin_report();
     if (!XCH && t < 64 && __builtin_amdgcn_readfirstlane(pub)) host_publish(f, st, lane, true);      // progress (and, from the M-step that finishes the registration, the results) into pinned host memory
     if (TRK && f.lle_next != nullptr) {
         // the M-step that finishes the registration without an error goes on (the host has its results already) to form the LLE regulariser

@@ -398,6 +398,57 @@ int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, 
                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                   int *n_out, int *n_raw_out, tdlo_stats *stats);
 
+/* ---- colour segmentation on the device: BGR + depth frames in one call ------------------------ */
+/* The callback's segmentation (trackdlo/src/trackdlo_node.cpp:158-180 with color_thresholding, :84-119): cv::cvtColor(BGR2HSV), cv::inRange over one
+ * range (the launch file's hsv_threshold_*) or four (multi_color_dlo), the AND with the occlusion mask -- so that a caller hands over what the camera
+ * delivers (bgr8 + 16UC1) and needs no OpenCV pass on the host.
+ * The arithmetic is OpenCV's published integer routine for 8-bit images, hsv_shift = 12, hue range 180: tables sdiv[i] = rint((255 << 12) / i) and
+ * hdiv[i] = rint((180 << 12) / (6 i)) (fp64, ties to even, entry 0 = 0), and per pixel in 32-bit integers
+ *   v = max(b, g, r); d = v - min(b, g, r); s = (d sdiv[v] + 2048) >> 12;
+ *   h = v == r ? g - b : v == g ? b - r + 2 d : r - g + 4 d;   h = (h hdiv[d] + 2048) >> 12;   h += h < 0 ? 180 : 0            (H in 0 .. 179)
+ * -- not the rounded float formula (the two differ on ~2 % of the colour cube).  A pixel passes range k when lower[k][c] <= hsv[c] <= upper[k][c] on all
+ * three channels; the mask is 255 where any range passes and the occluder byte (when an occluder image is given) is not 0, else 0.
+ * PARITY UNPINNED against OpenCV: the routine is restated from its published algorithm (OpenCV is not part of the build image), like the painter test
+ * above; tests/colour_ref.py is the numpy statement that the device code is held to bit for bit over all 2^24 colours (tests/test_colour_gpu.py).
+ * Reference values (H, S, V): the launch file's range {1, {{90, 90, 30}}, {{130, 255, 255}}, 0}; color_thresholding's four:
+ * {90, 90, 60} - {130, 255, 255}, {130, 60, 50} - {255, 255, 255}, {0, 60, 50} - {10, 255, 255}, {15, 100, 80} - {40, 255, 255}. */
+typedef struct {
+    int n_ranges;        /* 1 .. 4; anything else: TDLO_E_INVALID */
+    int lower[4][3];     /* H, S, V; clamped to 0 .. 255 */
+    int upper[4][3];
+    int rgb_order;       /* 0: the image's bytes are B G R (the node's bgr8); 1: R G B (trackdlo/src/initialize.py:59) */
+} tdlo_colour_params;
+/* The segmentation on its own (one kernel, k_colour_mask: a thread takes four pixels).  colour: rows x cols x 3 uint8, occluder: rows x cols uint8 or NULL,
+ * both row-major.  The mask is left in the context's device mask buffer; mask_out (rows x cols uint8) and hsv_out (rows x cols x 3 uint8: what
+ * utils/color_picker.py shows, for tuning the ranges) are host buffers and may be NULL. */
+int tdlo_colour_mask(tdlo_ctx *ctx, const unsigned char *colour, int rows, int cols, const tdlo_colour_params *params, const unsigned char *occluder,
+                     unsigned char *mask_out, unsigned char *hsv_out);
+/* Pinned host buffers of the context for a rows x cols colour image and occluder image, with the lifetime rules of tdlo_image_buffers.  A caller that
+ * passes exactly these pointers (occluder: this one or NULL) to the calls below has the kernel read the images where they are, over PCIe; any other
+ * pointer is copied to the device first.  (The depth image is read in place when it is tdlo_image_buffers' depth pointer.) */
+int tdlo_colour_buffers(tdlo_ctx *ctx, int rows, int cols, unsigned char **colour, unsigned char **occluder);
+/* tdlo_depth_to_cloud / tdlo_depth_to_cloud_visibility with the segmentation formed from the colour image instead of a mask handed in: the one-launch
+ * kernels (k_cloud_team / k_cloud_fused, colour instantiation) read each thread's four pixels as 12 colour bytes + 4 occluder bytes where they read a
+ * mask word, and everything behind it -- depth only where the mask is set, compaction, voxel grid, the riding pre-pass -- is the same code: the bits of
+ * the mask calls fed the segmentation's mask.  Frames the one-launch kernel does not serve (more than 32 704 masked pixels, too many cell bits, PCL's
+ * pass-through, a team that gave its launch up; TDLO_CLOUD_FUSED=0) take k_colour_mask and then the multi-launch form; TDLO_COLOUR_FUSED=0 (read when
+ * the context is made; the comparator): k_colour_mask, then the mask route as it is.  tdlo_debug_route_count 15 / 16 count the two. */
+int tdlo_colour_depth_to_cloud(tdlo_ctx *ctx, int slot, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                               const unsigned char *occluder, int rows, int cols, double fx, double fy, double cx, double cy, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out);
+int tdlo_colour_depth_to_cloud_visibility(tdlo_ctx *ctx, int slot, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                                          const unsigned char *occluder, int rows, int cols, double fx, double fy, double cx, double cy, double leaf_size,
+                                          const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                          double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                          int *n_out, int *n_raw_out);
+/* tdlo_tracker_frame_from_depth from the two sensor images: the callback from the images to the nodes (trackdlo_node.cpp:158-277, :345-369) in one call.
+ * The self-occlusion switch applies as it does there; a frame none of whose pixels pass is TDLO_E_EMPTY, the tracker's state untouched. */
+int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                                   const unsigned char *occluder, int rows, int cols,
+                                   double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                   int *n_out, int *n_raw_out, tdlo_stats *stats);
+
 /* The callback's self-occlusion ("painter") test, trackdlo/src/trackdlo_node.cpp:279-343: the edges between consecutive nodes are taken nearest the camera
  * first (:279-290, by the camera distance of their mid-points) and each is drawn as a line of dlo_pixel_width pixels (:337-341) after its two end nodes
  * were looked up in what had been drawn before (:304-334): a node whose projected pixel (proj: 3 x 4 row-major, the reference's proj_matrix; pixel
@@ -500,6 +551,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * refused under its finer range limits (the repeat runs under the coarse limits of every other mode; only its verdict is reported).
  * 11, 12, 13: always 0 -- these indices belonged to experiments that were measured slower and removed (the spin-ahead loop TDLO_SPIN_AHEAD, a batch's loop
  * in one launch TDLO_BATCH_PERSIST and its repeats; docs/HISTORY.md has the numbers); the indices are not reused.
+ * 14: registrations run with one launch per iteration (k_iter_fused).  15 / 16: colour frames (tdlo_colour_depth_to_cloud and the calls built on it) whose
+ * segmentation rode in the depth -> cloud launch / that took the mask kernel k_colour_mask (TDLO_COLOUR_FUSED=0, TDLO_CLOUD_FUSED=0, frames passed on).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

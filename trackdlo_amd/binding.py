@@ -44,6 +44,10 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ColourParams(C.Structure):
+    _fields_ = [("n_ranges", C.c_int), ("lower", (C.c_int * 3) * 4), ("upper", (C.c_int * 3) * 4), ("rgb_order", C.c_int)]
+
+
 # every symbol include/trackdlo_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "tdlo_abi_version", "tdlo_device_count", "tdlo_default_config", "tdlo_create", "tdlo_destroy", "tdlo_last_error",
@@ -58,6 +62,7 @@ SYMBOLS = [
     "tdlo_tracker_get_correspondence_pairs", "tdlo_tracker_tracking_step", "tdlo_calc_lle_weights", "tdlo_calc_lle_regulariser",
     "tdlo_line_sphere_intersection", "tdlo_traverse_euclidean", "tdlo_profile_kernel", "tdlo_profile_iteration", "tdlo_debug_stamps", "tdlo_debug_exp2", "tdlo_debug_mstep_dense", "tdlo_debug_mstep_lle_dense", "tdlo_debug_band_retries", "tdlo_debug_lle_band_device", "tdlo_debug_route_count", "tdlo_debug_fail_hip", "tdlo_set_timing", "tdlo_set_sort_reuse", "tdlo_set_xch_self", "tdlo_pci_bus_id", "tdlo_debug_read_cloud", "tdlo_debug_read_setup", "tdlo_image_buffers", "tdlo_debug_cloud_stamps", "tdlo_visibility_prepass", "tdlo_depth_to_cloud_visibility", "tdlo_tracker_frame_from_depth", "tdlo_piecewise_error", "tdlo_compute_error",
     "tdlo_depth_to_cloud", "tdlo_reg", "tdlo_self_occlusion_visible", "tdlo_extend_visible_nodes", "tdlo_tracker_set_self_occlusion",
+    "tdlo_colour_mask", "tdlo_colour_buffers", "tdlo_colour_depth_to_cloud", "tdlo_colour_depth_to_cloud_visibility", "tdlo_tracker_frame_from_colour",
 ]
 
 _lib = None
@@ -206,6 +211,13 @@ def load_library(path: str | None = None):
     lib.tdlo_self_occlusion_visible.argtypes = [vp, ci, vp, ci, vp, cd, vp, C.POINTER(ci)]
     lib.tdlo_extend_visible_nodes.argtypes = [vp, ci, vp, cd, vp, C.POINTER(ci)]
     lib.tdlo_tracker_set_self_occlusion.argtypes = [vp, vp, ci]
+    cpp = C.POINTER(ColourParams)
+    lib.tdlo_colour_mask.argtypes = [vp, vp, ci, ci, cpp, vp, vp, vp]
+    lib.tdlo_colour_buffers.argtypes = [vp, ci, ci, C.POINTER(vp), C.POINTER(vp)]
+    lib.tdlo_colour_depth_to_cloud.argtypes = [vp, ci, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
+    lib.tdlo_colour_depth_to_cloud_visibility.argtypes = [vp, ci, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci),
+                                                          C.POINTER(ci), C.POINTER(ci)]
+    lib.tdlo_tracker_frame_from_colour.argtypes = [vp, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
     if path is None:
         _lib = lib
     return lib
@@ -275,6 +287,37 @@ def make_params(beta, lambda_, lle_weight, mu, max_iter=30, tol=1e-4, include_ll
                 visibility_threshold=0.01, precision=PREC_F32) -> Params:
     return Params(beta, lambda_, lle_weight, mu, int(max_iter), tol, int(bool(include_lle)), alpha, k_vis,
                   visibility_threshold, int(precision))
+
+
+# trackdlo_node.cpp: the launch file's range (hsv_threshold_*) and color_thresholding's four (:88-99: blue, red above 130, red below 10, yellow), H S V
+COLOUR_LAUNCH = ([[90, 90, 30]], [[130, 255, 255]])
+COLOUR_MULTI = ([[90, 90, 60], [130, 60, 50], [0, 60, 50], [15, 100, 80]], [[130, 255, 255], [255, 255, 255], [10, 255, 255], [40, 255, 255]])
+
+
+def make_colour_params(lower=COLOUR_LAUNCH[0], upper=COLOUR_LAUNCH[1], rgb_order=0) -> ColourParams:
+    """tdlo_colour_params from 1 .. 4 ranges: lower / upper are [n][3] (or one [3]) H, S, V bounds, inclusive, clamped to 0 .. 255 by the library."""
+    lo = np.asarray(lower, dtype=np.int64).reshape(-1, 3); hi = np.asarray(upper, dtype=np.int64).reshape(-1, 3)
+    if lo.shape != hi.shape or not 1 <= len(lo) <= 4:
+        raise ValueError("1 .. 4 ranges, as many lower as upper bounds")
+    p = ColourParams()
+    p.n_ranges = len(lo); p.rgb_order = int(rgb_order)
+    for k in range(len(lo)):
+        for c in range(3):
+            p.lower[k][c] = int(lo[k, c]); p.upper[k][c] = int(hi[k, c])
+    return p
+
+
+def _colour_images(depth, colour, occluder):
+    if depth is not None:
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+    colour = np.ascontiguousarray(colour, dtype=np.uint8)
+    if colour.ndim != 3 or colour.shape[2] != 3 or (depth is not None and depth.shape != colour.shape[:2]):
+        raise ValueError("colour must be rows x cols x 3, depth rows x cols")
+    if occluder is not None:
+        occluder = np.ascontiguousarray(occluder, dtype=np.uint8)
+        if occluder.shape != colour.shape[:2]:
+            raise ValueError("occluder must be rows x cols")
+    return depth, colour, occluder, (occluder.ctypes.data_as(C.c_void_p) if occluder is not None else None)
 
 
 class Context:
@@ -503,6 +546,58 @@ class Context:
         mask = np.ctypeslib.as_array(C.cast(m, C.POINTER(C.c_uint8)), shape=(rows, cols))
         return depth, mask
 
+    def colour_route_counts(self):
+        """[colour frames whose segmentation rode in the depth -> cloud launch, colour frames that took the mask kernel] (tdlo_debug_route_count 15 / 16)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (15, 16)]
+
+    def colour_buffers(self, rows, cols):
+        """The context's pinned colour / occluder buffers as numpy views (uint8 [rows x cols x 3], uint8 [rows x cols]): images written into them and handed
+        to the colour calls as they are get read by the kernel where they lie (tdlo_colour_buffers)."""
+        a = C.c_void_p(); o = C.c_void_p()
+        self._chk(self.lib.tdlo_colour_buffers(self.h, int(rows), int(cols), C.byref(a), C.byref(o)))
+        colour = np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint8)), shape=(rows, cols, 3))
+        occ = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint8)), shape=(rows, cols))
+        return colour, occ
+
+    def colour_mask(self, colour, params: ColourParams, occluder=None, *, hsv=False):
+        """trackdlo_node.cpp:158-180 on the device: the segmentation mask [rows x cols uint8, 0 / 255] of a BGR image; hsv=True: (mask, HSV image)."""
+        _, colour, occluder, op = _colour_images(None, colour, occluder)
+        rows, cols = colour.shape[:2]
+        mask = np.zeros((rows, cols), dtype=np.uint8)
+        out = np.zeros((rows, cols, 3), dtype=np.uint8) if hsv else None
+        self._chk(self.lib.tdlo_colour_mask(self.h, colour.ctypes.data_as(C.c_void_p), rows, cols, C.byref(params), op, mask.ctypes.data_as(C.c_void_p),
+                                            out.ctypes.data_as(C.c_void_p) if hsv else None))
+        return (mask, out) if hsv else mask
+
+    def colour_depth_to_cloud(self, slot, depth, colour, params: ColourParams, occluder, fx, fy, cx, cy, leaf_size, *, fetch=True):
+        """depth_to_cloud with the segmentation formed from the colour image on the device (tdlo_colour_depth_to_cloud).
+        Returns (X [n x 3] or None, n, n_raw)."""
+        depth, colour, occluder, op = _colour_images(depth, colour, occluder)
+        rows, cols = depth.shape
+        cap = rows * cols if fetch else 0          # (the mask is not known here: a point per pixel at most)
+        buf = np.zeros(3 * max(cap, 1)) if fetch else None
+        n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_colour_depth_to_cloud(self.h, slot, depth.ctypes.data_as(C.c_void_p), colour.ctypes.data_as(C.c_void_p), C.byref(params), op, rows, cols,
+                                                      float(fx), float(fy), float(cx), float(cy), float(leaf_size), _ptr(buf), cap, C.byref(n), C.byref(nraw)))
+        X = buf[:3 * n.value].reshape(3, n.value).T.copy() if fetch else None
+        return X, n.value, nraw.value
+
+    def colour_depth_to_cloud_visibility(self, slot, depth, colour, params: ColourParams, occluder, fx, fy, cx, cy, leaf_size, Y, visibility_threshold, d_vis,
+                                         geodesic_coord):
+        """depth_to_cloud_visibility from the colour image (tdlo_colour_depth_to_cloud_visibility).
+        Returns (node_dist, visible_nodes, visible_nodes_extended, n, n_raw)."""
+        depth, colour, occluder, op = _colour_images(depth, colour, occluder)
+        rows, cols = depth.shape
+        Y = _f64(Y); M = Y.shape[0]
+        coord = np.ascontiguousarray(geodesic_coord, dtype=np.float64)
+        dist = np.zeros(M); vis = np.zeros(M, dtype=np.int32); ext = np.zeros(M, dtype=np.int32)
+        nv = C.c_int(0); ne = C.c_int(0); n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_colour_depth_to_cloud_visibility(self.h, slot, depth.ctypes.data_as(C.c_void_p), colour.ctypes.data_as(C.c_void_p), C.byref(params), op,
+                                                                 rows, cols, float(fx), float(fy), float(cx), float(cy), float(leaf_size), _ptr(Y), M,
+                                                                 float(visibility_threshold), float(d_vis), _ptr(coord), _ptr(dist), _ptr(vis), C.byref(nv),
+                                                                 _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
+        return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
     def depth_to_cloud(self, slot, depth, mask, fx, fy, cx, cy, leaf_size, *, fetch=True):
         """trackdlo_node.cpp:195-241: masked back-projection + pcl::VoxelGrid; the result becomes the slot's resident cloud.
         Returns (X [n x 3] or None, n, n_raw)."""
@@ -679,6 +774,28 @@ class trackdlo:
         v, e, nv, ne, n, nraw = self._fv
         rc = self.ctx.lib.tdlo_tracker_frame_from_depth(self.h, depth.ctypes.data, mask.ctypes.data, rows, cols, fx, fy, cx, cy, leaf_size, d_vis,
                                                         v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
+        self._stats_raw = self._st
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def frame_from_colour(self, depth, colour, params: ColourParams, occluder, fx, fy, cx, cy, leaf_size=0.008, d_vis=0.06):
+        """frame_from_depth from the two sensor images (trackdlo_node.cpp:158-369): the segmentation is formed from the BGR image on the device, in the
+        same launch as the cloud (tdlo_tracker_frame_from_colour; the context's image / colour buffers are read in place).
+        Returns (visible_nodes, visible_nodes_extended, n, n_raw); the nodes: get_tracking_result()."""
+        if depth.dtype != np.uint16 or colour.dtype != np.uint8 or not depth.flags.c_contiguous or not colour.flags.c_contiguous:
+            depth = np.ascontiguousarray(depth, dtype=np.uint16); colour = np.ascontiguousarray(colour, dtype=np.uint8)
+        if occluder is not None and (occluder.dtype != np.uint8 or not occluder.flags.c_contiguous):
+            occluder = np.ascontiguousarray(occluder, dtype=np.uint8)
+        rows, cols = depth.shape
+        if colour.shape != (rows, cols, 3) or (occluder is not None and occluder.shape != (rows, cols)):
+            raise ValueError("colour must be rows x cols x 3, occluder rows x cols")
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        rc = self.ctx.lib.tdlo_tracker_frame_from_colour(self.h, depth.ctypes.data, colour.ctypes.data, C.byref(params), occluder.ctypes.data if occluder is not None else None,
+                                                         rows, cols, fx, fy, cx, cy, leaf_size, d_vis,
+                                                         v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
         self._stats_raw = self._st
         if rc:
             self.ctx._chk(rc)

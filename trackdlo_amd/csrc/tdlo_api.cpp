@@ -185,6 +185,16 @@ struct tdlo_ctx {
     double *vis_nodes_pin = nullptr;     // 3 x 64 doubles in pinned host memory: the nodes of a pre-pass that rides in the depth -> cloud team kernel
     long long cloud_vis_rides = 0;       // how many frames' pre-passes did (tdlo_debug_route_count 8)
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
+    // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
+    // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
+    // kernel (k_colour_mask), then the mask route as it is without colour (comparator)
+    char *col_pin = nullptr;
+    size_t col_pin_cap = 0;
+    int col_pin_rows = 0, col_pin_cols = 0;
+    void *col_dev = nullptr;
+    size_t col_dev_cap = 0;
+    bool colour_fused_on = !(getenv("TDLO_COLOUR_FUSED") && atoi(getenv("TDLO_COLOUR_FUSED")) == 0);
+    long long colour_route[2] = {0, 0};  // tdlo_debug_route_count 15 / 16: frames whose segmentation rode in the depth -> cloud launch / that took the mask kernel
     size_t pin_doubles = 0;
     std::string err;
     int last_F = 0;
@@ -1662,6 +1672,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->vis_nodes_pin) hipHostFree(c->vis_nodes_pin);
     if (c->cloud_res) hipHostFree(c->cloud_res);
     if (c->img_pin) hipHostFree(c->img_pin);
+    if (c->col_pin) hipHostFree(c->col_pin);
+    if (c->col_dev) hipFree(c->col_dev);
     if (c->reg_ws) hipFree(c->reg_ws);
     if (c->pin) hipHostFree(c->pin);
     if (c->pin2) hipHostFree(c->pin2);
@@ -2322,6 +2334,101 @@ int tdlo_image_buffers(tdlo_ctx *c, int rows, int cols, unsigned short **depth, 
     return TDLO_OK;
 }
 
+// ---- colour segmentation in front of depth -> cloud (trackdlo_node.cpp:84-119, :158-180) -------------------------------
+static size_t img_colour_bytes(size_t P) { return (3 * P + 16 + 255) & ~(size_t)255; }      // (the last thread's 12-byte load ends up to 9 bytes beyond the image)
+static size_t img_occ_bytes(size_t P) { return (P + 16 + 255) & ~(size_t)255; }
+
+struct ColourIn { const unsigned char *colour; const tdlo_colour_params *params; const unsigned char *occluder; };
+
+// tdlo_colour_params as the kernels take it: bounds clamped to 0 .. 255 and packed H | S << 8 | V << 16, upper - lower per channel beside them; a range
+// whose lower bound lies above its upper bound on a channel passes nothing and is left out
+static bool colour_pack(const tdlo_colour_params *p, CloudColour &cc) {
+    if (!p || p->n_ranges < 1 || p->n_ranges > 4) return false;
+    cc = CloudColour{};
+    cc.rgb = p->rgb_order ? 1 : 0;
+    for (int k = 0; k < p->n_ranges; ++k) {
+        unsigned lo = 0, sp = 0;
+        bool empty = false;
+        for (int ch = 0; ch < 3; ++ch) {
+            const int l = std::min(std::max(p->lower[k][ch], 0), 255), u = std::min(std::max(p->upper[k][ch], 0), 255);
+            if (l > u) empty = true;
+            lo |= (unsigned)l << (8 * ch); sp |= (unsigned)(u - l) << (8 * ch);
+        }
+        if (!empty) { cc.lo[cc.n] = lo; cc.span[cc.n] = sp; ++cc.n; }
+    }
+    return true;
+}
+
+int tdlo_colour_buffers(tdlo_ctx *c, int rows, int cols, unsigned char **colour, unsigned char **occluder) {
+    if (!c) return TDLO_E_INVALID;
+    if (rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26) || !colour || !occluder) return fail(c, TDLO_E_INVALID, "bad image");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)rows * cols, need = img_colour_bytes(P) + img_occ_bytes(P);
+    if (need > c->col_pin_cap) {
+        HIPCHK(c, drain_for_realloc(c));
+        if (c->col_pin) hipHostFree(c->col_pin);
+        c->col_pin = nullptr; c->col_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->col_pin, need, hipHostMallocDefault));
+        std::memset(c->col_pin, 0, need);
+        c->col_pin_cap = need;
+    }
+    c->col_pin_rows = rows; c->col_pin_cols = cols;
+    *colour = (unsigned char *)c->col_pin;
+    *occluder = (unsigned char *)(c->col_pin + img_colour_bytes(P));
+    return TDLO_OK;
+}
+
+// where the kernels read the frame's colour and occluder images: the context's pinned buffers when the caller passes exactly those (tdlo_colour_buffers),
+// else device copies made here; *d_hsv (optional): room for the HSV image behind them
+static int colour_stage(tdlo_ctx *c, const ColourIn &ci, int rows, int cols, CloudColour &cc, unsigned char **d_hsv) {
+    const size_t P = (size_t)rows * cols;
+    const size_t need = img_colour_bytes(P) + img_occ_bytes(P) + (d_hsv ? img_colour_bytes(P) : 0);
+    const bool in_place = c->col_pin != nullptr && (const char *)ci.colour == c->col_pin && c->col_pin_rows == rows && c->col_pin_cols == cols &&
+                          (!ci.occluder || (const char *)ci.occluder == c->col_pin + img_colour_bytes(P));
+    if ((!in_place || d_hsv) && need > c->col_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->col_dev) hipFree(c->col_dev);
+        c->col_dev = nullptr; c->col_dev_cap = 0;
+        HIPCHK(c, hipMalloc(&c->col_dev, need));
+        c->col_dev_cap = need;
+    }
+    char *base = (char *)c->col_dev;
+    if (in_place) { cc.colour = ci.colour; cc.occluder = ci.occluder; }
+    else {
+        cc.colour = (const unsigned char *)base;
+        cc.occluder = ci.occluder ? (const unsigned char *)(base + img_colour_bytes(P)) : nullptr;
+        HIPCHK(c, hipMemcpyAsync(base, ci.colour, 3 * P, hipMemcpyHostToDevice, c->stream));
+        if (ci.occluder) HIPCHK(c, hipMemcpyAsync(base + img_colour_bytes(P), ci.occluder, P, hipMemcpyHostToDevice, c->stream));
+    }
+    if (d_hsv) *d_hsv = (unsigned char *)(base + img_colour_bytes(P) + img_occ_bytes(P));
+    return TDLO_OK;
+}
+
+static int ensure_cloud_ws(tdlo_ctx *c, int P);
+
+// The segmentation on its own (k_colour_mask): the mask goes into the context's device mask buffer (where the multi-launch depth -> cloud form reads it) and,
+// when asked for, to the host together with the HSV image
+int tdlo_colour_mask(tdlo_ctx *c, const unsigned char *colour, int rows, int cols, const tdlo_colour_params *params, const unsigned char *occluder,
+                     unsigned char *mask_out, unsigned char *hsv_out) {
+    if (!c) return TDLO_E_INVALID;
+    CloudColour cc;
+    if (!colour_pack(params, cc)) return fail(c, TDLO_E_INVALID, "tdlo_colour_params: 1 .. 4 ranges");
+    if (!colour || rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26)) return fail(c, TDLO_E_INVALID, "bad image");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int P = rows * cols;
+    int rc = ensure_cloud_ws(c, P);
+    if (rc) return rc;
+    unsigned char *d_hsv = nullptr;
+    const ColourIn ci{colour, params, occluder};
+    if ((rc = colour_stage(c, ci, rows, cols, cc, hsv_out ? &d_hsv : nullptr))) return rc;
+    unsigned char *d_mask = (unsigned char *)c->cloud_ws + img_depth_bytes(P);
+    HIPCHK(c, launch_colour_mask(cc, P, d_mask, d_hsv, c->stream));
+    if (mask_out) HIPCHK(c, hipMemcpyAsync(mask_out, d_mask, (size_t)P, hipMemcpyDeviceToHost, c->stream));
+    if (hsv_out) HIPCHK(c, hipMemcpyAsync(hsv_out, d_hsv, 3 * (size_t)P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TDLO_OK;
+}
+
 // the visibility pre-pass's device / pinned words (shared by tdlo_visibility_prepass's one-launch route and the depth -> cloud team kernel's own pre-pass)
 static int ensure_vis_state(tdlo_ctx *c) {
     if (!c->vis_state) {
@@ -2341,28 +2448,41 @@ static int ensure_vis_state(tdlo_ctx *c) {
 
 // vis_Y != nullptr: the caller wants the frame's visibility pre-pass as well; *vis_done = true when the one-launch team kernel has left the M squared
 // minima in c->vis_res[1 ..] (otherwise the caller runs tdlo_visibility_prepass on the resident cloud)
+static int ensure_cloud_ws(tdlo_ctx *c, int P) {      // the device images (depth | mask) and the multi-launch form's workspace behind them
+    const size_t need = img_depth_bytes(P) + img_mask_bytes(P) + cloud_ws_bytes(P);
+    if (need > c->cloud_ws_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->cloud_ws) hipFree(c->cloud_ws);
+        c->cloud_ws = nullptr; c->cloud_ws_cap = 0;
+        HIPCHK(c, hipMalloc(&c->cloud_ws, need));
+        c->cloud_ws_cap = need;
+    }
+    return TDLO_OK;
+}
+
+// colour != nullptr (tdlo_colour_*): no mask is handed in -- the frame's segmentation is formed from the colour image, inside the one-launch kernel where
+// that serves the frame, else by k_colour_mask into the device mask buffer in front of the mask route
 static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
                                double fx, double fy, double cx, double cy, double leaf_size,
-                               double *X_out, int x_capacity, int *n_out, int *n_raw_out, const double *vis_Y, int vis_M, bool *vis_done) {
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out, const double *vis_Y, int vis_M, bool *vis_done,
+                               const ColourIn *colour = nullptr) {
     if (!c) return TDLO_E_INVALID;
     if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
-    if (!depth || !mask || rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26)) return fail(c, TDLO_E_INVALID, "bad image");
+    CloudColour cc{};
+    if (colour) {
+        if (!colour_pack(colour->params, cc)) return fail(c, TDLO_E_INVALID, "tdlo_colour_params: 1 .. 4 ranges");
+        if (!colour->colour) return fail(c, TDLO_E_INVALID, "bad image");
+    }
+    if (!depth || (!mask && !colour) || rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26)) return fail(c, TDLO_E_INVALID, "bad image");
     if (!(leaf_size > 0) || fx == 0 || fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
     HIPCHK(c, hipSetDevice(c->device));
     Slot &s = c->slots[slot];
     hipStream_t st = c->stream;
     const int P = rows * cols;
     const size_t img = img_depth_bytes(P) + img_mask_bytes(P);
-    const size_t need = img + cloud_ws_bytes(P);
-    if (need > c->cloud_ws_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cloud_ws) hipFree(c->cloud_ws);
-        c->cloud_ws = nullptr; c->cloud_ws_cap = 0;
-        HIPCHK(c, hipMalloc(&c->cloud_ws, need));
-        c->cloud_ws_cap = need;
-    }
-    int rc = ensure_pin(c, 16);
+    int rc = ensure_cloud_ws(c, P);
     if (rc) return rc;
+    if ((rc = ensure_pin(c, 16))) return rc;
     if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;      // (a cloud tracking_step staged for this slot is superseded; its copy is harmless and ordered)
     char *base = (char *)c->cloud_ws;
     const unsigned short *d_depth = (unsigned short *)base;
@@ -2372,7 +2492,19 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
     // images the caller wrote into the context's pinned buffers (tdlo_image_buffers) are read where they are; anything else is copied first
     const bool in_place = c->img_pin != nullptr && (const char *)depth == c->img_pin && (const char *)mask == c->img_pin + img_depth_bytes(P) &&
                           c->img_pin_rows == rows && c->img_pin_cols == cols;
-    if (in_place) { d_depth = depth; d_mask = mask; }
+    bool mask_ready = true;                   // d_mask holds the frame's mask
+    if (colour) {
+        // the depth image where it is when it lies in the context's pinned buffer, the colour and occluder images likewise (tdlo_colour_buffers); the mask is
+        // always the device buffer: k_colour_mask writes it when the one-launch kernel does not serve the frame
+        if (c->img_pin != nullptr && (const char *)depth == c->img_pin && c->img_pin_rows == rows && c->img_pin_cols == cols) d_depth = depth;
+        else HIPCHK(c, hipMemcpyAsync((void *)d_depth, depth, (size_t)P * 2, hipMemcpyHostToDevice, st));
+        if ((rc = colour_stage(c, *colour, rows, cols, cc, nullptr))) return rc;
+        mask_ready = false;
+        if (!(c->colour_fused_on && c->cloud_fused_on && cloud_fused_ok(P))) {
+            HIPCHK(c, launch_colour_mask(cc, P, (unsigned char *)d_mask, nullptr, st));
+            mask_ready = true; ++c->colour_route[1];
+        }
+    } else if (in_place) { d_depth = depth; d_mask = mask; }
     else {
         HIPCHK(c, hipMemcpyAsync((void *)d_depth, depth, (size_t)P * 2, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync((void *)d_mask, mask, (size_t)P, hipMemcpyHostToDevice, st));
@@ -2406,7 +2538,7 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
             std::memcpy(c->vis_nodes_pin, vis_Y, sizeof(double) * 3 * (size_t)vis_M);
         }
         HIPCHK(c, launch_cloud_fused(d_depth, d_mask, P, cols, cam, inv, ws, c->cloud_fws, c->cloud_fused_first, c->cloud_team_on, s.Xraw, s.cap_points, c->cloud_res, c->cloud_epoch, st,
-                                     vis_ride ? c->vis_nodes_pin : nullptr, vis_ride ? vis_M : 0, c->vis_state, c->vis_res));
+                                     vis_ride ? c->vis_nodes_pin : nullptr, vis_ride ? vis_M : 0, c->vis_state, c->vis_res, mask_ready ? nullptr : &cc));
         c->cloud_fused_first = false;
         const int status = cloud_wait(c, st, c->cloud_epoch);
         if (status != 1 && vis_ride) c->vis_armed = false;      // (whatever the team left in the minima: armed again before their next use)
@@ -2414,12 +2546,17 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
         if (status == 0) { c->cloud_fused_first = true; return fail(c, TDLO_E_HIP, "the stream drained, but the depth -> cloud kernel did not report"); }
         const unsigned long long w1 = __atomic_load_n(c->cloud_res + 1, __ATOMIC_RELAXED);
         nraw = (int)(unsigned)(w1 >> 32);
+        if (status == 1 && !mask_ready) ++c->colour_route[0];
         if (status == 1) { n = (int)(unsigned)w1; ++c->cloud_route[0]; if (vis_ride && vis_done) { *vis_done = true; ++c->cloud_vis_rides; } }
         else if (status == 3) return fail(c, TDLO_E_HIP, "voxel grid produced more points than the slot holds");
         else if (status == 4) { c->cloud_fused_first = true; ++c->cloud_route[1]; }      // the team gave the launch up (a wait of 2 s): state words initialised again, the multi-launch form below
         else ++c->cloud_route[1];                 // not taken (too many masked pixels / cells, pass-through): the multi-launch form below
     }
     if (n < 0) {
+        if (!mask_ready) {                    // the one-launch kernel passed a colour frame on: its segmentation by the mask kernel, then as for any mask
+            HIPCHK(c, launch_colour_mask(cc, P, (unsigned char *)d_mask, nullptr, st));
+            mask_ready = true; ++c->colour_route[1];
+        }
         // ---- the multi-launch form: bounding box + count, a host round trip, compaction, radix sort passes, centroids
         // the last 64 ints of the workspace: bounding box (6 ordered floats), masked-pixel count, output count
         unsigned *d_bbox = (unsigned *)(ws + cloud_ws_bytes(P) - 256);
@@ -2472,6 +2609,13 @@ int tdlo_depth_to_cloud(tdlo_ctx *c, int slot, const unsigned short *depth, cons
                         double fx, double fy, double cx, double cy, double leaf_size,
                         double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
     return depth_to_cloud_impl(c, slot, depth, mask, rows, cols, fx, fy, cx, cy, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
+}
+
+int tdlo_colour_depth_to_cloud(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                               const unsigned char *occluder, int rows, int cols, double fx, double fy, double cx, double cy, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+    const ColourIn ci{colour, params, occluder};
+    return depth_to_cloud_impl(c, slot, depth, nullptr, rows, cols, fx, fy, cx, cy, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr, &ci);
 }
 
 // ---- caller-side visibility pre-pass ------------------------------------------------------------
@@ -2570,16 +2714,16 @@ static void vis_threshold_and_fill(const double *min_d2, int M, double visibilit
 // pre-pass of the tracker's current nodes against that cloud.  With up to 64 nodes and the one-launch team kernel the pre-pass rides in the same launch
 // (every team member takes the minima over the centroids it has just formed): one launch and one hand-over through pinned memory for both steps.
 // Otherwise -- more nodes, TDLO_CLOUD_TEAM=0, too many masked pixels, a team that gave up -- tdlo_visibility_prepass runs behind it: the same numbers.
-int tdlo_depth_to_cloud_visibility(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
-                                   double fx, double fy, double cx, double cy, double leaf_size,
-                                   const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
-                                   double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
-                                   int *n_out, int *n_raw_out) {
+static int depth_to_cloud_visibility_impl(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *mask, const ColourIn *colour, int rows, int cols,
+                                          double fx, double fy, double cx, double cy, double leaf_size,
+                                          const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                          double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                          int *n_out, int *n_raw_out) {
     if (!c) return TDLO_E_INVALID;
     if (!Y || M < 1 || !geodesic_coord) return fail(c, TDLO_E_INVALID, "null Y / geodesic_coord");
     bool vis_done = false;
     int n = 0;
-    int rc = depth_to_cloud_impl(c, slot, depth, mask, rows, cols, fx, fy, cx, cy, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done);
+    int rc = depth_to_cloud_impl(c, slot, depth, mask, rows, cols, fx, fy, cx, cy, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done, colour);
     if (n_out) *n_out = n;
     if (rc) return rc;
     if (n_vis) *n_vis = 0;
@@ -2590,6 +2734,25 @@ int tdlo_depth_to_cloud_visibility(tdlo_ctx *c, int slot, const unsigned short *
     std::memcpy(c->pin, c->vis_res + 1, sizeof(double) * M);
     vis_threshold_and_fill(c->pin, M, visibility_threshold, d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext);
     return TDLO_OK;
+}
+
+int tdlo_depth_to_cloud_visibility(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
+                                   double fx, double fy, double cx, double cy, double leaf_size,
+                                   const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                   double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                   int *n_out, int *n_raw_out) {
+    return depth_to_cloud_visibility_impl(c, slot, depth, mask, nullptr, rows, cols, fx, fy, cx, cy, leaf_size, Y, M, visibility_threshold, d_vis, geodesic_coord,
+                                          node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
+}
+
+int tdlo_colour_depth_to_cloud_visibility(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                                          const unsigned char *occluder, int rows, int cols, double fx, double fy, double cx, double cy, double leaf_size,
+                                          const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                          double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                          int *n_out, int *n_raw_out) {
+    const ColourIn ci{colour, params, occluder};
+    return depth_to_cloud_visibility_impl(c, slot, depth, nullptr, &ci, rows, cols, fx, fy, cx, cy, leaf_size, Y, M, visibility_threshold, d_vis, geodesic_coord,
+                                          node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
 }
 
 // ---- measurement ---------------------------------------------------------------------------------
@@ -2789,7 +2952,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 14) return -1;
+    if (!c || which < 0 || which > 16) return -1;
+    if (which >= 15) return c->colour_route[which - 15];
     if (which == 14) return c->fused_calls;
     if (which >= 11 && which <= 13) return 0;      // (belonged to experiments that were removed; not reused)
     if (which == 10) return c->boost_retries;
@@ -3189,10 +3353,10 @@ int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N, const in
 
 // One frame of the ROS node's callback, images in, nodes out (trackdlo_node.cpp:195-369): depth image + mask -> cloud -> voxel grid and the visibility
 // pre-pass of the tracker's nodes (tdlo_depth_to_cloud_visibility: one launch), then tracking_step on the cloud resident in the tracker's slot.
-int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
-                                  double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
-                                  int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
-                                  int *n_out, int *n_raw_out, tdlo_stats *stats) {
+static int tracker_frame_impl(tdlo_tracker *t, const unsigned short *depth, const unsigned char *mask, const ColourIn *colour, int rows, int cols,
+                              double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                              int *n_out, int *n_raw_out, tdlo_stats *stats) {
     if (!t) return TDLO_E_INVALID;
     tdlo_ctx *c = t->ctx;
     const int M = t->M;
@@ -3201,7 +3365,7 @@ int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, 
     v.resize(M); ve.resize(M);
     int nv = 0, ne = 0, n = 0;
     t->frame_dist.resize(M);
-    int rc = tdlo_depth_to_cloud_visibility(c, t->slot, depth, mask, rows, cols, fx, fy, cx, cy, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis,
+    int rc = depth_to_cloud_visibility_impl(c, t->slot, depth, mask, colour, rows, cols, fx, fy, cx, cy, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis,
                                             t->geodesic_coord.data(), t->frame_dist.data(), v.data(), &nv, ve.data(), &ne, &n, n_raw_out);
     if (!rc && t->painter_on && n > 0) {
         // the callback's self-occlusion test (trackdlo_node.cpp:279-343) between the distance pre-pass and the gap fill, when the tracker was given a
@@ -3222,6 +3386,25 @@ int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, 
     if (n == 0) return fail(c, TDLO_E_EMPTY, "the mask selects no pixel: no cloud for this frame");
     if (ne == 0) return fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)");
     return tdlo_tracker_tracking_step(t, nullptr, 0, v.data(), nv, ve.data(), ne, nullptr, stats);
+}
+
+int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
+                                  double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                                  int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                  int *n_out, int *n_raw_out, tdlo_stats *stats) {
+    return tracker_frame_impl(t, depth, mask, nullptr, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext,
+                              n_out, n_raw_out, stats);
+}
+
+// The same from the two sensor images (trackdlo_node.cpp:158-277, :345-369): the segmentation is formed from the colour image on the device
+int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth, const unsigned char *colour, const tdlo_colour_params *params,
+                                   const unsigned char *occluder, int rows, int cols,
+                                   double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                   int *n_out, int *n_raw_out, tdlo_stats *stats) {
+    const ColourIn ci{colour, params, occluder};
+    return tracker_frame_impl(t, depth, nullptr, &ci, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext,
+                              n_out, n_raw_out, stats);
 }
 
 // trackdlo_node.cpp:279-343 on the host (tdlo_host.cpp, self_occlusion_visible): O(M^2) integer tests, no kernel warranted

@@ -313,6 +313,76 @@ __global__ __launch_bounds__(kCB) void k_cloud_centroid(const unsigned short *__
 // Bit-exact to the multi-launch form and to the oracle: the same float operations in the same order.
 namespace {
 
+// ---- colour segmentation in front of the cloud (trackdlo_node.cpp:84-119, :158-180): cv::cvtColor(BGR2HSV), one or four cv::inRange, the AND with the
+// occluder image.  8-bit BGR -> HSV is OpenCV's published integer routine (hsv_shift = 12, hue range 180): two tables of fixed-point quotients,
+//   sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)), fp64 division, ties to even, entry 0 = 0,
+// and per pixel, in 32-bit integers, s = (d sdiv[v] + 2048) >> 12, h = (h' hdiv[d] + 2048) >> 12 (+ 180 when negative).  NOT the rounded float formula: the
+// tables' rounding decides ~2 % of the colour cube.  Restated from the algorithm (OpenCV is not part of the build image): PARITY UNPINNED against OpenCV;
+// tests/colour_ref.py is the numpy statement that every colour of the cube is held to, bit for bit.
+// The tables are formed by the workgroup itself (512 threads, one fp64 division each: correctly rounded, v_rndne_f64) while its pixels' bytes travel.
+__device__ __forceinline__ void colour_fill_tables(int *tab, int i) {         // tab[0 .. 255] = sdiv, tab[256 .. 511] = hdiv; i < 512
+    const int k = i & 255;
+    const double q = i < 256 ? (double)(255 << 12) / (1.0 * (double)k) : (double)(180 << 12) / (6.0 * (double)k);
+    tab[i] = k ? (int)::rint(q) : 0;
+}
+// H | S << 8 | V << 16
+__device__ __forceinline__ unsigned colour_hsv(int b, int g, int r, const int *tab) {
+    const int v = max(max(b, g), r), vmin = min(min(b, g), r), d = v - vmin;
+    const int s = (d * tab[v] + 2048) >> 12;
+    int h = (v == r) ? g - b : ((v == g) ? b - r + 2 * d : r - g + 4 * d);
+    h = (h * tab[256 + d] + 2048) >> 12;                                      // (arithmetic shift)
+    h += h < 0 ? 180 : 0;
+    return (unsigned)h | ((unsigned)s << 8) | ((unsigned)v << 16);
+}
+// the HSV words of the four pixels whose 12 colour bytes are c0 c1 c2 (little endian), and their mask word: byte k = 255 when pixel k passes one of the
+// ranges (per channel: x - lo <= hi - lo as unsigned bytes, the bounds packed by the host) and its occluder byte (o4) is not 0
+__device__ __forceinline__ unsigned colour_quad(unsigned c0, unsigned c1, unsigned c2, unsigned o4, const CloudColour &cc, const int *tab, unsigned w[4]) {
+    const int y[12] = {(int)(c0 & 255u), (int)((c0 >> 8) & 255u), (int)((c0 >> 16) & 255u), (int)(c0 >> 24),
+                       (int)(c1 & 255u), (int)((c1 >> 8) & 255u), (int)((c1 >> 16) & 255u), (int)(c1 >> 24),
+                       (int)(c2 & 255u), (int)((c2 >> 8) & 255u), (int)((c2 >> 16) & 255u), (int)(c2 >> 24)};
+    unsigned m4 = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x0 = y[3 * k], x2 = y[3 * k + 2];
+        w[k] = colour_hsv(cc.rgb ? x2 : x0, y[3 * k + 1], cc.rgb ? x0 : x2, tab);
+        bool ok = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q < cc.n) {                                                   // (uniform)
+                const unsigned lo = cc.lo[q], sp = cc.span[q];
+                ok = ok || (((w[k] & 255u) - (lo & 255u)) <= (sp & 255u) && (((w[k] >> 8) & 255u) - ((lo >> 8) & 255u)) <= ((sp >> 8) & 255u) &&
+                            ((w[k] >> 16) - (lo >> 16)) <= (sp >> 16));
+            }
+        if (ok && ((o4 >> (8 * k)) & 255u) != 0u) m4 |= 255u << (8 * k);      // :172-174
+    }
+    return m4;
+}
+
+// the segmentation on its own: thread = 4 consecutive pixels (12 colour bytes in, one mask word out; the HSV image when asked for) -- the comparator of the
+// colour instantiation of the one-launch kernels, and what the multi-launch form runs on when they pass a frame on
+__global__ __launch_bounds__(kCB) void k_colour_mask(const CloudColour cc, int P, unsigned char *__restrict__ mask, unsigned char *__restrict__ hsv) {
+    __shared__ int tab[512];
+    const int t = threadIdx.x;
+    const int p0 = (blockIdx.x * kCB + t) * 4;
+    unsigned c0 = 0u, c1 = 0u, c2 = 0u, o4 = 0x01010101u;
+    if (p0 < P) {
+        const unsigned *cp = (const unsigned *)(cc.colour + 3 * (size_t)p0);
+        c0 = cp[0]; c1 = cp[1]; c2 = cp[2];
+        if (cc.occluder) o4 = *(const unsigned *)(cc.occluder + p0);
+    }
+    colour_fill_tables(tab, t); colour_fill_tables(tab, t + kCB);
+    __syncthreads();
+    if (p0 >= P) return;
+    unsigned w[4];
+    unsigned m4 = colour_quad(c0, c1, c2, o4, cc, tab, w);
+    if (p0 + 4 > P) m4 &= 0xffffffffu >> (8 * (4 - (P - p0)));                // (the last word of the image; the buffers are padded)
+    *(unsigned *)(mask + p0) = m4;
+    if (hsv) {
+        unsigned *hp = (unsigned *)(hsv + 3 * (size_t)p0);
+        hp[0] = w[0] | (w[1] << 24); hp[1] = (w[1] >> 8) | (w[2] << 16); hp[2] = (w[2] >> 16) | (w[3] << 8);
+    }
+}
+
 constexpr int kFT = 1024;                // threads per workgroup
 constexpr int kFW = kFT / 64;            // waves
 constexpr int kFPix = 4 * kFT;           // pixels per tile
@@ -325,6 +395,7 @@ constexpr size_t kFLds = kFLdsE + kFLdsCnt;         // 163 584 B; with the kerne
 
 struct FusedCloud {
     const unsigned short *depth; const unsigned char *mask;     // padded to 8 bytes beyond P pixels
+    CloudColour col;                     // the colour instantiation forms its mask words from these (12 colour bytes + 4 occluder bytes per thread; padded likewise)
     int P, cols, T;
     Cam cam;
     float inv_leaf;
@@ -411,6 +482,7 @@ __device__ __forceinline__ void cloud_grid(const unsigned *sbox, int n, float in
 
 // phase A of the one-launch kernels, every workgroup: its tile of 4096 pixels -- compaction in pixel order, back-projection, the points to the tile's
 // region, count, bounding box -- and a ticket (returned to every thread: 0 .. T - 1 in the order the workgroups finished)
+template <bool kColour>
 __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot, unsigned *sticket, unsigned *sbx /* kFW x 6 words of LDS nobody uses yet */) {
     const int t = threadIdx.x, lane = t & 63, b = blockIdx.x;
 #ifdef TDLO_CLOUD_STAMPS      // wall-clock (100 MHz) split of phase A in the middle tile: words 12 .. 18 behind the state words (scripts/archive/gpu_cloud_stamps.py)
@@ -422,7 +494,23 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
     {
         const int p0 = b * kFPix + 4 * t;
         unsigned m4 = 0;
-        if (p0 < a.P) m4 = *(const unsigned *)(a.mask + p0);
+        if constexpr (kColour) {
+            // the four pixels' 12 colour bytes (12-byte aligned: one load, coalesced) and their occluder bytes are requested; while they travel the
+            // workgroup forms the two tables of quotients in dynamic LDS that nobody uses during this phase (behind sbx)
+            unsigned c0 = 0u, c1 = 0u, c2 = 0u, o4 = 0x01010101u;
+            if (p0 < a.P) {
+                const unsigned *cp = (const unsigned *)(a.col.colour + 3 * (size_t)p0);
+                c0 = cp[0]; c1 = cp[1]; c2 = cp[2];
+                if (a.col.occluder) o4 = *(const unsigned *)(a.col.occluder + p0);
+            }
+            int *tab = (int *)(sbx + 128);                                    // 2 KB
+            if (t < 512) colour_fill_tables(tab, t);
+            __syncthreads();
+            unsigned w[4];
+            if (p0 < a.P) m4 = colour_quad(c0, c1, c2, o4, a.col, tab, w);
+        } else {
+            if (p0 < a.P) m4 = *(const unsigned *)(a.mask + p0);
+        }
         ASTAMP(1);
         if (p0 + 4 > a.P) {                                                   // (the last word of the image: bytes beyond it do not count)
             const int keep = a.P - p0;
@@ -496,6 +584,7 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
 
 
 
+template <bool kColour>
 __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     unsigned *E = (unsigned *)fsm;                                           // kFNmax sort words (through sw(): bank swizzle)
@@ -513,7 +602,7 @@ __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
 #endif
 
     // ================= phase A: this tile
-    if (cloud_phase_a(a, wtot, &sticket, (unsigned *)fsm) != (unsigned)(a.T - 1)) return;
+    if (cloud_phase_a<kColour>(a, wtot, &sticket, (unsigned *)fsm) != (unsigned)(a.T - 1)) return;
 
     // ================= phase B: the workgroup with the last ticket
     FSTAMP(0);
@@ -830,6 +919,7 @@ __device__ __forceinline__ bool team_barrier(unsigned *state, int idx, int K, in
     return *sflag != 0;
 }
 
+template <bool kColour>
 __global__ __launch_bounds__(kFT) void k_cloud_team(const FusedCloud a) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     unsigned short *cnt = (unsigned short *)fsm;                             // [chunk][digit]: lanes of the chunk with the digit, then their start inside the chunk's quarter
@@ -855,7 +945,7 @@ __global__ __launch_bounds__(kFT) void k_cloud_team(const FusedCloud a) {
 #ifdef TDLO_CLOUD_STAMPS
     const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();    // (100 MHz) this workgroup's start
 #endif
-    const unsigned ticket = cloud_phase_a(a, wtot, &sticket, (unsigned *)fsm);
+    const unsigned ticket = cloud_phase_a<kColour>(a, wtot, &sticket, (unsigned *)fsm);
     const int K = a.T < kTK ? a.T : kTK;
     if ((int)ticket < a.T - K) return;                                       // not in the team: done, having waited for nobody
     const int k = (int)ticket - (a.T - K);                                   // rank in the team
@@ -1209,15 +1299,17 @@ bool cloud_fused_ok(int P) { return ((size_t)P + kFPix - 1) / kFPix <= (size_t)k
 // bytes kept by the kernels themselves between the launches (first == true: the state words are initialised by a copy in front of the launch)
 hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], float inv_leaf, void *ws, void *fws,
                               bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
-                              const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned) {
+                              const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned, const CloudColour *colour) {
     {   // on every launch, for the CURRENT device, like every other launcher of the library: HIP keeps the attribute per device function, so a
         // process-wide "done once" flag would leave a second context on another GPU (the exchange tests, a one-process multi-GPU caller) launching
         // 116 / 160 KB of dynamic LDS without it; the call is a table look-up
-        hipError_t e = team ? hipFuncSetAttribute((const void *)k_cloud_team, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTLds)
-                            : hipFuncSetAttribute((const void *)k_cloud_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds);
+        const void *fn = team ? (colour ? (const void *)k_cloud_team<true> : (const void *)k_cloud_team<false>)
+                              : (colour ? (const void *)k_cloud_fused<true> : (const void *)k_cloud_fused<false>);
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, team ? (int)kTLds : (int)kFLds);
         if (e != hipSuccess) return e;
     }
     FusedCloud a;
+    a.col = colour ? *colour : CloudColour{};
     a.depth = depth; a.mask = mask; a.P = P; a.cols = cols; a.T = (P + kFPix - 1) / kFPix;
     a.cam = Cam{cam[0], cam[1], cam[2], cam[3]};
     a.inv_leaf = inv_leaf;
@@ -1238,8 +1330,18 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
         const hipError_t e = hipMemcpyAsync(a.state, init, sizeof init, hipMemcpyHostToDevice, s);
         if (e != hipSuccess) return e;
     }
-    if (team) hipLaunchKernelGGL(k_cloud_team, dim3(a.T), dim3(kFT), kTLds, s, a);
-    else hipLaunchKernelGGL(k_cloud_fused, dim3(a.T), dim3(kFT), kFLds, s, a);
+    if (team) {
+        if (colour) hipLaunchKernelGGL(k_cloud_team<true>, dim3(a.T), dim3(kFT), kTLds, s, a);
+        else hipLaunchKernelGGL(k_cloud_team<false>, dim3(a.T), dim3(kFT), kTLds, s, a);
+    } else {
+        if (colour) hipLaunchKernelGGL(k_cloud_fused<true>, dim3(a.T), dim3(kFT), kFLds, s, a);
+        else hipLaunchKernelGGL(k_cloud_fused<false>, dim3(a.T), dim3(kFT), kFLds, s, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s) {
+    hipLaunchKernelGGL(k_colour_mask, dim3((P + kTile - 1) / kTile), dim3(kCB), 0, s, colour, P, mask, hsv);
     return hipGetLastError();
 }
 

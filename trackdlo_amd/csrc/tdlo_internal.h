@@ -281,6 +281,10 @@ size_t reg_ws_doubles(int M, int nblk);
 int reg_max_nodes();        // the E-step's per-wave accumulators must fit 160 KB of LDS
 hipError_t launch_reg(const double *X, int N, int M, double mu, int max_iter, int nblk, double *ws, hipStream_t s);
 // tdlo_cloud.hip: depth image -> cloud -> voxel grid
+// colour segmentation in front of it (tdlo_colour_params as the kernels take it): the colour image (3 bytes a pixel) and the optional occluder image, readable by
+// the device and padded to 16 bytes beyond the image; per range the lower bounds H | S << 8 | V << 16 and upper - lower per channel (ranges that
+// cannot pass -- lower > upper on a channel -- are left out by the host: n <= 4 may be 0); rgb: the image's bytes are R G B
+struct CloudColour { const unsigned char *colour, *occluder; unsigned lo[4], span[4]; int n, rgb; };
 size_t cloud_ws_bytes(int P);
 hipError_t launch_cloud_bbox(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], unsigned *bbox, void *ws, hipStream_t s);
 hipError_t launch_cloud_voxels(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4],
@@ -292,7 +296,11 @@ int cloud_fused_max_points();
 bool cloud_fused_ok(int P);
 hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], float inv_leaf, void *ws, void *fws,
                               bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
-                              const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr, unsigned long long *vis_out_pinned = nullptr);
+                              const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr, unsigned long long *vis_out_pinned = nullptr,
+                              const CloudColour *colour = nullptr);
+// colour != nullptr above: `mask` is not read, the kernel forms its mask words from the colour image (tdlo_colour_*).  The segmentation on its own
+// (k_colour_mask): mask (rows x cols bytes, 0 / 255) and, when hsv != nullptr, the HSV image (3 bytes a pixel), both device memory padded to 16 bytes beyond the image
+hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s);
 int check_device_image();
 
 }  // namespace tdlo

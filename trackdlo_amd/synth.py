@@ -126,3 +126,59 @@ def depth_scene(M: int, config: int = 0, frame: int = 0, *, radius: float = 0.00
         on = np.nonzero(mask)[0]
         depth[on[rng.choice(len(on), size=min(zero_depth_pixels, len(on)), replace=False)]] = 0
     return depth.astype(np.uint16).reshape(cam["rows"], cam["cols"]), mask.reshape(cam["rows"], cam["cols"]), cam, Y0
+
+
+def _bgr_to_hsv(c):
+    """8-bit B, G, R [n x 3] -> H, S, V [n x 3] by the integer routine the library implements (include/trackdlo_hip.h, tdlo_colour_params)."""
+    i = np.arange(1, 256, dtype=np.float64)
+    sdiv = np.concatenate([[0], np.rint((255 << 12) / (1.0 * i))]).astype(np.int64)
+    hdiv = np.concatenate([[0], np.rint((180 << 12) / (6.0 * i))]).astype(np.int64)
+    b, g, r = (c[:, k].astype(np.int64) for k in range(3))
+    v = np.maximum(np.maximum(b, g), r); d = v - np.minimum(np.minimum(b, g), r)
+    s = (d * sdiv[v] + 2048) >> 12
+    h = np.where(v == r, g - b, np.where(v == g, b - r + 2 * d, r - g + 4 * d))
+    h = (h * hdiv[d] + 2048) >> 12
+    h = h + np.where(h < 0, 180, 0)
+    return np.stack([h, s, v], axis=1)
+
+
+def colour_scene(M: int, lower, upper, config: int = 0, frame: int = 0, *, occluder=None, razor: float = 0.25, rgb_order: int = 0,
+                 pool: int = 1 << 18, **kw):
+    """depth_scene plus the colour image the camera would deliver with it (what trackdlo_node.cpp:123 receives) and, optionally, the occlusion mask of
+    :172-174.  lower / upper: 1 .. 4 H, S, V ranges (inclusive).  Every rope pixel of depth_scene's mask gets a colour that passes one of the ranges,
+    every other pixel one that fails all of them (drawn from a random pool of `pool` colours classified with the integer BGR -> HSV routine); the share
+    `razor` of both are colours whose H, S or V equals one of the bounds or lies one unit beside it -- the colours on which the rounding of the
+    routine's tables decides.  occluder = (r0, r1, c0, c1): an occluder image that is 0 inside that rectangle and 255 elsewhere.  rgb_order = 1: the
+    image's bytes are R, G, B.  kw: depth_scene's (rows, cols, ...).
+    Returns (depth, colour [rows x cols x 3 uint8], occluder image or None, mask [the segmentation these images define], camera dict, Y0)."""
+    depth, rope, cam, Y0 = depth_scene(M, config=config, frame=frame, **kw)
+    rng = np.random.default_rng(BASE_SEED + 1000 * config + frame + 177)
+    lo = np.clip(np.asarray(lower, dtype=np.int64).reshape(-1, 3), 0, 255); hi = np.clip(np.asarray(upper, dtype=np.int64).reshape(-1, 3), 0, 255)
+    cand = rng.integers(0, 256, size=(pool, 3), dtype=np.int64)
+    hsv = _bgr_to_hsv(cand)
+    ok = np.zeros(pool, dtype=bool)
+    for l, u in zip(lo, hi):
+        ok |= np.all((hsv >= l) & (hsv <= u), axis=1)
+    bounds = np.concatenate([lo, hi])                                  # [2 n x 3]
+    edge = np.any(np.abs(hsv[:, None, :] - bounds[None, :, :]) <= 1, axis=(1, 2))
+    pools = {(p, e): cand[(ok == p) & (edge == e)] for p in (True, False) for e in (True, False)}
+    if min(len(v) for v in pools.values()) == 0:
+        raise ValueError("the ranges leave no colour to draw from (passing / failing, on / off a bound)")
+    on = rope.reshape(-1) != 0
+    img = np.zeros((on.size, 3), dtype=np.uint8)
+    for p in (True, False):
+        idx = np.nonzero(on == p)[0]
+        rz = rng.random(len(idx)) < razor
+        for e in (True, False):
+            sel = idx[rz == e]
+            img[sel] = pools[(p, e)][rng.integers(0, len(pools[(p, e)]), size=len(sel))]
+    if rgb_order:
+        img = img[:, ::-1]
+    occ = None
+    mask = rope.copy()
+    if occluder is not None:
+        r0, r1, c0, c1 = occluder
+        occ = np.full(rope.shape, 255, dtype=np.uint8)
+        occ[r0:r1, c0:c1] = 0
+        mask[occ == 0] = 0
+    return depth, np.ascontiguousarray(img.reshape(rope.shape + (3,))), occ, mask, cam, Y0

@@ -109,6 +109,45 @@ int tdlo_synchronize(tdlo_ctx *ctx);
  * Replaces the by-value `MatrixXd X_orig` argument of cpd_lle / tracking_step (trackdlo.h:80, :96). */
 int tdlo_set_cloud(tdlo_ctx *ctx, int slot, const double *X, int N);
 
+/* ---- clouds as they arrive: float32 or float64, any strides, host or device memory ------------- */
+/* A view of N points somewhere in memory; nothing is copied to build one.  The reference's own cloud is float (pcl::PointXYZRGB: x, y, z at a
+ * 32-byte point stride; widened and transposed on the host at trackdlo_node.cpp:242): view_of(&points[0].x, 8).  float -> double is exact, so a
+ * cloud imported through a view is, bit for bit, what tdlo_set_cloud makes of the widened column-major copy. */
+enum { TDLO_F32 = 0, TDLO_F64 = 1 };                        /* tdlo_cloud_view.dtype */
+enum { TDLO_MEM_AUTO = 0, TDLO_MEM_HOST = 1, TDLO_MEM_DEVICE = 2 };   /* tdlo_cloud_view.location */
+enum { TDLO_VIEW_ASYNC = 1 };                               /* tdlo_cloud_view.flags */
+typedef struct {
+    const void *data;          /* address of x of point 0 */
+    int dtype, location;
+    long long stride_point;    /* in ELEMENTS: component c of point n is element n*stride_point + c*stride_comp */
+    long long stride_comp;     /* signed; packed row-major N x 3: (3, 1); PCL PointXYZ / XYZRGB: (4, 1) / (8, 1); column-major with leading dimension ld: (1, ld) */
+    void *ready_stream;        /* device sources: hipStream_t whose work so far produces the data; NULL = the data is ready */
+    int flags;
+} tdlo_cloud_view;
+/* Whether (v, N) describes a cloud: TDLO_E_INVALID for a null view or null data, N <= 0, an unknown dtype, location or flag bit, stride_point == 0
+ * with N > 1, stride_comp == 0, data not aligned to its element size, an extent that does not fit 64-bit byte offsets.  Negative strides are legal
+ * (a reversed view is a cloud).  Needs no context and no GPU; every call below that takes a view runs it first. */
+int tdlo_cloud_view_check(const tdlo_cloud_view *v, int N);
+/* The bytes the view addresses, relative to v->data: [*lo_bytes, *hi_bytes), from the first byte of its lowest element to one past the last byte of
+ * its highest.  The library never reads a byte outside them, with any load. */
+int tdlo_cloud_view_extent(const tdlo_cloud_view *v, int N, long long *lo_bytes, long long *hi_bytes);
+/* tdlo_set_cloud from a view: the slot's resident cloud becomes the widened, column-major copy of the view (one kernel, k_cloud_import,
+ * csrc/tdlo_import.hip; non-finite values are widened as (double) widens them -- the prune drops such points).
+ *   location  TDLO_MEM_AUTO asks hipPointerGetAttributes; a pointer the runtime does not know is host memory.  Device memory of another GPU:
+ *             TDLO_E_INVALID.  Managed and caller-pinned memory is treated as host memory and copied; no kernel dereferences it.
+ *   host source    x, y, z are packed in the source precision into the context's pinned staging buffer (12 bytes per float point) and widened by the
+ *             kernel, which reads that block in place over PCIe (TDLO_VIEW_INPLACE=0, read when the context is made: copied to the device first,
+ *             the comparator).  The caller's memory is theirs again when the call returns.
+ *   device source  the kernel reads the caller's memory in place.  The call returns after the import has finished; with TDLO_VIEW_ASYNC it is only
+ *             enqueued on tdlo_stream(ctx), and the source must stay valid and unchanged until the caller's next call that waits for that stream
+ *             (any registration, tdlo_get_cloud or tdlo_synchronize).  ready_stream: an event recorded on it makes the context's stream wait for
+ *             the work that produces the data -- no host wait. */
+int tdlo_set_cloud_view(tdlo_ctx *ctx, int slot, const tdlo_cloud_view *v, int N);
+/* Copies the slot's resident cloud as it stands -- whatever tdlo_set_cloud, tdlo_set_cloud_view, tdlo_depth_to_cloud or a tracker frame left there
+ * (what the node publishes on /trackdlo/filtered_pointcloud, trackdlo_node.cpp:480-484): n x 3 column-major, leading dimension n; *n_out = n.
+ * x_capacity < n: TDLO_E_INVALID with *n_out set.  Waits for the context's stream. */
+int tdlo_get_cloud(tdlo_ctx *ctx, int slot, double *X_out, int x_capacity, int *n_out);
+
 /* trackdlo::cpd_lle (trackdlo/src/trackdlo.cpp:161-441) on the cloud resident in `slot`.
  *   Y        in/out  M x 3 column-major           (MatrixXd& Y)
  *   sigma2   in/out                                (double& sigma2; 0 => initialised as at :271-273)
@@ -315,6 +354,15 @@ int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N,
                                const int *visible_nodes, int n_vis,
                                const int *visible_nodes_extended, int n_vis_ext,
                                const double *H_pre, tdlo_stats *stats);
+/* tdlo_tracker_tracking_step with a view (above) in the place of X, N; everything behind the placing of the cloud is the same code, the same bits.
+ *  - A HOST view of up to 16 384 points, where tdlo_tracker_tracking_step stages X in pinned memory: the host widens the view straight into that
+ *    staging buffer (one pass over the points, where the memcpy stands), and the frame is the route described above -- four kernels and no copy in
+ *    the steady state, stats[1].sort_reused == 2 (tdlo_debug_route_count 18).
+ *  - A device view, or a larger cloud: tdlo_set_cloud_view enqueued without a host wait (a device source must stay valid until this call returns:
+ *    the pre-processing registration waits for the stream), then the X == NULL route (tdlo_debug_route_count 17). */
+int tdlo_tracker_tracking_step_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N,
+                                    const int *visible_nodes, int n_vis, const int *visible_nodes_extended, int n_vis_ext,
+                                    const double *H_pre, tdlo_stats *stats);
 
 /* ---- plain GMM-EM initial registration ------------------------------------ */
 /* reg(pts, Y, sigma2, M, mu, max_iter), trackdlo/src/utils.cpp:21-82 (declared trackdlo/include/utils.h): M centroids
@@ -553,6 +601,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * in one launch TDLO_BATCH_PERSIST and its repeats; docs/HISTORY.md has the numbers); the indices are not reused.
  * 14: registrations run with one launch per iteration (k_iter_fused).  15 / 16: colour frames (tdlo_colour_depth_to_cloud and the calls built on it) whose
  * segmentation rode in the depth -> cloud launch / that took the mask kernel k_colour_mask (TDLO_COLOUR_FUSED=0, TDLO_CLOUD_FUSED=0, frames passed on).
+ * 17: cloud views imported by k_cloud_import (tdlo_set_cloud_view, and the tracker frames that take it).  18: host views that
+ * tdlo_tracker_tracking_step_view widened on the host straight into the pinned staging of a small frame.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

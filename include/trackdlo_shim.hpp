@@ -30,6 +30,9 @@ namespace tdlo {
 
 struct ctx_deleter { void operator()(tdlo_ctx *c) const { tdlo_destroy(c); } };
 
+// A float cloud where it lies: xyz = address of x of point 0, the point stride in floats (3: packed; sizeof(pcl::PointXYZRGB) / 4 = 8 for the node's cloud)
+inline tdlo_cloud_view view_of(const float *xyz, long long stride_point_elems) { return tdlo_cloud_view{xyz, TDLO_F32, TDLO_MEM_AUTO, stride_point_elems, 1, nullptr, 0}; }
+
 template <class Matrix>
 class trackdlo_t {
 public:
@@ -106,12 +109,38 @@ public:
         return st.converged != 0;
     }
 
+    // the same on a cloud where it lies (tdlo::view_of): no widened, transposed copy on the host
+    bool cpd_lle(const tdlo_cloud_view &X_view, int N, Matrix &Y, double &sigma2, double beta, double lambda, double lle_weight, double mu,
+                 int max_iter = 30, double tol = 0.0001, bool include_lle = true,
+                 std::vector<Matrix> correspondence_priors = {}, double alpha = 0, std::vector<int> visible_nodes = {},
+                 double k_vis = 0, double visibility_threshold = 0.01) {
+        need_ctx();
+        tdlo_params p{};
+        p.beta = beta; p.lambda = lambda; p.lle_weight = lle_weight; p.mu = mu; p.max_iter = max_iter; p.tol = tol;
+        p.include_lle = include_lle ? 1 : 0; p.alpha = alpha; p.k_vis = k_vis; p.visibility_threshold = visibility_threshold;
+        p.precision = precision_;
+        std::vector<double> pri;
+        for (auto &r : correspondence_priors) for (int c = 0; c < 4; ++c) pri.push_back(r(0, c));
+        tdlo_stats st{};
+        check(tdlo_set_cloud_view(ctx_.get(), 0, &X_view, N));
+        check(tdlo_cpd_lle_resident(ctx_.get(), 0, Y.data(), (int)Y.rows(), &sigma2, &p, pri.empty() ? nullptr : pri.data(),
+                                    (int)correspondence_priors.size(), visible_nodes.empty() ? nullptr : visible_nodes.data(),
+                                    (int)visible_nodes.size(), nullptr, &st));
+        return st.converged != 0;
+    }
+
     // trackdlo.h:96-101; proj_matrix / img_rows / img_cols are unused by the reference body (trackdlo.cpp:900-999)
     void tracking_step(Matrix X_orig, std::vector<int> visible_nodes, std::vector<int> visible_nodes_extended,
                        Matrix /*proj_matrix*/, int /*img_rows*/, int /*img_cols*/) {
         need();
         check(tdlo_tracker_tracking_step(trk_, X_orig.data(), (int)X_orig.rows(), visible_nodes.data(), (int)visible_nodes.size(),
                                          visible_nodes_extended.data(), (int)visible_nodes_extended.size(), nullptr, nullptr));
+    }
+
+    void tracking_step(const tdlo_cloud_view &X_view, int N, std::vector<int> visible_nodes, std::vector<int> visible_nodes_extended) {
+        need();
+        check(tdlo_tracker_tracking_step_view(trk_, &X_view, N, visible_nodes.data(), (int)visible_nodes.size(),
+                                              visible_nodes_extended.data(), (int)visible_nodes_extended.size(), nullptr, nullptr));
     }
 
     // not in the reference: choose fp32 E-step (default) or fp64 everywhere

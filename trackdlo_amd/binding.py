@@ -48,6 +48,17 @@ class ColourParams(C.Structure):
     _fields_ = [("n_ranges", C.c_int), ("lower", (C.c_int * 3) * 4), ("upper", (C.c_int * 3) * 4), ("rgb_order", C.c_int)]
 
 
+F32, F64 = 0, 1                                     # tdlo_cloud_view.dtype
+MEM_AUTO, MEM_HOST, MEM_DEVICE = 0, 1, 2            # tdlo_cloud_view.location
+VIEW_ASYNC = 1                                      # tdlo_cloud_view.flags
+
+
+class CloudView(C.Structure):
+    """tdlo_cloud_view.  Built by cloud_view(), which also sets .N (points) and keeps the viewed object alive in .owner."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("location", C.c_int), ("stride_point", C.c_longlong), ("stride_comp", C.c_longlong),
+                ("ready_stream", C.c_void_p), ("flags", C.c_int)]
+
+
 # every symbol include/trackdlo_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "tdlo_abi_version", "tdlo_device_count", "tdlo_default_config", "tdlo_create", "tdlo_destroy", "tdlo_last_error",
@@ -62,6 +73,7 @@ SYMBOLS = [
     "tdlo_tracker_get_correspondence_pairs", "tdlo_tracker_tracking_step", "tdlo_calc_lle_weights", "tdlo_calc_lle_regulariser",
     "tdlo_line_sphere_intersection", "tdlo_traverse_euclidean", "tdlo_profile_kernel", "tdlo_profile_iteration", "tdlo_debug_stamps", "tdlo_debug_exp2", "tdlo_debug_mstep_dense", "tdlo_debug_mstep_lle_dense", "tdlo_debug_band_retries", "tdlo_debug_lle_band_device", "tdlo_debug_route_count", "tdlo_debug_fail_hip", "tdlo_set_timing", "tdlo_set_sort_reuse", "tdlo_set_xch_self", "tdlo_pci_bus_id", "tdlo_debug_read_cloud", "tdlo_debug_read_setup", "tdlo_image_buffers", "tdlo_debug_cloud_stamps", "tdlo_visibility_prepass", "tdlo_depth_to_cloud_visibility", "tdlo_tracker_frame_from_depth", "tdlo_piecewise_error", "tdlo_compute_error",
     "tdlo_depth_to_cloud", "tdlo_reg", "tdlo_self_occlusion_visible", "tdlo_extend_visible_nodes", "tdlo_tracker_set_self_occlusion",
+    "tdlo_cloud_view_check", "tdlo_cloud_view_extent", "tdlo_set_cloud_view", "tdlo_get_cloud", "tdlo_tracker_tracking_step_view",
     "tdlo_colour_mask", "tdlo_colour_buffers", "tdlo_colour_depth_to_cloud", "tdlo_colour_depth_to_cloud_visibility", "tdlo_tracker_frame_from_colour",
 ]
 
@@ -218,6 +230,12 @@ def load_library(path: str | None = None):
     lib.tdlo_colour_depth_to_cloud_visibility.argtypes = [vp, ci, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci),
                                                           C.POINTER(ci), C.POINTER(ci)]
     lib.tdlo_tracker_frame_from_colour.argtypes = [vp, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+    cvp = C.POINTER(CloudView)
+    lib.tdlo_cloud_view_check.argtypes = [cvp, ci]
+    lib.tdlo_cloud_view_extent.argtypes = [cvp, ci, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.tdlo_set_cloud_view.argtypes = [vp, ci, cvp, ci]
+    lib.tdlo_get_cloud.argtypes = [vp, ci, vp, ci, C.POINTER(ci)]
+    lib.tdlo_tracker_tracking_step_view.argtypes = [vp, cvp, ci, vp, ci, vp, ci, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -283,6 +301,43 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def cloud_view(obj, ready_stream=None, asynchronous=False) -> CloudView:
+    """tdlo_cloud_view of a cloud where it lies, without a copy: a numpy array (host memory, through __array_interface__) or any object with
+    __cuda_array_interface__ (device memory: a ROCm torch tensor, say -- torch is not imported here).  Shape (N, 3), or (N, k >= 3) taking the first
+    three columns; float32 or float64, any strides (a transposed, sliced or reversed array is a view like any other).  ready_stream: the raw
+    hipStream_t (an integer) whose work so far produces a device source; asynchronous: TDLO_VIEW_ASYNC.  The result carries .N and .owner."""
+    device = hasattr(obj, "__cuda_array_interface__")
+    if not device and not hasattr(obj, "__array_interface__"):
+        raise TypeError("cloud_view: a numpy array or an object with __cuda_array_interface__")
+    ai = obj.__cuda_array_interface__ if device else obj.__array_interface__
+    typestr = ai["typestr"]
+    if typestr[1:] not in ("f4", "f8") or typestr[0] not in "<=|" + ("<" if np.little_endian else ">"):
+        raise TypeError(f"cloud_view: float32 or float64 in native byte order, not {typestr!r}")
+    shape = tuple(int(d) for d in ai["shape"])
+    if len(shape) != 2 or shape[1] < 3:
+        raise TypeError(f"cloud_view: shape (N, 3) or (N, k >= 3), not {shape}")
+    es = int(typestr[2:])
+    strides = ai.get("strides")
+    if strides is None:
+        strides = (shape[1] * es, es)                # C-contiguous
+    if strides[0] % es or strides[1] % es:
+        raise TypeError("cloud_view: strides that are no multiple of the element size")
+    v = CloudView(int(ai["data"][0]) or None, F32 if es == 4 else F64, MEM_DEVICE if device else MEM_HOST, int(strides[0]) // es, int(strides[1]) // es,
+                  int(ready_stream) if ready_stream else None, VIEW_ASYNC if asynchronous else 0)
+    v.N = shape[0]
+    v.owner = obj
+    return v
+
+
+def cloud_view_extent(v: CloudView, N=None):
+    """[lo, hi) in bytes relative to v.data: what the library may read of the view (tdlo_cloud_view_extent)."""
+    lo = C.c_longlong(0); hi = C.c_longlong(0)
+    rc = load_library().tdlo_cloud_view_extent(C.byref(v), int(v.N if N is None else N), C.byref(lo), C.byref(hi))
+    if rc:
+        raise TdloError(rc, "tdlo_cloud_view_extent: not a cloud view")
+    return lo.value, hi.value
+
+
 def make_params(beta, lambda_, lle_weight, mu, max_iter=30, tol=1e-4, include_lle=True, alpha=0.0, k_vis=0.0,
                 visibility_threshold=0.01, precision=PREC_F32) -> Params:
     return Params(beta, lambda_, lle_weight, mu, int(max_iter), tol, int(bool(include_lle)), alpha, k_vis,
@@ -333,6 +388,7 @@ class Context:
         if not self.h:
             raise TdloError(err.value, "tdlo_create failed (no usable gfx950 device? there is no CPU fallback)")
         self.max_frames = max_frames
+        self._async_src = None      # the source of an asynchronous set_cloud_view that the stream may still be reading
         self.set_timing(timing)
 
     def pci_bus_id(self):
@@ -370,6 +426,23 @@ class Context:
 
     def synchronize(self):
         self._chk(self.lib.tdlo_synchronize(self.h))
+        self._async_src = None
+
+    def set_cloud_view(self, slot, obj, ready_stream=None, asynchronous=False):
+        """tdlo_set_cloud_view: the slot's cloud from obj where it lies (cloud_view(); a CloudView is taken as it is).  An asynchronously imported
+        device source is kept alive here until the next call of this context that waits for its stream."""
+        v = obj if isinstance(obj, CloudView) else cloud_view(obj, ready_stream, asynchronous)
+        self._chk(self.lib.tdlo_set_cloud_view(self.h, slot, C.byref(v), int(v.N)))
+        self._async_src = v if v.flags & VIEW_ASYNC else None
+
+    def get_cloud(self, slot):
+        """The slot's resident cloud as it stands [n x 3, column-major storage] (tdlo_get_cloud)."""
+        n = C.c_int(0)
+        self.lib.tdlo_get_cloud(self.h, slot, None, 0, C.byref(n))          # (the size; refused for want of room unless the slot is empty)
+        X = np.zeros((n.value, 3), order="F")
+        self._chk(self.lib.tdlo_get_cloud(self.h, slot, _ptr(X), n.value, C.byref(n)))
+        self._async_src = None
+        return X
 
     def stream_ptr(self):
         """Raw hipStream_t of the context (an integer), for callers that order their own work on it."""
@@ -398,6 +471,8 @@ class Context:
         s2 = C.c_double(float(sigma2)); st = Stats()
         rc = self.lib.tdlo_cpd_lle_resident(self.h, slot, _ptr(Y), M, C.byref(s2), C.byref(params), _ptr(pri), K,
                                             _ptr(vis), nv, _ptr(Hm), C.byref(st))
+        if rc == 0:
+            self._async_src = None      # (the registration waited for the stream)
         if check:
             self._chk(rc)
         return dict(Y=Y, sigma2=s2.value, converged=bool(st.converged), iters=st.iters, n_kept=st.n_kept, rc=rc,
@@ -813,6 +888,18 @@ class trackdlo:
         rc = self.ctx.lib.tdlo_tracker_tracking_step(self.h, _ptr(X), X.shape[0] if X is not None else 0, _ptr(v), len(v), _ptr(ve), len(ve), _ptr(Hm),
                                                      self._st_ptr)
         self._stats_raw = st
+        if rc:
+            self.ctx._chk(rc)
+
+
+    def tracking_step_view(self, obj, visible_nodes, visible_nodes_extended, *, ready_stream=None, H_pre=None):
+        """tracking_step on a cloud where it lies (tdlo_tracker_tracking_step_view): obj as for cloud_view(), or a CloudView."""
+        cv = obj if isinstance(obj, CloudView) else cloud_view(obj, ready_stream)
+        v = np.ascontiguousarray(visible_nodes, dtype=np.int32)
+        ve = np.ascontiguousarray(visible_nodes_extended, dtype=np.int32)
+        Hm = _f64(H_pre) if H_pre is not None else None
+        rc = self.ctx.lib.tdlo_tracker_tracking_step_view(self.h, C.byref(cv), int(cv.N), _ptr(v), len(v), _ptr(ve), len(ve), _ptr(Hm), self._st_ptr)
+        self._stats_raw = self._st
         if rc:
             self.ctx._chk(rc)
 

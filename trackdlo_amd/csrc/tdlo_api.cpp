@@ -260,6 +260,13 @@ struct tdlo_ctx {
     size_t cloud_pin_doubles = 0;
     int cloud_pending = -1;
     bool cloud_direct_on = !(getenv("TDLO_DIRECT_CLOUD") && atoi(getenv("TDLO_DIRECT_CLOUD")) == 0);
+    // cloud views (tdlo_set_cloud_view): a host view is packed into cloud_pin in its own precision and widened by k_cloud_import, which reads the pinned
+    // block in place, as k_prologue reads Xhost (measured faster than a copy in front of the kernel at 5 000, 50 000 and 2 000 000 points,
+    // profiles/cloud_view_ab.txt).  TDLO_VIEW_INPLACE=0: the block is copied to the device first (into the slot's Xs, which the next prune rewrites
+    // anyway) -- the comparator.  view_route: tdlo_debug_route_count 17 / 18
+    bool view_inplace = !(getenv("TDLO_VIEW_INPLACE") && atoi(getenv("TDLO_VIEW_INPLACE")) == 0);
+    long long view_route[2] = {0, 0};
+    hipEvent_t ev_view = nullptr;          // recorded on a view's ready_stream; the context's stream waits for it
     // early exit, one frame per call: how many iterations go out before the host first looks at the registration's state.  1 unless the caller
     // knows better -- tracking_step passes what the same registration took in the previous frame (consecutive frames of a tracker take about
     // the same number; capped: a wrong guess costs a no-op iteration, ~4 us, per iteration too many).  Consumed by the next run_frames.
@@ -1595,6 +1602,17 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
     return k.results_out(t_host0);
 }
 
+// dst[c * N + n] = (D)src[n * stride_point + c * stride_comp]: the one pass over a host view's points (D = S: packed in the source precision for
+// the import kernel; D = double: widened straight into a small tracker frame's staging)
+template <typename D, typename S>
+void view_gather(D *dst, const S *src, long long sp, long long sc, int N) {
+    D *x = dst, *y = dst + (size_t)N, *z = dst + 2 * (size_t)N;
+    for (long long n = 0; n < N; ++n) {
+        const S *p = src + n * sp;
+        x[n] = (D)p[0]; y[n] = (D)p[sc]; z[n] = (D)p[2 * sc];
+    }
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1688,6 +1706,7 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->own_comm) { const RcclApi *r = rccl_api(nullptr, nullptr); if (r) r->CommDestroy(c->own_comm); }
     for (auto &e : c->evx) if (e) hipEventDestroy(e);
     for (auto &e : c->evj) if (e) hipEventDestroy(e);
+    if (c->ev_view) hipEventDestroy(c->ev_view);
     for (auto &q : c->stream2) if (q) hipStreamDestroy(q);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -1719,6 +1738,119 @@ static int set_cloud_impl(tdlo_ctx *c, int slot, const double *X, int N, bool sy
 }
 
 int tdlo_set_cloud(tdlo_ctx *c, int slot, const double *X, int N) { return set_cloud_impl(c, slot, X, N, true); }
+
+// ---- cloud views: float32 / float64, any strides, host or device memory --------------------------------------------------------------------------
+// lowest and highest element offset the view addresses (n * stride_point + c * stride_comp over n < N, c < 3), in 128 bits: a stride is any long long
+static void view_span(const tdlo_cloud_view *v, int N, __int128 *lo, __int128 *hi) {
+    const __int128 a = (__int128)(N - 1) * v->stride_point, b = (__int128)2 * v->stride_comp;
+    *lo = (a < 0 ? a : 0) + (b < 0 ? b : 0);
+    *hi = (a > 0 ? a : 0) + (b > 0 ? b : 0);
+}
+
+// nullptr: (v, N) describes a cloud; otherwise what is wrong with it
+static const char *view_fault(const tdlo_cloud_view *v, int N) {
+    if (!v) return "cloud view: null view";
+    if (!v->data) return "cloud view: null data";
+    if (N <= 0) return "cloud view: empty cloud";
+    if (v->dtype != TDLO_F32 && v->dtype != TDLO_F64) return "cloud view: unknown dtype";
+    if (v->location != TDLO_MEM_AUTO && v->location != TDLO_MEM_HOST && v->location != TDLO_MEM_DEVICE) return "cloud view: unknown location";
+    if (v->flags & ~TDLO_VIEW_ASYNC) return "cloud view: unknown flag";
+    if (v->stride_point == 0 && N > 1) return "cloud view: stride_point is 0";
+    if (v->stride_comp == 0) return "cloud view: stride_comp is 0";
+    const int es = v->dtype == TDLO_F32 ? 4 : 8;
+    if ((uintptr_t)v->data % (uintptr_t)es) return "cloud view: data is not aligned to its element size";
+    __int128 lo, hi;
+    view_span(v, N, &lo, &hi);
+    const __int128 lim = (__int128)1 << 62;
+    if (lo * es <= -lim || (hi + 1) * es >= lim) return "cloud view: the extent does not fit 64-bit byte offsets";
+    return nullptr;
+}
+
+int tdlo_cloud_view_check(const tdlo_cloud_view *v, int N) { return view_fault(v, N) ? TDLO_E_INVALID : TDLO_OK; }
+
+int tdlo_cloud_view_extent(const tdlo_cloud_view *v, int N, long long *lo_bytes, long long *hi_bytes) {
+    if (view_fault(v, N) || !lo_bytes || !hi_bytes) return TDLO_E_INVALID;
+    const int es = v->dtype == TDLO_F32 ? 4 : 8;
+    __int128 lo, hi;
+    view_span(v, N, &lo, &hi);
+    *lo_bytes = (long long)(lo * es); *hi_bytes = (long long)((hi + 1) * es);
+    return TDLO_OK;
+}
+
+// Where a (checked) view's memory is: *device = a kernel on the context's GPU may read it.  Everything else -- memory the runtime does not know,
+// caller-pinned and managed memory -- is host memory: copied, never dereferenced by a kernel.
+static int view_location(tdlo_ctx *c, const tdlo_cloud_view *v, bool *device) {
+    *device = false;
+    if (v->location == TDLO_MEM_HOST) return TDLO_OK;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, v->data) != hipSuccess) {
+        (void)hipGetLastError();                           // (a pointer the runtime does not know; the error must not reach the next launch check)
+        if (v->location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, "cloud view: location says device memory, the runtime does not know the pointer");
+        return TDLO_OK;
+    }
+    if (at.type != hipMemoryTypeDevice) {
+        if (v->location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, "cloud view: location says device memory, the runtime says otherwise");
+        return TDLO_OK;
+    }
+    if (at.device != c->device) return fail(c, TDLO_E_INVALID, "cloud view: device memory of another GPU");
+    *device = true;
+    return TDLO_OK;
+}
+
+// tdlo_set_cloud_view on a checked view.  wait: the call returns when the import has finished (a host source always waits unless the caller is
+// tracking_step, whose first registration waits for the stream before it returns: the pinned staging is free again by then).
+static int import_view(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, bool device, bool wait) {
+    Slot &s = c->slots[slot];
+    int rc;
+    if ((rc = flush_pending_cloud(c)) || (rc = ensure_points(c, s, N))) return rc;
+    const bool f64 = v->dtype == TDLO_F64;
+    if (device) {
+        if (v->ready_stream) {
+            if (!c->ev_view) HIPCHK(c, hipEventCreateWithFlags(&c->ev_view, hipEventDisableTiming));
+            HIPCHK(c, hipEventRecord(c->ev_view, (hipStream_t)v->ready_stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_view, 0));
+        }
+        HIPCHK(c, launch_cloud_import(v->data, f64, v->stride_point, v->stride_comp, N, s.Xraw, c->stream));
+    } else {
+        const size_t bytes = 3 * (size_t)N * (f64 ? 8 : 4);
+        if ((rc = ensure_cloud_pin(c, (bytes + 7) / 8))) return rc;
+        if (f64) view_gather((double *)c->cloud_pin, (const double *)v->data, v->stride_point, v->stride_comp, N);
+        else view_gather((float *)c->cloud_pin, (const float *)v->data, v->stride_point, v->stride_comp, N);
+        const void *src = c->cloud_pin;
+        if (!c->view_inplace) {
+            HIPCHK(c, hipMemcpyAsync(s.Xs, c->cloud_pin, bytes, hipMemcpyHostToDevice, c->stream));
+            src = s.Xs;
+        }
+        HIPCHK(c, launch_cloud_import(src, f64, 1, N, N, s.Xraw, c->stream));
+    }
+    s.N0 = N; s.sorted_valid = false;
+    ++c->view_route[0];
+    if (wait) HIPCHK(c, wait_stream(c->stream));
+    return TDLO_OK;
+}
+
+int tdlo_set_cloud_view(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N) {
+    if (!c) return TDLO_E_INVALID;
+    if (const char *why = view_fault(v, N)) return fail(c, TDLO_E_INVALID, why);
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool device = false;
+    if (int rc = view_location(c, v, &device)) return rc;
+    return import_view(c, slot, v, N, device, !(device && (v->flags & TDLO_VIEW_ASYNC)));
+}
+
+int tdlo_get_cloud(tdlo_ctx *c, int slot, double *X_out, int x_capacity, int *n_out) {
+    if (!c) return TDLO_E_INVALID;
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    Slot &s = c->slots[slot];
+    if (n_out) *n_out = s.N0;
+    if (s.N0 > 0 && (!X_out || x_capacity < s.N0)) return fail(c, TDLO_E_INVALID, "tdlo_get_cloud: X_out is too small for the slot's cloud");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = flush_pending_cloud(c)) return rc;
+    if (s.N0 > 0) HIPCHK(c, hipMemcpyAsync(X_out, s.Xraw, 3 * (size_t)s.N0 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, wait_stream(c->stream));
+    return TDLO_OK;
+}
 
 // run_frames for the entry points that register caller-supplied nodes (tdlo_cpd_lle_resident, tdlo_cpd_lle_batch): a registration whose fused
 // prologue was abandoned at its grid barrier (TDLO_E_FUSE: internal, no caller ever sees the code) has touched neither Y, sigma2 nor the slots'
@@ -2952,7 +3084,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 16) return -1;
+    if (!c || which < 0 || which > 18) return -1;
+    if (which >= 17) return c->view_route[which - 17];
     if (which >= 15) return c->colour_route[which - 15];
     if (which == 14) return c->fused_calls;
     if (which >= 11 && which <= 13) return 0;      // (belonged to experiments that were removed; not reused)
@@ -3196,8 +3329,9 @@ int tdlo_tracker_get_correspondence_pairs(const tdlo_tracker *t, double *out, in
     return K;
 }
 
-int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N, const int *vis, int n_vis,
-                               const int *vis_ext, int n_ext, const double *H_pre, tdlo_stats *stats) {
+// tdlo_tracker_tracking_step / _view: the frame's cloud is X (N x 3 column-major doubles), the view v, or -- both null -- what is resident in the slot
+static int tracking_step_impl(tdlo_tracker *t, const double *X, const tdlo_cloud_view *v, int N, const int *vis, int n_vis,
+                              const int *vis_ext, int n_ext, const double *H_pre, tdlo_stats *stats) {
     if (!t || !vis_ext) return TDLO_E_INVALID;
     tdlo_ctx *c = t->ctx;
     const int M = t->M;
@@ -3220,6 +3354,23 @@ int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N, const in
     }
     else if (X) rc = set_cloud_impl(c, t->slot, X, N, false);            // X_orig by value: one upload for both registrations (X stays the caller's
                                                                          // until this function returns; the first registration's read-back waits for the copy)
+    else if (v) {
+        HIPCHK(c, hipSetDevice(c->device));
+        bool device = false;
+        if ((rc = view_location(c, v, &device))) return rc;
+        if (!device && c->cloud_direct_on && c->direct_in && c->fuse_on && N <= 16384) {
+            // a host view of a small frame: widened straight into the pinned staging, where the memcpy above stands -- the same route from there on
+            Slot &s = c->slots[t->slot];
+            if ((rc = flush_pending_cloud(c)) || (rc = ensure_points(c, s, N)) || (rc = ensure_cloud_pin(c, 3 * (size_t)N))) return rc;
+            if (v->dtype == TDLO_F64) view_gather(c->cloud_pin, (const double *)v->data, v->stride_point, v->stride_comp, N);
+            else view_gather(c->cloud_pin, (const float *)v->data, v->stride_point, v->stride_comp, N);
+            s.N0 = N; s.sorted_valid = false;
+            c->cloud_pending = t->slot;
+            staged = true;
+            ++c->view_route[1];
+        }
+        else rc = import_view(c, t->slot, v, N, device, false);         // enqueued: the first registration's read-back waits for it
+    }
     else if (c->slots[t->slot].N0 <= 0) rc = fail(c, TDLO_E_INVALID, "X is NULL and no cloud is resident in the tracker's slot");
     if (rc) return rc;
     g_prof.mark(0);
@@ -3349,6 +3500,18 @@ int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N, const in
     if (c->cloud_pending >= 0) { const int frc = flush_pending_cloud(c); if (!rc) rc = frc; }
     if (stats) stats[1] = st_main;
     return rc;
+}
+
+int tdlo_tracker_tracking_step(tdlo_tracker *t, const double *X, int N, const int *vis, int n_vis,
+                               const int *vis_ext, int n_ext, const double *H_pre, tdlo_stats *stats) {
+    return tracking_step_impl(t, X, nullptr, N, vis, n_vis, vis_ext, n_ext, H_pre, stats);
+}
+
+int tdlo_tracker_tracking_step_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, const int *vis, int n_vis,
+                                    const int *vis_ext, int n_ext, const double *H_pre, tdlo_stats *stats) {
+    if (!t) return TDLO_E_INVALID;
+    if (const char *why = view_fault(v, N)) return fail(t->ctx, TDLO_E_INVALID, why);
+    return tracking_step_impl(t, nullptr, v, N, vis, n_vis, vis_ext, n_ext, H_pre, stats);
 }
 
 // One frame of the ROS node's callback, images in, nodes out (trackdlo_node.cpp:195-369): depth image + mask -> cloud -> voxel grid and the visibility

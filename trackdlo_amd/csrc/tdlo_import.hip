@@ -1,0 +1,83 @@
+// tdlo_import.hip -- k_cloud_import: a cloud as its producer holds it (float32 or float64, any strides) -> the slot's resident cloud
+// (Slot::Xraw: N x 3 column-major doubles).  Component c of point n is read from src + n * stride_point + c * stride_comp (elements) and written
+// to Xraw[c * N + n] = (double)value.  Element-wise and memory-bound: 12 + 24 algorithmic bytes per point for packed float32.
+//
+// THE RULE OF THIS FILE: no load, vector or scalar, touches a byte outside the view's extent (tdlo_cloud_view_extent).  A device source is the
+// caller's allocation and carries no padding of ours -- the licence tdlo_cloud.hip's colour path has on our own padded image buffers (up to 9 bytes
+// past the image) does not exist here.  Every form below therefore loads whole elements of the view and nothing else: a lane's vector covers
+// elements the view addresses, or the lane loads element by element.
+//
+// Forms (chosen from the strides and the alignment of `data` only, cloud_import_form):
+//   kGeneric   any strides, float32 / float64: three scalar loads per point (a float64 scalar is an 8-byte load already).
+//   kXyz12     float32, stride_comp == 1, stride_point in {3, 4, 8}: ONE 12-byte load per point (x, y, z are adjacent; 4-byte alignment is all a
+//              global 12-byte load needs) -- exactly the point's three elements, so neither heads, tails nor the unused lanes of a padded point
+//              (PointXYZ's fourth float, PointXYZRGB's rgb + padding) are ever read.
+//              (A 16-byte load of a whole padded point from 16-byte aligned data was tried as a form of its own: the compiler drops the unused
+//              fourth lane and emits the same 12-byte load, so there is one form.)
+//   kCols2     float32, stride_point == 1 (column-major), stride_comp even, data 8-byte aligned: a lane takes two consecutive points, one aligned
+//              8-byte load per column; an odd last point is loaded element by element.
+// Stores: a lane writes its point's three doubles to the three output columns -- consecutive lanes, consecutive addresses (kCols2: pairs).
+// Offsets are 64-bit throughout: n * stride_point may pass 2^31 elements, 3 N doubles pass 2^32 bytes at N = 2^28.
+#include "tdlo_internal.h"
+
+namespace tdlo {
+
+namespace {
+
+enum ImportForm { kGeneric = 0, kXyz12 = 1, kCols2 = 2 };
+
+struct __attribute__((packed, aligned(4))) Xyz12 { float x, y, z; };
+
+template <typename T, int FORM>
+__global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ src, long long sp, long long sc, int N, double *__restrict__ X) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const size_t ld = (size_t)N;
+    if constexpr (FORM == kCols2) {
+        const long long n = 2 * i;
+        if (n >= N) return;
+        const T *p = src + n;
+        if (n + 1 < N) {
+            const float2 a = *reinterpret_cast<const float2 *>(p), b = *reinterpret_cast<const float2 *>(p + sc), c = *reinterpret_cast<const float2 *>(p + 2 * sc);
+            X[n] = (double)a.x; X[n + 1] = (double)a.y;
+            X[ld + n] = (double)b.x; X[ld + n + 1] = (double)b.y;
+            X[2 * ld + n] = (double)c.x; X[2 * ld + n + 1] = (double)c.y;
+        } else {
+            X[n] = (double)p[0]; X[ld + n] = (double)p[sc]; X[2 * ld + n] = (double)p[2 * sc];
+        }
+    } else {
+        if (i >= N) return;
+        const T *p = src + i * sp;
+        double x, y, z;
+        if constexpr (FORM == kXyz12) {
+            const Xyz12 v = *reinterpret_cast<const Xyz12 *>(p); x = (double)v.x; y = (double)v.y; z = (double)v.z;
+        } else {
+            x = (double)p[0]; y = (double)p[sc]; z = (double)p[2 * sc];
+        }
+        X[i] = x; X[ld + i] = y; X[2 * ld + i] = z;
+    }
+}
+
+}  // namespace
+
+int cloud_import_form(const void *src, bool f64, long long sp, long long sc) {
+    if (f64) return kGeneric;
+    const uintptr_t a = (uintptr_t)src;
+    if (sc == 1 && (sp == 3 || sp == 4 || sp == 8)) return kXyz12;
+    if (sp == 1 && sc % 2 == 0 && a % 8 == 0) return kCols2;
+    return kGeneric;
+}
+
+hipError_t launch_cloud_import(const void *src, bool f64, long long sp, long long sc, int N, double *Xraw, hipStream_t s) {
+    if (N <= 0) return hipErrorInvalidValue;
+    const int form = cloud_import_form(src, f64, sp, sc);
+    const long long lanes = form == kCols2 ? ((long long)N + 1) / 2 : (long long)N;
+    const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock)), block(kBlock);
+    const float *f = (const float *)src;
+    if (f64) hipLaunchKernelGGL((k_cloud_import<double, kGeneric>), grid, block, 0, s, (const double *)src, sp, sc, N, Xraw);
+    else if (form == kXyz12) hipLaunchKernelGGL((k_cloud_import<float, kXyz12>), grid, block, 0, s, f, sp, sc, N, Xraw);
+    else if (form == kCols2) hipLaunchKernelGGL((k_cloud_import<float, kCols2>), grid, block, 0, s, f, sp, sc, N, Xraw);
+    else hipLaunchKernelGGL((k_cloud_import<float, kGeneric>), grid, block, 0, s, f, sp, sc, N, Xraw);
+    return hipGetLastError();
+}
+
+}  // namespace tdlo

@@ -497,6 +497,65 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
                                    int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                    int *n_out, int *n_raw_out, tdlo_stats *stats);
 
+/* ---- the tracking-result image on the device: blend, edges and nodes in one kernel ----------------- */
+/* The picture the node publishes every frame (trackdlo/src/trackdlo_node.cpp:377-452), so that a caller of tdlo_tracker_frame_from_colour needs no OpenCV
+ * pass on the host for it either (a full-image cv::addWeighted, M - 1 cv::line and 2 (M - 1) cv::circle calls).  Stated exactly:
+ *   blend   per byte, a = the colour byte, b = a & o (o: the pixel's occluder byte, 255 without an occluder -- the reference ANDs with a BGR occlusion
+ *           image, this library's occluder is one byte per pixel): s = a + b, out = (s >> 1) + ((s & 1) & ((s >> 1) & 1)), i.e. 0.5 a + 0.5 b rounded half
+ *           to even, what cv::addWeighted does for 8-bit images (cvRound);
+ *   pixels  node m -> u = ((p0 x + p1 y) + p2 z) + p3, v, w likewise (fp64), col = (int)(u / w), row = (int)(v / w).  w <= 0, a non-finite quotient or a
+ *           pixel coordinate outside [-8192, 8191]: TDLO_E_INVALID, nothing is drawn, the output is untouched; so are images beyond 8192 rows or columns;
+ *   order   edge i joins nodes i and i + 1; key sqrt(mx^2 + my^2 + mz^2) of its mid-point m = (Y_i + Y_i+1) / 2; ascending by (key, i), then REVERSED:
+ *           the farthest edge first (:378-390);
+ *   per edge, in that order: a line from pixel i to pixel i + 1 of line_width (every pixel within line_width / 2 of the segment between the end pixels,
+ *           in exact integers: the rule of the self-occlusion test below), the disc of node i, the disc of node i + 1 (dx^2 + dy^2 <= node_radius^2);
+ *   colours node k: node_visible when k is in vis, else node_hidden; edge i: edge_hidden only when neither i nor i + 1 is in vis, else edge_visible
+ *           (:409-424).  A later primitive overwrites an earlier one; primitives are clipped to the image; one node draws nothing (the blend alone).
+ * PARITY UNPINNED against OpenCV: line and disc are their geometric content, not OpenCV's own fixed-point rasterisers (OpenCV is not part of the build
+ * image; boundary pixels may differ), like the painter test and the colour routine; tests/render_ref.py is the numpy statement the kernel is held to byte
+ * for byte.  NOT drawn: the text label cv::putText(... "occlusion" ...) of :446-449 -- its Hershey font is OpenCV's data.  The occlusion corners it is
+ * placed by (:198-208) are returned instead, so that the caller can place the label: corners = {row, col of the first pixel in row-major order whose
+ * occluder byte is 0, row, col of the last one}, all -1 when there is none or no occluder. */
+typedef struct {
+    int line_width, node_radius;              /* 1 .. 255 each; the reference: 5 and 7 */
+    unsigned char node_visible[3], node_hidden[3], edge_visible[3], edge_hidden[3];      /* in the image's byte order; the reference (bgr8):
+                                                                                           * {0,150,255}, {0,0,255}, {0,255,0}, {0,0,255} */
+} tdlo_render_params;
+void tdlo_default_render_params(tdlo_render_params *p);
+/* The host half, no device work (exported like the other host helpers so that a test can address it on a machine without a GPU).  prims: room for
+ * 3 (M - 1) records of 8 ints {kind 0 line / 1 disc, c0, r0, c1, r1 (a disc: its centre twice), size (width / radius), colour b | g << 8 | r << 16, 0} in
+ * drawing order; *n_prims = 3 (M - 1).  p == NULL: the defaults.  vis entries outside 0 .. M - 1, a size outside 1 .. 255, a node that cannot be drawn:
+ * TDLO_E_INVALID, prims untouched. */
+int tdlo_render_primitives(const double *Y, int M, const double proj[12], const int *vis, int n_vis, const tdlo_render_params *p, int *prims, int *n_prims);
+/* A pinned host buffer of the context for a rows x cols x 3 result image, with the lifetime rules of tdlo_colour_buffers.  Passed as image_out, it is
+ * written by the kernel itself, over PCIe -- no device-to-host copy behind the kernel. */
+int tdlo_result_image_buffer(tdlo_ctx *ctx, int rows, int cols, unsigned char **image);
+/* One launch (k_render, csrc/tdlo_render.hip) and the call returns when the image is complete.
+ *   colour     rows x cols x 3 uint8, staged exactly as the colour calls stage it (tdlo_colour_buffers' pointers are read in place), occluder rows x cols or
+ *              NULL.  colour == NULL: the colour and occluder images of the context's most recent colour call (tdlo_colour_mask, tdlo_colour_depth_to_cloud*,
+ *              tdlo_tracker_frame_from_colour, or an earlier tdlo_render_result that was given a colour image: it stages one like the others), read
+ *              where that call left them -- its device copy, or the pinned buffers as they are NOW -- with no second upload; the occluder argument is
+ *              ignored.  TDLO_E_INVALID when there was no such call or its shape differs (tdlo_last_colour_shape tells the shape).
+ *   Y, M       1 .. 1024 nodes, column-major; proj 3 x 4 row-major; vis, n_vis: the index set behind the colours.
+ *   image_out  rows x cols x 3: pageable host memory, tdlo_result_image_buffer's pointer, or device memory of the context's GPU (asked of the runtime
+ *              as tdlo_set_cloud_view asks).  The kernel writes the latter two itself; a device pointer that is not 4-byte aligned receives a copy.
+ *              TDLO_RENDER_INPLACE=0, read when the context is made: the kernel always writes a device image of the context that is then copied out
+ *              -- the comparator, the same bytes (tdlo_debug_route_count 19 / 20).
+ *   corners    may be NULL.
+ * Every refusal leaves image_out untouched. */
+int tdlo_render_result(tdlo_ctx *ctx, const unsigned char *colour, const unsigned char *occluder, int rows, int cols,
+                       const double *Y, int M, const double proj[12], const int *vis, int n_vis,
+                       const tdlo_render_params *p /* NULL: defaults */, unsigned char *image_out, int corners[4] /* may be NULL */);
+/* The shape of the context's most recent colour call, i.e. what tdlo_render_result with colour == NULL and tdlo_tracker_render_result draw over and the
+ * shape their image_out has.  TDLO_E_INVALID (rows and cols untouched) when there was none.  No device work. */
+int tdlo_last_colour_shape(tdlo_ctx *ctx, int *rows, int *cols);
+/* The tracker's current nodes (the result of its last step) over the last colour frame of its context (colour == NULL above).  vis is the reference's
+ * not_self_occluded_nodes (:401): with tdlo_tracker_set_self_occlusion on, the nodes that test leaves with an infinite distance threshold, formed from the
+ * nodes the last tdlo_tracker_frame_from_* call STARTED from, as the callback does at :279-343; off: every node.  proj == NULL: the matrix given to
+ * tdlo_tracker_set_self_occlusion, else {fx, 0, cx, 0,  0, fy, cy, 0,  0, 0, 1, 0} from the last frame call's intrinsics.  The tracker's state is not
+ * touched: a tracker that renders and one that does not give the same nodes, bit for bit. */
+int tdlo_tracker_render_result(tdlo_tracker *t, const double proj[12], const tdlo_render_params *p, unsigned char *image_out, int corners[4]);
+
 /* The callback's self-occlusion ("painter") test, trackdlo/src/trackdlo_node.cpp:279-343: the edges between consecutive nodes are taken nearest the camera
  * first (:279-290, by the camera distance of their mid-points) and each is drawn as a line of dlo_pixel_width pixels (:337-341) after its two end nodes
  * were looked up in what had been drawn before (:304-334): a node whose projected pixel (proj: 3 x 4 row-major, the reference's proj_matrix; pixel
@@ -603,6 +662,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * segmentation rode in the depth -> cloud launch / that took the mask kernel k_colour_mask (TDLO_COLOUR_FUSED=0, TDLO_CLOUD_FUSED=0, frames passed on).
  * 17: cloud views imported by k_cloud_import (tdlo_set_cloud_view, and the tracker frames that take it).  18: host views that
  * tdlo_tracker_tracking_step_view widened on the host straight into the pinned staging of a small frame.
+ * 19 / 20: result images (tdlo_render_result) that k_render wrote where the caller wanted them -- the pinned result buffer, device memory -- / that were
+ * copied out of the context's device image (pageable destinations; TDLO_RENDER_INPLACE=0: all of them).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -48,6 +48,11 @@ class ColourParams(C.Structure):
     _fields_ = [("n_ranges", C.c_int), ("lower", (C.c_int * 3) * 4), ("upper", (C.c_int * 3) * 4), ("rgb_order", C.c_int)]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("line_width", C.c_int), ("node_radius", C.c_int), ("node_visible", C.c_ubyte * 3), ("node_hidden", C.c_ubyte * 3),
+                ("edge_visible", C.c_ubyte * 3), ("edge_hidden", C.c_ubyte * 3)]
+
+
 F32, F64 = 0, 1                                     # tdlo_cloud_view.dtype
 MEM_AUTO, MEM_HOST, MEM_DEVICE = 0, 1, 2            # tdlo_cloud_view.location
 VIEW_ASYNC = 1                                      # tdlo_cloud_view.flags
@@ -75,6 +80,8 @@ SYMBOLS = [
     "tdlo_depth_to_cloud", "tdlo_reg", "tdlo_self_occlusion_visible", "tdlo_extend_visible_nodes", "tdlo_tracker_set_self_occlusion",
     "tdlo_cloud_view_check", "tdlo_cloud_view_extent", "tdlo_set_cloud_view", "tdlo_get_cloud", "tdlo_tracker_tracking_step_view",
     "tdlo_colour_mask", "tdlo_colour_buffers", "tdlo_colour_depth_to_cloud", "tdlo_colour_depth_to_cloud_visibility", "tdlo_tracker_frame_from_colour",
+    "tdlo_default_render_params", "tdlo_render_primitives", "tdlo_result_image_buffer", "tdlo_render_result", "tdlo_tracker_render_result",
+    "tdlo_last_colour_shape",
 ]
 
 _lib = None
@@ -230,6 +237,14 @@ def load_library(path: str | None = None):
     lib.tdlo_colour_depth_to_cloud_visibility.argtypes = [vp, ci, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci),
                                                           C.POINTER(ci), C.POINTER(ci)]
     lib.tdlo_tracker_frame_from_colour.argtypes = [vp, vp, vp, cpp, vp, ci, ci, cd, cd, cd, cd, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+    rpp = C.POINTER(RenderParams)
+    lib.tdlo_default_render_params.argtypes = [rpp]
+    lib.tdlo_default_render_params.restype = None
+    lib.tdlo_render_primitives.argtypes = [vp, ci, vp, vp, ci, rpp, vp, C.POINTER(ci)]
+    lib.tdlo_result_image_buffer.argtypes = [vp, ci, ci, C.POINTER(vp)]
+    lib.tdlo_render_result.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, ci, rpp, vp, vp]
+    lib.tdlo_tracker_render_result.argtypes = [vp, vp, rpp, vp, vp]
+    lib.tdlo_last_colour_shape.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
     cvp = C.POINTER(CloudView)
     lib.tdlo_cloud_view_check.argtypes = [cvp, ci]
     lib.tdlo_cloud_view_extent.argtypes = [cvp, ci, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -360,6 +375,35 @@ def make_colour_params(lower=COLOUR_LAUNCH[0], upper=COLOUR_LAUNCH[1], rgb_order
         for c in range(3):
             p.lower[k][c] = int(lo[k, c]); p.upper[k][c] = int(hi[k, c])
     return p
+
+
+def make_render_params(line_width=None, node_radius=None, node_visible=None, node_hidden=None, edge_visible=None, edge_hidden=None) -> RenderParams:
+    """tdlo_render_params: the reference's values (lines 5 wide, radius 7, {0,150,255}, {0,0,255}, {0,255,0}, {0,0,255} in the image's byte order,
+    trackdlo_node.cpp:409-440) with whatever is given in their place."""
+    p = RenderParams()
+    load_library().tdlo_default_render_params(C.byref(p))
+    if line_width is not None:
+        p.line_width = int(line_width)
+    if node_radius is not None:
+        p.node_radius = int(node_radius)
+    for name, v in (("node_visible", node_visible), ("node_hidden", node_hidden), ("edge_visible", edge_visible), ("edge_hidden", edge_hidden)):
+        if v is not None:
+            setattr(p, name, (C.c_ubyte * 3)(*[int(x) for x in v]))
+    return p
+
+
+def render_primitives(Y, proj, vis, params: RenderParams = None):
+    """The host half of the result image (tdlo_render_primitives; no GPU): [3 (M - 1) x 8] int32 records {kind 0 line / 1 disc, c0, r0, c1, r1, size,
+    colour b | g << 8 | r << 16, 0} in drawing order.  Raises TdloError(TDLO_E_INVALID) for nodes that cannot be drawn."""
+    Y = _f64(Y); M = Y.shape[0]
+    pj = np.ascontiguousarray(proj, dtype=np.float64).reshape(12)
+    v = np.ascontiguousarray(vis, dtype=np.int32).reshape(-1)
+    prims = np.zeros((3 * max(M - 1, 0), 8), dtype=np.int32); n = C.c_int(-1)
+    rc = load_library().tdlo_render_primitives(_ptr(Y), M, _ptr(pj), _ptr(v), len(v), C.byref(params) if params is not None else None, _ptr(prims), C.byref(n))
+    if rc:
+        raise TdloError(rc, "tdlo_render_primitives: nodes, vis or sizes that cannot be drawn")
+    assert n.value == len(prims)
+    return prims
 
 
 def _colour_images(depth, colour, occluder):
@@ -634,6 +678,59 @@ class Context:
         occ = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint8)), shape=(rows, cols))
         return colour, occ
 
+    def render_route_counts(self):
+        """[result images the kernel wrote where the caller wanted them, result images copied out of the device image] (tdlo_debug_route_count 19 / 20)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (19, 20)]
+
+    def result_image_buffer(self, rows, cols):
+        """The context's pinned result image as a numpy view (uint8 [rows x cols x 3]): passed as render_result's `out`, the kernel writes it in place
+        (tdlo_result_image_buffer)."""
+        a = C.c_void_p()
+        self._chk(self.lib.tdlo_result_image_buffer(self.h, int(rows), int(cols), C.byref(a)))
+        return np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_uint8)), shape=(rows, cols, 3))
+
+    @staticmethod
+    def _render_out(out, rows, cols):
+        """(array to return, its address): a new numpy image, the caller's numpy array / pinned view, or anything with __cuda_array_interface__ (a torch device tensor)."""
+        if out is None:
+            out = np.zeros((rows, cols, 3), dtype=np.uint8)
+        if hasattr(out, "__cuda_array_interface__"):
+            ai = out.__cuda_array_interface__
+            if tuple(ai["shape"]) != (rows, cols, 3) or ai["typestr"] != "|u1" or ai.get("strides") is not None:
+                raise ValueError("out: a contiguous rows x cols x 3 uint8 device array")
+            return out, int(ai["data"][0])
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != (rows, cols, 3) or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("out: a contiguous, writeable rows x cols x 3 uint8 array")
+        return out, out.ctypes.data
+
+    def last_colour_shape(self):
+        """(rows, cols) of the context's most recent colour call: what a render call without images of its own draws over (tdlo_last_colour_shape).
+        TdloError when there was none."""
+        rows = C.c_int(0); cols = C.c_int(0)
+        self._chk(self.lib.tdlo_last_colour_shape(self.h, C.byref(rows), C.byref(cols)))
+        return rows.value, cols.value
+
+    def render_result(self, colour, occluder, Y, proj, vis, params: RenderParams = None, *, shape=None, out=None, corners=True):
+        """The tracking-result image (trackdlo_node.cpp:377-452; tdlo_render_result): the blend of the colour image with its occluded copy, the rope's edges
+        and nodes drawn over it farthest first.  colour None: the images of the context's last colour call (shape = (rows, cols) is needed then).  out: None
+        (a new array), a numpy array, result_image_buffer()'s view, or a device array (a torch tensor on the context's GPU).
+        Returns (image, [row, col of the first zero occluder pixel, row, col of the last] or None)."""
+        if colour is not None:
+            _, colour, occluder, op = _colour_images(None, colour, occluder)
+            rows, cols = colour.shape[:2]
+            cp = colour.ctypes.data_as(C.c_void_p)
+        else:
+            rows, cols = (int(v) for v in (shape if shape is not None else self.last_colour_shape()))
+            cp = op = None
+        Y = _f64(Y); M = Y.shape[0]
+        pj = np.ascontiguousarray(proj, dtype=np.float64).reshape(12)
+        v = np.ascontiguousarray(vis, dtype=np.int32).reshape(-1)
+        out, addr = self._render_out(out, rows, cols)
+        cor = np.zeros(4, dtype=np.int32)
+        self._chk(self.lib.tdlo_render_result(self.h, cp, op, rows, cols, _ptr(Y), M, _ptr(pj), _ptr(v), len(v), C.byref(params) if params is not None else None,
+                                              C.c_void_p(addr), _ptr(cor) if corners else None))
+        return out, ([int(x) for x in cor] if corners else None)
+
     def colour_mask(self, colour, params: ColourParams, occluder=None, *, hsv=False):
         """trackdlo_node.cpp:158-180 on the device: the segmentation mask [rows x cols uint8, 0 / 255] of a BGR image; hsv=True: (mask, HSV image)."""
         _, colour, occluder, op = _colour_images(None, colour, occluder)
@@ -875,6 +972,18 @@ class trackdlo:
         if rc:
             self.ctx._chk(rc)
         return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def render_result(self, proj=None, params: RenderParams = None, *, out=None, corners=True):
+        """The published image of this frame (trackdlo_node.cpp:377-452; tdlo_tracker_render_result): the tracker's current nodes over the last colour frame
+        of its context (whose shape the image has).  proj None: set_self_occlusion's matrix, else the last frame call's intrinsics.  out as for
+        Context.render_result.  Returns (image, corners or None)."""
+        rows, cols = self.ctx.last_colour_shape()
+        pj = None if proj is None else np.ascontiguousarray(proj, dtype=np.float64).reshape(12)
+        out, addr = Context._render_out(out, rows, cols)
+        cor = np.zeros(4, dtype=np.int32)
+        self.ctx._chk(self.ctx.lib.tdlo_tracker_render_result(self.h, _ptr(pj), C.byref(params) if params is not None else None, C.c_void_p(addr),
+                                                              _ptr(cor) if corners else None))
+        return out, ([int(x) for x in cor] if corners else None)
 
     def tracking_step(self, X_orig, visible_nodes, visible_nodes_extended, proj_matrix=None, img_rows=0, img_cols=0, *,
                       H_pre=None):

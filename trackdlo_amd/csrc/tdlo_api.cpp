@@ -7,6 +7,7 @@
 #include "tdlo_rccl.h"
 
 #include <algorithm>
+#include <limits>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -195,6 +196,21 @@ struct tdlo_ctx {
     size_t col_dev_cap = 0;
     bool colour_fused_on = !(getenv("TDLO_COLOUR_FUSED") && atoi(getenv("TDLO_COLOUR_FUSED")) == 0);
     long long colour_route[2] = {0, 0};  // tdlo_debug_route_count 15 / 16: frames whose segmentation rode in the depth -> cloud launch / that took the mask kernel
+    // the tracking-result image (tdlo_render_result, k_render).  last_*: where the most recent colour call left its colour and occluder images for the
+    // device (colour_stage: the device copies, or the pinned buffers) -- what a render call without images of its own draws over.  res_pin: the pinned
+    // result image a caller may ask for (tdlo_result_image_buffer); res_dev: the device image that is copied out for any other destination; rnd_pin /
+    // rnd_dev: [primitive table | the two corner words], staged and resident.  TDLO_RENDER_INPLACE=0: the kernel never writes the caller's memory
+    // itself -- always res_dev and a copy (the comparator; profiles/render_frame_ab.txt).  render_route: tdlo_debug_route_count 19 / 20
+    const unsigned char *last_colour = nullptr, *last_occluder = nullptr;
+    int last_col_rows = 0, last_col_cols = 0;
+    char *res_pin = nullptr;
+    size_t res_pin_cap = 0;
+    int res_pin_rows = 0, res_pin_cols = 0;
+    void *res_dev = nullptr;
+    size_t res_dev_cap = 0;
+    char *rnd_pin = nullptr, *rnd_dev = nullptr;
+    bool render_inplace = !(getenv("TDLO_RENDER_INPLACE") && atoi(getenv("TDLO_RENDER_INPLACE")) == 0);
+    long long render_route[2] = {0, 0};  // images the kernel wrote where the caller wanted them / images copied out of res_dev
     size_t pin_doubles = 0;
     std::string err;
     int last_F = 0;
@@ -1692,6 +1708,10 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->img_pin) hipHostFree(c->img_pin);
     if (c->col_pin) hipHostFree(c->col_pin);
     if (c->col_dev) hipFree(c->col_dev);
+    if (c->res_pin) hipHostFree(c->res_pin);
+    if (c->res_dev) hipFree(c->res_dev);
+    if (c->rnd_pin) hipHostFree(c->rnd_pin);
+    if (c->rnd_dev) hipFree(c->rnd_dev);
     if (c->reg_ws) hipFree(c->reg_ws);
     if (c->pin) hipHostFree(c->pin);
     if (c->pin2) hipHostFree(c->pin2);
@@ -2499,6 +2519,7 @@ int tdlo_colour_buffers(tdlo_ctx *c, int rows, int cols, unsigned char **colour,
     if (need > c->col_pin_cap) {
         HIPCHK(c, drain_for_realloc(c));
         if (c->col_pin) hipHostFree(c->col_pin);
+        if (c->last_colour == (const unsigned char *)c->col_pin) c->last_colour = c->last_occluder = nullptr;      // (a render call has nothing to draw over until the next colour call)
         c->col_pin = nullptr; c->col_pin_cap = 0;
         HIPCHK(c, hipHostMalloc((void **)&c->col_pin, need, hipHostMallocDefault));
         std::memset(c->col_pin, 0, need);
@@ -2517,6 +2538,7 @@ static int colour_stage(tdlo_ctx *c, const ColourIn &ci, int rows, int cols, Clo
     const size_t need = img_colour_bytes(P) + img_occ_bytes(P) + (d_hsv ? img_colour_bytes(P) : 0);
     const bool in_place = c->col_pin != nullptr && (const char *)ci.colour == c->col_pin && c->col_pin_rows == rows && c->col_pin_cols == cols &&
                           (!ci.occluder || (const char *)ci.occluder == c->col_pin + img_colour_bytes(P));
+    c->last_colour = c->last_occluder = nullptr;
     if ((!in_place || d_hsv) && need > c->col_dev_cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->col_dev) hipFree(c->col_dev);
@@ -2533,6 +2555,7 @@ static int colour_stage(tdlo_ctx *c, const ColourIn &ci, int rows, int cols, Clo
         if (ci.occluder) HIPCHK(c, hipMemcpyAsync(base + img_colour_bytes(P), ci.occluder, P, hipMemcpyHostToDevice, c->stream));
     }
     if (d_hsv) *d_hsv = (unsigned char *)(base + img_colour_bytes(P) + img_occ_bytes(P));
+    c->last_colour = cc.colour; c->last_occluder = cc.occluder; c->last_col_rows = rows; c->last_col_cols = cols;      // (tdlo_render_result with colour == NULL)
     return TDLO_OK;
 }
 
@@ -2558,6 +2581,117 @@ int tdlo_colour_mask(tdlo_ctx *c, const unsigned char *colour, int rows, int col
     if (mask_out) HIPCHK(c, hipMemcpyAsync(mask_out, d_mask, (size_t)P, hipMemcpyDeviceToHost, c->stream));
     if (hsv_out) HIPCHK(c, hipMemcpyAsync(hsv_out, d_hsv, 3 * (size_t)P, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TDLO_OK;
+}
+
+// ---- the tracking-result image (trackdlo_node.cpp:377-452): blend, edges and nodes in one launch (tdlo_render.hip) ------------------------------------
+static constexpr size_t kRenderPrimBytes = (size_t)3 * (kMaxNodes - 1) * 8 * sizeof(int);      // the table of the longest chain; the two corner words behind it
+
+void tdlo_default_render_params(tdlo_render_params *p) {
+    if (!p) return;
+    const tdlo_render_params d = {5, 7, {0, 150, 255}, {0, 0, 255}, {0, 255, 0}, {0, 0, 255}};      // :409-440, bytes in the image's order (the node's bgr8)
+    *p = d;
+}
+
+int tdlo_render_primitives(const double *Y, int M, const double proj[12], const int *vis, int n_vis, const tdlo_render_params *p, int *prims, int *n_prims) {
+    tdlo_render_params d;
+    tdlo_default_render_params(&d);
+    if (!p) p = &d;
+    if (!prims || !n_prims) return TDLO_E_INVALID;
+    if (render_primitives(Y, M, proj, vis, n_vis, p->line_width, p->node_radius, p->node_visible, p->node_hidden, p->edge_visible, p->edge_hidden, prims)) return TDLO_E_INVALID;
+    *n_prims = 3 * (M - 1);
+    return TDLO_OK;
+}
+
+int tdlo_result_image_buffer(tdlo_ctx *c, int rows, int cols, unsigned char **image) {
+    if (!c) return TDLO_E_INVALID;
+    if (rows <= 0 || cols <= 0 || rows > 8192 || cols > 8192 || !image) return fail(c, TDLO_E_INVALID, "bad image");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t need = img_colour_bytes((size_t)rows * cols);
+    if (need > c->res_pin_cap) {
+        HIPCHK(c, drain_for_realloc(c));
+        if (c->res_pin) hipHostFree(c->res_pin);
+        c->res_pin = nullptr; c->res_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->res_pin, need, hipHostMallocDefault));
+        std::memset(c->res_pin, 0, need);
+        c->res_pin_cap = need;
+    }
+    c->res_pin_rows = rows; c->res_pin_cols = cols;
+    *image = (unsigned char *)c->res_pin;
+    return TDLO_OK;
+}
+
+int tdlo_last_colour_shape(tdlo_ctx *c, int *rows, int *cols) {
+    if (!c) return TDLO_E_INVALID;
+    if (!rows || !cols) return fail(c, TDLO_E_INVALID, "tdlo_last_colour_shape: rows and cols");
+    if (!c->last_colour) return fail(c, TDLO_E_INVALID, "no colour call of this context yet");
+    *rows = c->last_col_rows; *cols = c->last_col_cols;
+    return TDLO_OK;
+}
+
+int tdlo_render_result(tdlo_ctx *c, const unsigned char *colour, const unsigned char *occluder, int rows, int cols, const double *Y, int M, const double proj[12],
+                       const int *vis, int n_vis, const tdlo_render_params *p, unsigned char *image_out, int corners[4]) {
+    if (!c) return TDLO_E_INVALID;
+    // everything that can be refused is refused before the first byte of image_out is written
+    if (rows <= 0 || cols <= 0 || rows > 8192 || cols > 8192 || !image_out) return fail(c, TDLO_E_INVALID, "tdlo_render_result: images of 1 .. 8192 rows and columns");
+    if (!Y || !proj || M < 1 || M > kMaxNodes) return fail(c, TDLO_E_INVALID, "tdlo_render_result: 1 .. 1024 nodes and a projection matrix");
+    if (!colour && !(c->last_colour && c->last_col_rows == rows && c->last_col_cols == cols))
+        return fail(c, TDLO_E_INVALID, "tdlo_render_result: colour == NULL needs a colour call of this context on an image of the same shape before it");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->rnd_pin) {
+        HIPCHK(c, hipHostMalloc((void **)&c->rnd_pin, kRenderPrimBytes + 16, hipHostMallocDefault));
+        const hipError_t e = hipMalloc((void **)&c->rnd_dev, kRenderPrimBytes + 16);
+        if (e != hipSuccess) { hipHostFree(c->rnd_pin); c->rnd_pin = nullptr; c->rnd_dev = nullptr; return fail(c, TDLO_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    }
+    int n_prims = 0;
+    if (tdlo_render_primitives(Y, M, proj, vis, n_vis, p, (int *)c->rnd_pin, &n_prims))        // (the staging table is free: every call returns with the stream drained)
+        return fail(c, TDLO_E_INVALID, "tdlo_render_result: a node that cannot be drawn (w <= 0, a non-finite pixel, a pixel beyond +-8192), vis out of range, or a "
+                                       "line width / node radius outside 1 .. 255");
+    // where the image goes: the pinned result buffer and device memory are written by the kernel itself; anything else (and everything under
+    // TDLO_RENDER_INPLACE=0) receives a copy of the device image
+    const size_t P = (size_t)rows * cols;
+    bool out_device = false;
+    const bool out_pinned = c->res_pin != nullptr && (char *)image_out == c->res_pin && c->res_pin_rows == rows && c->res_pin_cols == cols;
+    if (!out_pinned) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, image_out) != hipSuccess) (void)hipGetLastError();      // (a pointer the runtime does not know: host memory)
+        else if (at.type == hipMemoryTypeDevice) {
+            if (at.device != c->device) return fail(c, TDLO_E_INVALID, "tdlo_render_result: image_out is device memory of another GPU");
+            out_device = true;
+        }
+    }
+    const bool direct = c->render_inplace && (out_pinned || (out_device && (uintptr_t)image_out % 4 == 0));
+    if (!direct && img_colour_bytes(P) > c->res_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->res_dev) hipFree(c->res_dev);
+        c->res_dev = nullptr; c->res_dev_cap = 0;
+        HIPCHK(c, hipMalloc(&c->res_dev, img_colour_bytes(P)));
+        c->res_dev_cap = img_colour_bytes(P);
+    }
+    const unsigned char *d_colour = c->last_colour, *d_occ = c->last_occluder;
+    if (colour) {
+        CloudColour cc{};
+        const ColourIn ci{colour, nullptr, occluder};
+        if (int rc = colour_stage(c, ci, rows, cols, cc, nullptr)) return rc;
+        d_colour = cc.colour; d_occ = cc.occluder;
+    }
+    hipStream_t st = c->stream;
+    unsigned *d_corner = (unsigned *)(c->rnd_dev + kRenderPrimBytes), *h_corner = (unsigned *)(c->rnd_pin + kRenderPrimBytes);
+    if (n_prims) HIPCHK(c, hipMemcpyAsync(c->rnd_dev, c->rnd_pin, (size_t)n_prims * 8 * sizeof(int), hipMemcpyHostToDevice, st));
+    if (d_occ && corners) HIPCHK(c, hipMemsetAsync(d_corner, 0xff, 8, st));                        // {0xffffffff, -1}: no zero byte seen
+    unsigned char *d_out = direct ? image_out : (unsigned char *)c->res_dev;
+    HIPCHK(c, launch_render(d_colour, d_occ, d_out, (const int *)c->rnd_dev, n_prims, (int)P, cols, (d_occ && corners) ? d_corner : nullptr, st));
+    if (!direct) HIPCHK(c, hipMemcpyAsync(image_out, c->res_dev, 3 * P, out_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (d_occ && corners) HIPCHK(c, hipMemcpyAsync(h_corner, d_corner, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, wait_stream(st));
+    ++c->render_route[direct ? 0 : 1];
+    if (corners) {
+        corners[0] = corners[1] = corners[2] = corners[3] = -1;
+        if (d_occ && h_corner[0] != 0xffffffffu) {
+            corners[0] = (int)(h_corner[0] / (unsigned)cols); corners[1] = (int)(h_corner[0] % (unsigned)cols);
+            corners[2] = (int)(h_corner[1] / (unsigned)cols); corners[3] = (int)(h_corner[1] % (unsigned)cols);
+        }
+    }
     return TDLO_OK;
 }
 
@@ -3084,7 +3218,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 18) return -1;
+    if (!c || which < 0 || which > 20) return -1;
+    if (which >= 19) return c->render_route[which - 19];
     if (which >= 17) return c->view_route[which - 17];
     if (which >= 15) return c->colour_route[which - 15];
     if (which == 14) return c->fused_calls;
@@ -3247,6 +3382,11 @@ struct tdlo_tracker {
     bool painter_on = false;                       // tdlo_tracker_set_self_occlusion: frame_from_depth applies trackdlo_node.cpp:279-343 (off by default)
     double painter_proj[12] = {0};
     int painter_width = 0;
+    // tdlo_tracker_render_result: the nodes the last frame_from_* call STARTED from (kept only while the self-occlusion test is on: the picture's
+    // not-self-occluded set is formed from them, trackdlo_node.cpp:279-343 / :401) and that call's intrinsics
+    std::vector<double> frame_Y0;
+    double frame_cam[4] = {0, 0, 0, 0};
+    bool frame_seen = false;
     int last_iters[2] = {0, 0};         // iterations the two registrations of the previous frame took: how many are enqueued before the host looks (tdlo_ctx::iter_hint;
                                         // the larger of the last two frames' counts was tried instead: no difference)
 };
@@ -3528,6 +3668,8 @@ static int tracker_frame_impl(tdlo_tracker *t, const unsigned short *depth, cons
     v.resize(M); ve.resize(M);
     int nv = 0, ne = 0, n = 0;
     t->frame_dist.resize(M);
+    t->frame_cam[0] = fx; t->frame_cam[1] = fy; t->frame_cam[2] = cx; t->frame_cam[3] = cy; t->frame_seen = true;
+    if (t->painter_on) t->frame_Y0 = t->Y; else t->frame_Y0.clear();
     int rc = depth_to_cloud_visibility_impl(c, t->slot, depth, mask, colour, rows, cols, fx, fy, cx, cy, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis,
                                             t->geodesic_coord.data(), t->frame_dist.data(), v.data(), &nv, ve.data(), &ne, &n, n_raw_out);
     if (!rc && t->painter_on && n > 0) {
@@ -3568,6 +3710,26 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
     const ColourIn ci{colour, params, occluder};
     return tracker_frame_impl(t, depth, nullptr, &ci, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext,
                               n_out, n_raw_out, stats);
+}
+
+// The picture of the tracker's current nodes over the last colour frame (trackdlo_node.cpp:377-452).  vis = the reference's not_self_occluded_nodes (:401):
+// the nodes the self-occlusion test leaves when no node is too far from the cloud, formed from the nodes the frame STARTED from (:279-343 run before
+// tracking_step); every node when the test is off.  Reads the tracker, changes nothing of it.
+int tdlo_tracker_render_result(tdlo_tracker *t, const double *proj, const tdlo_render_params *p, unsigned char *image_out, int corners[4]) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    const int M = t->M;
+    double pj[12] = {0};
+    if (proj) std::copy(proj, proj + 12, pj);
+    else if (t->painter_on) std::copy(t->painter_proj, t->painter_proj + 12, pj);
+    else if (t->frame_seen) { pj[0] = t->frame_cam[0]; pj[2] = t->frame_cam[2]; pj[5] = t->frame_cam[1]; pj[6] = t->frame_cam[3]; pj[10] = 1.0; }
+    else return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result: no projection matrix (none given, no tdlo_tracker_set_self_occlusion, no frame call yet)");
+    std::vector<int> vis;
+    if (t->painter_on && t->frame_Y0.size() == 3 * (size_t)M) {
+        const std::vector<double> zero(M, 0.0);
+        self_occlusion_visible(t->frame_Y0.data(), M, t->painter_proj, t->painter_width, zero.data(), std::numeric_limits<double>::infinity(), vis);
+    } else { vis.resize(M); for (int m = 0; m < M; ++m) vis[m] = m; }
+    return tdlo_render_result(c, nullptr, nullptr, c->last_col_rows, c->last_col_cols, t->Y.data(), M, pj, vis.data(), (int)vis.size(), p, image_out, corners);
 }
 
 // trackdlo_node.cpp:279-343 on the host (tdlo_host.cpp, self_occlusion_visible): O(M^2) integer tests, no kernel warranted

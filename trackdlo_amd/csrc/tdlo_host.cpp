@@ -8,6 +8,7 @@
 // Written against the behaviour of those functions, not their text: chain traversal is expressed
 // as one "pursuit" routine parameterised by direction instead of four unrolled copies.
 #include "tdlo_host.h"
+#include "tdlo_thick_line.h"
 
 #include <algorithm>
 #include <cmath>
@@ -419,17 +420,7 @@ double piecewise_error(const double *Ytrack, int n1, const double *Ytrue, int n2
 // node: rank of its nearer incident edge in the painting order, then "does any edge of smaller rank cover my pixel" -- O(M^2) integer tests on the
 // host, no image.  Coverage is the geometric content of the thick line (within width / 2 of the segment between the end pixels, in exact integer
 // arithmetic); OpenCV's own rasteriser is not available here to pin its boundary pixels against.
-namespace {
-struct Px { long long c, r; };
-inline bool within_half_width(const Px &p, const Px &a, const Px &b, long long w) {
-    const long long ex = b.c - a.c, ey = b.r - a.r, fx = p.c - a.c, fy = p.r - a.r;
-    const long long len2 = ex * ex + ey * ey, along = fx * ex + fy * ey;
-    if (along <= 0 || len2 == 0) return 4 * (fx * fx + fy * fy) <= w * w;                 // in front of the first end pixel (or a zero-length edge): its cap
-    if (along >= len2) { const long long gx = p.c - b.c, gy = p.r - b.r; return 4 * (gx * gx + gy * gy) <= w * w; }
-    const long long area = fx * ey - fy * ex;                                               // twice the triangle's area: distance = |area| / len
-    return 4 * area * area <= w * w * len2;
-}
-}  // namespace
+// (within_half_width: tdlo_thick_line.h, shared with the result image's kernel)
 
 void self_occlusion_visible(const double *Y, int M, const double proj[12], int dlo_pixel_width, const double *node_dist, double visibility_threshold, std::vector<int> &vis) {
     vis.clear();
@@ -458,6 +449,50 @@ void self_occlusion_visible(const double *Y, int M, const double proj[12], int d
         for (int r = 0; r < first && !hidden; ++r) { const int e = key[r].second; hidden = within_half_width(px[m], px[e], px[e + 1], dlo_pixel_width); }
         if (!hidden) vis.push_back(m);
     }
+}
+
+// ---- trackdlo_node.cpp:377-444: what the tracking-result image draws over the blended frame, as a table ----------------------------------------------
+// Node pixels as above (:394-397, :405-406: homogeneous projection, truncated), the edges sorted by the camera distance of their mid-points and REVERSED
+// (:378-390: farthest first), per edge a line, the disc of its first node and the disc of its second (:431-443), colours by membership in `vis`
+// (:409-424).  Records of eight ints {kind 0 line / 1 disc, c0, r0, c1, r1, size, b | g << 8 | r << 16, 0} in drawing order: a later one overwrites.
+// Every pixel coordinate must lie in [-8192, 8191], so that the coverage test's products fit (tdlo_thick_line.h).  Returns 0, or -1 for anything
+// that cannot be drawn (w <= 0, a non-finite quotient, a pixel out of range, vis out of range, a size outside 1 .. 255); nothing is written then.
+int render_primitives(const double *Y, int M, const double proj[12], const int *vis, int n_vis, int line_width, int node_radius,
+                      const unsigned char node_visible[3], const unsigned char node_hidden[3], const unsigned char edge_visible[3],
+                      const unsigned char edge_hidden[3], int *prims) {
+    if (!Y || !proj || M < 1 || n_vis < 0 || (n_vis > 0 && !vis)) return -1;
+    if (line_width < 1 || line_width > 255 || node_radius < 1 || node_radius > 255) return -1;
+    std::vector<char> in_vis(M, 0);
+    for (int k = 0; k < n_vis; ++k) { if (vis[k] < 0 || vis[k] >= M) return -1; in_vis[vis[k]] = 1; }
+    std::vector<int> pc(M), pr(M);
+    for (int m = 0; m < M; ++m) {
+        const double x = Y[m], y = Y[M + m], z = Y[2 * (size_t)M + m];
+        const double u = ((proj[0] * x + proj[1] * y) + proj[2] * z) + proj[3] * 1.0, v = ((proj[4] * x + proj[5] * y) + proj[6] * z) + proj[7] * 1.0,
+                     w = ((proj[8] * x + proj[9] * y) + proj[10] * z) + proj[11] * 1.0;
+        if (!(w > 0)) return -1;
+        const double qc = u / w, qr = v / w;
+        if (!(qc > -8193.0 && qc < 8192.0 && qr > -8193.0 && qr < 8192.0)) return -1;      // (NaN and infinities fail here; truncation then lands in [-8192, 8191])
+        pc[m] = (int)qc; pr[m] = (int)qr;
+    }
+    const int nE = M - 1;
+    std::vector<std::pair<double, int>> key(nE);
+    for (int i = 0; i < nE; ++i) {
+        const double mx = (Y[i] + Y[i + 1]) / 2, my = (Y[M + i] + Y[M + i + 1]) / 2, mz = (Y[2 * (size_t)M + i] + Y[2 * (size_t)M + i + 1]) / 2;
+        key[i] = {std::sqrt(mx * mx + my * my + mz * mz), i};
+    }
+    std::sort(key.begin(), key.end());                              // equal distances: ascending index, as in self_occlusion_visible
+    auto word = [](const unsigned char *c) { return (int)c[0] | ((int)c[1] << 8) | ((int)c[2] << 16); };
+    const int nv = word(node_visible), nh = word(node_hidden), ev = word(edge_visible), eh = word(edge_hidden);
+    int *q = prims;
+    for (int r = nE - 1; r >= 0; --r) {                             // :390 std::reverse
+        const int i = key[r].second;
+        const int rec[3][8] = {{0, pc[i], pr[i], pc[i + 1], pr[i + 1], line_width, (in_vis[i] || in_vis[i + 1]) ? ev : eh, 0},
+                               {1, pc[i], pr[i], pc[i], pr[i], node_radius, in_vis[i] ? nv : nh, 0},
+                               {1, pc[i + 1], pr[i + 1], pc[i + 1], pr[i + 1], node_radius, in_vis[i + 1] ? nv : nh, 0}};
+        std::memcpy(q, rec, sizeof(rec));
+        q += 24;
+    }
+    return 0;
 }
 
 }  // namespace tdlo

@@ -23,6 +23,12 @@ int traverse_euclidean(const std::vector<double> &coord, const double *guide, in
 // projected pixel is not under an edge nearer the camera (edges = thick lines of dlo_pixel_width pixels).  proj: 3 x 4 row-major.  Ascending.
 void self_occlusion_visible(const double *Y, int M, const double proj[12], int dlo_pixel_width, const double *node_dist, double visibility_threshold, std::vector<int> &vis);
 
+// The primitives of the tracking-result image (trackdlo_node.cpp:377-444) in drawing order: 3 (M - 1) records of eight ints, see tdlo_host.cpp.
+// Returns 0, or -1 when something cannot be drawn (prims is untouched then).
+int render_primitives(const double *Y, int M, const double proj[12], const int *vis, int n_vis, int line_width, int node_radius,
+                      const unsigned char node_visible[3], const unsigned char node_hidden[3], const unsigned char edge_visible[3],
+                      const unsigned char edge_hidden[3], int *prims);
+
 // evaluator::get_piecewise_error (evaluator.cpp:258-283); chains are n x 3 column-major.
 double piecewise_error(const double *Ytrack, int n1, const double *Ytrue, int n2);
 

@@ -302,6 +302,10 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
 // (k_colour_mask): mask (rows x cols bytes, 0 / 255) and, when hsv != nullptr, the HSV image (3 bytes a pixel), both device memory padded to 16 bytes beyond the image
 hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s);
 int check_device_image();
+// tdlo_render.hip: the tracking-result image (k_render: blend, edges and nodes in one launch).  colour / occluder / out: readable / writable by the device, 4-byte
+// aligned; prims: n_prims records of eight ints in device memory (tdlo_host.cpp, render_primitives); corner: nullptr, or two device words set to {0xffffffff, -1}
+hipError_t launch_render(const unsigned char *colour, const unsigned char *occluder, unsigned char *out, const int *prims, int n_prims, int P, int cols,
+                         unsigned *corner, hipStream_t s);
 // tdlo_import.hip: a cloud view (float32 / float64 elements at src, strides in elements) -> Xraw (N x 3 column-major doubles); the form -- 0 generic,
 // 1 one 12-byte load per point, 2 column-major pairs -- follows from the strides and the alignment of src only
 int cloud_import_form(const void *src, bool f64, long long stride_point, long long stride_comp);

@@ -497,6 +497,78 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
                                    int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                    int *n_out, int *n_raw_out, tdlo_stats *stats);
 
+/* ---- frames as they arrive: image views in device or host memory ------------------------------------ */
+/* A view of one rows x cols image where its producer holds it; nothing is copied to build one.  The packed calls above take one shape only (packed
+ * rows, 3-channel colour, uint16 millimetres, a host pointer); a renderer, simulator or decoder on the same GPU, or a torch tensor, delivers RGBA8 /
+ * BGRA8 colour, 32FC1 depth in metres, pitched or bottom-up rows, in DEVICE memory.  Formats per image:
+ *   depth            TDLO_IMG_U16C1 (millimetres) or TDLO_IMG_F32C1 (metres)
+ *   colour           TDLO_IMG_U8C3 or TDLO_IMG_U8C4: the first three bytes of a pixel are the channels, a fourth byte is ignored.  Which channel is which
+ *                    stays what tdlo_colour_params.rgb_order says; a view never swaps channels
+ *   occluder, mask   TDLO_IMG_U8C1, as in the packed calls
+ * The CANONICAL image of a view is the packed, row-major image it stands for: uint16 depth, 3 bytes a pixel of colour, one byte a pixel of occluder or
+ * mask.  THE CONTRACT: a view call computes, bit for bit, what the packed call computes from the canonical images (tests/image_view_ref.py is the numpy
+ * statement) -- cloud, n, n_raw, node distances, visible sets, the tracker's nodes and sigma2, and the picture tdlo_tracker_render_result draws afterwards.
+ * 32FC1 -> millimetres is this library's own rule (the reference reads 16UC1 only, trackdlo_node.cpp:219):
+ *   mm = floor(1000 d + 1/2) in exact arithmetic when 0 <= 1000 d + 1/2 < 65536, else 0 (NaN, +-inf, negative values, d >= 65.5355; 0 is the sensor's
+ *   "no return", which the path handles already).  It is evaluated as floor((double)d * 1000.0 + 0.5): product and sum are exact in fp64 wherever the
+ *   result can depend on them (1000 d >= 0.125; below that the sum stays under 1), so a fused multiply-add cannot change a bit and numpy's
+ *   d.astype(float64) * 1000.0 + 0.5 is the same function.  (The float32 form d * 1000.0f + 0.5f is NOT: its result depends on whether the compiler
+ *   fuses it.)  k / 1000 rounded to float32 converts back to k for every k in 0 .. 65535: a depth image written in metres reproduces its millimetre image. */
+enum { TDLO_IMG_U8C1 = 0, TDLO_IMG_U8C3 = 1, TDLO_IMG_U8C4 = 2, TDLO_IMG_U16C1 = 3, TDLO_IMG_F32C1 = 4 };     /* tdlo_image_view.format */
+enum { TDLO_ROLE_DEPTH = 0, TDLO_ROLE_COLOUR = 1, TDLO_ROLE_OCCLUDER = 2, TDLO_ROLE_MASK = 3 };              /* the `role` of tdlo_image_view_check */
+typedef struct {
+    const void *data;        /* first byte of pixel (0, 0); NULL: this image is absent */
+    int format, location;    /* TDLO_IMG_*, TDLO_MEM_AUTO / _HOST / _DEVICE (as tdlo_cloud_view) */
+    long long row_stride;    /* BYTES from row r to row r + 1; signed (bottom-up images are images); ROS sensor_msgs/Image.step, cv::Mat::step */
+    void *ready_stream;      /* device sources: hipStream_t whose work so far produces the data; NULL = the data is ready */
+} tdlo_image_view;
+typedef struct { tdlo_image_view depth, colour, occluder, mask; } tdlo_frame_view;
+/* Whether (v, rows, cols) describes an image in that role: TDLO_E_INVALID for a null view or null data, an unknown format, location or role, a format
+ * the role does not take, data or row_stride that is no multiple of the element size (1, 2 or 4), |row_stride| < cols x bytes per pixel with rows > 1
+ * (rows would overlap; with one row any stride is legal), an extent that does not fit 64-bit offsets, rows or cols <= 0, rows x cols > 2^26.  A pitch
+ * larger than the row and a negative one are legal.  Needs no context and no GPU; every call below that takes a view runs it first. */
+int tdlo_image_view_check(const tdlo_image_view *v, int rows, int cols, int role);
+/* The bytes the view addresses, relative to v->data: [*lo_bytes, *hi_bytes) = [min over rows of the row's start, max over rows of the row's start +
+ * cols x bytes per pixel).  The library reads no byte outside it, with any load, on host or device (of a pitched image the bytes between the rows lie
+ * inside it; they are not read either). */
+int tdlo_image_view_extent(const tdlo_image_view *v, int rows, int cols, long long *lo_bytes, long long *hi_bytes);
+/* How the import kernel loads a device view, from data, row_stride and cols only: 0 element by element, 1 dword loads, 2 one 8- / 16-byte load per four
+ * pixels (csrc/tdlo_image.hip).  Host helper, no device work: exported so that the chooser can be tested on a machine without a GPU. */
+int tdlo_image_view_form(const tdlo_image_view *v, int cols);
+/* The canonical image of a HOST view, written to canonical_out (rows x cols x {2, 3, 1, 1} bytes by role): what the calls below do with a host view.
+ * Host helper, no device work. */
+int tdlo_image_view_pack(const tdlo_image_view *v, int rows, int cols, int role, void *canonical_out);
+/* tdlo_depth_to_cloud (fv->mask given) or tdlo_colour_depth_to_cloud (fv->colour given; fv->occluder optional; colour_params as there) from views.
+ * Both or neither of mask and colour, no depth, a mask together with an occluder, a view that fails tdlo_image_view_check: TDLO_E_INVALID, and nothing
+ * of the context -- the slot's cloud, the canonical images -- has been touched.
+ *   location  as tdlo_set_cloud_view: TDLO_MEM_AUTO asks the runtime; device memory of another GPU is TDLO_E_INVALID; managed and caller-pinned
+ *             memory is host memory.
+ *   device sources   ONE kernel launch (k_image_import, csrc/tdlo_image.hip) normalises all of the frame's device images into the context's device
+ *             image buffers, where the kernels behind it read them as they do after the copy route; ready_stream: an event recorded on it makes the
+ *             context's stream wait for the work that produces the image -- no host wait.
+ *   host sources     the host packs and converts the view, row by row, into the context's pinned image buffers (those of tdlo_image_buffers and
+ *             tdlo_colour_buffers, whose lifetime rules apply: a view call counts as a call of them), and the call takes their in-place route: one host
+ *             pass and no second copy.  (In a frame that mixes host and device images the packed host images are copied to the device buffers.)  A host
+ *             view must not lie inside those pinned buffers.
+ * The calls are synchronous like the packed ones: the caller's memory is theirs again on return. */
+int tdlo_frame_to_cloud_view(tdlo_ctx *ctx, int slot, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                             double fx, double fy, double cx, double cy, double leaf_size, double *X_out, int x_capacity, int *n_out, int *n_raw_out);
+int tdlo_frame_to_cloud_visibility_view(tdlo_ctx *ctx, int slot, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                                        double fx, double fy, double cx, double cy, double leaf_size,
+                                        const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                        double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                        int *n_out, int *n_raw_out);
+/* tdlo_tracker_frame_from_depth (fv->mask given) / tdlo_tracker_frame_from_colour (fv->colour given) from views; a refused frame leaves the tracker's
+ * state untouched.  tdlo_tracker_render_result afterwards draws over the canonical colour image of this frame. */
+int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                            double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                            int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                            int *n_out, int *n_raw_out, tdlo_stats *stats);
+/* Test aid: copies out the canonical images the context's last view call left (device buffers or the pinned ones), each to a host buffer that may be
+ * NULL.  TDLO_E_INVALID when there was no such call, its shape differs, or an image is asked for that the frame did not have. */
+int tdlo_debug_read_images(tdlo_ctx *ctx, int rows, int cols, unsigned short *depth_out, unsigned char *colour_out, unsigned char *occluder_out,
+                           unsigned char *mask_out);
+
 /* ---- the tracking-result image on the device: blend, edges and nodes in one kernel ----------------- */
 /* The picture the node publishes every frame (trackdlo/src/trackdlo_node.cpp:377-452), so that a caller of tdlo_tracker_frame_from_colour needs no OpenCV
  * pass on the host for it either (a full-image cv::addWeighted, M - 1 cv::line and 2 (M - 1) cv::circle calls).  Stated exactly:

@@ -64,6 +64,21 @@ class CloudView(C.Structure):
                 ("ready_stream", C.c_void_p), ("flags", C.c_int)]
 
 
+IMG_U8C1, IMG_U8C3, IMG_U8C4, IMG_U16C1, IMG_F32C1 = 0, 1, 2, 3, 4       # tdlo_image_view.format
+ROLE_DEPTH, ROLE_COLOUR, ROLE_OCCLUDER, ROLE_MASK = 0, 1, 2, 3          # the role of tdlo_image_view_check
+IMG_BYTES_PER_PIXEL = {IMG_U8C1: 1, IMG_U8C3: 3, IMG_U8C4: 4, IMG_U16C1: 2, IMG_F32C1: 4}
+
+
+class ImageView(C.Structure):
+    """tdlo_image_view.  Built by image_view(), which also sets .rows, .cols and keeps the viewed object alive in .owner."""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_int), ("location", C.c_int), ("row_stride", C.c_longlong), ("ready_stream", C.c_void_p)]
+
+
+class FrameView(C.Structure):
+    """tdlo_frame_view: the images of one frame; an image whose data is NULL is absent."""
+    _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
+
+
 # every symbol include/trackdlo_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "tdlo_abi_version", "tdlo_device_count", "tdlo_default_config", "tdlo_create", "tdlo_destroy", "tdlo_last_error",
@@ -82,6 +97,8 @@ SYMBOLS = [
     "tdlo_colour_mask", "tdlo_colour_buffers", "tdlo_colour_depth_to_cloud", "tdlo_colour_depth_to_cloud_visibility", "tdlo_tracker_frame_from_colour",
     "tdlo_default_render_params", "tdlo_render_primitives", "tdlo_result_image_buffer", "tdlo_render_result", "tdlo_tracker_render_result",
     "tdlo_last_colour_shape",
+    "tdlo_image_view_check", "tdlo_image_view_extent", "tdlo_image_view_form", "tdlo_image_view_pack", "tdlo_frame_to_cloud_view",
+    "tdlo_frame_to_cloud_visibility_view", "tdlo_tracker_frame_view", "tdlo_debug_read_images",
 ]
 
 _lib = None
@@ -251,6 +268,17 @@ def load_library(path: str | None = None):
     lib.tdlo_set_cloud_view.argtypes = [vp, ci, cvp, ci]
     lib.tdlo_get_cloud.argtypes = [vp, ci, vp, ci, C.POINTER(ci)]
     lib.tdlo_tracker_tracking_step_view.argtypes = [vp, cvp, ci, vp, ci, vp, ci, vp, vp]
+    if hasattr(lib, "tdlo_frame_to_cloud_view"):        # (a library of an earlier commit handed over through TDLO_LIBRARY, the comparator of the A/B scripts, lacks them)
+        ivp, fvp = C.POINTER(ImageView), C.POINTER(FrameView)
+        lib.tdlo_image_view_check.argtypes = [ivp, ci, ci, ci]
+        lib.tdlo_image_view_extent.argtypes = [ivp, ci, ci, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        lib.tdlo_image_view_form.argtypes = [ivp, ci]
+        lib.tdlo_image_view_pack.argtypes = [ivp, ci, ci, ci, vp]
+        lib.tdlo_frame_to_cloud_view.argtypes = [vp, ci, fvp, cpp, ci, ci, cd, cd, cd, cd, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_frame_to_cloud_visibility_view.argtypes = [vp, ci, fvp, cpp, ci, ci, cd, cd, cd, cd, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci),
+                                                            C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_tracker_frame_view.argtypes = [vp, fvp, cpp, ci, ci, cd, cd, cd, cd, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+        lib.tdlo_debug_read_images.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -351,6 +379,76 @@ def cloud_view_extent(v: CloudView, N=None):
     if rc:
         raise TdloError(rc, "tdlo_cloud_view_extent: not a cloud view")
     return lo.value, hi.value
+
+
+_IMG_INFER = {("u1", 1): IMG_U8C1, ("u1", 3): IMG_U8C3, ("u1", 4): IMG_U8C4, ("u2", 1): IMG_U16C1, ("f4", 1): IMG_F32C1}
+
+
+def image_view(obj, format=None, ready_stream=None) -> ImageView:
+    """tdlo_image_view of an image where it lies, without a copy: a numpy array (host memory) or any object with __cuda_array_interface__ (device memory:
+    a ROCm torch tensor, say -- torch is not imported here).  Shape (rows, cols) or (rows, cols, channels) with the pixels' bytes adjacent; the row
+    stride -- a pitch, or negative for a flipped image -- comes straight from the object's strides.  The format is inferred from dtype and channels
+    (uint8 x 1 / 3 / 4, uint16, float32); format= overrides that for elements of the same size carried in another dtype (uint16 millimetres in an int16
+    tensor, RGBA in an int32 one).  ready_stream: the raw hipStream_t (an integer) whose work so far produces a device source.
+    The result carries .rows, .cols and .owner."""
+    device = hasattr(obj, "__cuda_array_interface__")
+    if not device and not hasattr(obj, "__array_interface__"):
+        raise TypeError("image_view: a numpy array or an object with __cuda_array_interface__")
+    ai = obj.__cuda_array_interface__ if device else obj.__array_interface__
+    typestr = ai["typestr"]
+    if typestr[0] not in "<=|" + ("<" if np.little_endian else ">"):
+        raise TypeError(f"image_view: native byte order, not {typestr!r}")
+    shape = tuple(int(d) for d in ai["shape"])
+    if len(shape) not in (2, 3):
+        raise TypeError(f"image_view: shape (rows, cols) or (rows, cols, channels), not {shape}")
+    es = int(typestr[2:])
+    ch = shape[2] if len(shape) == 3 else 1
+    strides = ai.get("strides")
+    if strides is None:
+        strides = (shape[1] * ch * es, ch * es, es)[:len(shape)]                # C-contiguous
+    if format is None:
+        format = _IMG_INFER.get((typestr[1:], ch))
+        if format is None:
+            raise TypeError(f"image_view: no image format for {typestr!r} with {ch} channel(s); pass format=")
+    bpp = IMG_BYTES_PER_PIXEL[format]
+    if ch * es != bpp or int(strides[1]) != bpp or (len(shape) == 3 and ch > 1 and int(strides[2]) != es):
+        raise TypeError("image_view: the pixels of a row must be adjacent and as large as the format says")
+    v = ImageView(int(ai["data"][0]) or None, int(format), MEM_DEVICE if device else MEM_HOST, int(strides[0]), int(ready_stream) if ready_stream else None)
+    v.rows, v.cols = shape[0], shape[1]
+    v.owner = obj
+    return v
+
+
+def frame_view(depth, colour=None, occluder=None, mask=None) -> FrameView:
+    """tdlo_frame_view of a frame's images: each an ImageView, anything image_view() takes, or None (absent).  Carries .rows, .cols and .owners."""
+    vs = [None if o is None else o if isinstance(o, ImageView) else image_view(o) for o in (depth, colour, occluder, mask)]
+    if vs[0] is None:
+        raise ValueError("frame_view: a frame has a depth image")
+    if any(v is not None and (v.rows, v.cols) != (vs[0].rows, vs[0].cols) for v in vs):
+        raise ValueError("frame_view: the images of a frame have one shape")
+    fv = FrameView(*[v if v is not None else ImageView() for v in vs])
+    fv.rows, fv.cols = vs[0].rows, vs[0].cols
+    fv.owners = vs
+    return fv
+
+
+def image_view_check(v: ImageView, role, rows=None, cols=None) -> int:
+    """tdlo_image_view_check: TDLO_OK or TDLO_E_INVALID.  No context, no GPU."""
+    return int(load_library().tdlo_image_view_check(C.byref(v), int(v.rows if rows is None else rows), int(v.cols if cols is None else cols), int(role)))
+
+
+def image_view_extent(v: ImageView, rows=None, cols=None):
+    """[lo, hi) in bytes relative to v.data: what the library may read of the view (tdlo_image_view_extent)."""
+    lo = C.c_longlong(0); hi = C.c_longlong(0)
+    rc = load_library().tdlo_image_view_extent(C.byref(v), int(v.rows if rows is None else rows), int(v.cols if cols is None else cols), C.byref(lo), C.byref(hi))
+    if rc:
+        raise TdloError(rc, "tdlo_image_view_extent: not an image view")
+    return lo.value, hi.value
+
+
+def image_view_form(v: ImageView, cols=None) -> int:
+    """How the import kernel would load this view: 0 element by element, 1 dword loads, 2 one 8- / 16-byte load per four pixels (tdlo_image_view_form)."""
+    return int(load_library().tdlo_image_view_form(C.byref(v), int(v.cols if cols is None else cols)))
 
 
 def make_params(beta, lambda_, lle_weight, mu, max_iter=30, tol=1e-4, include_lle=True, alpha=0.0, k_vis=0.0,
@@ -804,6 +902,51 @@ class Context:
                                                           _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
 
+    @staticmethod
+    def _frame(fv):
+        return fv if isinstance(fv, FrameView) else frame_view(*fv) if isinstance(fv, (tuple, list)) else frame_view(**fv)
+
+    def frame_to_cloud_view(self, slot, fv, params: ColourParams, fx, fy, cx, cy, leaf_size, *, fetch=True):
+        """depth_to_cloud (fv has a mask) / colour_depth_to_cloud (fv has a colour image) from images where they lie (tdlo_frame_to_cloud_view).  fv: a
+        FrameView, or the arguments of frame_view() as a tuple or dict.  params may be None for a mask frame.  Returns (X [n x 3] or None, n, n_raw)."""
+        fv = self._frame(fv)
+        cap = fv.rows * fv.cols if fetch else 0
+        buf = np.zeros(3 * max(cap, 1)) if fetch else None
+        n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_frame_to_cloud_view(self.h, slot, C.byref(fv), C.byref(params) if params is not None else None, fv.rows, fv.cols,
+                                                    float(fx), float(fy), float(cx), float(cy), float(leaf_size), _ptr(buf), cap, C.byref(n), C.byref(nraw)))
+        X = buf[:3 * n.value].reshape(3, n.value).T.copy() if fetch else None
+        return X, n.value, nraw.value
+
+    def frame_to_cloud_visibility_view(self, slot, fv, params: ColourParams, fx, fy, cx, cy, leaf_size, Y, visibility_threshold, d_vis, geodesic_coord):
+        """depth_to_cloud_visibility / colour_depth_to_cloud_visibility from images where they lie (tdlo_frame_to_cloud_visibility_view).
+        Returns (node_dist, visible_nodes, visible_nodes_extended, n, n_raw)."""
+        fv = self._frame(fv)
+        Y = _f64(Y); M = Y.shape[0]
+        coord = np.ascontiguousarray(geodesic_coord, dtype=np.float64)
+        dist = np.zeros(M); vis = np.zeros(M, dtype=np.int32); ext = np.zeros(M, dtype=np.int32)
+        nv = C.c_int(0); ne = C.c_int(0); n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_frame_to_cloud_visibility_view(self.h, slot, C.byref(fv), C.byref(params) if params is not None else None, fv.rows, fv.cols,
+                                                               float(fx), float(fy), float(cx), float(cy), float(leaf_size), _ptr(Y), M,
+                                                               float(visibility_threshold), float(d_vis), _ptr(coord), _ptr(dist), _ptr(vis), C.byref(nv),
+                                                               _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
+        return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
+    def debug_read_images(self, rows, cols, depth=False, colour=False, occluder=False, mask=False):
+        """The canonical images the last view call left (tdlo_debug_read_images): a dict of those asked for -- depth uint16 [rows x cols], colour uint8
+        [rows x cols x 3], occluder / mask uint8 [rows x cols]."""
+        out = {}
+        if depth:
+            out["depth"] = np.zeros((rows, cols), dtype=np.uint16)
+        if colour:
+            out["colour"] = np.zeros((rows, cols, 3), dtype=np.uint8)
+        if occluder:
+            out["occluder"] = np.zeros((rows, cols), dtype=np.uint8)
+        if mask:
+            out["mask"] = np.zeros((rows, cols), dtype=np.uint8)
+        self._chk(self.lib.tdlo_debug_read_images(self.h, int(rows), int(cols), *[_ptr(out.get(k)) for k in ("depth", "colour", "occluder", "mask")]))
+        return out
+
     def debug_read_cloud(self, max_points, frame=0):
         """The pruned, centred, node-sorted cloud [n x 3] and the centring offset of frame `frame` of the last call (tdlo_debug_read_cloud)."""
         out = np.zeros((3, max(max_points, 1))); ctr = np.zeros(3)
@@ -968,6 +1111,21 @@ class trackdlo:
         rc = self.ctx.lib.tdlo_tracker_frame_from_colour(self.h, depth.ctypes.data, colour.ctypes.data, C.byref(params), occluder.ctypes.data if occluder is not None else None,
                                                          rows, cols, fx, fy, cx, cy, leaf_size, d_vis,
                                                          v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
+        self._stats_raw = self._st
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def frame_view(self, fv, params: ColourParams, fx, fy, cx, cy, leaf_size=0.008, d_vis=0.06):
+        """frame_from_depth (fv has a mask) / frame_from_colour (fv has a colour image) from images where they lie -- device tensors, pitched, 4-channel,
+        float-metre or flipped images (tdlo_tracker_frame_view).  fv: a FrameView, or the arguments of frame_view() as a tuple or dict.
+        Returns (visible_nodes, visible_nodes_extended, n, n_raw); the nodes: get_tracking_result()."""
+        fv = Context._frame(fv)
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        rc = self.ctx.lib.tdlo_tracker_frame_view(self.h, C.byref(fv), C.byref(params) if params is not None else None, fv.rows, fv.cols, fx, fy, cx, cy, leaf_size, d_vis,
+                                                  v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
         self._stats_raw = self._st
         if rc:
             self.ctx._chk(rc)

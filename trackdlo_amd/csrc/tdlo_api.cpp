@@ -4,6 +4,7 @@
 #include "../../include/trackdlo_hip.h"
 #include "tdlo_internal.h"
 #include "tdlo_host.h"
+#include "tdlo_image.h"
 #include "tdlo_rccl.h"
 
 #include <algorithm>
@@ -202,6 +203,10 @@ struct tdlo_ctx {
     // rnd_dev: [primitive table | the two corner words], staged and resident.  TDLO_RENDER_INPLACE=0: the kernel never writes the caller's memory
     // itself -- always res_dev and a copy (the comparator; profiles/render_frame_ab.txt).  render_route: tdlo_debug_route_count 19 / 20
     const unsigned char *last_colour = nullptr, *last_occluder = nullptr;
+    // where the last view call (tdlo_frame_to_cloud_view and its kin) left the frame's canonical images, by role (depth, colour, occluder, mask): the device
+    // buffers or the pinned ones; nullptr: the frame had no such image (tdlo_debug_read_images)
+    const void *view_img[4] = {nullptr, nullptr, nullptr, nullptr};
+    int view_rows = 0, view_cols = 0;
     int last_col_rows = 0, last_col_cols = 0;
     char *res_pin = nullptr;
     size_t res_pin_cap = 0;
@@ -1799,23 +1804,24 @@ int tdlo_cloud_view_extent(const tdlo_cloud_view *v, int N, long long *lo_bytes,
 
 // Where a (checked) view's memory is: *device = a kernel on the context's GPU may read it.  Everything else -- memory the runtime does not know,
 // caller-pinned and managed memory -- is host memory: copied, never dereferenced by a kernel.
-static int view_location(tdlo_ctx *c, const tdlo_cloud_view *v, bool *device) {
+static int pointer_location(tdlo_ctx *c, const void *data, int location, const char *what, bool *device) {
     *device = false;
-    if (v->location == TDLO_MEM_HOST) return TDLO_OK;
+    if (location == TDLO_MEM_HOST) return TDLO_OK;
     hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, v->data) != hipSuccess) {
+    if (hipPointerGetAttributes(&at, data) != hipSuccess) {
         (void)hipGetLastError();                           // (a pointer the runtime does not know; the error must not reach the next launch check)
-        if (v->location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, "cloud view: location says device memory, the runtime does not know the pointer");
+        if (location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, std::string(what) + ": location says device memory, the runtime does not know the pointer");
         return TDLO_OK;
     }
     if (at.type != hipMemoryTypeDevice) {
-        if (v->location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, "cloud view: location says device memory, the runtime says otherwise");
+        if (location == TDLO_MEM_DEVICE) return fail(c, TDLO_E_INVALID, std::string(what) + ": location says device memory, the runtime says otherwise");
         return TDLO_OK;
     }
-    if (at.device != c->device) return fail(c, TDLO_E_INVALID, "cloud view: device memory of another GPU");
+    if (at.device != c->device) return fail(c, TDLO_E_INVALID, std::string(what) + ": device memory of another GPU");
     *device = true;
     return TDLO_OK;
 }
+static int view_location(tdlo_ctx *c, const tdlo_cloud_view *v, bool *device) { return pointer_location(c, v->data, v->location, "cloud view", device); }
 
 // tdlo_set_cloud_view on a checked view.  wait: the call returns when the import has finished (a host source always waits unless the caller is
 // tracking_step, whose first registration waits for the stream before it returns: the pinned staging is free again by then).
@@ -2538,6 +2544,9 @@ static int colour_stage(tdlo_ctx *c, const ColourIn &ci, int rows, int cols, Clo
     const size_t need = img_colour_bytes(P) + img_occ_bytes(P) + (d_hsv ? img_colour_bytes(P) : 0);
     const bool in_place = c->col_pin != nullptr && (const char *)ci.colour == c->col_pin && c->col_pin_rows == rows && c->col_pin_cols == cols &&
                           (!ci.occluder || (const char *)ci.occluder == c->col_pin + img_colour_bytes(P));
+    // a view call's import has written the images into the device buffers already (stage_frame_view sized them): nothing to copy
+    const bool on_dev = c->col_dev != nullptr && (const void *)ci.colour == c->col_dev && !d_hsv && need <= c->col_dev_cap &&
+                        (!ci.occluder || (const char *)ci.occluder == (const char *)c->col_dev + img_colour_bytes(P));
     c->last_colour = c->last_occluder = nullptr;
     if ((!in_place || d_hsv) && need > c->col_dev_cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2547,7 +2556,7 @@ static int colour_stage(tdlo_ctx *c, const ColourIn &ci, int rows, int cols, Clo
         c->col_dev_cap = need;
     }
     char *base = (char *)c->col_dev;
-    if (in_place) { cc.colour = ci.colour; cc.occluder = ci.occluder; }
+    if (in_place || on_dev) { cc.colour = ci.colour; cc.occluder = ci.occluder; }
     else {
         cc.colour = (const unsigned char *)base;
         cc.occluder = ci.occluder ? (const unsigned char *)(base + img_colour_bytes(P)) : nullptr;
@@ -2763,7 +2772,7 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
         // the depth image where it is when it lies in the context's pinned buffer, the colour and occluder images likewise (tdlo_colour_buffers); the mask is
         // always the device buffer: k_colour_mask writes it when the one-launch kernel does not serve the frame
         if (c->img_pin != nullptr && (const char *)depth == c->img_pin && c->img_pin_rows == rows && c->img_pin_cols == cols) d_depth = depth;
-        else HIPCHK(c, hipMemcpyAsync((void *)d_depth, depth, (size_t)P * 2, hipMemcpyHostToDevice, st));
+        else if ((const char *)depth != base) HIPCHK(c, hipMemcpyAsync((void *)d_depth, depth, (size_t)P * 2, hipMemcpyHostToDevice, st));      // (== base: a view call's import wrote it there)
         if ((rc = colour_stage(c, *colour, rows, cols, cc, nullptr))) return rc;
         mask_ready = false;
         if (!(c->colour_fused_on && c->cloud_fused_on && cloud_fused_ok(P))) {
@@ -2771,6 +2780,7 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
             mask_ready = true; ++c->colour_route[1];
         }
     } else if (in_place) { d_depth = depth; d_mask = mask; }
+    else if ((const char *)depth == base && (const char *)mask == base + img_depth_bytes(P)) { }      // a view call's import wrote both there
     else {
         HIPCHK(c, hipMemcpyAsync((void *)d_depth, depth, (size_t)P * 2, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync((void *)d_mask, mask, (size_t)P, hipMemcpyHostToDevice, st));
@@ -3019,6 +3029,147 @@ int tdlo_colour_depth_to_cloud_visibility(tdlo_ctx *c, int slot, const unsigned 
     const ColourIn ci{colour, params, occluder};
     return depth_to_cloud_visibility_impl(c, slot, depth, nullptr, &ci, rows, cols, fx, fy, cx, cy, leaf_size, Y, M, visibility_threshold, d_vis, geodesic_coord,
                                           node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
+}
+
+// ---- frames as they arrive: image views in device or host memory (tdlo_image_view; tdlo_image.h) ---------------------------------------------
+// The canonical images of a checked frame view, where the packed routes read them without a copy of their own.
+struct StagedFrame { const unsigned short *depth = nullptr; const unsigned char *mask = nullptr; ColourIn ci{nullptr, nullptr, nullptr}; bool colour = false; };
+
+// nullptr: fv describes a frame of rows x cols images; otherwise what is wrong with it
+static const char *frame_view_fault(const tdlo_frame_view *fv, int rows, int cols) {
+    if (!fv) return "frame view: null";
+    if (!fv->depth.data) return "frame view: no depth image";
+    if ((fv->mask.data != nullptr) == (fv->colour.data != nullptr)) return "frame view: exactly one of mask and colour";
+    if (fv->mask.data && fv->occluder.data) return "frame view: an occluder goes with a colour image, not with a mask";
+    const tdlo_image_view *iv[4] = {&fv->depth, &fv->colour, &fv->occluder, &fv->mask};
+    for (int r = 0; r < 4; ++r)
+        if (iv[r]->data)
+            if (const char *why = image_view_fault(iv[r], rows, cols, r)) return why;
+    return nullptr;
+}
+
+// Everything a view call refuses before it touches the context: the frame, the colour parameters, the slot, the leaf and the intrinsics
+static int frame_view_refusal(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, const tdlo_colour_params *cp, int rows, int cols, double fx, double fy, double leaf_size) {
+    if (const char *why = frame_view_fault(fv, rows, cols)) return fail(c, TDLO_E_INVALID, why);
+    CloudColour cc;
+    if (fv->colour.data && !colour_pack(cp, cc)) return fail(c, TDLO_E_INVALID, "tdlo_colour_params: 1 .. 4 ranges");
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    if (!(leaf_size > 0) || fx == 0 || fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
+    return TDLO_OK;
+}
+
+// A checked frame view -> its canonical images.  Device sources: one launch of k_image_import into the device image buffers (cloud_ws: depth | mask,
+// col_dev: colour | occluder), which depth_to_cloud_impl / colour_stage recognise by their addresses.  Host sources: packed and converted by the host
+// into the pinned buffers of tdlo_image_buffers / tdlo_colour_buffers, i.e. the in-place route; in a frame that has device sources too they are
+// copied on to the device buffers.
+static int stage_frame_view(tdlo_ctx *c, const tdlo_frame_view *fv, const tdlo_colour_params *cp, int rows, int cols, StagedFrame &sf) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t P = (size_t)rows * cols;
+    const tdlo_image_view *iv[4] = {&fv->depth, &fv->colour, &fv->occluder, &fv->mask};
+    const size_t bytes[4] = {2 * P, 3 * P, P, P};
+    bool dev[4] = {false, false, false, false}, any_dev = false, any_host = false;
+    for (int r = 0; r < 4; ++r) {
+        if (!iv[r]->data) continue;
+        if (int rc = pointer_location(c, iv[r]->data, iv[r]->location, "image view", &dev[r])) return rc;
+        if (dev[r]) { any_dev = true; continue; }
+        any_host = true;
+        long long lo, hi;
+        image_view_span(iv[r], rows, cols, &lo, &hi);
+        const char *a = (const char *)iv[r]->data + lo, *b = (const char *)iv[r]->data + hi;
+        if ((c->img_pin && a < c->img_pin + c->img_pin_cap && b > c->img_pin) || (c->col_pin && a < c->col_pin + c->col_pin_cap && b > c->col_pin))
+            return fail(c, TDLO_E_INVALID, "image view: a host view inside the context's pinned image buffers (hand those to the packed calls)");
+    }
+    sf.colour = fv->colour.data != nullptr;
+    const bool want_col = sf.colour;
+    unsigned char *pin[4] = {nullptr, nullptr, nullptr, nullptr}, *dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (any_host) {
+        unsigned short *pd = nullptr;
+        if (int rc = tdlo_image_buffers(c, rows, cols, &pd, &pin[kRoleMask])) return rc;
+        pin[kRoleDepth] = (unsigned char *)pd;
+        if (want_col)
+            if (int rc = tdlo_colour_buffers(c, rows, cols, &pin[kRoleColour], &pin[kRoleOccluder])) return rc;
+        for (int r = 0; r < 4; ++r)
+            if (iv[r]->data && !dev[r]) image_pack_host(iv[r], rows, cols, pin[r]);
+    }
+    if (any_dev) {
+        if (int rc = ensure_cloud_ws(c, (int)P)) return rc;
+        dst[kRoleDepth] = (unsigned char *)c->cloud_ws;
+        dst[kRoleMask] = (unsigned char *)c->cloud_ws + img_depth_bytes(P);
+        if (want_col) {
+            const size_t need = img_colour_bytes(P) + img_occ_bytes(P);
+            if (need > c->col_dev_cap) {
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                if (c->col_dev) hipFree(c->col_dev);
+                c->col_dev = nullptr; c->col_dev_cap = 0; c->last_colour = c->last_occluder = nullptr;
+                HIPCHK(c, hipMalloc(&c->col_dev, need));
+                c->col_dev_cap = need;
+            }
+            dst[kRoleColour] = (unsigned char *)c->col_dev;
+            dst[kRoleOccluder] = (unsigned char *)c->col_dev + img_colour_bytes(P);
+        }
+        ImageJob job{};
+        job.P = (int)P; job.cols = cols;
+        for (int r = 0; r < 4; ++r) {
+            if (!iv[r]->data) continue;
+            if (!dev[r]) { HIPCHK(c, hipMemcpyAsync(dst[r], pin[r], bytes[r], hipMemcpyHostToDevice, c->stream)); continue; }
+            if (iv[r]->ready_stream) {
+                if (!c->ev_view) HIPCHK(c, hipEventCreateWithFlags(&c->ev_view, hipEventDisableTiming));
+                HIPCHK(c, hipEventRecord(c->ev_view, (hipStream_t)iv[r]->ready_stream));
+                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_view, 0));
+            }
+            job.src[r] = ImageSrc{(const unsigned char *)iv[r]->data, iv[r]->row_stride, iv[r]->format, image_import_form(iv[r]->data, iv[r]->row_stride, cols, iv[r]->format)};
+            job.dst[r] = dst[r];
+        }
+        HIPCHK(c, launch_image_import(job, c->stream));
+    }
+    unsigned char **where = any_dev ? dst : pin;
+    for (int r = 0; r < 4; ++r) c->view_img[r] = iv[r]->data ? where[r] : nullptr;
+    c->view_rows = rows; c->view_cols = cols;
+    sf.depth = (const unsigned short *)where[kRoleDepth];
+    sf.mask = fv->mask.data ? where[kRoleMask] : nullptr;
+    sf.ci = ColourIn{want_col ? where[kRoleColour] : nullptr, cp, fv->occluder.data ? where[kRoleOccluder] : nullptr};
+    return TDLO_OK;
+}
+
+int tdlo_frame_to_cloud_view(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                             double fx, double fy, double cx, double cy, double leaf_size, double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+    if (!c) return TDLO_E_INVALID;
+    int rc = frame_view_refusal(c, slot, fv, colour_params, rows, cols, fx, fy, leaf_size);
+    if (rc) return rc;
+    StagedFrame sf;
+    if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
+    return depth_to_cloud_impl(c, slot, sf.depth, sf.mask, rows, cols, fx, fy, cx, cy, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr,
+                               sf.colour ? &sf.ci : nullptr);
+}
+
+int tdlo_frame_to_cloud_visibility_view(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                                        double fx, double fy, double cx, double cy, double leaf_size,
+                                        const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                        double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                        int *n_out, int *n_raw_out) {
+    if (!c) return TDLO_E_INVALID;
+    if (!Y || M < 1 || !geodesic_coord) return fail(c, TDLO_E_INVALID, "null Y / geodesic_coord");
+    int rc = frame_view_refusal(c, slot, fv, colour_params, rows, cols, fx, fy, leaf_size);
+    if (rc) return rc;
+    StagedFrame sf;
+    if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
+    return depth_to_cloud_visibility_impl(c, slot, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, rows, cols, fx, fy, cx, cy, leaf_size, Y, M, visibility_threshold,
+                                          d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
+}
+
+int tdlo_debug_read_images(tdlo_ctx *c, int rows, int cols, unsigned short *depth_out, unsigned char *colour_out, unsigned char *occluder_out,
+                           unsigned char *mask_out) {
+    if (!c) return TDLO_E_INVALID;
+    if (c->view_rows != rows || c->view_cols != cols || rows <= 0 || cols <= 0) return fail(c, TDLO_E_INVALID, "tdlo_debug_read_images: no view call of this shape yet");
+    void *out[4] = {depth_out, colour_out, occluder_out, mask_out};
+    const size_t P = (size_t)rows * cols, bytes[4] = {2 * P, 3 * P, P, P};
+    for (int r = 0; r < 4; ++r)
+        if (out[r] && !c->view_img[r]) return fail(c, TDLO_E_INVALID, "tdlo_debug_read_images: the last view frame had no such image");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < 4; ++r)
+        if (out[r]) HIPCHK(c, hipMemcpy(out[r], c->view_img[r], bytes[r], hipMemcpyDefault));
+    return TDLO_OK;
 }
 
 // ---- measurement ---------------------------------------------------------------------------------
@@ -3710,6 +3861,22 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
     const ColourIn ci{colour, params, occluder};
     return tracker_frame_impl(t, depth, nullptr, &ci, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext,
                               n_out, n_raw_out, stats);
+}
+
+// The same from views of the images where they lie (tdlo_image_view): refused before the tracker's state is touched, staged, then the packed route
+int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const tdlo_colour_params *colour_params, int rows, int cols,
+                            double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
+                            int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                            int *n_out, int *n_raw_out, tdlo_stats *stats) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    if (t->geodesic_coord.size() != (size_t)t->M) return fail(c, TDLO_E_INVALID, "the tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)");
+    int rc = frame_view_refusal(c, t->slot, fv, colour_params, rows, cols, fx, fy, leaf_size);
+    if (rc) return rc;
+    StagedFrame sf;
+    if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
+    return tracker_frame_impl(t, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis,
+                              visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
 }
 
 // The picture of the tracker's current nodes over the last colour frame (trackdlo_node.cpp:377-452).  vis = the reference's not_self_occluded_nodes (:401):

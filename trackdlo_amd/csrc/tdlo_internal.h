@@ -310,5 +310,8 @@ hipError_t launch_render(const unsigned char *colour, const unsigned char *occlu
 // 1 one 12-byte load per point, 2 column-major pairs -- follows from the strides and the alignment of src only
 int cloud_import_form(const void *src, bool f64, long long stride_point, long long stride_comp);
 hipError_t launch_cloud_import(const void *src, bool f64, long long stride_point, long long stride_comp, int N, double *Xraw, hipStream_t s);
+// tdlo_image.hip: a frame's device-resident image views -> the packed canonical images, all of them in one launch (k_image_import; tdlo_image.h)
+struct ImageJob;
+hipError_t launch_image_import(const ImageJob &job, hipStream_t s);
 
 }  // namespace tdlo

@@ -446,6 +446,57 @@ int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, 
                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                   int *n_out, int *n_raw_out, tdlo_stats *stats);
 
+/* ---- down-sample clouds as they arrive: the voxel grid on cloud views ---------------------------- */
+/* For a caller that holds a cloud rather than a depth image -- a PointCloud2 (organized, NaN where there is no return), a simulator's or lidar's
+ * points, a tensor on the same GPU: pcl::VoxelGrid (trackdlo_node.cpp:235-241) on the view's points, on the device, into the slot's resident cloud.
+ * The reference's prototype works that way (utils/tracking_test.py:452-505: organized cloud x colour mask, then the voxel down-sample).
+ *
+ * V(view, N, select, leaf) is the restated PCL 1.10 VoxelGrid::applyFilter of the depth path (downsample_all_data, min_points_per_voxel = 0, no filter
+ * field), applied to the view's points in input order:
+ *   1. Point k is ((float)x, (float)y, (float)z) of view element k.  float32 passes through unchanged; float64 is rounded to nearest-even, so a
+ *      double beyond float range becomes +-inf.
+ *   2. A point is kept iff all three floats are finite (PCL's !is_dense branch, always taken) and, when select != NULL, select[k] != 0.  select: N
+ *      packed bytes in host or device memory (a host array is copied to the context's device mask buffer) -- an organized cloud plus the mask that
+ *      tdlo_colour_mask or the caller made.
+ *   3. n_raw = the number of kept points.
+ *   4. n_raw == 0: TDLO_OK, *n_out = 0, and the slot is left as tdlo_depth_to_cloud leaves it for an all-zero mask (empty).
+ *   5. leaf = (float)leaf_size, inv = 1.0f / leaf, a float bounding box mn, mx over the kept points;
+ *        dd[d] = (long long)((mx[d] - mn[d]) * inv) + 1,  min_b[d] = (int)floorf(mn[d] * inv),  div_b[d] = (int)floorf(mx[d] * inv) - min_b[d] + 1.
+ *   6. Pass-through (PCL's "leaf size too small") iff the exact product dd[0] dd[1] dd[2] exceeds 2^31 - 1.  It is evaluated without overflow: an
+ *      extent term (mx[d] - mn[d]) * inv that is not finite or is >= 2^31 is pass-through outright, and the product is formed stepwise.
+ *   7. Pass-through output: the KEPT points in input order.  DEPARTURE FROM PCL, which copies the non-finite points as well; the prune of
+ *      trackdlo.cpp:177-195 drops those anyway.
+ *   8. No pass-through and a floorf(mn[d] * inv) or floorf(mx[d] * inv) outside int32: TDLO_E_INVALID, "cloud too far from the origin for this leaf
+ *      size"; the slot's cloud is untouched.  DEPARTURE FROM PCL, whose cast to int is undefined there.  (So is a div_b[d] beyond int32.)
+ *   9. div_b[0] div_b[1] div_b[2] >= 0xffffffff: TDLO_E_INVALID ("too many cells"), as in the depth path; the slot's cloud is untouched.
+ *  10. Cell of a point p: ijk[d] = (int)(floorf(p[d] * inv) - (float)min_b[d]); key = ijk0 + ijk1 div_b0 + ijk2 div_b0 div_b1.
+ *  11. One output point per occupied cell, in ascending key: float sums taken in input order, each divided by (float)count with a correctly rounded
+ *      division, the result widened to double.
+ *  12. The result becomes the slot's resident cloud; n, n_raw and the optional X_out are returned exactly as tdlo_depth_to_cloud returns them.
+ * Consequence (the heart of tests/test_voxel_view_gpu.py): for a depth image and a mask, with P the float32 points of the masked pixels in row-major
+ * order formed by the arithmetic of trackdlo_node.cpp:219-224, V(P) is bit for bit what tdlo_depth_to_cloud leaves in the slot.  Depth-born points
+ * never come near the cases of 6 and 8, so the depth path's results are what they were.  tests/voxel_ref.py is the numpy statement of V.
+ *
+ * tdlo_voxel_grid_dims: the grid arithmetic of 5, 6 and 8 as a host helper (no context, no GPU); the depth path and the view path both go through it.
+ * *nodown = 1 for pass-through (min_b = 0, div_b = 1 then).  TDLO_E_INVALID: a null pointer, (float)leaf_size not a positive finite float, a box with
+ * mn > mx or a component that is not finite, the cloud-too-far case of 8. */
+int tdlo_voxel_grid_dims(const float mn[3], const float mx[3], double leaf_size, int min_b[3], int div_b[3], int *nodown);
+/* V on a view into `slot`.  tdlo_cloud_view_check first; location, ready_stream (which covers a device `select` too) and the staging of a host view follow
+ * tdlo_set_cloud_view: a host view is packed in its own precision into the pinned staging block and the kernels read it there, a device view is read
+ * in place, and no load of any width touches a byte outside tdlo_cloud_view_extent.  TDLO_E_INVALID, with the slot's cloud intact: TDLO_VIEW_ASYNC (the
+ * call needs a host round trip for the box), N > 2^26 (refused before anything is allocated; the workspace is 16 N bytes), a device view that overlaps
+ * the slot's resident cloud, cases 8 and 9.  Every view call takes the multi-launch form (k_cloud_bbox / k_cloud_keys / k_cloud_centroid over the view
+ * source, csrc/tdlo_cloud.hip; radix passes as for the depth path); tdlo_debug_route_count 21 counts the calls. */
+int tdlo_cloud_view_voxel_grid(tdlo_ctx *ctx, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out);
+/* A whole frame from a cloud view: tdlo_cloud_view_voxel_grid into the tracker's slot, tdlo_visibility_prepass with the tracker's nodes, threshold and
+ * geodesic coordinates, tdlo_tracker_tracking_step with X == NULL -- one behind the other, the same bits as the three calls made by hand.  The rules of
+ * tdlo_tracker_frame_from_depth hold: the self-occlusion switch, TDLO_E_EMPTY (no kept point, or no visible node) with the tracker's state untouched,
+ * stats.  A refused view leaves tracker and slot as they were. */
+int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size, double d_vis,
+                                       int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                       int *n_out, int *n_raw_out, tdlo_stats *stats);
+
 /* ---- colour segmentation on the device: BGR + depth frames in one call ------------------------ */
 /* The callback's segmentation (trackdlo/src/trackdlo_node.cpp:158-180 with color_thresholding, :84-119): cv::cvtColor(BGR2HSV), cv::inRange over one
  * range (the launch file's hsv_threshold_*) or four (multi_color_dlo), the AND with the occlusion mask -- so that a caller hands over what the camera
@@ -736,6 +787,7 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * tdlo_tracker_tracking_step_view widened on the host straight into the pinned staging of a small frame.
  * 19 / 20: result images (tdlo_render_result) that k_render wrote where the caller wanted them -- the pinned result buffer, device memory -- / that were
  * copied out of the context's device image (pageable destinations; TDLO_RENDER_INPLACE=0: all of them).
+ * 21: tdlo_cloud_view_voxel_grid calls that reached the kernels (tdlo_tracker_frame_from_cloud_view's among them).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -99,6 +99,7 @@ SYMBOLS = [
     "tdlo_last_colour_shape",
     "tdlo_image_view_check", "tdlo_image_view_extent", "tdlo_image_view_form", "tdlo_image_view_pack", "tdlo_frame_to_cloud_view",
     "tdlo_frame_to_cloud_visibility_view", "tdlo_tracker_frame_view", "tdlo_debug_read_images",
+    "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view",
 ]
 
 _lib = None
@@ -279,6 +280,11 @@ def load_library(path: str | None = None):
                                                             C.POINTER(ci), C.POINTER(ci)]
         lib.tdlo_tracker_frame_view.argtypes = [vp, fvp, cpp, ci, ci, cd, cd, cd, cd, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
         lib.tdlo_debug_read_images.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+    if hasattr(lib, "tdlo_cloud_view_voxel_grid"):
+        i3, f3 = C.POINTER(ci * 3), C.POINTER(C.c_float * 3)
+        lib.tdlo_voxel_grid_dims.argtypes = [f3, f3, cd, i3, i3, C.POINTER(ci)]
+        lib.tdlo_cloud_view_voxel_grid.argtypes = [vp, ci, cvp, ci, vp, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_tracker_frame_from_cloud_view.argtypes = [vp, cvp, ci, vp, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
     if path is None:
         _lib = lib
     return lib
@@ -370,6 +376,37 @@ def cloud_view(obj, ready_stream=None, asynchronous=False) -> CloudView:
     v.N = shape[0]
     v.owner = obj
     return v
+
+
+def _select_ptr(select, N):
+    """(address, owner) of N packed selection bytes: a numpy array (host memory; bool or uint8, made contiguous) or any object with
+    __cuda_array_interface__ (device memory; N contiguous one-byte elements)."""
+    if select is None:
+        return None, None
+    if hasattr(select, "__cuda_array_interface__"):
+        ai = select.__cuda_array_interface__
+        shape = tuple(int(d) for d in ai["shape"])
+        if ai["typestr"][1:] not in ("u1", "b1", "i1") or int(np.prod(shape)) != N:
+            raise TypeError(f"select: {N} one-byte elements, not {ai['typestr']!r} of shape {shape}")
+        st = ai.get("strides")
+        if st is not None and tuple(st) != tuple(int(np.prod(shape[i + 1:])) for i in range(len(shape))):
+            raise TypeError("select: a device array must be contiguous")
+        return int(ai["data"][0]), select
+    a = np.ascontiguousarray(np.asarray(select).reshape(-1) != 0, dtype=np.uint8) if np.asarray(select).dtype != np.uint8 else np.ascontiguousarray(np.asarray(select).reshape(-1))
+    if a.size != N:
+        raise ValueError(f"select: {N} bytes, one per point, not {a.size}")
+    return a.ctypes.data, a
+
+
+def voxel_grid_dims(mn, mx, leaf_size):
+    """pcl::VoxelGrid's grid of a float bounding box (tdlo_voxel_grid_dims; no GPU): (min_b [3], div_b [3], nodown).  TdloError for a leaf that is
+    no positive finite float, a box with mn > mx, or a cloud too far from the origin for the leaf."""
+    a = (C.c_float * 3)(*[float(np.float32(x)) for x in mn]); b = (C.c_float * 3)(*[float(np.float32(x)) for x in mx])
+    lo = (C.c_int * 3)(); dv = (C.c_int * 3)(); nd = C.c_int(0)
+    rc = load_library().tdlo_voxel_grid_dims(C.byref(a), C.byref(b), float(leaf_size), C.byref(lo), C.byref(dv), C.byref(nd))
+    if rc:
+        raise TdloError(rc, "tdlo_voxel_grid_dims: no grid for this box and leaf size")
+    return np.array(lo[:], dtype=np.int32), np.array(dv[:], dtype=np.int32), bool(nd.value)
 
 
 def cloud_view_extent(v: CloudView, N=None):
@@ -576,6 +613,22 @@ class Context:
         v = obj if isinstance(obj, CloudView) else cloud_view(obj, ready_stream, asynchronous)
         self._chk(self.lib.tdlo_set_cloud_view(self.h, slot, C.byref(v), int(v.N)))
         self._async_src = v if v.flags & VIEW_ASYNC else None
+
+    def voxel_grid_view(self, slot, view, leaf_size, select=None, want_cloud=True, ready_stream=None):
+        """pcl::VoxelGrid on a cloud where it lies (tdlo_cloud_view_voxel_grid): the points of `view` (cloud_view(); a CloudView is taken as it is) that
+        are finite and, with `select` (N bytes: a numpy array, or anything with a device pointer), selected are down-sampled into the slot's resident
+        cloud.  Returns (X [n x 3] or None, n, n_raw)."""
+        v = view if isinstance(view, CloudView) else cloud_view(view, ready_stream)
+        N = int(v.N)
+        sp, _keep = _select_ptr(select, N)
+        n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_cloud_view_voxel_grid(self.h, slot, C.byref(v), N, sp, float(leaf_size), None, 0, C.byref(n), C.byref(nraw)))
+        self._async_src = None
+        return (self.get_cloud(slot) if want_cloud else None), n.value, nraw.value
+
+    def voxel_view_calls(self):
+        """tdlo_debug_route_count 21: voxel-grid calls on cloud views that reached the kernels."""
+        return int(self.lib.tdlo_debug_route_count(self.h, 21))
 
     def get_cloud(self, slot):
         """The slot's resident cloud as it stands [n x 3, column-major storage] (tdlo_get_cloud)."""
@@ -1111,6 +1164,23 @@ class trackdlo:
         rc = self.ctx.lib.tdlo_tracker_frame_from_colour(self.h, depth.ctypes.data, colour.ctypes.data, C.byref(params), occluder.ctypes.data if occluder is not None else None,
                                                          rows, cols, fx, fy, cx, cy, leaf_size, d_vis,
                                                          v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
+        self._stats_raw = self._st
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def frame_from_cloud_view(self, view, leaf_size=0.008, d_vis=0.06, select=None, ready_stream=None):
+        """A frame from a cloud where it lies (tdlo_tracker_frame_from_cloud_view): the voxel grid on the view (Context.voxel_grid_view) into the
+        tracker's slot, the visibility pre-pass, tracking_step on the resident cloud.
+        Returns (visible_nodes, visible_nodes_extended, n, n_raw); the nodes: get_tracking_result()."""
+        cv = view if isinstance(view, CloudView) else cloud_view(view, ready_stream)
+        N = int(cv.N)
+        sp, _keep = _select_ptr(select, N)
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        rc = self.ctx.lib.tdlo_tracker_frame_from_cloud_view(self.h, C.byref(cv), N, sp, leaf_size, d_vis,
+                                                             v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
         self._stats_raw = self._st
         if rc:
             self.ctx._chk(rc)

@@ -287,6 +287,7 @@ struct tdlo_ctx {
     // anyway) -- the comparator.  view_route: tdlo_debug_route_count 17 / 18
     bool view_inplace = !(getenv("TDLO_VIEW_INPLACE") && atoi(getenv("TDLO_VIEW_INPLACE")) == 0);
     long long view_route[2] = {0, 0};
+    long long voxel_view_calls = 0;       // tdlo_cloud_view_voxel_grid calls that reached the kernels (tdlo_debug_route_count 21)
     hipEvent_t ev_view = nullptr;          // recorded on a view's ready_stream; the context's stream waits for it
     // early exit, one frame per call: how many iterations go out before the host first looks at the registration's state.  1 unless the caller
     // knows better -- tracking_step passes what the same registration took in the previous frame (consecutive frames of a tracker take about
@@ -2735,6 +2736,62 @@ static int ensure_cloud_ws(tdlo_ctx *c, int P) {      // the device images (dept
     return TDLO_OK;
 }
 
+// pcl/filters/impl/voxel_grid.hpp applyFilter: the leaf-size check and min_b / div_b in float arithmetic from the float bounding box -- the ONE statement
+// of the rule for the multi-launch form, whatever its point source (include/trackdlo_hip.h has the contract).  why: what a refusal says.
+static int voxel_grid_dims(const float mn[3], const float mx[3], double leaf_size, int min_b[3], int div_b[3], int *nodown, const char **why) {
+    const float leaf = (float)leaf_size;
+    if (!(leaf > 0.0f) || !std::isfinite(leaf)) { *why = "voxel grid: the leaf size is not a positive finite float"; return TDLO_E_INVALID; }
+    for (int d = 0; d < 3; ++d)
+        if (!(mn[d] <= mx[d]) || !std::isfinite(mn[d]) || !std::isfinite(mx[d])) { *why = "voxel grid: not a bounding box (min > max, or not finite)"; return TDLO_E_INVALID; }
+    const float inv = 1.0f / leaf;
+    // "leaf size too small": the exact product dd0 dd1 dd2 > 2^31 - 1, formed stepwise -- every factor is at most 2^31 and the product so far at most
+    // 2^31 - 1, so nothing overflows; an extent term that is not a number below 2^31 decides at once
+    long long prod = 1;
+    bool pass = false;
+    for (int d = 0; d < 3 && !pass; ++d) {
+        const float ext = (mx[d] - mn[d]) * inv;
+        if (!(ext < 2147483648.0f)) { pass = true; break; }
+        prod *= (long long)ext + 1;
+        if (prod > 2147483647ll) pass = true;
+    }
+    *nodown = pass ? 1 : 0;
+    for (int d = 0; d < 3; ++d) { min_b[d] = 0; div_b[d] = 1; }
+    if (pass) return TDLO_OK;
+    int mb[3], db[3];
+    for (int d = 0; d < 3; ++d) {
+        const float lo = std::floor(mn[d] * inv), hi = std::floor(mx[d] * inv);
+        const long long dv = (lo >= -2147483648.0f && hi < 2147483648.0f) ? (long long)hi - (long long)lo + 1 : -1;      // (PCL's cast to int is undefined out there)
+        if (dv < 1 || dv > 2147483647ll) { *why = "voxel grid: cloud too far from the origin for this leaf size"; return TDLO_E_INVALID; }
+        mb[d] = (int)lo; db[d] = (int)dv;
+    }
+    for (int d = 0; d < 3; ++d) { min_b[d] = mb[d]; div_b[d] = db[d]; }
+    return TDLO_OK;
+}
+
+int tdlo_voxel_grid_dims(const float mn[3], const float mx[3], double leaf_size, int min_b[3], int div_b[3], int *nodown) {
+    if (!mn || !mx || !min_b || !div_b || !nodown) return TDLO_E_INVALID;
+    const char *why = nullptr;
+    return voxel_grid_dims(mn, mx, leaf_size, min_b, div_b, nodown, &why);
+}
+
+// div_b0 div_b1 as the kernels' 32-bit multiplier of ijk2: with fewer than 2^32 - 1 cells a product of 2^31 or more leaves div_b2 = 1, i.e. ijk2 = 0
+static int voxel_mul2(const int div_b[3]) { return (int)(unsigned)((long long)div_b[0] * div_b[1]); }
+
+// the grid of a non-empty point set from the box the bounding-box pass left (ordered bits): dims, the cell-count refusal, the radix passes
+static int voxel_grid_from_box(tdlo_ctx *c, const unsigned *hb, double leaf_size, int min_b[3], int div_b[3], int *nodown, int *passes) {
+    auto decode = [](unsigned o) { const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; std::memcpy(&f, &u, 4); return f; };
+    float mn[3], mx[3];
+    for (int d = 0; d < 3; ++d) { mn[d] = decode(hb[d]); mx[d] = decode(hb[3 + d]); }
+    const char *why = nullptr;
+    if (int rc = voxel_grid_dims(mn, mx, leaf_size, min_b, div_b, nodown, &why)) return fail(c, rc, why);
+    long long cells = 1;                                         // (each factor below 2^31: saturate stepwise)
+    for (int d = 0; d < 3; ++d) cells = cells >= 0xffffffffll ? cells : cells * div_b[d];
+    if (cells >= 0xffffffffll) return fail(c, TDLO_E_INVALID, "voxel grid has too many cells");
+    *passes = 1;
+    while (*passes < 4 && (1ll << (8 * *passes)) <= cells) ++*passes;      // every valid key must stay below the all-ones sentinel
+    return TDLO_OK;
+}
+
 // colour != nullptr (tdlo_colour_*): no mask is handed in -- the frame's segmentation is formed from the colour image, inside the one-launch kernel where
 // that serves the frame, else by k_colour_mask into the device mask buffer in front of the mask route
 static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *depth, const unsigned char *mask, int rows, int cols,
@@ -2846,24 +2903,11 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
         nraw = (int)hb[6];
         if (n_raw_out) *n_raw_out = nraw;
         if (nraw == 0) return TDLO_OK;
-        auto decode = [](unsigned o) { const unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o; float f; std::memcpy(&f, &u, 4); return f; };
-        float mn[3], mx[3];
-        for (int d = 0; d < 3; ++d) { mn[d] = decode(hb[d]); mx[d] = decode(hb[3 + d]); }
-        // pcl/filters/impl/voxel_grid.hpp applyFilter: leaf-size check, min_b / div_b / divb_mul (float arithmetic)
-        long long dd[3]; int min_b[3], div_b[3];
-        for (int d = 0; d < 3; ++d) {
-            dd[d] = (long long)((mx[d] - mn[d]) * inv) + 1;
-            min_b[d] = (int)std::floor(mn[d] * inv);
-            div_b[d] = (int)std::floor(mx[d] * inv) - min_b[d] + 1;
-        }
-        const int nodown = (dd[0] * dd[1] * dd[2] > 2147483647ll) ? 1 : 0;
-        const long long cells = nodown ? 1 : (long long)div_b[0] * div_b[1] * div_b[2];
-        if (cells >= 0xffffffffll) return fail(c, TDLO_E_INVALID, "voxel grid has too many cells");
-        int passes = 1;
-        while (passes < 4 && (1ll << (8 * passes)) <= cells) ++passes;      // every valid key must stay below the all-ones sentinel
+        int min_b[3], div_b[3], nodown = 0, passes = 1;
+        if ((rc = voxel_grid_from_box(c, hb, leaf_size, min_b, div_b, &nodown, &passes))) return rc;
         rc = ensure_points(c, s, nraw);
         if (rc) return rc;
-        HIPCHK(c, launch_cloud_voxels(d_depth, d_mask, P, cols, cam, min_b, div_b[0], div_b[0] * div_b[1], inv, nodown, passes, nraw,
+        HIPCHK(c, launch_cloud_voxels(d_depth, d_mask, P, cols, cam, min_b, div_b[0], voxel_mul2(div_b), inv, nodown, passes, nraw,
                                       ws, d_total, s.cap_points, s.Xraw, st));
         HIPCHK(c, hipMemcpyAsync(hb, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -2892,6 +2936,95 @@ int tdlo_colour_depth_to_cloud(tdlo_ctx *c, int slot, const unsigned short *dept
                                double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
     const ColourIn ci{colour, params, occluder};
     return depth_to_cloud_impl(c, slot, depth, nullptr, rows, cols, fx, fy, cx, cy, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr, &ci);
+}
+
+// ---- the voxel grid on a cloud view (include/trackdlo_hip.h: V(view, N, select, leaf)) ---------------------------------------------------------
+// Everything that can refuse the call without a look at the points; nothing of the context or the slot is touched.
+static int voxel_view_refusal(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, double leaf_size) {
+    if (const char *why = view_fault(v, N)) return fail(c, TDLO_E_INVALID, why);
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    if (v->flags & TDLO_VIEW_ASYNC) return fail(c, TDLO_E_INVALID, "voxel grid on a view: TDLO_VIEW_ASYNC is not available (the call reads the bounding box back)");
+    if (N > (1 << 26)) return fail(c, TDLO_E_INVALID, "voxel grid on a view: more than 2^26 points");
+    const float leaf = (float)leaf_size;
+    if (!(leaf > 0.0f) || !std::isfinite(leaf)) return fail(c, TDLO_E_INVALID, "voxel grid: the leaf size is not a positive finite float");
+    return TDLO_OK;
+}
+
+int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+    if (!c) return TDLO_E_INVALID;
+    int rc = voxel_view_refusal(c, slot, v, N, leaf_size);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    bool device = false, sel_device = false;
+    if ((rc = view_location(c, v, &device))) return rc;
+    if (select && (rc = pointer_location(c, select, TDLO_MEM_AUTO, "select", &sel_device))) return rc;
+    Slot &s = c->slots[slot];
+    const bool f64 = v->dtype == TDLO_F64;
+    if (device && s.Xraw) {                                      // the centroids are written while the view is still being read
+        long long lo = 0, hi = 0;
+        (void)tdlo_cloud_view_extent(v, N, &lo, &hi);
+        const char *a0 = (const char *)v->data + lo, *a1 = (const char *)v->data + hi;
+        const char *x0 = (const char *)s.Xraw, *x1 = x0 + 3 * (size_t)s.cap_points * sizeof(double);
+        if (a0 < x1 && x0 < a1) return fail(c, TDLO_E_INVALID, "voxel grid on a view: the view aliases the slot's resident cloud");
+    }
+    hipStream_t st = c->stream;
+    if ((rc = ensure_cloud_ws(c, N)) || (rc = ensure_pin(c, 16)) || (rc = flush_pending_cloud(c))) return rc;
+    char *base = (char *)c->cloud_ws;
+    char *ws = base + img_depth_bytes(N) + img_mask_bytes(N);
+    CloudViewSrc src{v->data, f64, v->stride_point, v->stride_comp, select};
+    if (device) {
+        if (v->ready_stream) {
+            if (!c->ev_view) HIPCHK(c, hipEventCreateWithFlags(&c->ev_view, hipEventDisableTiming));
+            HIPCHK(c, hipEventRecord(c->ev_view, (hipStream_t)v->ready_stream));
+            HIPCHK(c, hipStreamWaitEvent(st, c->ev_view, 0));
+        }
+    } else {
+        // a host view: packed column-major in its own precision into the pinned staging block, which the kernels read in place (the bounding-box and key
+        // passes once each, the centroid pass the kept points)
+        const size_t bytes = 3 * (size_t)N * (f64 ? 8 : 4);
+        if ((rc = ensure_cloud_pin(c, (bytes + 7) / 8))) return rc;
+        if (f64) view_gather((double *)c->cloud_pin, (const double *)v->data, v->stride_point, v->stride_comp, N);
+        else view_gather((float *)c->cloud_pin, (const float *)v->data, v->stride_point, v->stride_comp, N);
+        src.data = c->cloud_pin; src.stride_point = 1; src.stride_comp = N;
+    }
+    if (select && !sel_device) {                                 // host selection bytes: to the context's device mask buffer
+        unsigned char *d_mask = (unsigned char *)(base + img_depth_bytes(N));
+        HIPCHK(c, hipMemcpyAsync(d_mask, select, (size_t)N, hipMemcpyHostToDevice, st));
+        src.select = d_mask;
+    }
+    ++c->voxel_view_calls;
+    // ---- the multi-launch form: bounding box + count, a host round trip, compaction, radix sort passes, centroids
+    unsigned *d_bbox = (unsigned *)(ws + cloud_ws_bytes(N) - 256);
+    int *d_total = (int *)(d_bbox + 8);
+    unsigned *hb = (unsigned *)c->pin;
+    hb[0] = hb[1] = hb[2] = ~0u; hb[3] = hb[4] = hb[5] = 0u; hb[6] = 0u; hb[7] = 0u; hb[8] = 0u;
+    HIPCHK(c, hipMemcpyAsync(d_bbox, hb, 9 * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_view_bbox(src, N, d_bbox, ws, st));
+    HIPCHK(c, hipMemcpyAsync(hb, d_bbox, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int nraw = (int)hb[6];
+    if (n_out) *n_out = 0;
+    if (n_raw_out) *n_raw_out = nraw;
+    if (nraw == 0) { s.N0 = 0; s.sorted_valid = false; return TDLO_OK; }      // the slot as tdlo_depth_to_cloud leaves it for an all-zero mask
+    int min_b[3], div_b[3], nodown = 0, passes = 1;
+    if ((rc = voxel_grid_from_box(c, hb, leaf_size, min_b, div_b, &nodown, &passes))) return rc;      // (the slot's cloud is untouched)
+    if ((rc = ensure_points(c, s, nraw))) return rc;
+    s.N0 = 0; s.sorted_valid = false;
+    const float inv = 1.0f / (float)leaf_size;
+    HIPCHK(c, launch_view_voxels(src, N, min_b, div_b[0], voxel_mul2(div_b), inv, nodown, passes, nraw, ws, d_total, s.cap_points, s.Xraw, st));
+    HIPCHK(c, hipMemcpyAsync(hb, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int n = (int)hb[0];
+    if (n < 0 || n > s.cap_points) return fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count");
+    s.N0 = n;
+    if (n_out) *n_out = n;
+    if (X_out && n > 0) {
+        if (n > x_capacity) return fail(c, TDLO_E_INVALID, "X_out too small for the down-sampled cloud");
+        HIPCHK(c, hipMemcpyAsync(X_out, s.Xraw, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    return TDLO_OK;
 }
 
 // ---- caller-side visibility pre-pass ------------------------------------------------------------
@@ -3369,7 +3502,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 20) return -1;
+    if (!c || which < 0 || which > 21) return -1;
+    if (which == 21) return c->voxel_view_calls;
     if (which >= 19) return c->render_route[which - 19];
     if (which >= 17) return c->view_route[which - 17];
     if (which >= 15) return c->colour_route[which - 15];
@@ -3877,6 +4011,43 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
     if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
     return tracker_frame_impl(t, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis,
                               visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
+}
+
+// The same from a cloud view: the voxel grid on the view into the tracker's slot, tdlo_visibility_prepass, tdlo_tracker_tracking_step -- one behind the
+// other, the bits of the three calls made by hand
+int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size, double d_vis,
+                                       int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                       int *n_out, int *n_raw_out, tdlo_stats *stats) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    const int M = t->M;
+    if (t->geodesic_coord.size() != (size_t)M) return fail(c, TDLO_E_INVALID, "the tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)");
+    int rc = voxel_view_refusal(c, t->slot, v, N, leaf_size);
+    if (rc) return rc;
+    std::vector<int> &ve = t->frame_vis_ext, &vv = t->frame_vis;
+    vv.resize(M); ve.resize(M);
+    int nv = 0, ne = 0, n = 0;
+    t->frame_dist.resize(M);
+    if (t->painter_on) t->frame_Y0 = t->Y; else t->frame_Y0.clear();
+    rc = tdlo_cloud_view_voxel_grid(c, t->slot, v, N, select, leaf_size, nullptr, 0, &n, n_raw_out);
+    if (!rc && n > 0)
+        rc = tdlo_visibility_prepass(c, t->slot, t->Y.data(), M, t->visibility_threshold, d_vis, t->geodesic_coord.data(), t->frame_dist.data(), vv.data(), &nv, ve.data(), &ne);
+    if (!rc && t->painter_on && n > 0) {      // the self-occlusion switch, as in tracker_frame_impl
+        std::vector<int> pv, pe;
+        self_occlusion_visible(t->Y.data(), M, t->painter_proj, t->painter_width, t->frame_dist.data(), t->visibility_threshold, pv);
+        fill_visible_gaps(pv, t->geodesic_coord.data(), d_vis, pe);
+        nv = (int)pv.size(); ne = (int)pe.size();
+        std::copy(pv.begin(), pv.end(), vv.begin()); std::copy(pe.begin(), pe.end(), ve.begin());
+    }
+    if (n_out) *n_out = n;
+    if (n_vis) *n_vis = nv;
+    if (n_vis_ext) *n_vis_ext = ne;
+    if (visible_nodes) std::copy(vv.begin(), vv.begin() + nv, visible_nodes);
+    if (visible_nodes_extended) std::copy(ve.begin(), ve.begin() + ne, visible_nodes_extended);
+    if (rc) return rc;
+    if (n == 0) return fail(c, TDLO_E_EMPTY, "no point of the view is kept: no cloud for this frame");
+    if (ne == 0) return fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)");
+    return tdlo_tracker_tracking_step(t, nullptr, 0, vv.data(), nv, ve.data(), ne, nullptr, stats);
 }
 
 // The picture of the tracker's current nodes over the last colour frame (trackdlo_node.cpp:377-452).  vis = the reference's not_self_occluded_nodes (:401):

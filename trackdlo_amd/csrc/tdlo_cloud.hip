@@ -22,6 +22,7 @@
 // would have uploaded, so cpd_lle / tracking_step run on it without a host round trip of the cloud.
 #include "tdlo_internal.h"
 #include "tdlo_devcommon.h"
+#include "tdlo_view_load.h"
 #include <cstdint>
 #include <cstdlib>
 
@@ -49,18 +50,69 @@ __device__ __forceinline__ unsigned ordered_bits(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// bbox[0..2] = min (ordered bits), bbox[3..5] = max, bbox[6] = number of masked pixels
-__global__ __launch_bounds__(kCB) void k_cloud_bbox(const unsigned short *__restrict__ depth, const unsigned char *__restrict__ mask, int P, int cols,
-                                                    const Cam cam, unsigned *__restrict__ bbox, int *__restrict__ blkcnt) {
+// ---- the POINT SOURCE of the multi-launch form.  k_cloud_bbox, k_cloud_keys and k_cloud_centroid ask a source two things:
+//   fetch(p, P, v)   is element p (< P) kept, and if so its three floats.  Called by every thread of the workgroup together (p may be >= P: not kept),
+//                    so that a source may let neighbouring lanes share a load.
+//   point(p, x, y, z) the floats of a kept element, by its number (the centroid pass gathers through val[], the input index).
+// DepthSrc is the depth image + mask (the masked pixels back-projected, trackdlo_node.cpp:212-224); ViewSrc a cloud view + optional selection bytes
+// (tdlo_cloud_view_voxel_grid): kept = select byte != 0 and three finite floats -- pcl::VoxelGrid's !is_dense branch.
+struct DepthSrc {
+    const unsigned short *__restrict__ depth; const unsigned char *__restrict__ mask; int cols; Cam cam;
+    __device__ __forceinline__ bool fetch(int p, int P, float v[3]) const {
+        if (!(p < P && mask[p] != 0)) return false;                 // :212
+        back_project(depth, p, cols, cam, v[0], v[1], v[2]);
+        return true;
+    }
+    __device__ __forceinline__ void point(int p, float &x, float &y, float &z) const { back_project(depth, p, cols, cam, x, y, z); }
+};
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return ((__float_as_uint(x) & 0x7f800000u) != 0x7f800000u) && ((__float_as_uint(y) & 0x7f800000u) != 0x7f800000u) && ((__float_as_uint(z) & 0x7f800000u) != 0x7f800000u);
+}
+
+// T = float: passes through; T = double: (float) rounds to nearest-even, a double beyond float range becomes +-inf (and is not kept).
+// The loads are tdlo_view_load.h's, under its rule: nothing outside the view's extent is read.  kXyz12 / kGeneric load a point only where its selection
+// byte is set; kCols2 (column-major, aligned): the even lane of a lane pair loads points p, p + 1 by one 8-byte load per column and hands p + 1's
+// to its odd neighbour (p's parity is the lane's: tiles and rounds start at even p) -- every point of the view, selected or not, all of them the view's.
+template <typename T, int FORM>
+struct ViewSrc {
+    const T *__restrict__ src; long long sp, sc; const unsigned char *__restrict__ sel;
+    __device__ __forceinline__ bool fetch(int p, int P, float v[3]) const {
+        bool on = p < P && (sel == nullptr || sel[p] != 0);
+        if constexpr (FORM == kCols2) {
+            float2 a = make_float2(0.0f, 0.0f), b = a, c = a;
+            if (p < P && !(p & 1)) {
+                if (p + 1 < P) view_load_pair(src, sc, (long long)p, a, b, c);
+                else view_load_point<float, kGeneric>(src, 1, sc, (long long)p, a.x, b.x, c.x);
+            }
+            const float ox = __shfl_xor(a.y, 1), oy = __shfl_xor(b.y, 1), oz = __shfl_xor(c.y, 1);
+            v[0] = (p & 1) ? ox : a.x; v[1] = (p & 1) ? oy : b.x; v[2] = (p & 1) ? oz : c.x;
+        } else {
+            if (!on) return false;
+            T x, y, z;
+            view_load_point<T, FORM>(src, sp, sc, (long long)p, x, y, z);
+            v[0] = (float)x; v[1] = (float)y; v[2] = (float)z;
+        }
+        return on && finite3(v[0], v[1], v[2]);
+    }
+    __device__ __forceinline__ void point(int p, float &x, float &y, float &z) const {
+        T a, b, c;
+        view_load_point<T, FORM>(src, sp, sc, (long long)p, a, b, c);
+        x = (float)a; y = (float)b; z = (float)c;
+    }
+};
+
+// bbox[0..2] = min (ordered bits), bbox[3..5] = max, bbox[6] = number of kept elements (masked pixels)
+template <class Src>
+__global__ __launch_bounds__(kCB) void k_cloud_bbox(const Src src, int P, unsigned *__restrict__ bbox, int *__restrict__ blkcnt) {
     __shared__ int wc[4];
     unsigned mn[3] = {~0u, ~0u, ~0u}, mx[3] = {0u, 0u, 0u};
     int cnt = 0;
 #pragma unroll
     for (int u = 0; u < kItems; ++u) {
         const int p = blockIdx.x * kTile + u * kCB + threadIdx.x;
-        if (p < P && mask[p] != 0) {                                // :212
-            float v[3];
-            back_project(depth, p, cols, cam, v[0], v[1], v[2]);
+        float v[3];
+        if (src.fetch(p, P, v)) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) { const unsigned o = ordered_bits(v[d]); mn[d] = o < mn[d] ? o : mn[d]; mx[d] = o > mx[d] ? o : mx[d]; }
             ++cnt;
@@ -99,8 +151,8 @@ struct Grid { int min_b[3]; int mul1, mul2; float inv; int nodown; };
 
 // Compaction + keys: the masked pixels of tile b go to positions blkoff[b] .. in pixel order (the order of the reference's
 // row-major scan, trackdlo_node.cpp:197-198); key = cell index, payload = pixel number.
-__global__ __launch_bounds__(kCB) void k_cloud_keys(const unsigned short *__restrict__ depth, const unsigned char *__restrict__ mask, int P, int cols,
-                                                    const Cam cam, const Grid g, const int *__restrict__ blkoff,
+template <class Src>
+__global__ __launch_bounds__(kCB) void k_cloud_keys(const Src src, int P, const Grid g, const int *__restrict__ blkoff,
                                                     unsigned *__restrict__ key, unsigned *__restrict__ val) {
     __shared__ int wc[4];
     __shared__ int run;
@@ -110,7 +162,8 @@ __global__ __launch_bounds__(kCB) void k_cloud_keys(const unsigned short *__rest
 #pragma unroll 1
     for (int u = 0; u < kItems; ++u) {
         const int p = blockIdx.x * kTile + u * kCB + t;
-        const bool on = p < P && mask[p] != 0;
+        float v[3];
+        const bool on = src.fetch(p, P, v);
         const unsigned long long bl = __ballot(on);
         const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         if (lane == 0) wc[w] = __popcll(bl);
@@ -120,8 +173,7 @@ __global__ __launch_bounds__(kCB) void k_cloud_keys(const unsigned short *__rest
             for (int ww = 0; ww < w; ++ww) dst += wc[ww];
             unsigned k = 0;                                         // "leaf size too small": output = input, pixel order
             if (!g.nodown) {
-                float x, y, z;
-                back_project(depth, p, cols, cam, x, y, z);
+                const float x = v[0], y = v[1], z = v[2];
                 const int i0 = (int)(floorf(x * g.inv) - (float)g.min_b[0]);     // voxel_grid.hpp: ijk = floor(p * inv_leaf) - min_b
                 const int i1 = (int)(floorf(y * g.inv) - (float)g.min_b[1]);
                 const int i2 = (int)(floorf(z * g.inv) - (float)g.min_b[2]);
@@ -245,7 +297,8 @@ __global__ __launch_bounds__(kCB) void k_cloud_heads(const unsigned *__restrict_
 }
 
 // one output point per cell; X is the slot's raw cloud: x[0..n) y[0..n) z[0..n) as doubles, n = *total
-__global__ __launch_bounds__(kCB) void k_cloud_centroid(const unsigned short *__restrict__ depth, int P, int cols, const Cam cam, int nodown,
+template <class Src>
+__global__ __launch_bounds__(kCB) void k_cloud_centroid(const Src src, int P, int nodown,
                                                         const unsigned *__restrict__ key, const unsigned *__restrict__ val,
                                                         const int *__restrict__ cnt_scan, const int *__restrict__ total, int cap, double *__restrict__ X) {
     __shared__ int ws[4];
@@ -271,7 +324,7 @@ __global__ __launch_bounds__(kCB) void k_cloud_centroid(const unsigned short *__
             int q = e;
             do {                                                     // CentroidPoint: float sums in input order
                 float x, y, z;
-                back_project(depth, (int)val[q], cols, cam, x, y, z);
+                src.point((int)val[q], x, y, z);
                 sx += x; sy += y; sz += z;
                 ++q;
             } while (!nodown && q < P && key[q] == k);
@@ -1356,25 +1409,24 @@ static int *blkcnt_of(void *ws, int P) {          // per-tile masked-pixel count
     return (int *)((unsigned *)ws + 4 * (size_t)P) + 256 * (size_t)nblk;
 }
 
-hipError_t launch_cloud_bbox(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], unsigned *bbox, void *ws, hipStream_t s) {
-    const Cam c{cam[0], cam[1], cam[2], cam[3]};
+template <class Src>
+static hipError_t cloud_bbox_from(const Src &src, int P, unsigned *bbox, void *ws, hipStream_t s) {
     const int nblk = (P + kTile - 1) / kTile;
-    hipLaunchKernelGGL(k_cloud_bbox, dim3(nblk), dim3(kCB), 0, s, depth, mask, P, cols, c, bbox, blkcnt_of(ws, P));
+    hipLaunchKernelGGL((k_cloud_bbox<Src>), dim3(nblk), dim3(kCB), 0, s, src, P, bbox, blkcnt_of(ws, P));
     return hipGetLastError();
 }
 
-hipError_t launch_cloud_voxels(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4],
-                               const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
-                               void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
-    const Cam c{cam[0], cam[1], cam[2], cam[3]};
+template <class Src>
+static hipError_t cloud_voxels_from(const Src &src, int P, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                                    void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
     Grid g; g.min_b[0] = min_b[0]; g.min_b[1] = min_b[1]; g.min_b[2] = min_b[2]; g.mul1 = mul1; g.mul2 = mul2; g.inv = inv_leaf; g.nodown = nodown;
-    // n = number of masked pixels (known to the host from the bounding-box pass): everything after the compaction
+    // n = number of kept elements (known to the host from the bounding-box pass): everything after the compaction
     // works on n elements, typically a few per cent of the image
     const int nblkP = (P + kTile - 1) / kTile, nblk = (n + kTile - 1) / kTile;
     unsigned *keyA = (unsigned *)ws, *valA = keyA + P, *keyB = valA + P, *valB = keyB + P;
     int *hist = (int *)(valB + P), *cnt = blkcnt_of(ws, P);
     hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, s, cnt, nblkP, (int *)nullptr);
-    hipLaunchKernelGGL(k_cloud_keys, dim3(nblkP), dim3(kCB), 0, s, depth, mask, P, cols, c, g, cnt, keyA, valA);
+    hipLaunchKernelGGL((k_cloud_keys<Src>), dim3(nblkP), dim3(kCB), 0, s, src, P, g, cnt, keyA, valA);
     for (int pass = 0; pass < passes; ++pass) {
         hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(kCB), 0, s, keyA, n, 8 * pass, nblk, hist);
         hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, s, hist, 256 * nblk, (int *)nullptr);
@@ -1384,8 +1436,38 @@ hipError_t launch_cloud_voxels(const unsigned short *depth, const unsigned char 
     }
     hipLaunchKernelGGL(k_cloud_heads, dim3(nblk), dim3(kCB), 0, s, keyA, n, nodown, cnt);
     hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, s, cnt, nblk, total_dev);
-    hipLaunchKernelGGL(k_cloud_centroid, dim3(nblk), dim3(kCB), 0, s, depth, n, cols, c, nodown, keyA, valA, cnt, total_dev, cap, Xraw);
+    hipLaunchKernelGGL((k_cloud_centroid<Src>), dim3(nblk), dim3(kCB), 0, s, src, n, nodown, keyA, valA, cnt, total_dev, cap, Xraw);
     return hipGetLastError();
+}
+
+hipError_t launch_cloud_bbox(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], unsigned *bbox, void *ws, hipStream_t s) {
+    return cloud_bbox_from(DepthSrc{depth, mask, cols, Cam{cam[0], cam[1], cam[2], cam[3]}}, P, bbox, ws, s);
+}
+
+hipError_t launch_cloud_voxels(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4],
+                               const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                               void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
+    return cloud_voxels_from(DepthSrc{depth, mask, cols, Cam{cam[0], cam[1], cam[2], cam[3]}}, P, min_b, mul1, mul2, inv_leaf, nodown, passes, n, ws, total_dev, cap, Xraw, s);
+}
+
+// the same two steps on a cloud view (tdlo_cloud_view_voxel_grid): the source's load form by cloud_import_form, as for k_cloud_import
+template <class F>
+static hipError_t with_view_src(const CloudViewSrc &v, F &&f) {
+    const int form = cloud_import_form(v.data, v.f64, v.stride_point, v.stride_comp);
+    if (v.f64) return f(ViewSrc<double, kGeneric>{(const double *)v.data, v.stride_point, v.stride_comp, v.select});
+    const float *d = (const float *)v.data;
+    if (form == kXyz12) return f(ViewSrc<float, kXyz12>{d, v.stride_point, v.stride_comp, v.select});
+    if (form == kCols2) return f(ViewSrc<float, kCols2>{d, v.stride_point, v.stride_comp, v.select});
+    return f(ViewSrc<float, kGeneric>{d, v.stride_point, v.stride_comp, v.select});
+}
+
+hipError_t launch_view_bbox(const CloudViewSrc &v, int N, unsigned *bbox, void *ws, hipStream_t s) {
+    return with_view_src(v, [&](const auto &src) { return cloud_bbox_from(src, N, bbox, ws, s); });
+}
+
+hipError_t launch_view_voxels(const CloudViewSrc &v, int N, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                              void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
+    return with_view_src(v, [&](const auto &src) { return cloud_voxels_from(src, N, min_b, mul1, mul2, inv_leaf, nodown, passes, n, ws, total_dev, cap, Xraw, s); });
 }
 
 }  // namespace tdlo

@@ -19,14 +19,11 @@
 // Stores: a lane writes its point's three doubles to the three output columns -- consecutive lanes, consecutive addresses (kCols2: pairs).
 // Offsets are 64-bit throughout: n * stride_point may pass 2^31 elements, 3 N doubles pass 2^32 bytes at N = 2^28.
 #include "tdlo_internal.h"
+#include "tdlo_view_load.h"      // the loaders and the forms' definitions: shared with the voxel grid's view source (tdlo_cloud.hip)
 
 namespace tdlo {
 
 namespace {
-
-enum ImportForm { kGeneric = 0, kXyz12 = 1, kCols2 = 2 };
-
-struct __attribute__((packed, aligned(4))) Xyz12 { float x, y, z; };
 
 template <typename T, int FORM>
 __global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ src, long long sp, long long sc, int N, double *__restrict__ X) {
@@ -35,25 +32,22 @@ __global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ s
     if constexpr (FORM == kCols2) {
         const long long n = 2 * i;
         if (n >= N) return;
-        const T *p = src + n;
         if (n + 1 < N) {
-            const float2 a = *reinterpret_cast<const float2 *>(p), b = *reinterpret_cast<const float2 *>(p + sc), c = *reinterpret_cast<const float2 *>(p + 2 * sc);
+            float2 a, b, c;
+            view_load_pair(src, sc, n, a, b, c);
             X[n] = (double)a.x; X[n + 1] = (double)a.y;
             X[ld + n] = (double)b.x; X[ld + n + 1] = (double)b.y;
             X[2 * ld + n] = (double)c.x; X[2 * ld + n + 1] = (double)c.y;
         } else {
-            X[n] = (double)p[0]; X[ld + n] = (double)p[sc]; X[2 * ld + n] = (double)p[2 * sc];
+            T x, y, z;
+            view_load_point<T, kGeneric>(src, 1, sc, n, x, y, z);
+            X[n] = (double)x; X[ld + n] = (double)y; X[2 * ld + n] = (double)z;
         }
     } else {
         if (i >= N) return;
-        const T *p = src + i * sp;
-        double x, y, z;
-        if constexpr (FORM == kXyz12) {
-            const Xyz12 v = *reinterpret_cast<const Xyz12 *>(p); x = (double)v.x; y = (double)v.y; z = (double)v.z;
-        } else {
-            x = (double)p[0]; y = (double)p[sc]; z = (double)p[2 * sc];
-        }
-        X[i] = x; X[ld + i] = y; X[2 * ld + i] = z;
+        T x, y, z;
+        view_load_point<T, FORM>(src, sp, sc, i, x, y, z);
+        X[i] = (double)x; X[ld + i] = (double)y; X[2 * ld + i] = (double)z;
     }
 }
 

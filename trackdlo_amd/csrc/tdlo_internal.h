@@ -290,6 +290,12 @@ hipError_t launch_cloud_bbox(const unsigned short *depth, const unsigned char *m
 hipError_t launch_cloud_voxels(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4],
                                const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
                                void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s);
+// the multi-launch form on a cloud view instead of the images (tdlo_cloud_view_voxel_grid): element k of N is kept when select[k] != 0 (select may be
+// null) and its three floats are finite; ws as above with P = N.  data and select are device-readable (device memory or pinned host memory).
+struct CloudViewSrc { const void *data; bool f64; long long stride_point, stride_comp; const unsigned char *select; };
+hipError_t launch_view_bbox(const CloudViewSrc &v, int N, unsigned *bbox, void *ws, hipStream_t s);
+hipError_t launch_view_voxels(const CloudViewSrc &v, int N, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                              void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s);
 // the same in ONE launch (k_cloud_fused): up to cloud_fused_max_points() masked pixels, images of up to 4095 tiles of 4096 pixels
 size_t cloud_fused_ws_bytes(int P);
 int cloud_fused_max_points();

@@ -408,7 +408,8 @@ int tdlo_image_buffers(tdlo_ctx *ctx, int rows, int cols, unsigned short **depth
  *   visible_nodes          = { m : dist_m <= visibility_threshold }, ascending          (:316, :326, :346)
  *   visible_nodes_extended = visible_nodes with occluded runs shorter than d_vis (in geodesic_coord) filled in (:350-360)
  * The OpenCV painter's-algorithm self-occlusion test (:279-343, cv::line rasterisation) is NOT part of it.
- * Output arrays need room for M entries; any output pointer may be NULL. */
+ * Points with a NaN coordinate take no part; dist_m is at most 100000, the value the reference's search starts from (:261) -- what a cloud
+ * without a point at a finite distance reports.  Output arrays need room for M entries; any output pointer may be NULL. */
 int tdlo_visibility_prepass(tdlo_ctx *ctx, int slot, const double *Y, int M, double visibility_threshold, double d_vis,
                             const double *geodesic_coord, double *node_dist, int *visible_nodes, int *n_vis,
                             int *visible_nodes_extended, int *n_vis_ext);
@@ -788,6 +789,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 19 / 20: result images (tdlo_render_result) that k_render wrote where the caller wanted them -- the pinned result buffer, device memory -- / that were
  * copied out of the context's device image (pageable destinations; TDLO_RENDER_INPLACE=0: all of them).
  * 21: tdlo_cloud_view_voxel_grid calls that reached the kernels (tdlo_tracker_frame_from_cloud_view's among them).
+ * 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel k_node_min_dist_direct / by two uploads, k_node_min_dist and a read-back
+ * (TDLO_DIRECT_UPLOAD=0); a pre-pass that rode in the depth -> cloud launch is counted by 8 alone.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -782,6 +782,10 @@ class Context:
         """Frames whose visibility pre-pass rode in the depth -> cloud launch (tdlo_debug_route_count 8)."""
         return int(self.lib.tdlo_debug_route_count(self.h, 8))
 
+    def prepass_route_counts(self):
+        """[tdlo_visibility_prepass calls served by the one-launch kernel, calls served by the copies + k_node_min_dist] (tdlo_debug_route_count 22 / 23)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (22, 23)]
+
     def estep2_frames(self):
         """Registrations whose E-step was k_estep2 -- two points per lane: clouds and batches that fill the GPU (tdlo_debug_route_count 9)."""
         return int(self.lib.tdlo_debug_route_count(self.h, 9))

@@ -186,6 +186,7 @@ struct tdlo_ctx {
     bool vis_armed = false;
     double *vis_nodes_pin = nullptr;     // 3 x 64 doubles in pinned host memory: the nodes of a pre-pass that rides in the depth -> cloud team kernel
     long long cloud_vis_rides = 0;       // how many frames' pre-passes did (tdlo_debug_route_count 8)
+    long long vis_route[2] = {0, 0};     // tdlo_debug_route_count 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel / by the copies + k_node_min_dist
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -3053,6 +3054,7 @@ int tdlo_visibility_prepass(tdlo_ctx *c, int slot, const double *Y, int M, doubl
         // memory (TDLO_DIRECT_UPLOAD=0: the copies + stream synchronisation below, the comparator)
         if ((rc = ensure_vis_state(c))) return rc;
         if (++c->vis_epoch == 0) ++c->vis_epoch;
+        ++c->vis_route[0];
         HIPCHK(c, launch_node_min_dist_direct(s.Xraw, s.N0, c->pin, M, c->vis_state, c->vis_res, c->vis_epoch, st));
         auto t_chk = std::chrono::steady_clock::now();
         for (unsigned spins = 1;; ++spins) {
@@ -3081,6 +3083,7 @@ int tdlo_visibility_prepass(tdlo_ctx *c, int slot, const double *Y, int M, doubl
         for (int m = 0; m < M; ++m) { const unsigned long long inf = 0x7ff0000000000000ull; std::memcpy(c->pin + 3 * M + m, &inf, 8); }
         HIPCHK(c, hipMemcpyAsync(dY, c->pin, sizeof(double) * 3 * M, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(dbits, c->pin + 3 * M, sizeof(double) * M, hipMemcpyHostToDevice, st));
+        ++c->vis_route[1];
         HIPCHK(c, launch_node_min_dist(s.Xraw, s.N0, dY, M, dbits, st));
         HIPCHK(c, hipMemcpyAsync(c->pin, dbits, sizeof(double) * M, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -3107,7 +3110,7 @@ static void vis_threshold_and_fill(const double *min_d2, int M, double visibilit
                                    int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext) {
     std::vector<int> vis;
     for (int m = 0; m < M; ++m) {
-        const double d = std::sqrt(min_d2[m]);
+        const double d = std::min(std::sqrt(min_d2[m]), 100000.0);       // :261: the reference's search starts from 100000 (a cloud without a finite point)
         if (node_dist) node_dist[m] = d;
         if (d <= visibility_threshold) vis.push_back(m);
     }
@@ -3502,7 +3505,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 21) return -1;
+    if (!c || which < 0 || which > 23) return -1;
+    if (which >= 22) return c->vis_route[which - 22];
     if (which == 21) return c->voxel_view_calls;
     if (which >= 19) return c->render_route[which - 19];
     if (which >= 17) return c->view_route[which - 17];

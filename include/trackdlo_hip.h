@@ -393,7 +393,9 @@ int tdlo_depth_to_cloud(tdlo_ctx *ctx, int slot, const unsigned short *depth, co
  * that cannot complete hands the frame to the multi-launch form -- and form the centroids; TDLO_CLOUD_TEAM=0: the ONE workgroup that finishes last does it
  * alone in LDS, k_cloud_fused) whose last workgroup reports the counts through pinned host memory; more masked pixels, a grid whose cell-index bits + rank bits exceed 32, or PCL's pass-through case take the multi-launch
  * form (bounding box, host round trip, radix sort passes, centroids) -- the same bits either way (TDLO_CLOUD_FUSED=0 forces it; tdlo_debug_route_count
- * 6 / 7 count the calls the one-launch kernel served / passed on).
+ * 6 / 7 count the calls the one-launch kernel served / passed on).  "The same bits" includes the sign of a zero: a cell's sums start from 0.0f on every route (a
+ * cell whose points are all -0.0f in a coordinate gives +0.0), and PCL's pass-through ("leaf size too small") returns the masked pixels' points themselves, widened to
+ * double with their bits (-0.0f stays -0.0), as step 7 of tdlo_cloud_view_voxel_grid's contract says for the view path.
  *
  * tdlo_image_buffers: pinned host buffers of the context for a rows x cols depth image and mask (valid until the next call with a larger image, or
  * tdlo_destroy).  A caller that lets its driver / segmentation write into them -- e.g. cv::Mat(rows, cols, CV_16UC1, depth) and
@@ -465,7 +467,7 @@ int tdlo_tracker_frame_from_depth(tdlo_tracker *t, const unsigned short *depth, 
  *        dd[d] = (long long)((mx[d] - mn[d]) * inv) + 1,  min_b[d] = (int)floorf(mn[d] * inv),  div_b[d] = (int)floorf(mx[d] * inv) - min_b[d] + 1.
  *   6. Pass-through (PCL's "leaf size too small") iff the exact product dd[0] dd[1] dd[2] exceeds 2^31 - 1.  It is evaluated without overflow: an
  *      extent term (mx[d] - mn[d]) * inv that is not finite or is >= 2^31 is pass-through outright, and the product is formed stepwise.
- *   7. Pass-through output: the KEPT points in input order.  DEPARTURE FROM PCL, which copies the non-finite points as well; the prune of
+ *   7. Pass-through output: the KEPT points in input order, each float widened to double as it is (the sign of a zero included).  DEPARTURE FROM PCL, which copies the non-finite points as well; the prune of
  *      trackdlo.cpp:177-195 drops those anyway.
  *   8. No pass-through and a floorf(mn[d] * inv) or floorf(mx[d] * inv) outside int32: TDLO_E_INVALID, "cloud too far from the origin for this leaf
  *      size"; the slot's cloud is untouched.  DEPARTURE FROM PCL, whose cast to int is undefined there.  (So is a div_b[d] beyond int32.)

@@ -187,15 +187,18 @@ def test_one_to_four_radix_passes(B, ctx, torch, div, passes):
 
 
 def test_pass_through(B, ctx, torch):
-    """PCL's "leaf size too small": two clusters 10^4 leaf sizes apart on each axis; the output is the kept points in input order."""
+    """PCL's "leaf size too small": two clusters 10^4 leaf sizes apart on each axis; the output is the kept points in input order, bit for bit
+    (points with -0.0f coordinates among them)."""
     rng = np.random.default_rng(33)
     N = 4099
     P = (rng.random((N, 3)) * 0.1 + np.where(rng.random((N, 1)) < 0.5, 0.0, 1e4 * 0.008)).astype(np.float32)
     P[::17, 1] = np.nan
+    P[5::29, 0] = -0.0; P[7::31] = (-0.0, -0.0, 0.0)             # the kept points come back as they are: PCL copies them, and -0.0f stays -0.0
     sel = (rng.random(N) < 0.8).astype(np.uint8)
     keep = np.isfinite(P).all(axis=1) & (sel != 0)
     want = R.voxel_ref(P, sel, 0.008)
     assert want[0].shape[0] == want[1] == keep.sum() and np.array_equal(_bits(want[0]), _bits(P[keep].astype(np.float64)))
+    assert (_bits(want[0]) == 1 << 63).sum() > 150
     _check(ctx.voxel_grid_view(0, P, 0.008, select=sel), want, "host")
     _check(ctx.voxel_grid_view(1, torch.from_numpy(P).cuda(), 0.008, select=sel), want, "device")
 

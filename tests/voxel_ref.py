@@ -75,16 +75,17 @@ class TooManyCells(ValueError):
     """Step 9: div_b0 div_b1 div_b2 >= 0xffffffff -- TDLO_E_INVALID."""
 
 
-def voxel_ref(P, select, leaf_size):
-    """V: returns (X [n x 3] float64, n_raw).  P: [N x >= 3] float32 or float64."""
-    P32 = to_float(P)
-    Q = P32[kept(P32, select)]                                    # kept points, input order
-    n_raw = Q.shape[0]
-    if n_raw == 0:
-        return np.zeros((0, 3)), 0
+def bits_for(values):
+    """Bits that hold 0 .. values - 1 (at least one)."""
+    return 1 if values <= 2 else (int(values) - 1).bit_length()
+
+
+def group(Q, leaf_size):
+    """Steps 5 .. 10 on the kept points Q [n_raw x 3] float32, n_raw > 0: (min_b, div_b, nodown, key, order, cell).  key [n_raw] int64 is every point's cell
+    index, order the stable ascending sort of key, cell [n_raw] the output index of every SORTED point.  With nodown the last three are None."""
     min_b, div_b, nodown = grid(Q.min(axis=0), Q.max(axis=0), leaf_size)
     if nodown:
-        return Q.astype(np.float64), n_raw                        # step 7: the kept points, input order
+        return min_b, div_b, True, None, None, None
     if int(div_b[0]) * int(div_b[1]) * int(div_b[2]) >= 0xffffffff:
         raise TooManyCells()
     inv = F(1.0) / F(leaf_size)
@@ -92,10 +93,42 @@ def voxel_ref(P, select, leaf_size):
     key = ijk[:, 0] + ijk[:, 1] * div_b[0] + ijk[:, 2] * div_b[0] * div_b[1]
     order = np.argsort(key, kind="stable")
     ks = key[order]
-    head = np.ones(n_raw, dtype=bool); head[1:] = ks[1:] != ks[:-1]
-    cell = np.cumsum(head) - 1                                    # output index of every sorted point
-    n = int(cell[-1]) + 1
+    head = np.ones(len(ks), dtype=bool); head[1:] = ks[1:] != ks[:-1]
+    return min_b, div_b, False, key, order, np.cumsum(head) - 1
+
+
+def centroids(Qs, cell):
+    """Step 10: Qs [n_raw x 3] float32 in sorted order, cell [n_raw] their output index.  Sequential float32 sums from 0 in the given order,
+    float32 division, widened."""
+    n = int(cell.max()) + 1
     sums = np.zeros((n, 3), dtype=F)
-    np.add.at(sums, cell, Q[order])                               # sequential float32 sums in input order
+    np.add.at(sums, cell, Qs)                                     # sequential float32 sums in input order
     cnt = np.bincount(cell, minlength=n).astype(F)
-    return (sums / cnt[:, None]).astype(np.float64), n_raw        # float32 division, correctly rounded; widened
+    return (sums / cnt[:, None]).astype(np.float64)               # float32 division, correctly rounded; widened
+
+
+def structure(P, select, leaf_size):
+    """What the reference's own arithmetic makes of a point set: a dict of n_raw, nodown, min_b, div_b, cells (div_b0 div_b1 div_b2), rb = bits_for(n_raw),
+    kb = bits_for(cells), runs (the occupied cells' point counts in ascending key order; with nodown every point is its own run) and n = len(runs)."""
+    P32 = to_float(P)
+    Q = P32[kept(P32, select)]
+    n_raw = Q.shape[0]
+    if n_raw == 0:
+        return dict(n_raw=0, nodown=False, min_b=None, div_b=None, cells=0, rb=1, kb=1, runs=np.zeros(0, dtype=np.int64), n=0)
+    min_b, div_b, nodown, _, _, cell = group(Q, leaf_size)
+    runs = np.ones(n_raw, dtype=np.int64) if nodown else np.bincount(cell).astype(np.int64)
+    cells = int(div_b[0]) * int(div_b[1]) * int(div_b[2])
+    return dict(n_raw=n_raw, nodown=nodown, min_b=min_b, div_b=div_b, cells=cells, rb=bits_for(n_raw), kb=bits_for(cells), runs=runs, n=len(runs))
+
+
+def voxel_ref(P, select, leaf_size):
+    """V: returns (X [n x 3] float64, n_raw).  P: [N x >= 3] float32 or float64."""
+    P32 = to_float(P)
+    Q = P32[kept(P32, select)]                                    # kept points, input order
+    n_raw = Q.shape[0]
+    if n_raw == 0:
+        return np.zeros((0, 3)), 0
+    _, _, nodown, _, order, cell = group(Q, leaf_size)
+    if nodown:
+        return Q.astype(np.float64), n_raw                        # step 7: the kept points, input order
+    return centroids(Q[order], cell), n_raw

@@ -318,16 +318,20 @@ __global__ __launch_bounds__(kCB) void k_cloud_centroid(const Src src, int P, in
         __syncthreads();
         int out = run + __popcll(bl & below);
         for (int ww = 0; ww < w; ++ww) out += ws[ww];
-        if (head) {
+        if (head && nodown) {                                        // "leaf size too small": PCL copies its input -- the point itself, the sign of a zero included
+            float x, y, z;                                           // ((0.0f + x) / 1.0f would turn -0.0f into +0.0f)
+            src.point((int)val[e], x, y, z);
+            X[out] = (double)x; X[(size_t)n + out] = (double)y; X[2 * (size_t)n + out] = (double)z;
+        } else if (head) {
             const unsigned k = key[e];
             float sx = 0.0f, sy = 0.0f, sz = 0.0f;
             int q = e;
-            do {                                                     // CentroidPoint: float sums in input order
+            do {                                                     // CentroidPoint: float sums in input order, from 0.0f
                 float x, y, z;
                 src.point((int)val[q], x, y, z);
                 sx += x; sy += y; sz += z;
                 ++q;
-            } while (!nodown && q < P && key[q] == k);
+            } while (q < P && key[q] == k);
             const float c = (float)(q - e);
             X[out] = (double)__fdiv_rn(sx, c); X[(size_t)n + out] = (double)__fdiv_rn(sy, c); X[2 * (size_t)n + out] = (double)__fdiv_rn(sz, c);
         }
@@ -875,8 +879,8 @@ __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
         int out = out0;
         for (int p = next_head(H, p_lo, n); p < p_hi;) {
             const int e = next_head(H, p + 1, n);
-            float sx = Vx[p], sy = Vy[p], sz = Vz[p];
-            int j = p + 1;
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f;                   // CentroidPoint starts from 0.0f: a cell of -0.0f only comes out +0.0, as in k_cloud_team and the multi-launch form
+            int j = p;
             for (; j + 4 <= e; j += 4) {
                 float vx[4], vy[4], vz[4];
 #pragma unroll
@@ -901,8 +905,8 @@ __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
             int out = out0;
             for (int p = next_head(H, p_lo, n); p < p_hi;) {
                 const int e = next_head(H, p + 1, n);
-                float sum = V[p];
-                int j = p + 1;
+                float sum = 0.0f;
+                int j = p;
                 for (; j + 8 <= e; j += 8) {
                     float v[8];
 #pragma unroll

@@ -784,7 +784,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * refused under its finer range limits (the repeat runs under the coarse limits of every other mode; only its verdict is reported).
  * 11, 12, 13: always 0 -- these indices belonged to experiments that were measured slower and removed (the spin-ahead loop TDLO_SPIN_AHEAD, a batch's loop
  * in one launch TDLO_BATCH_PERSIST and its repeats; docs/HISTORY.md has the numbers); the indices are not reused.
- * 14: registrations run with one launch per iteration (k_iter_fused).  15 / 16: colour frames (tdlo_colour_depth_to_cloud and the calls built on it) whose
+ * 14: registrations run with one launch per iteration (k_iter_fused, or k_iter_fused_w0 for chains of up to 61 nodes; TDLO_FUSED_W0=0: k_iter_fused for
+ * every chain, the comparator); 24 counts those of them whose launches were k_iter_fused_w0.  15 / 16: colour frames (tdlo_colour_depth_to_cloud and the calls built on it) whose
  * segmentation rode in the depth -> cloud launch / that took the mask kernel k_colour_mask (TDLO_COLOUR_FUSED=0, TDLO_CLOUD_FUSED=0, frames passed on).
  * 17: cloud views imported by k_cloud_import (tdlo_set_cloud_view, and the tracker frames that take it).  18: host views that
  * tdlo_tracker_tracking_step_view widened on the host straight into the pinned staging of a small frame.
@@ -793,6 +794,7 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 21: tdlo_cloud_view_voxel_grid calls that reached the kernels (tdlo_tracker_frame_from_cloud_view's among them).
  * 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel k_node_min_dist_direct / by two uploads, k_node_min_dist and a read-back
  * (TDLO_DIRECT_UPLOAD=0); a pre-pass that rode in the depth -> cloud launch is counted by 8 alone.
+ * 24: registrations of 14 whose per-iteration launches were k_iter_fused_w0 (recorded where the kernel is chosen).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -314,6 +314,9 @@ struct tdlo_ctx {
     // (the two-launch loop, the comparator); =1: also beyond the point count up to which it is the default; unset: by eligibility.
     int fused_iter_mode = getenv("TDLO_FUSED_ITER") ? (atoi(getenv("TDLO_FUSED_ITER")) != 0 ? 1 : 0) : -1;
     long long fused_calls = 0;            // registrations run that way (tdlo_debug_route_count 14)
+    // ... with k_iter_fused_w0 where the chain's step slots all fit wave 0 (up to 61 nodes).  TDLO_FUSED_W0=0: k_iter_fused for every chain (the comparator)
+    bool fused_w0_on = !(getenv("TDLO_FUSED_W0") && atoi(getenv("TDLO_FUSED_W0")) == 0);
+    long long fused_w0_calls = 0;         // registrations of the one-launch loop whose iterations were k_iter_fused_w0, as launch_iter_fused reports them (tdlo_debug_route_count 24)
     long long estep2_frames = 0;          // registrations whose E-step was k_estep2 (tdlo_debug_route_count 9)
     bool timing = false;                  // tdlo_set_timing: record the four events behind tdlo_stats.loop_ms / total_ms (~15 us per call)
     EnqueuePool *pool = nullptr;          // made by the first batch that runs on several streams
@@ -997,6 +1000,7 @@ struct FramesCall {
     bool ahead = false;           // ... or whose whole first iteration up to the M-step has run beside the previous registration, in the twin slot (PairNext::ahead)
     bool use_mbox = false;        // the results come back through the pinned mailbox
     bool fused_mode = false;      // one launch per iteration (tdlo_iter_fused.hip)
+    bool fused_w0_seen = false;   // ... and one of them was k_iter_fused_w0: the registration is counted once (tdlo_debug_route_count 24)
     bool late_async = false;      // the late priors are formed beside the set-up kernel
     bool lle_next = false;        // the M-step that finishes the registration leaves the next frame's LLE regulariser behind
     // streams
@@ -1305,7 +1309,11 @@ hipError_t FramesCall::iterate(int n) {
         if (fused_mode) {
             const int k = enqueued - 1;
             if (k == 0) TDLO_RET(launch_estep_only(fdp, c->fh.data(), 1, 0, s));
-            if (k + 1 < p->max_iter) TDLO_RET(launch_iter_fused(fused_copy(k), fused_copy(k + 1), k, s));
+            if (k + 1 < p->max_iter) {
+                bool ran_w0 = false;
+                TDLO_RET(launch_iter_fused(fused_copy(k), fused_copy(k + 1), k, c->fused_w0_on, s, &ran_w0));
+                if (ran_w0 && !fused_w0_seen) { fused_w0_seen = true; ++c->fused_w0_calls; }      // (what the launcher launched, not what the host expects of it)
+            }
             else TDLO_RET(launch_mstep_chain_close(fused_copy(k), k, s));
             continue;
         }
@@ -3505,7 +3513,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 23) return -1;
+    if (!c || which < 0 || which > 24) return -1;
+    if (which == 24) return c->fused_w0_calls;
     if (which >= 22) return c->vis_route[which - 22];
     if (which == 21) return c->voxel_view_calls;
     if (which >= 19) return c->render_route[which - 19];

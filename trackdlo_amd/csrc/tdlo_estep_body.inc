@@ -1,8 +1,10 @@
 // tdlo_estep_body.inc -- the E-step's statements (trackdlo.cpp:278-389), included into the body of a kernel (see tdlo_estep_body.h).  The including scope provides:
 //   template parameters / constants   T, NCH, VIS, EB, SINGLE  and  constexpr bool FUSED
 //   const FrameDev &f;  char smem[] (the dynamic LDS);  const EstepHand<T> *hand  (FUSED: what the M-step half hands over; otherwise nullptr)
+//   (an EstepHand<T, true>: the kernel has zeroed the wave's accumulators and stands behind a barrier with nothing written to LDS since -- FRONT below)
 // The statements `return` from the including kernel, so they come last in it.  What the E-step computes and what bounds it: the head of tdlo_device.hip.
     constexpr int NWE = EB / 64;
+    constexpr bool FRONT = std::remove_cv_t<std::remove_pointer_t<decltype(hand)>>::kFront;
 #ifdef TDLO_ESTEP_STAMPS
     if (threadIdx.x == 0) atomicMin(&f.dbg[32], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 #endif
@@ -35,13 +37,14 @@
     constexpr int RT = (NCH == 1 && SINGLE) ? kChunk : TR;
     constexpr int RS = (RT / TR) * TR;                     // stored rows: whole chunks only
     const int rows = M < RT ? M : RT;
-    // LDS carve (every offset a multiple of 16 bytes)
+    // LDS carve (every offset a multiple of 16 bytes).  FRONT: taken from estep_carve (tdlo_estep_body.h), the definition the kernel zeroed the accumulators by --
+    // the same expressions; as one shared definition for every instantiation they came out of the compiler as different code for k_estep and k_iter_fused
     V4<T> *nodesL = (V4<T> *)smem;                                    // M
-    V4<T> *pts = nodesL + M;                                          // NWE x kPtsStride: point i of a wave at i + (i >> 4), see the column sums
-    T *lvL = (T *)(pts + NWE * kPtsStride);                           // M rounded up to 4
-    T *pbase = lvL + ((M + 3) & ~3);
+    V4<T> *pts = FRONT ? estep_carve<T, NWE>(smem, M, rows).pts : nodesL + M;                                          // NWE x kPtsStride: point i of a wave at i + (i >> 4), see the column sums
+    T *lvL = FRONT ? estep_carve<T, NWE>(smem, M, rows).lvL : (T *)(pts + NWE * kPtsStride);                           // M rounded up to 4
+    T *pbase = FRONT ? estep_carve<T, NWE>(smem, M, rows).pbase : lvL + ((M + 3) & ~3);
     T *pb = pbase + (size_t)wave * rows * kPStride;
-    double *scratch = (double *)(pbase + (((size_t)NWE * rows * kPStride + 7) & ~(size_t)3));   // 16-byte aligned, stays an LDS pointer
+    double *scratch = FRONT ? estep_carve<T, NWE>(smem, M, rows).scratch : (double *)(pbase + (((size_t)NWE * rows * kPStride + 7) & ~(size_t)3));   // 16-byte aligned, stays an LDS pointer
 
     const auto nodes = TDLO_AS_CONST(V4<T>, f.nodes);
     const auto xs = TDLO_AS_GLOBAL(T, f.Xs);
@@ -69,7 +72,7 @@
     int N; T k2, cn;
     if constexpr (FUSED) { N = hand->st->N; k2 = (T)hand->st->k2; cn = (T)hand->st->c_norm; }
     else if constexpr (EARLY) { N = stg->N; k2 = (T)stg->k2; cn = (T)stg->c_norm; }
-    const int shb_e = FUSED ? hand->st->sh_boost : (EARLY ? stg->sh_boost : 0);
+    const int shb_e = FRONT ? 0 : (FUSED ? hand->st->sh_boost : (EARLY ? stg->sh_boost : 0));     // (FRONT: fp32 mode, where the M-step half sets 0 by construction)
     const double rwin_e = FUSED ? hand->st->rwin32 : (EARLY ? stg->rwin32 : 0.0);
     const int par_e = FUSED ? hand->acc_buf : (it0 & 1);
     const auto qg = TDLO_AS_GLOBAL(V4<T>, f.nodes);
@@ -136,7 +139,7 @@
             lvL[m] = (T)(-f.k_vis * d * 1.4426950408889634 - ::log2(tot));
         }
     }
-    __syncthreads();
+    if constexpr (!FRONT) __syncthreads();
     ESTAMP(1);
     EPHASE(0);
 
@@ -157,9 +160,9 @@
     // [M][4] 64-bit accumulators in LDS (ds_add_u64 without return: integer sums, so neither the order nor who adds matters).  Up to 64 nodes: one set
     // per wave (no contention, 1.6 KB each at M = 50).  Longer chains: ONE set per workgroup -- per-lane register accumulators (4 x NCH 64-bit values
     // and a cross-lane gather per chunk) had held the fp64 kernel at 227 VGPRs, and a set per wave would cost the second workgroup of a CU its LDS
-    long long *accL = (long long *)(scratch + 16) + (NCH == 1 ? (size_t)wave * M * 4 : (size_t)0);
+    long long *accL = FRONT ? estep_accL(scratch, M, wave, true) : (long long *)(scratch + 16) + (NCH == 1 ? (size_t)wave * M * 4 : (size_t)0);
     if (NCH == 1) {
-        for (int i = lane; i < M * 4; i += 64) accL[i] = 0;
+        if constexpr (!FRONT) for (int i = lane; i < M * 4; i += 64) accL[i] = 0;
     } else {
         for (int i = tid; i < M * 4; i += EB) accL[i] = 0;
         __syncthreads();

@@ -263,7 +263,7 @@ bool mstep_mcu_enabled();          // TDLO_MSTEP_BIG=1wg: false (the dense M-ste
 hipError_t launch_mstep_chain(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);
 // tdlo_iter_fused.hip: M-step (iteration) and E-step (iteration + 1) of one frame in ONE launch; fr / fw: the descriptor with the copies of state, Y, Yout and
 // nodes the launch reads / its workgroup 0 writes.  launch_mstep_chain_close: the k_mstep_chain that closes that loop, in place on f's copies
-hipError_t launch_iter_fused(const FrameDev &fr, const FrameDev &fw, int iteration, hipStream_t s);
+hipError_t launch_iter_fused(const FrameDev &fr, const FrameDev &fw, int iteration, bool w0, hipStream_t s, bool *ran_w0);
 size_t iter_fused_lds_bytes(int M);
 hipError_t launch_mstep_chain_close(const FrameDev &f, int iteration, hipStream_t s);
 void mstep_parity_hint(int iteration);          // (tdlo_mstep_chain.hip) the iteration this thread's next chain M-step launches belong to; -1: unknown

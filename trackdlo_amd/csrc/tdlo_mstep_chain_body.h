@@ -106,7 +106,14 @@ struct ChainCarve {
 //      -- the OTHER copies (st_w, Y_w, Yout_w, nodes_w), the accumulator buffer after next (acc_clr) and the mailbox: nothing a launch reads is written in it.
 //   2  the k_mstep_chain that closes that loop (one workgroup, in place on the copies its descriptor names): sums from buffer par_hint (0 .. 2), nothing cleared
 //      (the set-up kernel clears the buffers a registration starts with, the loop the third one).
-//   Both honour the loop's sticky error word (kFusedErrWord).
+//   3  policy 1 for chains whose step slots all fit wave 0 (ChainCarve(M).nSl <= 64, i.e. up to 61 nodes; k_iter_fused_w0).  The same statements in the same
+//      order; what changes is who holds which value when.  Records, gains, the backward walk and the tail are all wave 0's: lane = slot reads its node's four
+//      sums from S[] ONCE, for the record, and keeps them for the tail; wave 0 goes from the records into the covariance pass behind a wave-local sync instead
+//      of a barrier (the other waves follow the progress counter, zeroed in front of the barrier behind the sums); lane 0 of wave 0 forms the new state straight
+//      from wave_sum4's rows, with no cross-wave sum and no barrier in front of it; the half's closing barrier is the kernel's (mstep_chain_w0_close).
+//      (Requesting the own node's sums -- all rows -- from lane = slot, with no S[] and no barrier in front of the records, was built and measured: 32 more
+//      requests and their row sums are ~190 more instructions on wave 0's serial path, 490 clocks MORE in front of the recursion.  profiles/fused_w0_ab.txt.)
+//   All honour the loop's sticky error word (kFusedErrWord).
 struct ChainFused {
     int iteration;                  // the M-step's iteration, counted by the host from the registration's first
     int err_r;                      // which of the loop's two error words this launch READS (its E-step half writes the other one: kFusedErrWord); FUSE 2 sets this alone
@@ -117,11 +124,14 @@ struct ChainFused {
     IterState *stL;                 // LDS: the state this M-step leaves (every workgroup)
     void *nodesL;                   // LDS: the E-step half's node copy (every workgroup)
     bool go;                        // out: the registration goes on -- the E-step half runs
+    int pub;                        // FUSE 3, out: lane 0 has something to tell the host -- the kernel closes the half itself (mstep_chain_w0_close)
 };
 template <typename T, bool SINGLE, bool XCH, bool TRK = false, int ROWS = kAccRows, bool HINT = false, int FUSE = 0>
 __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums, char *smem, int par_hint = 0, ChainFused *fz = nullptr) {
     static_assert(FUSE == 0 || (SINGLE && HINT && !XCH && !TRK), "the one-launch iteration: one frame, told its accumulator buffer, no exchange / tracker extras");
     constexpr int MB = kCB;
+    constexpr bool F1 = FUSE == 1 || FUSE == 3;        // the M-step half of a one-launch iteration
+    constexpr bool W0 = FUSE == 3;                      // ... whose step slots are all lanes of wave 0
     // One wave walks a chain of dependent instructions.  In a batch the other stream groups' E-steps fill the same SIMDs with waves that always have
     // something to issue: at the default priority this wave takes its turn among them (C3: 10.0 us per M-step against 7.4 us with the GPU to itself)
     IterState *st = f.st;
@@ -139,7 +149,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     // s_memtime behind a full lgkmcnt wait plus a store behind an exec branch, eight of them per launch.  The M-step half of k_iter_fused (FUSE 1) stamps in
     // workgroup 0 alone and into words 56 .. 63, which the k_mstep_chain that closes its loop does not overwrite (scripts/gpu_fused_stamps.py)
 #ifdef TDLO_CHAIN_STAMPS
-#define CSTAMP(i) do { if (t == 0 && (FUSE != 1 || blockIdx.x == 0)) f.dbg[(FUSE == 1 ? 56 : 0) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define CSTAMP(i) do { if (t == 0 && (!F1 || blockIdx.x == 0)) f.dbg[(F1 ? 56 : 0) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CSTAMP(i) do { } while (0)
 #endif
@@ -159,7 +169,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     int pri = f.has_priors;
     // (FUSE 1: the word as a value the compiler has to KEEP -- a kernel argument it would rather fetch again where the slot's requests branch on it, with a
     //  wait of its own in the middle of them: the kernel is short of scalar registers)
-    if constexpr (FUSE == 1) asm volatile("" : "+s"(pri));
+    if constexpr (F1) asm volatile("" : "+s"(pri));
     const double ctr0 = f.ctr[0], ctr1 = f.ctr[1], ctr2 = f.ctr[2];
     const auto ndg = TDLO_AS_GLOBAL(V4<T>, f.nodes);
     const auto Yg = TDLO_AS_GLOBAL(double, f.Y);
@@ -206,13 +216,13 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     // for the iteration counter (M <= 512: at most 9 elements per thread).  Requested before the slot: its index arithmetic
     // runs while these are in flight.
     const bool spec_wait = TRK && f.spec_flag != nullptr;      // launched ahead of its priors (FrameDev::spec_flag): the wait sits behind the requests below
-    const int itn = FUSE == 1 ? fz->iteration : stg->it;
+    const int itn = F1 ? fz->iteration : stg->it;
     // FUSE 1: the state this launch reads, whole, for the LDS copy (the tail below replaces what an M-step sets, the rest is carried).  Requested here into a
     // register -- index clamped, no branch -- and stored to LDS behind the last request below: a store inside `if (t < 13)` at this place is a full wait for
     // wave 0's loads so far, one memory round trip before the sums have even been asked for.
     constexpr int kStWords = (int)((sizeof(IterState) + 7) / 8);
     unsigned long long st_word = 0;
-    if constexpr (FUSE == 1) st_word = TDLO_AS_GLOBAL(unsigned long long, st)[t < kStWords ? t : kStWords - 1];
+    if constexpr (F1) st_word = TDLO_AS_GLOBAL(unsigned long long, st)[t < kStWords ? t : kStWords - 1];
     double sq[9];
     SlotQ q0;
     // FUSE 1: the sums' rows as the integers they are, converted behind the last request (fused_sum below).  acc_read_par converts on the spot, and its shift
@@ -223,13 +233,13 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     const int fi0 = t < nS ? t : nS - 1, fi1 = t + MB < nS ? t + MB : nS - 1;
     // (the first element without a branch -- index clamped, the accumulators exist in every mode: inside a conditional block the compiler sums the
     //  16 rows on the spot, i.e. waits for them BEFORE it requests the slot below: two memory round trips in a row instead of one)
-    if constexpr (FUSE == 1) {
+    if constexpr (F1) {
         const auto rows = TDLO_AS_GLOBAL(long long, f.acc) + (size_t)par_hint * kAccRows * acc_stride(M);
         const int stride = acc_stride(M);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) fr0[r] = rows[(size_t)r * stride + fi0];
         // (chains of 64 nodes: a second element per thread, its rows in the same batch -- a uniform branch around requests alone, nothing is summed in it)
-        if (nS > MB) {
+        if (!W0 && nS > MB) {      // (W0: at most 61 nodes, 245 elements)
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) fr1[r] = rows[(size_t)r * stride + fi1];
         } else {
@@ -241,7 +251,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     sq[0] = HINT ? acc_read_par<ROWS>(f, t < nS ? t : nS - 1, par_hint) : acc_read_both<ROWS>(f, t < nS ? t : nS - 1, itn);
 #pragma unroll
     for (int u = 1; u < 9; ++u) sq[u] = 0.0;
-    if constexpr (FUSE == 1) {         // (at most 64 nodes, launch_iter_fused: every slot is a thread's first one)
+    if constexpr (F1) {         // (at most 64 nodes, launch_iter_fused: every slot is a thread's first one)
         q0 = load_slot(t, true);
     } else if (nS <= MB) {             // up to 63 nodes: the slot's loads follow the sums' in the same basic block (nothing is waited for in between)
         q0 = load_slot(t, !spec_wait);
@@ -332,7 +342,8 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     }
     dbl2 ch0 = dbl2{0.0, 0.0}, ch1 = dbl2{0.0, 0.0};
     double Nc_f = 0.0;
-    if constexpr (FUSE == 1) {
+    double w_p1 = 0.0, w_r[3] = {0.0, 0.0, 0.0};      // W0: the slot's own sums (P1, R of its node), read from S[] once for the record and held for the tail
+    if constexpr (F1) {
         ch0 = chg[0]; ch1 = chg[1]; Nc_f = stg->Nc;      // (the last three requests: below they are made where they are first used)
         // Everything this half reads before its first barrier has been requested: ONE memory round trip.  The marker is a compiler barrier for memory
         // operations (no request moves behind it, the LDS stores below do not move in front of it) and the line tests/test_fused_prologue_isa.py looks for:
@@ -349,20 +360,20 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
             return ::ldexp((double)a, -sh);
         };
         sq[0] = fused_sum(fr0, fi0);
-        if (t + MB < nS) sq[1] = fused_sum(fr1, fi1);
+        if (!W0 && t + MB < nS) sq[1] = fused_sum(fr1, fi1);
         if (t < kStWords) ((unsigned long long *)fz->stL)[t] = st_word;
     }
-    const double pinf0 = FUSE == 1 ? ch0.x : chg[0].x, pinf1 = FUSE == 1 ? ch0.y : chg[0].y;  // sf2, s^2 sf2
+    const double pinf0 = F1 ? ch0.x : chg[0].x, pinf1 = F1 ? ch0.y : chg[0].y;  // sf2, s^2 sf2
     const double c2 = f.lambda * sigma2, rc2 = fast_rcp(c2);
-    const double cp0 = c2 * (FUSE == 1 ? ch1.x : chg[1].x), cp1 = c2 * (FUSE == 1 ? ch1.y : chg[1].y);  // Pinf^-1 in the units of the filter (P = covariance / c); reciprocals from k_setup
+    const double cp0 = c2 * (F1 ? ch1.x : chg[1].x), cp1 = c2 * (F1 ? ch1.y : chg[1].y);  // Pinf^-1 in the units of the filter (P = covariance / c); reciprocals from k_setup
     // what the kernel's last thread needs of set_iter_consts, formed while the loads are in flight: c of :300 / c' of :378 is
     // (2 pi sigma2)^(3/2) times this factor
-    const double Nc = FUSE == 1 ? Nc_f : stg->Nc;
+    const double Nc = F1 ? Nc_f : stg->Nc;
     const double kc = f.mu / (1.0 - f.mu) * (f.vis_branch ? 1.0 / Nc : (double)M / Nc);
 #ifdef TDLO_TIMELINE      // wall-clock (100 MHz) begin / end of iterations 20..27, scripts/gpu_timeline.py
     if (t == 0 && itn >= 20 && itn < 28) f.dbg[4 * (itn - 20) + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
-    if constexpr (FUSE == 1) {
+    if constexpr (F1) {
         if (done) {
             // a finished registration: the launch is a no-op but for workgroup 0, which passes state and result on to the copies the next launch reads
             // (the error word's verdict written into them) and reports a registration that ended on an error, as the two-launch M-step does
@@ -398,8 +409,11 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
 #pragma unroll
         for (int u = 0; u < 9; ++u) { const int i = t + u * MB; if (i < nS) sq[u] = acc_read_both<ROWS>(f, i, itn); }
     }
+    // W0: no barrier stands behind the records, and the means wave and wave 2 poll the progress counter: zeroed here, in front of the barrier behind the sums
+    // (every other thread stores to the dump area: no branch)
+    if constexpr (W0) *(int *)(t == 0 ? red + 28 : dump) = 0;
     if (from_sums != 1) {
-        constexpr int nU = FUSE == 1 ? 2 : 9;       // (FUSE 1: at most 64 nodes, two elements per thread)
+        constexpr int nU = F1 ? 2 : 9;       // (FUSE 1: at most 64 nodes, two elements per thread)
 #pragma unroll
         for (int u = 0; u < nU; ++u) { const int i = t + u * MB; if (i < nS) S[i] = sq[u]; }
     } else {
@@ -459,20 +473,24 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     for (int sl = t, r = 0; sl < nSl; sl += MB, ++r) {
         dbl2 *o = (dbl2 *)(slots + (size_t)kSlot * sl);
         const SlotQ q = r == 0 ? q0 : load_slot(sl, true);
-        const double p1 = q.obs ? S[q.node] : 0.0;
+        if constexpr (W0) { w_p1 = S[q.node]; w_r[0] = S[M + q.node]; w_r[1] = S[2 * M + q.node]; w_r[2] = S[3 * M + q.node]; }
+        const double p1 = q.obs ? (W0 ? w_p1 : S[q.node]) : 0.0;
         const bool idl = q.li == 0;     // identity link: a direction's first step, dummy steps
         o[0] = dbl2{idl ? 1.0 : q.l[0].x, idl ? 0.0 : q.l[0].y}; o[1] = dbl2{idl ? 0.0 : q.l[1].x, idl ? 1.0 : q.l[1].y};
         o[2] = dbl2{idl ? 0.0 : q.l[2].x * rc2, idl ? 0.0 : q.l[2].y * rc2};
         o[3] = dbl2{idl ? 0.0 : q.l[3].x * rc2, q.obs ? p1 + q.aj : 0.0};
 #pragma unroll
-        for (int d = 0; d < 3; ++d) o[4 + d] = dbl2{q.obs ? S[(1 + d) * M + q.node] + (p1 * (q.y[d] - q.y0[d]) + q.ay[d]) : 0.0, 0.0};
+        for (int d = 0; d < 3; ++d) o[4 + d] = dbl2{q.obs ? (W0 ? w_r[d] : S[(1 + d) * M + q.node]) + (p1 * (q.y[d] - q.y0[d]) + q.ay[d]) : 0.0, 0.0};
     }
-    if (t == 0) { *(int *)(red + 28) = 0; red[26] = 0.0; red[27] = 0.0; }      // progress counter of the covariance pass; the spike columns' right-hand side
-    if (t >= MB - kAhead) {     // the slots the loops read ahead into: identity, nothing observed
-        dbl2 *o = (dbl2 *)(slots + (size_t)kSlot * (nSl + (t - (MB - kAhead))));
+    // W0: all of this is wave 0's (every slot is one of its lanes; its last kAhead lanes write the look-ahead slots as well), and wave 0 goes on into the
+    // covariance pass without a barrier: a wave's LDS operations execute in order, and the other waves read a record only behind the progress counter
+    constexpr int LW = W0 ? 64 : MB;        // the threads the look-ahead slots are taken from the end of
+    if (t == 0) { if constexpr (!W0) *(int *)(red + 28) = 0; red[26] = 0.0; red[27] = 0.0; }      // progress counter of the covariance pass; the spike columns' right-hand side
+    if (t >= LW - kAhead && (!W0 || t < LW)) {     // the slots the loops read ahead into: identity, nothing observed
+        dbl2 *o = (dbl2 *)(slots + (size_t)kSlot * (nSl + (t - (LW - kAhead))));
         o[0] = dbl2{1.0, 0.0}; o[1] = dbl2{0.0, 1.0}; o[2] = dbl2{0.0, 0.0}; o[3] = dbl2{0.0, 0.0}; o[4] = dbl2{0.0, 0.0}; o[5] = dbl2{0.0, 0.0}; o[6] = dbl2{0.0, 0.0};
     }
-    __syncthreads();
+    if constexpr (W0) wave_lds_sync(); else __syncthreads();
     CSTAMP(3);
 
     // ---- 3. forward pass, two waves in a pipeline.  A lone wave issues one instruction per ~8 cycles whatever the instruction is
@@ -595,7 +613,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (wr) *(dbl2 *)(red + 32 + 2 * (dir * 5 + hl)) = dbl2{acc0, acc1};
     } else {
         // waves 2 and 3 have nothing to do in this phase: they clear the other parity's accumulator rows for the next E-step
-        if constexpr (FUSE == 1) {
+        if constexpr (F1) {
             if (blockIdx.x == 0) { const int n = kAccRows * acc_stride(M); for (int i = t - 128; i < n; i += MB - 128) fz->acc_clr[i] = 0; }
         } else if constexpr (FUSE == 2) {
         } else
@@ -715,7 +733,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     //         (direction, coordinate); a step is ~10 instructions with two dependent FMAs, the records are requested two steps ahead) --
     //         cheaper than the strided form below while a direction has fewer than ~25 steps (its two parallel phases and two barriers cost
     //         ~2000 clocks before the first anchor moves).
-    const bool direct = nQ <= kDirectMax;
+    const bool direct = W0 || nQ <= kDirectMax;      // (W0: at most 16 steps per direction)
     if (direct) {
         if (wv == 0) {
             const int dir = lane >> 4, hl = lane & 15;
@@ -849,7 +867,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (!q.obs) continue;
         const int m = q.node;
         const double *o = slots + (size_t)kSlot * sl;
-        const double p1 = S[m];
+        const double p1 = W0 ? w_p1 : S[m];
         // smoothed state: junction and anchors hold it; every other slot is one composite step below its anchor
         const int ks = sl - slot_dir(sl) * nQ, r4 = (nQ - 1 - ks) & 3;
         double Vd[3];
@@ -867,11 +885,11 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         for (int d = 0; d < 3; ++d) {
             Td[d] = q.y0[d] + Vd[d];
             const double del = Td[d] - q.y[d], ex = q.yp[d] - Td[d];
-            dr = fma(del, S[(1 + d) * M + m], dr); pd2 = fma(del, del, pd2); cr2 = fma(ex, ex, cr2);
+            dr = fma(del, W0 ? w_r[d] : S[(1 + d) * M + m], dr); pd2 = fma(del, del, pd2); cr2 = fma(ex, ex, cr2);
         }
         s_np += p1; s_dr += dr; s_pd += p1 * pd2; s_cr += ::sqrt(cr2);
         V4<T> w; w.x = (T)Td[0]; w.y = (T)Td[1]; w.z = (T)Td[2]; w.w = (T)q.w;      // .w = chain coordinate, unchanged
-        if constexpr (FUSE == 1) {
+        if constexpr (F1) {
             ((V4<T> *)fz->nodesL)[m] = w;
             if (blockIdx.x == 0) {
                 ((V4<T> *)fz->nodes_w)[m] = w;
@@ -888,19 +906,28 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
     }
     // the wave's four sums at once (wave_sum4: 21 instructions, no LDS round trips); rows 0..3 of the wave end up with sums 0, 2, 1, 3
     // (waves without slots contribute zeros)
-    {
+    // W0: all four partial sums are wave 0's and the other waves' are zeros -- the wave's totals replace the lanes' partial sums (lane 0 takes the three other
+    // rows' by v_readlane: rows 1, 2, 3 hold sums 2, 1, 3) and lane 0 forms the state at once, without the barrier and the round trip through red[0..15].
+    if constexpr (W0) {
+        const double tot = wave_sum4(s_np, s_dr, s_pd, s_cr);
+        auto lane_f64 = [&](double v, int src) __attribute__((always_inline)) {
+            return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+        };
+        s_np = tot; s_pd = lane_f64(tot, 16); s_dr = lane_f64(tot, 32); s_cr = lane_f64(tot, 48);
+    } else {
         const double tot = wave_sum4(s_np, s_dr, s_pd, s_cr);
         const int row = lane >> 4, which = ((row & 1) << 1) | (row >> 1);
         double *dst = (lane & 15) == 0 ? red + 4 * wv + which : dump;
         *dst = tot;
     }
-    __syncthreads();
+    if constexpr (!W0) __syncthreads();
     CSTAMP(7);
-    IterState *const sto = FUSE == 1 ? fz->stL : st;      // (FUSE 1: every workgroup forms the new state, in LDS; workgroup 0 stores it below)
+    IterState *const sto = F1 ? fz->stL : st;      // (FUSE 1: every workgroup forms the new state, in LDS; workgroup 0 stores it below)
     int pub = 0;        // lane 0: this M-step has something to tell the host (results mailbox, FrameDev::host_prog)
     if (t == 0) {
-        const double t_np = ((red[0] + red[4]) + red[8]) + red[12], t_dr = ((red[1] + red[5]) + red[9]) + red[13];
-        const double t_pd = ((red[2] + red[6]) + red[10]) + red[14], t_cr = ((red[3] + red[7]) + red[11]) + red[15];
+        // (W0: the other waves' zeros are still added -- x + 0 turns a total of -0 into +0, as the sum over the waves does)
+        const double t_np = W0 ? ((s_np + 0.0) + 0.0) + 0.0 : ((red[0] + red[4]) + red[8]) + red[12], t_dr = W0 ? ((s_dr + 0.0) + 0.0) + 0.0 : ((red[1] + red[5]) + red[9]) + red[13];
+        const double t_pd = W0 ? ((s_pd + 0.0) + 0.0) + 0.0 : ((red[2] + red[6]) + red[10]) + red[14], t_cr = W0 ? ((s_cr + 0.0) + 0.0) + 0.0 : ((red[3] + red[7]) + red[11]) + red[15];
         const double new_sigma2 = (S[4 * M] - 2.0 * t_dr + t_pd) * fast_rcp(t_np * 3.0);
         const double crit = t_cr / (double)M;
         const int it = itn + 1;
@@ -912,7 +939,7 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
             sto->k2 = -1.4426950408889634 * 0.5 * fast_rcp(new_sigma2);
             sto->c_norm = tp * rtp * kc;
             sto->rwin32 = f.win_e32 * 1.3862943611198906 * new_sigma2; sto->rwin64 = f.win_e64 * 1.3862943611198906 * new_sigma2;      // the E-step's node window (set_iter_consts)
-            sto->sh_boost = FUSE == 1 ? 0 : acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts; FUSE 1 is fp32 mode: 0, see the prologue)
+            sto->sh_boost = F1 ? 0 : acc_boost(f, new_sigma2);      // the next E-step's resolution (set_iter_consts; FUSE 1 is fp32 mode: 0, see the prologue)
         } else { sto->status = TDLO_E_NUMERIC; sto->done = 1; sto->converged = 0; pub = 1; }
         if (crit < f.tol) { sto->done = 1; pub = 1; }                                   // :424-428
         else if (it >= f.max_iter) { sto->converged = 0; sto->done = 1; pub = 1; }      // :433-437
@@ -921,7 +948,8 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (itn >= 20 && itn < 28) f.dbg[4 * (itn - 20) + 3] = __builtin_amdgcn_s_memrealtime();
 #endif
     }
-    if constexpr (FUSE == 1) {
+    if constexpr (W0) { fz->pub = pub; return; }      // (closed by the kernel, behind what it moves in front of the barrier: mstep_chain_w0_close)
+    if constexpr (F1) {
         __syncthreads();          // the state in LDS is whole: the E-step half reads it, workgroup 0 sends it to memory -- and the registration may have ended here
         fz->go = fz->stL->done == 0;
         if (blockIdx.x == 0 && t < 64) {
@@ -940,6 +968,19 @@ __device__ __forceinline__ void mstep_chain_run(const FrameDev &f, int from_sums
         if (red[30] != 0.0 && M <= 256) lle_band_device<MB>(f.Yout, M, f.lle_next, slots, t);
     }
 #undef CSTAMP
+}
+
+// FUSE 3: the end of the M-step half -- the ONE barrier behind the recursion, which publishes the nodes and the state in LDS to the E-step half; workgroup 0
+// sends the state to memory and tells the host.  The statements of FUSE 1's end, called by the kernel where the other waves have nothing left to do in front of it.
+__device__ __forceinline__ void mstep_chain_w0_close(const FrameDev &f, ChainFused *fz) {
+    const int t = threadIdx.x, lane = t & 63;
+    __syncthreads();
+    fz->go = fz->stL->done == 0;
+    if (blockIdx.x == 0 && t < 64) {
+        constexpr int nst = (int)((sizeof(IterState) + 7) / 8);
+        if (lane < nst) ((unsigned long long *)fz->st_w)[lane] = ((const unsigned long long *)fz->stL)[lane];
+        if (__builtin_amdgcn_readfirstlane(fz->pub)) host_publish_at(f, fz->Yout_w, fz->st_w, lane, true);
+    }
 }
 
 }  // namespace tdlo

@@ -27,6 +27,9 @@
 extern "C" {
 #endif
 
+/* Counts INCOMPATIBLE changes of this interface: a changed signature, structure layout or meaning.  Entry points that are only added (the cloud and
+ * image views, tdlo_sort_pts, tdlo_tracker_initialize_from_cloud, ...) leave it alone: a caller built against an earlier header of the same version
+ * runs unchanged, and a caller that needs a newer entry point finds out by looking the symbol up. */
 #define TDLO_ABI_VERSION 3
 
 enum {
@@ -371,6 +374,41 @@ int tdlo_tracker_tracking_step_view(tdlo_tracker *t, const tdlo_cloud_view *v, i
  * accumulators in LDS; more is TDLO_E_INVALID).  pts == NULL: use the
  * cloud resident in `slot`.  A centroid that attracts no probability mass comes back NaN, as in the reference. */
 int tdlo_reg(tdlo_ctx *ctx, int slot, const double *pts, int N, double *Y, double *sigma2, int M, double mu, int max_iter);
+
+/* ---- chain order of unordered nodes, and a tracker started from its first cloud -------------------- */
+/* MatrixXd sort_pts(MatrixXd Y_0), trackdlo/src/utils.cpp:95-170 (declared utils.h:26; prototype utils/tracking_test.py:174-229): reg returns its
+ * centroids in no particular order; this puts them in chain order.  Node 0 is first; a minimum spanning tree is grown from it, each of the M - 1 rounds
+ * taking the pair (a in the tree, b outside) of smallest non-zero squared distance -- fp64, (dx dx + dy dy) + dz dz with every product and sum
+ * rounded, ties to the smallest a, then the smallest b -- and b enters the list by the reference's reverse / insertion bookkeeping (:134-157).
+ * One workgroup, thread = node (k_sort_pts, csrc/tdlo_init.hip); 2 <= M <= 1024, anything else TDLO_E_INVALID.
+ *   Y         M x 3 column-major, host memory.
+ *   Y_sorted  M x 3 column-major: row i is row perm[i] of Y (may be Y itself; optional).
+ *   perm      M ints (optional); the permutation is the reference's EXACTLY: the decisions compare identical fp64 values.
+ *   coord     M doubles (optional): coord[0] = 0, coord[i] = coord[i - 1] + |Y_sorted[i] - Y_sorted[i - 1]|, added serially in chain order as
+ *             trackdlo_node.cpp:135-141 and the prototype (:531-537) do -- what tdlo_tracker_initialize_geodesic_coord wants.
+ * TDLO_E_NUMERIC, outputs untouched, the reason in tdlo_last_error: a non-finite coordinate; two nodes whose three coordinates are equal (as
+ * values: -0.0 equals 0.0 -- the reference finds rows of its list by value and would confuse them); a round that finds no edge (every
+ * remaining squared distance underflowed to zero or is infinite; the reference would repeat node 0). */
+int tdlo_sort_pts(tdlo_ctx *ctx, const double *Y, int M, double *Y_sorted, int *perm, double *coord);
+/* The same rule, outputs and verdicts in plain C++ on the host, no device and no context: the twin the CPU tests hold to the rule, and the comparator
+ * route of tdlo_tracker_initialize_from_cloud. */
+int tdlo_sort_pts_host(const double *Y, int M, double *Y_sorted, int *perm, double *coord);
+/* The prototype's first-frame initialiser (utils/tracking_test.py:523-541): register(cloud, M, mu), sort_pts, cumulative segment lengths -- with M the
+ * tracker's node count -- and the result installed as tdlo_tracker_initialize_nodes and tdlo_tracker_initialize_geodesic_coord would (trackdlo_node.cpp:131-146),
+ * except that the coordinates REPLACE the tracker's instead of being appended.  This is NOT initialize.py's initialiser (skeleton, spline fit; skimage,
+ * OpenCV, scipy), which stays out of scope: it is the one the E-step provides.
+ *   X, N        the cloud (N x 3 column-major); X == NULL: the cloud resident in the tracker's slot, as tdlo_tracker_tracking_step does -- what
+ *               tdlo_depth_to_cloud, tdlo_colour_depth_to_cloud, tdlo_frame_to_cloud_view, tdlo_cloud_view_voxel_grid or tdlo_set_cloud_view left
+ *               there: such a cloud becomes a running tracker without visiting the host.
+ *   mu, max_iter  reg's (the prototype calls 0.05, 100).
+ *   sigma2_out  reg's sigma2 (optional).  The tracker's own sigma2 is left alone: the node sets nodes and coordinates only.
+ * reg's whole loop and k_sort_pts, which reads reg's centroids where reg left them, are enqueued together: one wait, one read-back.
+ * TDLO_INIT_SORT=host (read when the context is made): the centroids are read back and ordered by tdlo_sort_pts_host -- the comparator, the same bits
+ * (tdlo_debug_route_count 25 / 26).  Errors leave the tracker EXACTLY as it was: TDLO_E_INVALID for fewer than 4 or more than 890 nodes (reg's limit),
+ * N <= 0, an empty slot, bad mu / max_iter; TDLO_E_NUMERIC when a centroid came back NaN (it attracted no mass) or tdlo_sort_pts would refuse the centroids. */
+int tdlo_tracker_initialize_from_cloud(tdlo_tracker *t, const double *X, int N, double mu, int max_iter, double *sigma2_out);
+/* tdlo_set_cloud_view (enqueued without a host wait; a device source must stay valid until this call returns), then the X == NULL route above. */
+int tdlo_tracker_initialize_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, double mu, int max_iter, double *sigma2_out);
 
 /* ---- depth image -> cloud -> voxel-grid down-sample ------------------------ */
 /* The step right upstream of tracking_step in the ROS node (trackdlo/src/trackdlo_node.cpp:195-241): every pixel
@@ -795,6 +833,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel k_node_min_dist_direct / by two uploads, k_node_min_dist and a read-back
  * (TDLO_DIRECT_UPLOAD=0); a pre-pass that rode in the depth -> cloud launch is counted by 8 alone.
  * 24: registrations of 14 whose per-iteration launches were k_iter_fused_w0 (recorded where the kernel is chosen).
+ * 25 / 26: node sets ordered by k_sort_pts (tdlo_sort_pts, tdlo_tracker_initialize_from_cloud*) / tdlo_tracker_initialize_from_cloud* calls whose
+ * centroids were ordered by the host twin (TDLO_INIT_SORT=host).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

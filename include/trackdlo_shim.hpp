@@ -33,6 +33,16 @@ struct ctx_deleter { void operator()(tdlo_ctx *c) const { tdlo_destroy(c); } };
 // A float cloud where it lies: xyz = address of x of point 0, the point stride in floats (3: packed; sizeof(pcl::PointXYZRGB) / 4 = 8 for the node's cloud)
 inline tdlo_cloud_view view_of(const float *xyz, long long stride_point_elems) { return tdlo_cloud_view{xyz, TDLO_F32, TDLO_MEM_AUTO, stride_point_elems, 1, nullptr, 0}; }
 
+// MatrixXd sort_pts(MatrixXd Y_0), trackdlo/include/utils.h:26 (utils.cpp:95-170): unordered nodes (reg's centroids) in chain order.  Like the
+// reference's it needs no context: the rule runs on the host (tdlo_sort_pts_host, the twin of the device kernel behind initialize_from_cloud).
+template <class Matrix>
+Matrix sort_pts_t(Matrix Y_0) {
+    Matrix Y_0_sorted((int)Y_0.rows(), 3);
+    if (tdlo_sort_pts_host(Y_0.data(), (int)Y_0.rows(), Y_0_sorted.data(), nullptr, nullptr) != TDLO_OK)
+        throw std::runtime_error("sort_pts: fewer than 2 or more than 1024 nodes, a non-finite coordinate, two equal nodes, or no edge to follow");
+    return Y_0_sorted;
+}
+
 template <class Matrix>
 class trackdlo_t {
 public:
@@ -143,6 +153,24 @@ public:
                                               visible_nodes_extended.data(), (int)visible_nodes_extended.size(), nullptr, nullptr));
     }
 
+    // not in the reference's class, but its prototype's first frame (utils/tracking_test.py:523-541): reg with this tracker's node count on the cloud,
+    // sort_pts behind it on the device, and the nodes and chain coordinates installed -- in place of waiting for initialize.py's /trackdlo/init_nodes.
+    // Returns reg's sigma2 (the tracker's own is left alone, as trackdlo_node.cpp:131-146 leaves it).
+    double initialize_from_cloud(const Matrix &X, double mu = 0.05, int max_iter = 100) {
+        need();
+        double sigma2 = 0.0;
+        check(tdlo_tracker_initialize_from_cloud(trk_, X.data(), (int)X.rows(), mu, max_iter, &sigma2));
+        coord_.clear();                                                    // (the tracker holds the coordinates it has just formed)
+        return sigma2;
+    }
+    double initialize_from_cloud(const tdlo_cloud_view &X_view, int N, double mu = 0.05, int max_iter = 100) {
+        need();
+        double sigma2 = 0.0;
+        check(tdlo_tracker_initialize_from_cloud_view(trk_, &X_view, N, mu, max_iter, &sigma2));
+        coord_.clear();
+        return sigma2;
+    }
+
     // not in the reference: choose fp32 E-step (default) or fp64 everywhere
     void set_precision(int precision) { precision_ = precision; if (trk_) tdlo_tracker_set_precision(trk_, precision); }
 
@@ -186,4 +214,5 @@ private:
 #if defined(EIGEN_WORLD_VERSION) || defined(TDLO_WITH_EIGEN)
 #include <Eigen/Dense>
 using trackdlo = tdlo::trackdlo_t<Eigen::MatrixXd>;      // the reference's class name and matrix type
+inline Eigen::MatrixXd sort_pts(Eigen::MatrixXd Y_0) { return tdlo::sort_pts_t<Eigen::MatrixXd>(Y_0); }      // utils.h:26
 #endif

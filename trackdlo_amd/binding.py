@@ -100,6 +100,7 @@ SYMBOLS = [
     "tdlo_image_view_check", "tdlo_image_view_extent", "tdlo_image_view_form", "tdlo_image_view_pack", "tdlo_frame_to_cloud_view",
     "tdlo_frame_to_cloud_visibility_view", "tdlo_tracker_frame_view", "tdlo_debug_read_images",
     "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view",
+    "tdlo_sort_pts", "tdlo_sort_pts_host", "tdlo_tracker_initialize_from_cloud", "tdlo_tracker_initialize_from_cloud_view",
 ]
 
 _lib = None
@@ -285,6 +286,11 @@ def load_library(path: str | None = None):
         lib.tdlo_voxel_grid_dims.argtypes = [f3, f3, cd, i3, i3, C.POINTER(ci)]
         lib.tdlo_cloud_view_voxel_grid.argtypes = [vp, ci, cvp, ci, vp, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
         lib.tdlo_tracker_frame_from_cloud_view.argtypes = [vp, cvp, ci, vp, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+    if hasattr(lib, "tdlo_sort_pts"):
+        lib.tdlo_sort_pts.argtypes = [vp, vp, ci, vp, vp, vp]
+        lib.tdlo_sort_pts_host.argtypes = [vp, ci, vp, vp, vp]
+        lib.tdlo_tracker_initialize_from_cloud.argtypes = [vp, vp, ci, cd, ci, C.POINTER(cd)]
+        lib.tdlo_tracker_initialize_from_cloud_view.argtypes = [vp, cvp, ci, cd, ci, C.POINTER(cd)]
     if path is None:
         _lib = lib
     return lib
@@ -811,6 +817,18 @@ class Context:
         self._chk(self.lib.tdlo_reg(self.h, slot, _ptr(X), X.shape[0] if X is not None else 0, _ptr(Y), C.byref(s2), int(M), float(mu), int(max_iter)))
         return Y, s2.value
 
+    def sort_pts(self, Y):
+        """sort_pts (utils.cpp:95-170) on the device (k_sort_pts): Y [M x 3] unordered.  Returns (Y_sorted [M x 3], perm [M], coord [M]): Y_sorted[i] is
+        Y[perm[i]], coord the cumulative segment lengths along the chain."""
+        Y = _f64(Y); M = Y.shape[0]
+        Ys = np.zeros((M, 3), order="F"); perm = np.zeros(M, dtype=np.int32); coord = np.zeros(M)
+        self._chk(self.lib.tdlo_sort_pts(self.h, _ptr(Y), M, _ptr(Ys), _ptr(perm), _ptr(coord)))
+        return Ys, perm, coord
+
+    def init_route_counts(self):
+        """[node sets ordered by k_sort_pts, initialize_from_cloud calls ordered by the host twin (TDLO_INIT_SORT=host)] (tdlo_debug_route_count 25 / 26)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (25, 26)]
+
     def image_buffers(self, rows, cols):
         """The context's pinned image buffers as numpy views (depth uint16 [rows x cols], mask uint8 [rows x cols]): images written into them and
         handed to depth_to_cloud as they are get read by the kernel where they lie (tdlo_image_buffers)."""
@@ -1109,6 +1127,22 @@ class trackdlo:
         c = np.ascontiguousarray(geodesic_coord, dtype=np.float64)
         self.ctx._chk(self.ctx.lib.tdlo_tracker_initialize_geodesic_coord(self.h, _ptr(c), len(c)))
 
+    def initialize_from_cloud(self, X, mu=0.05, max_iter=100):
+        """The prototype's first-frame initialiser (tracking_test.py:523-541) in one call: reg with this tracker's node count on the cloud X (None: the
+        cloud resident in the tracker's slot), sort_pts on the device behind it, and nodes and chain coordinates installed.  Returns reg's sigma2."""
+        Xf = _f64(X) if X is not None else None
+        s2 = C.c_double(0.0)
+        self.ctx._chk(self.ctx.lib.tdlo_tracker_initialize_from_cloud(self.h, _ptr(Xf), Xf.shape[0] if Xf is not None else 0, float(mu), int(max_iter), C.byref(s2)))
+        return s2.value
+
+    def initialize_from_cloud_view(self, obj, mu=0.05, max_iter=100, *, ready_stream=None):
+        """initialize_from_cloud on a cloud where it lies (tdlo_tracker_initialize_from_cloud_view): obj as for cloud_view() -- a torch device tensor,
+        a numpy array -- or a CloudView."""
+        cv = obj if isinstance(obj, CloudView) else cloud_view(obj, ready_stream)
+        s2 = C.c_double(0.0)
+        self.ctx._chk(self.ctx.lib.tdlo_tracker_initialize_from_cloud_view(self.h, C.byref(cv), int(cv.N), float(mu), int(max_iter), C.byref(s2)))
+        return s2.value
+
     def get_tracking_result(self):
         out = np.zeros((self.M, 3), order="F")
         self.ctx.lib.tdlo_tracker_get_tracking_result(self.h, _ptr(out))
@@ -1285,6 +1319,17 @@ def traverse_euclidean(geodesic_coord, guide_nodes, visible_nodes, alignment, al
     if n < 0:
         raise TdloError(n, "traverse_euclidean: out-of-bounds in the reference")
     return out[:n].copy()
+
+
+def sort_pts_host(Y):
+    """tdlo_sort_pts_host: sort_pts (utils.cpp:95-170) by the host twin of k_sort_pts, no device.  Returns (Y_sorted [M x 3], perm [M], coord [M])."""
+    lib = load_library()
+    Y = _f64(Y); M = Y.shape[0]
+    Ys = np.zeros((M, 3), order="F"); perm = np.zeros(M, dtype=np.int32); coord = np.zeros(M)
+    rc = lib.tdlo_sort_pts_host(_ptr(Y), M, _ptr(Ys), _ptr(perm), _ptr(coord))
+    if rc:
+        raise TdloError(rc, "tdlo_sort_pts_host")
+    return Ys, perm, coord
 
 
 def get_piecewise_error(Y_track, Y_true):

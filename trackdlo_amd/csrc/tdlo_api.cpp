@@ -186,6 +186,10 @@ struct tdlo_ctx {
     bool vis_armed = false;
     double *vis_nodes_pin = nullptr;     // 3 x 64 doubles in pinned host memory: the nodes of a pre-pass that rides in the depth -> cloud team kernel
     long long cloud_vis_rides = 0;       // how many frames' pre-passes did (tdlo_debug_route_count 8)
+    // tdlo_tracker_initialize_from_cloud: TDLO_INIT_SORT=host orders reg's centroids with the host twin (sort_pts_host) after reading them back -- the comparator,
+    // the same bits; init_route: tdlo_debug_route_count 25 / 26 -- calls ordered by k_sort_pts (tdlo_sort_pts among them) / by the host twin
+    bool init_sort_host = getenv("TDLO_INIT_SORT") && getenv("TDLO_INIT_SORT")[0] == 'h';
+    long long init_route[2] = {0, 0};
     long long vis_route[2] = {0, 0};     // tdlo_debug_route_count 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel / by the copies + k_node_min_dist
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
@@ -2416,6 +2420,38 @@ int tdlo_split_run(tdlo_ctx *c, void *nccl_comm, double *Y, int M, double *sigma
 }
 
 // ---- plain GMM-EM `reg` ---------------------------------------------------------------------------
+// The `reg` workspace holds at least `doubles` (a context's one device scratch for reg and sort_pts: grown, never shrunk)
+static int ensure_reg_ws(tdlo_ctx *c, size_t doubles) {
+    if (doubles <= c->reg_ws_cap) return TDLO_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->reg_ws) hipFree(c->reg_ws);
+    c->reg_ws = nullptr; c->reg_ws_cap = 0;
+    HIPCHK(c, hipMalloc((void **)&c->reg_ws, doubles * sizeof(double)));
+    c->reg_ws_cap = doubles;
+    return TDLO_OK;
+}
+
+// reg's whole loop on the cloud resident in the slot, enqueued: state and centroids are left at reg_ws (state 8 | Y 3 M); `extra` more doubles of
+// the workspace behind reg's own are handed out at *extra_dev (8-byte aligned), and the pinned staging holds 8 + 3 M + extra doubles
+static int reg_enqueue(tdlo_ctx *c, Slot &s, int M, double mu, int max_iter, size_t extra, double **extra_dev) {
+    const int n = s.N0;
+    const int nblk = std::max(1, std::min((n + 255) / 256, 256));
+    const size_t need = reg_ws_doubles(M, nblk);
+    int rc;
+    if ((rc = ensure_reg_ws(c, need + extra)) || (rc = ensure_pin(c, 8 + 3 * (size_t)M + extra))) return rc;
+    double *h = c->pin;
+    for (int i = 0; i < 8; ++i) h[i] = 0.0;
+    for (int i = 0; i < M; ++i) {                                         // utils.cpp:24-29
+        h[8 + i] = 0.0;
+        h[8 + M + i] = 0.1 / static_cast<double>(M) * static_cast<double>(i);
+        h[8 + 2 * M + i] = 0.0;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->reg_ws, h, sizeof(double) * (8 + 3 * (size_t)M), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_reg(s.Xraw, n, M, mu, max_iter, nblk, c->reg_ws, c->stream));
+    if (extra_dev) *extra_dev = c->reg_ws + need;
+    return TDLO_OK;
+}
+
 int tdlo_reg(tdlo_ctx *c, int slot, const double *pts, int N, double *Y, double *sigma2, int M, double mu, int max_iter) {
     if (!c) return TDLO_E_INVALID;
     if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
@@ -2426,32 +2462,45 @@ int tdlo_reg(tdlo_ctx *c, int slot, const double *pts, int N, double *Y, double 
     if (pts) rc = tdlo_set_cloud(c, slot, pts, N);
     else if (c->slots[slot].N0 <= 0) rc = fail(c, TDLO_E_INVALID, "pts is NULL and no cloud is resident in the slot");
     if (rc) return rc;
-    Slot &s = c->slots[slot];
-    const int n = s.N0;
-    const int nblk = std::max(1, std::min((n + 255) / 256, 256));
-    const size_t need = reg_ws_doubles(M, nblk);
-    if (need > c->reg_ws_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->reg_ws) hipFree(c->reg_ws);
-        c->reg_ws = nullptr; c->reg_ws_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->reg_ws, need * sizeof(double)));
-        c->reg_ws_cap = need;
-    }
-    rc = ensure_pin(c, 8 + 3 * (size_t)M);
-    if (rc) return rc;
+    if ((rc = reg_enqueue(c, c->slots[slot], M, mu, max_iter, 0, nullptr))) return rc;
     double *h = c->pin;
-    for (int i = 0; i < 8; ++i) h[i] = 0.0;
-    for (int i = 0; i < M; ++i) {                                         // utils.cpp:24-29
-        h[8 + i] = 0.0;
-        h[8 + M + i] = 0.1 / static_cast<double>(M) * static_cast<double>(i);
-        h[8 + 2 * M + i] = 0.0;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->reg_ws, h, sizeof(double) * (8 + 3 * (size_t)M), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_reg(s.Xraw, n, M, mu, max_iter, nblk, c->reg_ws, c->stream));
     HIPCHK(c, hipMemcpyAsync(h, c->reg_ws, sizeof(double) * (8 + 3 * (size_t)M), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *sigma2 = h[0];
     std::memcpy(Y, h + 8, sizeof(double) * 3 * (size_t)M);
+    return TDLO_OK;
+}
+
+// ---- `sort_pts`: chain order and chain coordinate (csrc/tdlo_init.hip) --------------------------------------------------------------
+static const char *sort_pts_reason(int status) {
+    return status == 1 ? "sort_pts: a node has a non-finite coordinate"
+         : status == 2 ? "sort_pts: two nodes coincide (the reference finds rows of its list by value, utils.cpp:146-150)"
+                       : "sort_pts: a round found no edge (every remaining squared distance is zero or infinite)";
+}
+
+int tdlo_sort_pts_host(const double *Y, int M, double *Y_sorted, int *perm, double *coord) {
+    if (!Y || M < 2 || M > kMaxNodes) return TDLO_E_INVALID;
+    return sort_pts_host(Y, M, Y_sorted, perm, coord) ? TDLO_E_NUMERIC : TDLO_OK;
+}
+
+int tdlo_sort_pts(tdlo_ctx *c, const double *Y, int M, double *Y_sorted, int *perm, double *coord) {
+    if (!c) return TDLO_E_INVALID;
+    if (!Y || M < 2 || M > kMaxNodes) return fail(c, TDLO_E_INVALID, "sort_pts: 2 .. " + std::to_string(kMaxNodes) + " nodes");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nin = 3 * (size_t)M + 1, nout = sort_pts_out_doubles(M);      // (+ 1: the output block stays 16-byte aligned)
+    int rc;
+    if ((rc = ensure_reg_ws(c, nin + nout)) || (rc = ensure_pin(c, nin + nout))) return rc;
+    double *h = c->pin, *ho = h + nin;
+    std::memcpy(h, Y, sizeof(double) * 3 * (size_t)M);
+    HIPCHK(c, hipMemcpyAsync(c->reg_ws, h, sizeof(double) * 3 * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_sort_pts(c->reg_ws, nullptr, M, c->reg_ws + nin, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ho, c->reg_ws + nin, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ++c->init_route[0];
+    if (ho[1] != 0.0) return fail(c, TDLO_E_NUMERIC, sort_pts_reason((int)ho[1]));
+    if (Y_sorted) std::memcpy(Y_sorted, ho + 2, sizeof(double) * 3 * (size_t)M);
+    if (coord) std::memcpy(coord, ho + 2 + 3 * (size_t)M, sizeof(double) * M);
+    if (perm) std::memcpy(perm, ho + 2 + 4 * (size_t)M, sizeof(int) * M);
     return TDLO_OK;
 }
 
@@ -3513,7 +3562,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 24) return -1;
+    if (!c || which < 0 || which > 26) return -1;
+    if (which >= 25) return c->init_route[which - 25];
     if (which == 24) return c->fused_w0_calls;
     if (which >= 22) return c->vis_route[which - 22];
     if (which == 21) return c->voxel_view_calls;
@@ -3732,6 +3782,74 @@ int tdlo_tracker_initialize_geodesic_coord(tdlo_tracker *t, const double *coord,
     if (!t || !coord || n < 0) return TDLO_E_INVALID;
     t->geodesic_coord.insert(t->geodesic_coord.end(), coord, coord + n);
     return TDLO_OK;
+}
+
+// tdlo_tracker_initialize_from_cloud / _view: reg with M = the tracker's node count on the cloud X, the view v, or -- both null -- what is resident in the
+// slot, k_sort_pts behind it on reg's device nodes, one wait, one read-back; the tracker is touched only when everything has succeeded
+static int initialize_from_cloud_enqueued(tdlo_tracker *t, const double *X, const tdlo_cloud_view *v, int N, double mu, int max_iter, double *sigma2_out) {
+    tdlo_ctx *c = t->ctx;
+    const int M = t->M;
+    Slot &s = c->slots[t->slot];
+    int rc = TDLO_OK;
+    if (X) rc = set_cloud_impl(c, t->slot, X, N, false);                 // (X stays the caller's until this call returns: the wait below, or the caller's on an error)
+    else if (v) {
+        bool device = false;
+        if ((rc = view_location(c, v, &device))) return rc;
+        rc = import_view(c, t->slot, v, N, device, false);
+    }
+    else if ((rc = flush_pending_cloud(c))) return rc;
+    else if (s.N0 <= 0) rc = fail(c, TDLO_E_INVALID, "X is NULL and no cloud is resident in the tracker's slot");
+    if (rc) return rc;
+    const size_t nout = sort_pts_out_doubles(M);
+    double *out_dev = nullptr;
+    if ((rc = reg_enqueue(c, s, M, mu, max_iter, nout, &out_dev))) return rc;
+    double *h = c->pin, *ho = h + 8 + 3 * (size_t)M;
+    double sigma2;
+    std::vector<double> Ys(3 * (size_t)M), coord(M);
+    if (!c->init_sort_host) {
+        HIPCHK(c, launch_sort_pts(c->reg_ws + 8, c->reg_ws, M, out_dev, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ho, out_dev, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ++c->init_route[0];
+        if (ho[1] != 0.0) return fail(c, TDLO_E_NUMERIC, sort_pts_reason((int)ho[1]));
+        sigma2 = ho[0];
+        std::memcpy(Ys.data(), ho + 2, sizeof(double) * 3 * (size_t)M);
+        std::memcpy(coord.data(), ho + 2 + 3 * (size_t)M, sizeof(double) * M);
+    } else {
+        HIPCHK(c, hipMemcpyAsync(h, c->reg_ws, sizeof(double) * (8 + 3 * (size_t)M), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ++c->init_route[1];
+        if (const int status = sort_pts_host(h + 8, M, Ys.data(), nullptr, coord.data())) return fail(c, TDLO_E_NUMERIC, sort_pts_reason(status));
+        sigma2 = h[0];
+    }
+    t->Y = Ys;                                                           // as tdlo_tracker_initialize_nodes
+    t->guide_nodes = t->Y; t->Mg = M;
+    t->geodesic_coord = coord;                                           // replaced, not appended to
+    if (sigma2_out) *sigma2_out = sigma2;
+    return TDLO_OK;
+}
+
+static int initialize_from_cloud_impl(tdlo_tracker *t, const double *X, const tdlo_cloud_view *v, int N, double mu, int max_iter, double *sigma2_out) {
+    tdlo_ctx *c = t->ctx;
+    if (t->M < 4) return fail(c, TDLO_E_INVALID, "initialize_from_cloud: a tracker has at least 4 nodes");
+    if (t->M > reg_max_nodes()) return fail(c, TDLO_E_INVALID, "initialize_from_cloud: reg fits at most " + std::to_string(reg_max_nodes()) + " centroids (tdlo_reg)");
+    if (max_iter < 0 || !(mu >= 0 && mu < 1)) return fail(c, TDLO_E_INVALID, "initialize_from_cloud: bad reg arguments");
+    if (X && N <= 0) return fail(c, TDLO_E_INVALID, "empty cloud");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = initialize_from_cloud_enqueued(t, X, v, N, mu, max_iter, sigma2_out);
+    if (rc && rc != TDLO_E_NUMERIC) (void)hipStreamSynchronize(c->stream);      // nothing of this call stays enqueued behind an error (X and v are the caller's again)
+    return rc;
+}
+
+int tdlo_tracker_initialize_from_cloud(tdlo_tracker *t, const double *X, int N, double mu, int max_iter, double *sigma2_out) {
+    if (!t) return TDLO_E_INVALID;
+    return initialize_from_cloud_impl(t, X, nullptr, N, mu, max_iter, sigma2_out);
+}
+
+int tdlo_tracker_initialize_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, double mu, int max_iter, double *sigma2_out) {
+    if (!t) return TDLO_E_INVALID;
+    if (const char *why = view_fault(v, N)) return fail(t->ctx, TDLO_E_INVALID, why);
+    return initialize_from_cloud_impl(t, nullptr, v, N, mu, max_iter, sigma2_out);
 }
 
 int tdlo_tracker_copy_state(tdlo_tracker *dst, const tdlo_tracker *src) {

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 namespace tdlo {
 
@@ -491,6 +492,67 @@ int render_primitives(const double *Y, int M, const double proj[12], const int *
                                {1, pc[i + 1], pr[i + 1], pc[i + 1], pr[i + 1], node_radius, in_vis[i + 1] ? nv : nh, 0}};
         std::memcpy(q, rec, sizeof(rec));
         q += 24;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sort_pts (trackdlo/src/utils.cpp:95-170) and the chain coordinate of trackdlo_node.cpp:135-141: the host twin of k_sort_pts
+// (tdlo_init.hip), the same rule in the same arithmetic.  The reference's triple loop takes, in each of its M - 1 rounds, the pair
+// (a selected, b unselected) of smallest non-zero G(a, b), first in a ascending then b ascending order; kept here, per unselected
+// node, as its smallest distance to the selected set and the smallest selected index attaining it -- the round's pair is then the
+// minimum by (distance, parent, node).  This unit is built without contraction (Makefile), so every product and sum is rounded.
+// ---------------------------------------------------------------------------------------------
+int sort_pts_host(const double *Y, int M, double *Y_sorted, int *perm, double *coord) {
+    const double *x = Y, *y = Y + M, *z = Y + 2 * (size_t)M;
+    for (int i = 0; i < 3 * M; ++i) if (!std::isfinite(Y[i])) return 1;
+    for (int i = 0; i < M; ++i) for (int j = i + 1; j < M; ++j) if (x[i] == x[j] && y[i] == y[j] && z[i] == z[j]) return 2;
+    auto G = [&](int i, int j) { const double dx = x[i] - x[j], dy = y[i] - y[j], dz = z[i] - z[j]; return (dx * dx + dy * dy) + dz * dz; };
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> best(M, inf);                  // inf: no edge yet (`minimum > G` never takes an infinite G either, :116 / :124)
+    std::vector<int> parent(M, 0), pos(M, -1);         // pos: place in the list, selected nodes only
+    std::vector<char> sel(M, 0);
+    auto fold = [&](int a) {                           // node a has been selected: its distances enter the unselected nodes' records
+        for (int n = 0; n < M; ++n) {
+            if (sel[n]) continue;
+            const double g = G(a, n);
+            if (g != 0.0 && (g < best[n] || (g == best[n] && a < parent[n]))) { best[n] = g; parent[n] = a; }
+        }
+    };
+    sel[0] = 1; pos[0] = 0;
+    fold(0);
+    int reverse = 0, reverse_on = 0, insertion_counter = 0, last_visited_b = 0;
+    for (int counter = 0; counter < M - 1; ++counter) {
+        int b = -1;
+        for (int n = 0; n < M; ++n)
+            if (!sel[n] && best[n] < inf && (b < 0 || best[n] < best[b] || (best[n] == best[b] && parent[n] < parent[b]))) b = n;
+        if (b < 0) return 3;
+        const int a = parent[b];
+        int p;                                          // where b enters the list (:134-157)
+        if (counter == 0) p = 1;
+        else {
+            if (last_visited_b != a) { reverse += 1; reverse_on = a; insertion_counter = 1; }
+            if (reverse % 2 == 1) p = pos[a];
+            else if (reverse != 0) { p = pos[reverse_on] + insertion_counter; insertion_counter += 1; }
+            else p = counter + 1;
+        }
+        for (int n = 0; n < M; ++n) if (sel[n] && pos[n] >= p) ++pos[n];
+        pos[b] = p; sel[b] = 1; last_visited_b = b;
+        fold(b);
+    }
+    std::vector<int> order(M);
+    for (int n = 0; n < M; ++n) order[pos[n]] = n;
+    // (coord before Y_sorted: Y_sorted may be Y itself)
+    if (coord) {
+        double cur = 0.0;
+        coord[0] = 0.0;
+        for (int i = 1; i < M; ++i) { cur += std::sqrt(G(order[i], order[i - 1])); coord[i] = cur; }
+    }
+    if (perm) std::copy(order.begin(), order.end(), perm);
+    if (Y_sorted) {
+        std::vector<double> out(3 * (size_t)M);
+        for (int i = 0; i < M; ++i) { out[i] = x[order[i]]; out[M + i] = y[order[i]]; out[2 * (size_t)M + i] = z[order[i]]; }
+        std::copy(out.begin(), out.end(), Y_sorted);
     }
     return 0;
 }

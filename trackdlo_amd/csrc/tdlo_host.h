@@ -32,4 +32,9 @@ int render_primitives(const double *Y, int M, const double proj[12], const int *
 // evaluator::get_piecewise_error (evaluator.cpp:258-283); chains are n x 3 column-major.
 double piecewise_error(const double *Ytrack, int n1, const double *Ytrue, int n2);
 
+// sort_pts (utils.cpp:95-170) with the chain coordinate of trackdlo_node.cpp:135-141, the host twin of k_sort_pts: Y is M x 3 column-major, M >= 2;
+// Y_sorted (3 M, may be Y), perm (M: perm[i] = the row of Y at place i) and coord (M) may each be null.  Returns 0, or 1 a non-finite coordinate,
+// 2 two equal nodes, 3 a round that finds no edge -- the outputs are untouched then.
+int sort_pts_host(const double *Y, int M, double *Y_sorted, int *perm, double *coord);
+
 }  // namespace tdlo

@@ -280,6 +280,11 @@ int mstep_set_lle_dense(int on);  // 1: registrations with the LLE term take the
 size_t reg_ws_doubles(int M, int nblk);
 int reg_max_nodes();        // the E-step's per-wave accumulators must fit 160 KB of LDS
 hipError_t launch_reg(const double *X, int N, int M, double mu, int max_iter, int nblk, double *ws, hipStream_t s);
+// tdlo_init.hip: `sort_pts` (utils.cpp:95-170) and the chain coordinate, one workgroup, 2 <= M <= kMaxNodes.  Y: M x 3 column-major in device memory (reg's
+// centroids: ws + 8); state: reg's state block (its sigma2 is copied into the output's header) or nullptr; out: sort_pts_out_doubles(M) doubles of device
+// memory: [sigma2 | status | Y sorted (3 M) | coord (M)] and M ints of perm -- status 1 .. 3: only the header is written
+size_t sort_pts_out_doubles(int M);
+hipError_t launch_sort_pts(const double *Y, const double *state, int M, double *out, hipStream_t s);
 // tdlo_cloud.hip: depth image -> cloud -> voxel grid
 // colour segmentation in front of it (tdlo_colour_params as the kernels take it): the colour image (3 bytes a pixel) and the optional occluder image, readable by
 // the device and padded to 16 bytes beyond the image; per range the lower bounds H | S << 8 | V << 16 and upper - lower per channel (ranges that

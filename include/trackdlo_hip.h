@@ -526,12 +526,28 @@ int tdlo_voxel_grid_dims(const float mn[3], const float mx[3], double leaf_size,
  * tdlo_set_cloud_view: a host view is packed in its own precision into the pinned staging block and the kernels read it there, a device view is read
  * in place, and no load of any width touches a byte outside tdlo_cloud_view_extent.  TDLO_E_INVALID, with the slot's cloud intact: TDLO_VIEW_ASYNC (the
  * call needs a host round trip for the box), N > 2^26 (refused before anything is allocated; the workspace is 16 N bytes), a device view that overlaps
- * the slot's resident cloud, cases 8 and 9.  Every view call takes the multi-launch form (k_cloud_bbox / k_cloud_keys / k_cloud_centroid over the view
- * source, csrc/tdlo_cloud.hip; radix passes as for the depth path); tdlo_debug_route_count 21 counts the calls. */
+ * the slot's resident cloud, cases 8 and 9.
+ * Routes (the same bits on each; tdlo_debug_route_count 21 counts every call that reached the kernels): a view of up to 4095 x 4096 elements is first
+ * handed to the ONE-LAUNCH kernel of the depth path, k_cloud_team with the view as its point source (csrc/tdlo_cloud.hip, csrc/tdlo_view_lane.h: a thread
+ * takes four consecutive elements; a device `select` needs neither alignment nor padding): one launch, the counts through pinned memory, no host round
+ * trip for the box.  The kernel serves up to 32 704 kept points whose cell-index bits and rank bits fit 32 (count 27) and passes everything else on
+ * (count 28) -- more kept points, pass-through (6), the refusals of 8 and 9, a result that the slot's present capacity does not hold, a team that gave
+ * up -- to the multi-launch form (k_cloud_bbox / k_cloud_keys / k_cloud_centroid over the view source; radix passes as for the depth path), which
+ * decides those cases as before; the kernel writes nothing to the slot unless it serves the call, so a refused call finds the resident cloud intact.
+ * TDLO_CLOUD_FUSED=0 or TDLO_CLOUD_TEAM=0: every view call takes the multi-launch form (the comparator; k_cloud_fused has no view instantiation). */
 int tdlo_cloud_view_voxel_grid(tdlo_ctx *ctx, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
                                double *X_out, int x_capacity, int *n_out, int *n_raw_out);
+/* The view counterpart of tdlo_depth_to_cloud_visibility: tdlo_cloud_view_voxel_grid into `slot` (no X_out) followed by tdlo_visibility_prepass of the
+ * nodes Y against the cloud it left, the outputs of the two calls bit for bit.  With M <= 64, the one-launch kernel serving the view and
+ * TDLO_DIRECT_UPLOAD on, the pre-pass rides in that launch (count 29); otherwise the two steps run one behind the other.  A view that keeps no point:
+ * TDLO_OK, *n_out = *n_vis = *n_vis_ext = 0.  Refusals are those of the two calls; Y, M and geodesic_coord are checked first. */
+int tdlo_cloud_view_voxel_grid_visibility(tdlo_ctx *ctx, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                                          const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                          double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                          int *n_out, int *n_raw_out);
 /* A whole frame from a cloud view: tdlo_cloud_view_voxel_grid into the tracker's slot, tdlo_visibility_prepass with the tracker's nodes, threshold and
- * geodesic coordinates, tdlo_tracker_tracking_step with X == NULL -- one behind the other, the same bits as the three calls made by hand.  The rules of
+ * geodesic coordinates (the two through tdlo_cloud_view_voxel_grid_visibility: one launch where the one-launch kernel serves the view),
+ * tdlo_tracker_tracking_step with X == NULL -- the same bits as the three calls made by hand.  The rules of
  * tdlo_tracker_frame_from_depth hold: the self-occlusion switch, TDLO_E_EMPTY (no kept point, or no visible node) with the tracker's state untouched,
  * stats.  A refused view leaves tracker and slot as they were. */
 int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size, double d_vis,
@@ -835,6 +851,9 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 24: registrations of 14 whose per-iteration launches were k_iter_fused_w0 (recorded where the kernel is chosen).
  * 25 / 26: node sets ordered by k_sort_pts (tdlo_sort_pts, tdlo_tracker_initialize_from_cloud*) / tdlo_tracker_initialize_from_cloud* calls whose
  * centroids were ordered by the host twin (TDLO_INIT_SORT=host).
+ * 27 / 28: tdlo_cloud_view_voxel_grid calls (those of tdlo_cloud_view_voxel_grid_visibility and tdlo_tracker_frame_from_cloud_view among them) served by the
+ * one-launch kernel / passed on by it to the multi-launch form, a team that gave up included; calls that the host never hands to it (TDLO_CLOUD_FUSED=0,
+ * TDLO_CLOUD_TEAM=0, more than 4095 tiles) count in 21 alone.  29: view frames whose visibility pre-pass rode in that launch.  6 / 7 / 8 count depth frames only.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

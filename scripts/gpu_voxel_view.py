@@ -15,6 +15,18 @@
   python scripts/gpu_voxel_view.py --mode summarize --trace DIR
       Per-kernel times from the kernel trace: total and share per kernel name (k_cloud_bbox / k_cloud_keys / k_cloud_centroid by source, the radix
       passes, k_scan_single -- its share at 2 000 000 points is the question the trace answers).
+  python scripts/gpu_voxel_view.py --mode team-frames --frames FILE.npz
+      Writes the frames of the one-launch route's measurement: organized clouds of 640 x 480 and 1280 x 720 (synth.depth_scene, the rope's radius chosen
+      so that the mask keeps about 10 000 and 30 000 pixels -- and 36 000, more than the kernel takes: a call it passes on), no GPU needed.
+  python scripts/gpu_voxel_view.py --mode team-ab --frames FILE.npz --parent-lib PATH
+      The view route in ONE launch (k_cloud_team over the view) against the parent commit: per frame tdlo_cloud_view_voxel_grid and
+      tdlo_tracker_frame_from_cloud_view on the organized cloud + mask, from a device tensor and from host memory, and beside them tdlo_depth_to_cloud and
+      tdlo_tracker_frame_from_depth on the same frame (the figure the route is modelled on).  --rounds alternating pairs of child processes (--mode
+      team-side; the parent's library through TDLO_LIBRARY), each under its own time limit; every value is printed, then per measured call whether every
+      value of this tree lies below every value of the parent.
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o vt -- python scripts/gpu_voxel_view.py --mode team-side --frames FILE.npz --calls 5
+  python scripts/gpu_voxel_view.py --mode summarize --trace DIR
+      k_cloud_team's view instantiations alone, in a run of their own.
 Any HIP error raises: the process exits non-zero."""
 import argparse
 import csv
@@ -28,11 +40,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=("ab", "depth", "view", "alone", "summarize"), required=True)
+ap.add_argument("--mode", choices=("ab", "depth", "view", "alone", "summarize", "team-frames", "team-side", "team-ab"), required=True)
 ap.add_argument("--calls", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--leaf", type=float, default=0.008)
 ap.add_argument("--parent-lib", default=None, help="ab: libtrackdlo_hip.so of the parent commit for side A")
+ap.add_argument("--frames", default=None, help="team-*: the .npz of frames (team-frames writes it)")
 ap.add_argument("--trace", default=None, help="summarize: the directory rocprofv3 wrote")
 args = ap.parse_args()
 
@@ -161,4 +174,99 @@ def summarize():
         print(f"{us:12.1f} us {100 * us / whole:5.1f} %  {cnt:6d} x {us / cnt:9.2f} us  {name}")
 
 
-{"ab": ab, "depth": depth_side, "view": view_side, "alone": alone, "summarize": summarize}[args.mode]()
+TEAM_FRAMES = (("640x480", 480, 640), ("1280x720", 720, 1280))
+TEAM_KEPT = (10000, 30000, 36000)      # the last: more kept points than the one-launch kernel takes (32 704) -- what a passed-on call costs, beside the condition
+
+
+def team_frames():
+    import numpy as np
+    from trackdlo_amd import synth
+    out = {}
+    for tag, rows, cols in TEAM_FRAMES:
+        for want in TEAM_KEPT:
+            radius = 0.006
+            for _ in range(4):
+                depth, mask, cam, Y0 = synth.depth_scene(45, config=4, rows=rows, cols=cols, radius=radius, samples=3000000)
+                got = int((mask != 0).sum())
+                if abs(got - want) <= want // 20:
+                    break
+                radius *= want / got
+            key = f"{tag}_{want}"
+            print(f"{key}: radius {radius:.5f} m, the mask keeps {got} pixels")
+            out[key + "_depth"] = depth; out[key + "_mask"] = mask; out[key + "_Y0"] = Y0
+            out[key + "_cam"] = np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"]])
+    np.savez_compressed(args.frames, **out)
+
+
+def team_side():
+    """One process, whatever library TDLO_LIBRARY names: RESULT <frame> <call> <ms per call> lines."""
+    import numpy as np
+    import torch
+    import voxel_ref as R
+    from trackdlo_amd import binding as B, synth
+    z = np.load(args.frames)
+    Pm = synth.LAUNCH_PARAMS
+    ctx = B.Context(device=0, max_frames=2, max_points=1 << 16, timing=False)
+    for tag, rows, cols in TEAM_FRAMES:
+        for want in TEAM_KEPT:
+            key = f"{tag}_{want}"
+            depth, mask, Y0, k = z[key + "_depth"], z[key + "_mask"], z[key + "_Y0"], tuple(float(x) for x in z[key + "_cam"])
+            org = R.backproject(depth, np.ones_like(mask), *k)
+            sel = np.ascontiguousarray(mask.reshape(-1))
+            org_d, sel_d = torch.from_numpy(org).cuda(), torch.from_numpy(sel.copy()).cuda()
+            Xa, n, n_raw = ctx.depth_to_cloud(1, depth, mask, *k, args.leaf)
+            for src, s in ((org, sel), (org_d, sel_d)):
+                Xb, nb, nrawb = ctx.voxel_grid_view(0, src, args.leaf, select=s)
+                assert (n, n_raw) == (nb, nrawb) and np.array_equal(Xa.view(np.uint64), Xb.view(np.uint64))
+            M = Y0.shape[0]
+            coord = synth.geodesic_coord(Y0)
+            # (visibility threshold 5 cm: the thick ropes' visible surface lies up to 27 mm from the centreline the nodes start on)
+            trk = B.trackdlo(M, 0.05, Pm["beta"], Pm["lambda_"], Pm["alpha"], Pm["k_vis"], Pm["mu"], 30, Pm["tol"], Pm["beta_pre_proc"],
+                             Pm["lambda_pre_proc"], Pm["lle_weight"], ctx=ctx)
+            trk.initialize_nodes(Y0); trk.initialize_geodesic_coord(coord)      # (the coordinates once: a second call appends, as the reference's does)
+
+            def timed(name, fn, tracker=False):
+                if tracker:
+                    trk.initialize_nodes(Y0)
+                ms(fn, 3)
+                print(f"RESULT {key}({n_raw}->{n}) {name} {ms(fn, args.calls):.4f}", flush=True)
+
+            timed("view_voxel_grid,device", lambda: ctx.voxel_grid_view(0, org_d, args.leaf, select=sel_d, want_cloud=False))
+            timed("view_voxel_grid,host", lambda: ctx.voxel_grid_view(0, org, args.leaf, select=sel, want_cloud=False))
+            timed("tracker_frame_from_cloud_view,device", lambda: trk.frame_from_cloud_view(org_d, args.leaf, 0.06, select=sel_d), True)
+            timed("tracker_frame_from_cloud_view,host", lambda: trk.frame_from_cloud_view(org, args.leaf, 0.06, select=sel), True)
+            timed("(model)depth_to_cloud", lambda: ctx.depth_to_cloud(1, depth, mask, *k, args.leaf, fetch=False))
+            timed("(model)tracker_frame_from_depth", lambda: trk.frame_from_depth(depth, mask, *k, args.leaf, 0.06), True)
+            del trk
+    rc = [int(ctx.lib.tdlo_debug_route_count(ctx.h, w)) for w in (21, 27, 28, 29)]
+    print(f"route counts 21 / 27 / 28 / 29: {rc}", flush=True)
+    ctx.close()
+
+
+def team_ab():
+    import subprocess
+    assert args.parent_lib and args.frames
+    me = [sys.executable, os.path.abspath(__file__), "--calls", str(args.calls), "--leaf", str(args.leaf), "--frames", args.frames, "--mode", "team-side"]
+    sides = (("parent", dict(os.environ, TDLO_LIBRARY=os.path.abspath(args.parent_lib))), ("this", dict(os.environ)))
+    vals = {}
+    for r in range(args.rounds):
+        for side, env in sides:
+            run = subprocess.run(me, env=env, timeout=240, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            out = run.stdout
+            if run.returncode != 0:
+                print(f"pair {r + 1}, {side} tree: exit status {run.returncode}\n" + out, flush=True)
+                sys.exit(1)
+            print(f"pair {r + 1}, {side} tree:\n" + out, flush=True)
+            for line in out.splitlines():
+                if line.startswith("RESULT "):
+                    _, frame, name, v = line.split()
+                    vals.setdefault((frame, name), {}).setdefault(side, []).append(float(v))
+    print("ms per call (mean of %d), every pair's value; below = every value of this tree below every value of the parent" % args.calls)
+    for (frame, name), d in vals.items():
+        p, t = d["parent"], d["this"]
+        passed_on = int(frame.split("(")[1].split("-")[0]) > 32704
+        verdict = "(model)" if name.startswith("(model)") else ("below" if max(t) < min(p) else "NOT BELOW") + (" (passed on: beside the condition)" if passed_on else "")
+        print(f"  {frame:26s} {name:38s} parent " + " ".join(f"{x:7.4f}" for x in p) + "   this " + " ".join(f"{x:7.4f}" for x in t) + f"   {verdict}")
+
+
+{"team-frames": team_frames, "team-side": team_side, "team-ab": team_ab, "ab": ab, "depth": depth_side, "view": view_side, "alone": alone, "summarize": summarize}[args.mode]()

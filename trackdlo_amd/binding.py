@@ -99,7 +99,7 @@ SYMBOLS = [
     "tdlo_last_colour_shape",
     "tdlo_image_view_check", "tdlo_image_view_extent", "tdlo_image_view_form", "tdlo_image_view_pack", "tdlo_frame_to_cloud_view",
     "tdlo_frame_to_cloud_visibility_view", "tdlo_tracker_frame_view", "tdlo_debug_read_images",
-    "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view",
+    "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view", "tdlo_cloud_view_voxel_grid_visibility",
     "tdlo_sort_pts", "tdlo_sort_pts_host", "tdlo_tracker_initialize_from_cloud", "tdlo_tracker_initialize_from_cloud_view",
 ]
 
@@ -286,6 +286,8 @@ def load_library(path: str | None = None):
         lib.tdlo_voxel_grid_dims.argtypes = [f3, f3, cd, i3, i3, C.POINTER(ci)]
         lib.tdlo_cloud_view_voxel_grid.argtypes = [vp, ci, cvp, ci, vp, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
         lib.tdlo_tracker_frame_from_cloud_view.argtypes = [vp, cvp, ci, vp, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+    if hasattr(lib, "tdlo_cloud_view_voxel_grid_visibility"):
+        lib.tdlo_cloud_view_voxel_grid_visibility.argtypes = [vp, ci, cvp, ci, vp, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     if hasattr(lib, "tdlo_sort_pts"):
         lib.tdlo_sort_pts.argtypes = [vp, vp, ci, vp, vp, vp]
         lib.tdlo_sort_pts_host.argtypes = [vp, ci, vp, vp, vp]
@@ -631,6 +633,27 @@ class Context:
         self._chk(self.lib.tdlo_cloud_view_voxel_grid(self.h, slot, C.byref(v), N, sp, float(leaf_size), None, 0, C.byref(n), C.byref(nraw)))
         self._async_src = None
         return (self.get_cloud(slot) if want_cloud else None), n.value, nraw.value
+
+    def voxel_grid_view_visibility(self, slot, view, leaf_size, Y, visibility_threshold, d_vis, geodesic_coord, select=None, ready_stream=None):
+        """voxel_grid_view into the slot and the visibility pre-pass of the nodes Y against the cloud it left, in one launch where the library can
+        (tdlo_cloud_view_voxel_grid_visibility).  Returns (node_dist, visible_nodes, visible_nodes_extended, n, n_raw)."""
+        v = view if isinstance(view, CloudView) else cloud_view(view, ready_stream)
+        N = int(v.N)
+        sp, _keep = _select_ptr(select, N)
+        Y = _f64(Y); M = Y.shape[0]
+        coord = np.ascontiguousarray(geodesic_coord, dtype=np.float64)
+        dist = np.zeros(M); vis = np.zeros(M, dtype=np.int32); ext = np.zeros(M, dtype=np.int32)
+        nv = C.c_int(0); ne = C.c_int(0); n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_cloud_view_voxel_grid_visibility(self.h, slot, C.byref(v), N, sp, float(leaf_size), _ptr(Y), M, float(visibility_threshold),
+                                                                 float(d_vis), _ptr(coord), _ptr(dist), _ptr(vis), C.byref(nv), _ptr(ext), C.byref(ne),
+                                                                 C.byref(n), C.byref(nraw)))
+        self._async_src = None
+        return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
+    def view_route_counts(self):
+        """[voxel-grid view calls served by the one-launch kernel, calls it passed on to the multi-launch form, view frames whose visibility pre-pass rode
+        in the launch] (tdlo_debug_route_count 27 / 28 / 29)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (27, 28, 29)]
 
     def voxel_view_calls(self):
         """tdlo_debug_route_count 21: voxel-grid calls on cloud views that reached the kernels."""

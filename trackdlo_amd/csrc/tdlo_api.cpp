@@ -192,6 +192,7 @@ struct tdlo_ctx {
     long long init_route[2] = {0, 0};
     long long vis_route[2] = {0, 0};     // tdlo_debug_route_count 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel / by the copies + k_node_min_dist
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
+    long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
     // kernel (k_colour_mask), then the mask route as it is without colour (comparator)
@@ -2794,6 +2795,31 @@ static int ensure_cloud_ws(tdlo_ctx *c, int P) {      // the device images (dept
     return TDLO_OK;
 }
 
+// the one-launch kernels' own workspace for P elements and the pinned words they report through (depth frames and view calls share both, and the state
+// words at the workspace's head: a reallocation has them initialised again)
+static int ensure_cloud_fws(tdlo_ctx *c, int P) {
+    const size_t fneed = cloud_fused_ws_bytes(P);
+    if (fneed > c->cloud_fws_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->cloud_fws) hipFree(c->cloud_fws);
+        c->cloud_fws = nullptr; c->cloud_fws_cap = 0;
+        HIPCHK(c, hipMalloc(&c->cloud_fws, fneed));
+        c->cloud_fws_cap = fneed; c->cloud_fused_first = true;
+    }
+    if (!c->cloud_res) {
+        HIPCHK(c, hipHostMalloc((void **)&c->cloud_res, 32 * sizeof(unsigned long long), hipHostMallocDefault));      // [0..1] the report, [4..] phase stamps of an instrumented build
+        std::memset(c->cloud_res, 0, 32 * sizeof(unsigned long long));
+    }
+    return TDLO_OK;
+}
+// the nodes of a pre-pass that rides in the team kernel: staged in pinned memory, the minima armed
+static int stage_vis_ride(tdlo_ctx *c, const double *vis_Y, int vis_M) {
+    if (int rc = ensure_vis_state(c)) return rc;
+    if (!c->vis_nodes_pin) HIPCHK(c, hipHostMalloc((void **)&c->vis_nodes_pin, sizeof(double) * 3 * 64, hipHostMallocDefault));
+    std::memcpy(c->vis_nodes_pin, vis_Y, sizeof(double) * 3 * (size_t)vis_M);
+    return TDLO_OK;
+}
+
 // pcl/filters/impl/voxel_grid.hpp applyFilter: the leaf-size check and min_b / div_b in float arithmetic from the float bounding box -- the ONE statement
 // of the rule for the multi-launch form, whatever its point source (include/trackdlo_hip.h has the contract).  why: what a refusal says.
 static int voxel_grid_dims(const float mn[3], const float mx[3], double leaf_size, int min_b[3], int div_b[3], int *nodown, const char **why) {
@@ -2907,27 +2933,12 @@ static int depth_to_cloud_impl(tdlo_ctx *c, int slot, const unsigned short *dept
     int n = -1, nraw = 0;
     if (c->cloud_fused_on && cloud_fused_ok(P)) {
         // ---- one launch (k_cloud_fused); its last workgroup reports through pinned host memory
-        const size_t fneed = cloud_fused_ws_bytes(P);
-        if (fneed > c->cloud_fws_cap) {
-            HIPCHK(c, hipStreamSynchronize(st));
-            if (c->cloud_fws) hipFree(c->cloud_fws);
-            c->cloud_fws = nullptr; c->cloud_fws_cap = 0;
-            HIPCHK(c, hipMalloc(&c->cloud_fws, fneed));
-            c->cloud_fws_cap = fneed; c->cloud_fused_first = true;
-        }
-        if (!c->cloud_res) {
-            HIPCHK(c, hipHostMalloc((void **)&c->cloud_res, 32 * sizeof(unsigned long long), hipHostMallocDefault));      // [0..1] the report, [4..] phase stamps of an instrumented build
-            std::memset(c->cloud_res, 0, 32 * sizeof(unsigned long long));
-        }
+        if ((rc = ensure_cloud_fws(c, P))) return rc;
         if ((rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;      // (an output point per masked pixel at most; sized once)
         if (++c->cloud_epoch == 0) ++c->cloud_epoch;
         // the frame's visibility pre-pass rides along when the team kernel runs (up to 64 nodes): the nodes staged in pinned memory, read by the kernel
         const bool vis_ride = vis_Y != nullptr && vis_M >= 1 && vis_M <= 64 && c->cloud_team_on && c->direct_in;
-        if (vis_ride) {
-            if ((rc = ensure_vis_state(c))) return rc;
-            if (!c->vis_nodes_pin) HIPCHK(c, hipHostMalloc((void **)&c->vis_nodes_pin, sizeof(double) * 3 * 64, hipHostMallocDefault));
-            std::memcpy(c->vis_nodes_pin, vis_Y, sizeof(double) * 3 * (size_t)vis_M);
-        }
+        if (vis_ride && (rc = stage_vis_ride(c, vis_Y, vis_M))) return rc;
         HIPCHK(c, launch_cloud_fused(d_depth, d_mask, P, cols, cam, inv, ws, c->cloud_fws, c->cloud_fused_first, c->cloud_team_on, s.Xraw, s.cap_points, c->cloud_res, c->cloud_epoch, st,
                                      vis_ride ? c->vis_nodes_pin : nullptr, vis_ride ? vis_M : 0, c->vis_state, c->vis_res, mask_ready ? nullptr : &cc));
         c->cloud_fused_first = false;
@@ -3008,8 +3019,10 @@ static int voxel_view_refusal(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, i
     return TDLO_OK;
 }
 
-int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
-                               double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+// vis_Y != nullptr: the caller wants the frame's visibility pre-pass as well; *vis_done = true when the team kernel has left the M squared minima in
+// c->vis_res[1 ..], as for depth_to_cloud_impl
+static int cloud_view_voxel_impl(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                                 double *X_out, int x_capacity, int *n_out, int *n_raw_out, const double *vis_Y, int vis_M, bool *vis_done) {
     if (!c) return TDLO_E_INVALID;
     int rc = voxel_view_refusal(c, slot, v, N, leaf_size);
     if (rc) return rc;
@@ -3052,6 +3065,42 @@ int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, 
         src.select = d_mask;
     }
     ++c->voxel_view_calls;
+    const float inv = 1.0f / (float)leaf_size;
+    if (c->cloud_fused_on && c->cloud_team_on && cloud_fused_ok(N)) {
+        // ---- one launch (k_cloud_team over the view; TDLO_CLOUD_FUSED=0 / TDLO_CLOUD_TEAM=0: the multi-launch form below, the comparator).  The kernel
+        // decides whether it serves the call: more than 32 704 kept points, pass-through, too many cell bits and every case that refuses the call go on to
+        // the multi-launch form, which decides them.  It is launched with the slot's capacity AS IT IS -- growing the slot frees its resident cloud, which a
+        // refusal must leave intact -- and writes nothing to the slot unless the result fits: "capacity" too goes on, to the code that grows the slot
+        if ((rc = ensure_cloud_fws(c, N))) return rc;
+        if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+        const bool vis_ride = vis_Y != nullptr && vis_M >= 1 && vis_M <= 64 && c->direct_in;
+        if (vis_ride && (rc = stage_vis_ride(c, vis_Y, vis_M))) return rc;
+        HIPCHK(c, launch_view_team(src, N, inv, ws, c->cloud_fws, c->cloud_fused_first, s.Xraw, s.cap_points, c->cloud_res, c->cloud_epoch, st,
+                                   vis_ride ? c->vis_nodes_pin : nullptr, vis_ride ? vis_M : 0, c->vis_state, c->vis_res));
+        c->cloud_fused_first = false;
+        const int status = cloud_wait(c, st, c->cloud_epoch);
+        if (status != 1 && vis_ride) c->vis_armed = false;      // (whatever the team left in the minima: armed again before their next use)
+        if (status < 0) { c->cloud_fused_first = true; return status; }
+        if (status == 0) { c->cloud_fused_first = true; return fail(c, TDLO_E_HIP, "the stream drained, but the voxel-grid kernel did not report"); }
+        if (status == 1) {
+            const unsigned long long w1 = __atomic_load_n(c->cloud_res + 1, __ATOMIC_RELAXED);
+            const int n = (int)(unsigned)w1, nraw = (int)(unsigned)(w1 >> 32);
+            ++c->view_team_route[0];
+            if (n < 0 || n > s.cap_points || n > nraw) return fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count");
+            s.N0 = n; s.sorted_valid = false;                   // (nraw == 0: n = 0, the slot as tdlo_depth_to_cloud leaves it for an all-zero mask)
+            if (n_out) *n_out = n;
+            if (n_raw_out) *n_raw_out = nraw;
+            if (n > 0 && vis_ride && vis_done) { *vis_done = true; ++c->view_team_route[2]; }
+            if (X_out && n > 0) {
+                if (n > x_capacity) return fail(c, TDLO_E_INVALID, "X_out too small for the down-sampled cloud");
+                HIPCHK(c, hipMemcpyAsync(X_out, s.Xraw, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+            return TDLO_OK;
+        }
+        if (status == 4) c->cloud_fused_first = true;           // the team gave the launch up (a wait of 2 s): state words initialised again
+        ++c->view_team_route[1];                                 // passed on: not taken (2), the slot has to grow first (3), given up (4)
+    }
     // ---- the multi-launch form: bounding box + count, a host round trip, compaction, radix sort passes, centroids
     unsigned *d_bbox = (unsigned *)(ws + cloud_ws_bytes(N) - 256);
     int *d_total = (int *)(d_bbox + 8);
@@ -3069,7 +3118,6 @@ int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, 
     if ((rc = voxel_grid_from_box(c, hb, leaf_size, min_b, div_b, &nodown, &passes))) return rc;      // (the slot's cloud is untouched)
     if ((rc = ensure_points(c, s, nraw))) return rc;
     s.N0 = 0; s.sorted_valid = false;
-    const float inv = 1.0f / (float)leaf_size;
     HIPCHK(c, launch_view_voxels(src, N, min_b, div_b[0], voxel_mul2(div_b), inv, nodown, passes, nraw, ws, d_total, s.cap_points, s.Xraw, st));
     HIPCHK(c, hipMemcpyAsync(hb, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -3083,6 +3131,11 @@ int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, 
         HIPCHK(c, hipStreamSynchronize(st));
     }
     return TDLO_OK;
+}
+
+int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+    return cloud_view_voxel_impl(c, slot, v, N, select, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
 }
 
 // ---- caller-side visibility pre-pass ------------------------------------------------------------
@@ -3193,6 +3246,28 @@ static int depth_to_cloud_visibility_impl(tdlo_ctx *c, int slot, const unsigned 
     bool vis_done = false;
     int n = 0;
     int rc = depth_to_cloud_impl(c, slot, depth, mask, rows, cols, fx, fy, cx, cy, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done, colour);
+    if (n_out) *n_out = n;
+    if (rc) return rc;
+    if (n_vis) *n_vis = 0;
+    if (n_vis_ext) *n_vis_ext = 0;
+    if (n == 0) return TDLO_OK;                  // no cloud, nothing visible (tdlo_visibility_prepass would refuse the empty slot)
+    if (!vis_done) return tdlo_visibility_prepass(c, slot, Y, M, visibility_threshold, d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext);
+    if ((rc = ensure_pin(c, (size_t)M + 8))) return rc;
+    std::memcpy(c->pin, c->vis_res + 1, sizeof(double) * M);
+    vis_threshold_and_fill(c->pin, M, visibility_threshold, d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext);
+    return TDLO_OK;
+}
+
+// The view counterpart: V(view, N, select, leaf) into the slot and the pre-pass against it; with up to 64 nodes it rides in the team kernel's launch
+int tdlo_cloud_view_voxel_grid_visibility(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
+                                          const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                          double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                          int *n_out, int *n_raw_out) {
+    if (!c) return TDLO_E_INVALID;
+    if (!Y || M < 1 || !geodesic_coord) return fail(c, TDLO_E_INVALID, "null Y / geodesic_coord");
+    bool vis_done = false;
+    int n = 0;
+    int rc = cloud_view_voxel_impl(c, slot, v, N, select, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done);
     if (n_out) *n_out = n;
     if (rc) return rc;
     if (n_vis) *n_vis = 0;
@@ -3562,7 +3637,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 26) return -1;
+    if (!c || which < 0 || which > 29) return -1;
+    if (which >= 27) return c->view_team_route[which - 27];
     if (which >= 25) return c->init_route[which - 25];
     if (which == 24) return c->fused_w0_calls;
     if (which >= 22) return c->vis_route[which - 22];
@@ -4144,8 +4220,8 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
                               visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
 }
 
-// The same from a cloud view: the voxel grid on the view into the tracker's slot, tdlo_visibility_prepass, tdlo_tracker_tracking_step -- one behind the
-// other, the bits of the three calls made by hand
+// The same from a cloud view: the voxel grid on the view into the tracker's slot and the visibility pre-pass (tdlo_cloud_view_voxel_grid_visibility: in one
+// launch where the team kernel serves the view), tdlo_tracker_tracking_step -- the bits of the three calls made by hand
 int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size, double d_vis,
                                        int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                        int *n_out, int *n_raw_out, tdlo_stats *stats) {
@@ -4160,9 +4236,8 @@ int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v
     int nv = 0, ne = 0, n = 0;
     t->frame_dist.resize(M);
     if (t->painter_on) t->frame_Y0 = t->Y; else t->frame_Y0.clear();
-    rc = tdlo_cloud_view_voxel_grid(c, t->slot, v, N, select, leaf_size, nullptr, 0, &n, n_raw_out);
-    if (!rc && n > 0)
-        rc = tdlo_visibility_prepass(c, t->slot, t->Y.data(), M, t->visibility_threshold, d_vis, t->geodesic_coord.data(), t->frame_dist.data(), vv.data(), &nv, ve.data(), &ne);
+    rc = tdlo_cloud_view_voxel_grid_visibility(c, t->slot, v, N, select, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis, t->geodesic_coord.data(),
+                                               t->frame_dist.data(), vv.data(), &nv, ve.data(), &ne, &n, n_raw_out);
     if (!rc && t->painter_on && n > 0) {      // the self-occlusion switch, as in tracker_frame_impl
         std::vector<int> pv, pe;
         self_occlusion_visible(t->Y.data(), M, t->painter_proj, t->painter_width, t->frame_dist.data(), t->visibility_threshold, pv);

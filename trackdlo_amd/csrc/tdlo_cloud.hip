@@ -23,6 +23,7 @@
 #include "tdlo_internal.h"
 #include "tdlo_devcommon.h"
 #include "tdlo_view_load.h"
+#include "tdlo_view_lane.h"
 #include <cstdint>
 #include <cstdlib>
 
@@ -470,6 +471,10 @@ struct FusedCloud {
     // them to pinned host memory (visOut[1 + m], the layout of k_node_min_dist_direct) and re-arms
     const double *visY; int visM; unsigned long long *visState, *visOut;
     int hook;                            // test hook (TDLO_CLOUD_TEAM_FORCE_TIMEOUT): the team's last workgroup leaves before its first barrier, the others wait out the limit
+    // the view instantiations of k_cloud_team (tdlo_cloud_view_voxel_grid): the points are the P elements of a cloud view -- strides in elements -- and the
+    // optional selection bytes, any alignment, no padding; depth, mask, col, cols and cam are not read.  At the END of the descriptor: the image
+    // instantiations find every field where it was
+    const void *vdata; long long vsp, vsc; const unsigned char *vsel;
 };
 
 __device__ __forceinline__ float ordered_decode(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
@@ -538,8 +543,12 @@ __device__ __forceinline__ void cloud_grid(const unsigned *sbox, int n, float in
 }
 
 // phase A of the one-launch kernels, every workgroup: its tile of 4096 pixels -- compaction in pixel order, back-projection, the points to the tile's
-// region, count, bounding box -- and a ticket (returned to every thread: 0 .. T - 1 in the order the workgroups finished)
-template <bool kColour>
+// region, count, bounding box -- and a ticket (returned to every thread: 0 .. T - 1 in the order the workgroups finished).
+// The ONLY part of the kernels that knows where the points come from: kSrcMask the depth image under a mask, kSrcColour under the segmentation it forms
+// itself, kSrcView the elements of a cloud view in the load form VFORM (tdlo_view_lane.h has the lane's loads and the rule they keep): a thread's four
+// consecutive elements, the kept ones -- selected, three finite floats -- to the tile's region in element order, as masked pixels go in pixel order.
+enum { kSrcMask = 0, kSrcColour = 1, kSrcView = 2 };
+template <int kSrc, typename VT = float, int VFORM = kGeneric>
 __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot, unsigned *sticket, unsigned *sbx /* kFW x 6 words of LDS nobody uses yet */) {
     const int t = threadIdx.x, lane = t & 63, b = blockIdx.x;
 #ifdef TDLO_CLOUD_STAMPS      // wall-clock (100 MHz) split of phase A in the middle tile: words 12 .. 18 behind the state words (scripts/archive/gpu_cloud_stamps.py)
@@ -551,7 +560,11 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
     {
         const int p0 = b * kFPix + 4 * t;
         unsigned m4 = 0;
-        if constexpr (kColour) {
+        [[maybe_unused]] float vx[4], vy[4], vz[4];
+        if constexpr (kSrc == kSrcView) {
+            const unsigned keep = view_lane4<VT, VFORM>((const VT *)a.vdata, a.vsp, a.vsc, a.vsel, p0, a.P, vx, vy, vz);
+            m4 = (keep & 1u) | ((keep & 2u) << 7) | ((keep & 4u) << 14) | ((keep & 8u) << 21);      // (a byte per element, as a mask word has)
+        } else if constexpr (kSrc == kSrcColour) {
             // the four pixels' 12 colour bytes (12-byte aligned: one load, coalesced) and their occluder bytes are requested; while they travel the
             // workgroup forms the two tables of quotients in dynamic LDS that nobody uses during this phase (behind sbx)
             unsigned c0 = 0u, c1 = 0u, c2 = 0u, o4 = 0x01010101u;
@@ -576,24 +589,29 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
         const int k0 = (m4 & 0xffu) != 0u, k1 = (m4 & 0xff00u) != 0u, k2 = (m4 & 0xff0000u) != 0u, k3 = (m4 & 0xff000000u) != 0u;
         const int c = k0 + k1 + k2 + k3;
         uint2 d4 = make_uint2(0u, 0u);
-        if (c) d4 = *(const uint2 *)(a.depth + p0);
+        if constexpr (kSrc != kSrcView) { if (c) d4 = *(const uint2 *)(a.depth + p0); }
         ASTAMP(2);
         int total;
         int rnk = block_excl_scan_i(c, wtot, t, &total);
         ASTAMP(3);
         unsigned mn[3] = {~0u, ~0u, ~0u}, mx[3] = {0u, 0u, 0u};
         if (c) {
-            int i = p0 / a.cols, j = p0 - i * a.cols;
+            int i = 0, j = 0;
+            if constexpr (kSrc != kSrcView) { i = p0 / a.cols; j = p0 - i * a.cols; }
             const size_t dst = (size_t)b * kFPix;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const bool on = (k == 0 ? k0 : (k == 1 ? k1 : (k == 2 ? k2 : k3))) != 0;
                 if (on) {
-                    const unsigned dv = ((k < 2 ? d4.x : d4.y) >> (16 * (k & 1))) & 0xffffu;
-                    const double pc_z = (double)dv / 1000.0;                              // trackdlo_node.cpp:220
-                    const float x = (float)(((double)j - a.cam.cx) * pc_z / a.cam.fx);    // :222
-                    const float y = (float)(((double)i - a.cam.cy) * pc_z / a.cam.fy);    // :223
-                    const float z = (float)pc_z;                                          // :224
+                    float x, y, z;
+                    if constexpr (kSrc == kSrcView) { x = vx[k]; y = vy[k]; z = vz[k]; }
+                    else {
+                        const unsigned dv = ((k < 2 ? d4.x : d4.y) >> (16 * (k & 1))) & 0xffffu;
+                        const double pc_z = (double)dv / 1000.0;                          // trackdlo_node.cpp:220
+                        x = (float)(((double)j - a.cam.cx) * pc_z / a.cam.fx);            // :222
+                        y = (float)(((double)i - a.cam.cy) * pc_z / a.cam.fy);            // :223
+                        z = (float)pc_z;                                                  // :224
+                    }
                     __hip_atomic_store(a.ex + dst + rnk, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(a.ey + dst + rnk, y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(a.ez + dst + rnk, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -603,7 +621,7 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
                     mn[1] = o1 < mn[1] ? o1 : mn[1]; mx[1] = o1 > mx[1] ? o1 : mx[1];
                     mn[2] = o2 < mn[2] ? o2 : mn[2]; mx[2] = o2 > mx[2] ? o2 : mx[2];
                 }
-                if (++j == a.cols) { j = 0; ++i; }
+                if constexpr (kSrc != kSrcView) { if (++j == a.cols) { j = 0; ++i; } }
             }
         }
         ASTAMP(4);
@@ -659,7 +677,7 @@ __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
 #endif
 
     // ================= phase A: this tile
-    if (cloud_phase_a<kColour>(a, wtot, &sticket, (unsigned *)fsm) != (unsigned)(a.T - 1)) return;
+    if (cloud_phase_a<kColour ? kSrcColour : kSrcMask>(a, wtot, &sticket, (unsigned *)fsm) != (unsigned)(a.T - 1)) return;
 
     // ================= phase B: the workgroup with the last ticket
     FSTAMP(0);
@@ -976,7 +994,7 @@ __device__ __forceinline__ bool team_barrier(unsigned *state, int idx, int K, in
     return *sflag != 0;
 }
 
-template <bool kColour>
+template <int kSrc, typename VT = float, int VFORM = kGeneric>      // the point source of phase A (cloud_phase_a); everything behind it is the same code
 __global__ __launch_bounds__(kFT) void k_cloud_team(const FusedCloud a) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     unsigned short *cnt = (unsigned short *)fsm;                             // [chunk][digit]: lanes of the chunk with the digit, then their start inside the chunk's quarter
@@ -1002,7 +1020,7 @@ __global__ __launch_bounds__(kFT) void k_cloud_team(const FusedCloud a) {
 #ifdef TDLO_CLOUD_STAMPS
     const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();    // (100 MHz) this workgroup's start
 #endif
-    const unsigned ticket = cloud_phase_a<kColour>(a, wtot, &sticket, (unsigned *)fsm);
+    const unsigned ticket = cloud_phase_a<kSrc, VT, VFORM>(a, wtot, &sticket, (unsigned *)fsm);
     const int K = a.T < kTK ? a.T : kTK;
     if ((int)ticket < a.T - K) return;                                       // not in the team: done, having waited for nobody
     const int k = (int)ticket - (a.T - K);                                   // rank in the team
@@ -1352,23 +1370,11 @@ size_t cloud_fused_ws_bytes(int P) {       // beside the multi-launch form's wor
 int cloud_fused_max_points() { return kFNmax; }
 bool cloud_fused_ok(int P) { return ((size_t)P + kFPix - 1) / kFPix <= (size_t)kFTmax; }
 
-// ws: the multi-launch form's workspace (three of its four P-word sort buffers serve as the tiles' regions), fws: cloud_fused_ws_bytes(P)
-// bytes kept by the kernels themselves between the launches (first == true: the state words are initialised by a copy in front of the launch)
-hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], float inv_leaf, void *ws, void *fws,
-                              bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
-                              const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned, const CloudColour *colour) {
-    {   // on every launch, for the CURRENT device, like every other launcher of the library: HIP keeps the attribute per device function, so a
-        // process-wide "done once" flag would leave a second context on another GPU (the exchange tests, a one-process multi-GPU caller) launching
-        // 116 / 160 KB of dynamic LDS without it (ADVICE r05); the call is a table look-up
-        const void *fn = team ? (colour ? (const void *)k_cloud_team<true> : (const void *)k_cloud_team<false>)
-                              : (colour ? (const void *)k_cloud_fused<true> : (const void *)k_cloud_fused<false>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, team ? (int)kTLds : (int)kFLds);
-        if (e != hipSuccess) return e;
-    }
-    FusedCloud a;
-    a.col = colour ? *colour : CloudColour{};
-    a.depth = depth; a.mask = mask; a.P = P; a.cols = cols; a.T = (P + kFPix - 1) / kFPix;
-    a.cam = Cam{cam[0], cam[1], cam[2], cam[3]};
+// what every launch of the one-launch kernels is told, whatever its point source.  ws: the multi-launch form's workspace (three of its four P-word sort
+// buffers serve as the tiles' regions), fws: cloud_fused_ws_bytes(P) bytes kept by the kernels themselves between the launches
+static void fused_describe(FusedCloud &a, int P, float inv_leaf, void *ws, void *fws, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch,
+                           const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned) {
+    a.P = P; a.T = (P + kFPix - 1) / kFPix;
     a.inv_leaf = inv_leaf;
     a.ex = (float *)ws; a.ey = a.ex + P; a.ez = a.ey + P;
     a.state = (unsigned *)fws;                                   // (at a fixed place: another image size finds the words re-armed by the last launch)
@@ -1378,18 +1384,38 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
     a.tcnt = a.thist + kTK * 256 + 64;
     a.X = Xraw; a.cap = cap; a.res = res_pinned; a.epoch = epoch;
     a.visY = vis_nodes_pinned; a.visM = (team && vis_nodes_pinned && vis_M > 0 && vis_M <= 64) ? vis_M : 0; a.visState = vis_state; a.visOut = vis_out_pinned;
+}
+// first == true: the state words are initialised by a copy in front of the launch
+static hipError_t fused_arm(const FusedCloud &a, bool first, hipStream_t s) {
+    if (!first) return hipSuccess;
+    static const unsigned init[16] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // box, tickets, team: abandon word, barrier counter, finish tickets (word 15)
+    return hipMemcpyAsync(a.state, init, sizeof init, hipMemcpyHostToDevice, s);
+}
+
+hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *mask, int P, int cols, const double cam[4], float inv_leaf, void *ws, void *fws,
+                              bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
+                              const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned, const CloudColour *colour) {
+    {   // on every launch, for the CURRENT device, like every other launcher of the library: HIP keeps the attribute per device function, so a
+        // process-wide "done once" flag would leave a second context on another GPU (the exchange tests, a one-process multi-GPU caller) launching
+        // 116 / 160 KB of dynamic LDS without it (ADVICE r05); the call is a table look-up
+        const void *fn = team ? (colour ? (const void *)k_cloud_team<kSrcColour> : (const void *)k_cloud_team<kSrcMask>)
+                              : (colour ? (const void *)k_cloud_fused<true> : (const void *)k_cloud_fused<false>);
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, team ? (int)kTLds : (int)kFLds);
+        if (e != hipSuccess) return e;
+    }
+    FusedCloud a{};
+    a.col = colour ? *colour : CloudColour{};
+    a.depth = depth; a.mask = mask; a.cols = cols;
+    a.cam = Cam{cam[0], cam[1], cam[2], cam[3]};
+    fused_describe(a, P, inv_leaf, ws, fws, team, Xraw, cap, res_pinned, epoch, vis_nodes_pinned, vis_M, vis_state, vis_out_pinned);
     {   // test hook: the n-th team launch of the process loses a team member (the others give the launch up after 2 s; the host runs the multi-launch form)
         static int hook_at = getenv("TDLO_CLOUD_TEAM_FORCE_TIMEOUT") ? atoi(getenv("TDLO_CLOUD_TEAM_FORCE_TIMEOUT")) : 0;
         a.hook = (team && hook_at > 0 && --hook_at == 0) ? 1 : 0;
     }
-    if (first) {
-        static const unsigned init[16] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // box, tickets, team: abandon word, barrier counter, finish tickets (word 15)
-        const hipError_t e = hipMemcpyAsync(a.state, init, sizeof init, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = fused_arm(a, first, s)) return e;
     if (team) {
-        if (colour) hipLaunchKernelGGL(k_cloud_team<true>, dim3(a.T), dim3(kFT), kTLds, s, a);
-        else hipLaunchKernelGGL(k_cloud_team<false>, dim3(a.T), dim3(kFT), kTLds, s, a);
+        if (colour) hipLaunchKernelGGL(k_cloud_team<kSrcColour>, dim3(a.T), dim3(kFT), kTLds, s, a);
+        else hipLaunchKernelGGL(k_cloud_team<kSrcMask>, dim3(a.T), dim3(kFT), kTLds, s, a);
     } else {
         if (colour) hipLaunchKernelGGL(k_cloud_fused<true>, dim3(a.T), dim3(kFT), kFLds, s, a);
         else hipLaunchKernelGGL(k_cloud_fused<false>, dim3(a.T), dim3(kFT), kFLds, s, a);
@@ -1472,6 +1498,30 @@ hipError_t launch_view_bbox(const CloudViewSrc &v, int N, unsigned *bbox, void *
 hipError_t launch_view_voxels(const CloudViewSrc &v, int N, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
                               void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
     return with_view_src(v, [&](const auto &src) { return cloud_voxels_from(src, N, min_b, mul1, mul2, inv_leaf, nodown, passes, n, ws, total_dev, cap, Xraw, s); });
+}
+
+// the team kernel over a view (the load form by cloud_import_form, as for the multi-launch form): N elements, at most 4095 tiles of 4096 (cloud_fused_ok);
+// ws, fws and the rest as for launch_cloud_fused.  k_cloud_fused has no view instantiation, and the test hook of the image launches does not count these.
+template <typename T, int FORM>
+static hipError_t view_team_launch(const FusedCloud &a, hipStream_t s) {
+    const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_team<kSrcView, T, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTLds);      // (per device: see launch_cloud_fused)
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_cloud_team<kSrcView, T, FORM>), dim3(a.T), dim3(kFT), kTLds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,
+                            unsigned epoch, hipStream_t s, const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state, unsigned long long *vis_out_pinned) {
+    if (N <= 0 || !cloud_fused_ok(N)) return hipErrorInvalidValue;
+    FusedCloud a{};
+    a.vdata = v.data; a.vsp = v.stride_point; a.vsc = v.stride_comp; a.vsel = v.select;
+    fused_describe(a, N, inv_leaf, ws, fws, true, Xraw, cap, res_pinned, epoch, vis_nodes_pinned, vis_M, vis_state, vis_out_pinned);
+    if (const hipError_t e = fused_arm(a, first, s)) return e;
+    const int form = cloud_import_form(v.data, v.f64, v.stride_point, v.stride_comp);
+    if (v.f64) return view_team_launch<double, kGeneric>(a, s);
+    if (form == kXyz12) return view_team_launch<float, kXyz12>(a, s);
+    if (form == kCols2) return view_team_launch<float, kCols2>(a, s);
+    return view_team_launch<float, kGeneric>(a, s);
 }
 
 }  // namespace tdlo

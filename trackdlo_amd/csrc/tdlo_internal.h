@@ -309,6 +309,11 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
                               bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
                               const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr, unsigned long long *vis_out_pinned = nullptr,
                               const CloudColour *colour = nullptr);
+// the team kernel with a cloud view as its point source (k_cloud_team's view instantiations; CloudViewSrc as for the multi-launch form): reports like
+// launch_cloud_fused's team launch -- 1 done, 2 not taken, 3 the slot's capacity `cap` does not hold the result (nothing of Xraw is written), 4 given up
+hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,
+                            unsigned epoch, hipStream_t s, const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr,
+                            unsigned long long *vis_out_pinned = nullptr);
 // colour != nullptr above: `mask` is not read, the kernel forms its mask words from the colour image (tdlo_colour_*).  The segmentation on its own
 // (k_colour_mask): mask (rows x cols bytes, 0 / 255) and, when hsv != nullptr, the HSV image (3 bytes a pixel), both device memory padded to 16 bytes beyond the image
 hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s);

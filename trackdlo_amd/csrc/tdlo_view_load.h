@@ -10,14 +10,19 @@
 //   kCols2     float32, stride_point == 1 (column-major), stride_comp even, data 8-byte aligned: two consecutive points (n even, n + 1 < N) by one
 //              aligned 8-byte load per column.
 // Offsets are 64-bit throughout: n * stride_point may pass 2^31 elements.
+// (The forms and the 12-byte point are plain C++, so that tdlo_view_lane.h -- a lane of the one-launch kernel's phase A over a view -- compiles for the host.)
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 
 namespace tdlo {
 
 enum ImportForm { kGeneric = 0, kXyz12 = 1, kCols2 = 2 };
 
 struct __attribute__((packed, aligned(4))) Xyz12 { float x, y, z; };
+
+#if defined(__HIPCC__)
 
 // point n of the view, element by element or (kXyz12) by its one 12-byte load; kCols2 reads a single point element by element
 template <typename T, int FORM>
@@ -35,5 +40,6 @@ __device__ __forceinline__ void view_load_pair(const float *__restrict__ src, lo
     const float *p = src + n;
     a = *reinterpret_cast<const float2 *>(p); b = *reinterpret_cast<const float2 *>(p + sc); c = *reinterpret_cast<const float2 *>(p + 2 * sc);
 }
+#endif
 
 }  // namespace tdlo

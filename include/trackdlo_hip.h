@@ -200,6 +200,19 @@ int tdlo_cpd_lle_batch(tdlo_ctx *ctx, int F, double *Y, int M, double *sigma2,
                        const int *visible_nodes, int n_vis, const double *H_override,
                        tdlo_stats *stats /* F entries */);
 
+/* The batch with per-frame arguments: frame i runs in slots[i] (distinct, any order; NULL: 0..F-1) with its own priors, visible set and H
+ * (args == NULL: none for any frame).  Everything else is as in tdlo_cpd_lle_batch; F == 1 is the one-frame route.  Per frame: priors, K, n_vis (hence the
+ * visibility weighting of trackdlo.cpp:358) and H_override.  Per batch: the E-step kernel, the replica rows of the sums, the sort reused only when every frame
+ * can reuse its own, the dense LLE kernels when one frame cannot take the banded solve.  The E-step is instantiated per launch with or without the
+ * visibility weights: frames that disagree there run as two batches one behind the other.
+ * Bits: with the same E-step kernel on both sides (contexts made under TDLO_ESTEP2=0, or =1) and, with the LLE term, every frame on the banded solve, each
+ * frame's nodes, sigma2 and counts are those of tdlo_cpd_lle_resident with the same arguments, bit for bit; otherwise within the gates DESIGN.md 4 states
+ * between k_estep and k_estep2 (1e-7 m, 1e-5 relative in sigma2) and between the banded and the dense solve.
+ * Every frame's stats are filled (stats[i].status: that frame's verdict); the call returns the first non-zero one. */
+typedef struct { const double *priors; int K; const int *visible_nodes; int n_vis; const double *H_override; } tdlo_frame_args;
+int tdlo_cpd_lle_batch_each(tdlo_ctx *ctx, int F, const int *slots /* distinct; NULL: 0..F-1 */, double *Y, int M, double *sigma2,
+                            const tdlo_params *params, const tdlo_frame_args *args /* F entries; NULL: none */, tdlo_stats *stats /* F */);
+
 /* ---- N-split building blocks (BASELINE.json configs[3]) --------------------------------------- */
 /* When one frame's cloud is split over several GPUs, each rank holds a shard in slot 0 and the
  * host interleaves these calls with an all-reduce (SUM) of the packed buffer
@@ -367,6 +380,40 @@ int tdlo_tracker_tracking_step_view(tdlo_tracker *t, const tdlo_cloud_view *v, i
                                     const int *visible_nodes, int n_vis, const int *visible_nodes_extended, int n_vis_ext,
                                     const double *H_pre, tdlo_stats *stats);
 
+/* ---- F trackers in one call ------------------------------------------------------------------------ */
+/* trackdlo::tracking_step for F trackers of ONE context -- several ropes in a work cell, one rope seen by several cameras, many recorded sequences at
+ * once -- on the clouds resident in the trackers' slots.  The steps are those of tdlo_tracker_tracking_step per tracker; the registrations run as
+ * batches (tdlo_cpd_lle_batch_each): the pre-processing registrations one batch per distinct chain length n_vis_ext[i] (steady state: one; a group of
+ * one takes the one-frame route), the priors per tracker on the host, then all main registrations as one batch of num_of_nodes nodes.  The single
+ * tracker's short cuts (paired set-up, handed-over sums, the M-step launched ahead, the H left behind, the mailbox) do not apply to a batch.
+ * Refused as a whole with TDLO_E_INVALID, before anything is touched, unless: all trackers share one context, their slots are distinct and hold a cloud,
+ * num_of_nodes, precision and the eleven reference parameters are the same, nodes and geodesic coordinates are initialised, and every index list is in
+ * range (visible_nodes_extended: 1 .. num_of_nodes indices).
+ *   visible_nodes / n_vis, visible_nodes_extended / n_vis_ext   F pointers / F counts; visible_nodes may be NULL (nobody visible by distance)
+ *   H_pre     NULL, or F entries each NULL or n_vis_ext[i]^2 doubles
+ *   stats     NULL or 2 F entries: [2 i] pre-processing, [2 i + 1] main registration of tracker i
+ *   rc_each   NULL or F codes.  A tracker whose step ends on TDLO_E_EMPTY, TDLO_E_TRAVERSE or TDLO_E_NUMERIC gets that code and is left as the single
+ *             call leaves it on that error; the other trackers' steps complete.  The call returns the first non-zero code.
+ * Bits: every tracker's nodes, sigma2, guide nodes, priors and counts are those of F tdlo_tracker_tracking_step calls when both sides run the same
+ * E-step kernel (contexts made under TDLO_ESTEP2=0, or =1) and every pre-processing registration takes the banded solve; otherwise they lie within the
+ * gates DESIGN.md 4 states between k_estep and k_estep2 (1e-7 m, 1e-5 relative in sigma2) and between the banded and the dense solve.
+ * Fewer than THREE trackers are stepped one by one by the single call (same route, same cost, same bits on a same-kernel context): at production size
+ * in steady state two trackers cost 0.128 ms as batches against 0.105 ms one by one, three 0.143 against 0.158 ms, 32 0.67 against 1.71 ms
+ * (profiles/tracker_batch_ab.txt; TDLO_TRACKER_BATCH_MIN=n moves the crossover). */
+int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F,
+                                     const int *const *visible_nodes, const int *n_vis,
+                                     const int *const *visible_nodes_extended, const int *n_vis_ext,
+                                     const double *const *H_pre /* NULL, or F entries each NULL or n_vis_ext[i]^2 */,
+                                     tdlo_stats *stats /* NULL or 2 F: [2i] pre-processing, [2i+1] main */, int *rc_each /* NULL or F */);
+/* The frame behind it: tdlo_visibility_prepass_batch of the trackers' current nodes against their resident clouds (visibility_threshold: the trackers'
+ * own), the self-occlusion test per tracker where tdlo_tracker_set_self_occlusion switched it on, then tdlo_tracker_tracking_step_batch -- the bits of
+ * tdlo_visibility_prepass + tdlo_tracker_tracking_step per tracker, under the conditions above.  A tracker without a visible node gets TDLO_E_EMPTY in
+ * rc_each and is not touched; the others go on.  visible_nodes / visible_nodes_extended: F rows of num_of_nodes entries, n_vis / n_vis_ext: F counts;
+ * any of them may be NULL.  stats / rc_each as above. */
+int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
+                             int *visible_nodes /* F x M or NULL */, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                             tdlo_stats *stats, int *rc_each);
+
 /* ---- plain GMM-EM initial registration ------------------------------------ */
 /* reg(pts, Y, sigma2, M, mu, max_iter), trackdlo/src/utils.cpp:21-82 (declared trackdlo/include/utils.h): M centroids
  * fitted to the cloud with the Euclidean membership only; Y (M x 3 column-major) and sigma2 are pure outputs (the
@@ -453,6 +500,21 @@ int tdlo_image_buffers(tdlo_ctx *ctx, int rows, int cols, unsigned short **depth
 int tdlo_visibility_prepass(tdlo_ctx *ctx, int slot, const double *Y, int M, double visibility_threshold, double d_vis,
                             const double *geodesic_coord, double *node_dist, int *visible_nodes, int *n_vis,
                             int *visible_nodes_extended, int *n_vis_ext);
+
+/* The same for F slots in ONE launch and one wait (k_node_min_dist_batch): slots distinct, in any order, each with a resident cloud; Y is F consecutive
+ * M x 3 column-major blocks, geodesic_coord and the outputs F rows of M entries (n_vis / n_vis_ext: F entries); any output pointer may be NULL.
+ * The outputs are those of F tdlo_visibility_prepass calls, bit for bit, on every route: where that call does not take its one-launch kernel
+ * (TDLO_DIRECT_UPLOAD=0, M > 1024), and for F == 1 (the single call is the cheaper one: it has no frame table to fetch), this one loops over it
+ * (tdlo_debug_route_count 30 / 31).  From two slots on the one launch wins: 0.038 against 0.069 ms for two, 0.054 against 1.09 ms for 32
+ * (5 000 points, 45 nodes; profiles/tracker_batch_ab.txt).  A duplicate or empty slot, F < 1, F > max_frames, M < 1:
+ * TDLO_E_INVALID, nothing touched. */
+int tdlo_visibility_prepass_batch(tdlo_ctx *ctx, int F, const int *slots,
+                                  const double *Y /* F consecutive M x 3 column-major blocks */, int M,
+                                  double visibility_threshold, double d_vis,
+                                  const double *geodesic_coord /* F x M */,
+                                  double *node_dist /* F x M */,
+                                  int *visible_nodes /* F x M */, int *n_vis /* F */,
+                                  int *visible_nodes_extended /* F x M */, int *n_vis_ext /* F */);
 
 /* One frame of the ROS node up to tracking_step in one call (trackdlo/src/trackdlo_node.cpp:195-277, :345-360): tdlo_depth_to_cloud followed by
  * tdlo_visibility_prepass of the tracker's current nodes Y against the cloud it has just made resident in `slot` -- the same outputs as the two
@@ -854,6 +916,7 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 27 / 28: tdlo_cloud_view_voxel_grid calls (those of tdlo_cloud_view_voxel_grid_visibility and tdlo_tracker_frame_from_cloud_view among them) served by the
  * one-launch kernel / passed on by it to the multi-launch form, a team that gave up included; calls that the host never hands to it (TDLO_CLOUD_FUSED=0,
  * TDLO_CLOUD_TEAM=0, more than 4095 tiles) count in 21 alone.  29: view frames whose visibility pre-pass rode in that launch.  6 / 7 / 8 count depth frames only.
+ * 30 / 31: tdlo_visibility_prepass_batch calls served by the one launch k_node_min_dist_batch / passed on to tdlo_visibility_prepass slot by slot.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

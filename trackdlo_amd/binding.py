@@ -74,6 +74,10 @@ class ImageView(C.Structure):
     _fields_ = [("data", C.c_void_p), ("format", C.c_int), ("location", C.c_int), ("row_stride", C.c_longlong), ("ready_stream", C.c_void_p)]
 
 
+class FrameArgs(C.Structure):                      # tdlo_frame_args: a frame's own priors, visible set and H in tdlo_cpd_lle_batch_each
+    _fields_ = [("priors", C.c_void_p), ("K", C.c_int), ("visible_nodes", C.c_void_p), ("n_vis", C.c_int), ("H_override", C.c_void_p)]
+
+
 class FrameView(C.Structure):
     """tdlo_frame_view: the images of one frame; an image whose data is NULL is absent."""
     _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
@@ -101,6 +105,7 @@ SYMBOLS = [
     "tdlo_frame_to_cloud_visibility_view", "tdlo_tracker_frame_view", "tdlo_debug_read_images",
     "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view", "tdlo_cloud_view_voxel_grid_visibility",
     "tdlo_sort_pts", "tdlo_sort_pts_host", "tdlo_tracker_initialize_from_cloud", "tdlo_tracker_initialize_from_cloud_view",
+    "tdlo_visibility_prepass_batch", "tdlo_cpd_lle_batch_each", "tdlo_tracker_tracking_step_batch", "tdlo_tracker_frame_batch",
 ]
 
 _lib = None
@@ -165,6 +170,10 @@ def load_library(path: str | None = None):
     lib.tdlo_cpd_lle_resident.argtypes = [vp, ci, vp, ci, C.POINTER(cd), C.POINTER(Params), vp, ci, vp, ci, vp, C.POINTER(Stats)]
     lib.tdlo_cpd_lle.argtypes = [vp, vp, ci, vp, ci, C.POINTER(cd), C.POINTER(Params), vp, ci, vp, ci, vp, C.POINTER(Stats)]
     lib.tdlo_cpd_lle_batch.argtypes = [vp, ci, vp, ci, vp, C.POINTER(Params), vp, ci, vp, ci, vp, vp]
+    lib.tdlo_cpd_lle_batch_each.argtypes = [vp, ci, vp, vp, ci, vp, C.POINTER(Params), vp, vp]
+    lib.tdlo_visibility_prepass_batch.argtypes = [vp, ci, vp, vp, ci, cd, cd, vp, vp, vp, vp, vp, vp]
+    lib.tdlo_tracker_tracking_step_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.tdlo_tracker_frame_batch.argtypes = [vp, ci, cd, vp, vp, vp, vp, vp, vp]
     lib.tdlo_split_begin.argtypes = [vp, vp, ci, cd, C.POINTER(Params), vp, ci, vp, ci, vp, vp]
     lib.tdlo_split_set_global.argtypes = [vp, cd, cd]
     lib.tdlo_split_dmin.argtypes = [vp, vp]
@@ -720,6 +729,31 @@ class Context:
         Yo = Yb.transpose(0, 2, 1)                                 # views: frame i is Yo[i] (M x 3, column-major storage)
         return dict(Y=Yo, sigma2=s2, stats=_StatsView(st))
 
+    def cpd_lle_batch_each(self, slots, Ys, sigma2s, params: Params, priors=None, visible_nodes=None, H=None, check=True):
+        """tdlo_cpd_lle_batch_each: frame i in slots[i] (None: 0..F-1) with its own priors[i] / visible_nodes[i] / H[i] (lists of F entries, an entry
+        or the whole list None: none).  Returns dict(Y, sigma2, stats, rc)."""
+        Ya = np.asarray(Ys, dtype=np.float64)                     # F x M x 3
+        F, M = Ya.shape[0], Ya.shape[1]
+        Yb = np.ascontiguousarray(Ya.transpose(0, 2, 1))           # F consecutive column-major M x 3 blocks
+        s2 = np.array(sigma2s, dtype=np.float64)
+        st = (Stats * F)()
+        sl = None if slots is None else np.ascontiguousarray(slots, dtype=np.int32)
+        assert sl is None or len(sl) == F
+        args = None; keep = []
+        if priors is not None or visible_nodes is not None or H is not None:
+            args = (FrameArgs * F)()
+            for i in range(F):
+                pri, K, vis, nv, Hm = self._opt(None if priors is None else priors[i], None if visible_nodes is None else visible_nodes[i], None if H is None else H[i])
+                keep.append((pri, vis, Hm))
+                args[i].priors = pri.ctypes.data if pri is not None else None; args[i].K = K
+                args[i].visible_nodes = vis.ctypes.data if vis is not None else None; args[i].n_vis = nv
+                args[i].H_override = Hm.ctypes.data if Hm is not None else None
+        rc = self.lib.tdlo_cpd_lle_batch_each(self.h, F, _ptr(sl), _ptr(Yb), M, _ptr(s2), C.byref(params), C.cast(args, C.c_void_p) if args is not None else None,
+                                              C.cast(st, C.c_void_p))
+        if check:
+            self._chk(rc)
+        return dict(Y=Yb.transpose(0, 2, 1), sigma2=s2, stats=_StatsView(st), rc=rc)
+
     # ---- the split registration driven from C++ (tdlo_split_run) -------------------------------------------------------
     def split_run(self, Y, sigma2, params: Params, comm=None, priors=None, visible_nodes=None, H=None, check=True):
         """trackdlo::cpd_lle with the cloud split over the ranks; this rank's shard is the cloud resident in slot 0.
@@ -832,6 +866,24 @@ class Context:
         self._chk(self.lib.tdlo_visibility_prepass(self.h, slot, _ptr(Y), M, float(visibility_threshold), float(d_vis), _ptr(coord),
                                                    _ptr(dist), _ptr(vis), C.byref(nv), _ptr(ext), C.byref(ne)))
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy()
+
+    def prepass_batch_route_counts(self):
+        """[tdlo_visibility_prepass_batch calls served by the one launch, calls passed on slot by slot] (tdlo_debug_route_count 30 / 31)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (30, 31)]
+
+    def visibility_prepass_batch(self, slots, Ys, visibility_threshold, d_vis, coords):
+        """tdlo_visibility_prepass for the F slots in one launch: Ys F x M x 3, coords F x M.  Returns (dist [F x M], [visible_nodes], [visible_nodes_extended])."""
+        Ya = np.asarray(Ys, dtype=np.float64)
+        F, M = Ya.shape[0], Ya.shape[1]
+        Yb = np.ascontiguousarray(Ya.transpose(0, 2, 1))           # F consecutive column-major M x 3 blocks
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        coord = np.ascontiguousarray(coords, dtype=np.float64)
+        assert len(sl) == F and coord.shape == (F, M)
+        dist = np.zeros((F, M)); vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+        nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32)
+        self._chk(self.lib.tdlo_visibility_prepass_batch(self.h, F, _ptr(sl), _ptr(Yb), M, float(visibility_threshold), float(d_vis), _ptr(coord),
+                                                         _ptr(dist), _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne)))
+        return dist, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)]
 
     def reg(self, pts, M, mu=0.05, max_iter=50, slot=0):
         """reg (utils.cpp:21-82): plain GMM-EM.  pts=None: the slot's resident cloud.  Returns (Y [M x 3], sigma2)."""
@@ -1300,6 +1352,50 @@ class trackdlo:
         self._stats_raw = self._st
         if rc:
             self.ctx._chk(rc)
+
+
+def _tracker_table(trackers):
+    F = len(trackers)
+    assert F >= 1
+    return F, (C.c_void_p * F)(*[t.h for t in trackers]), (Stats * (2 * F))(), np.zeros(F, dtype=np.int32)
+
+
+def _batch_done(trackers, st, rcs, rc, check):
+    for i, t in enumerate(trackers):           # the trackers' last_stats, as the single calls fill them
+        t._st[0] = st[2 * i]; t._st[1] = st[2 * i + 1]
+        t._stats_raw = t._st
+    if rc and check:
+        trackers[0].ctx._chk(rc)
+    return [int(r) for r in rcs]
+
+
+def tracking_step_batch(trackers, vis, vext, H_pre=None, check=True):
+    """tdlo_tracker_tracking_step_batch: tracking_step of every tracker (one context, distinct slots) on the cloud resident in its slot; vis / vext /
+    H_pre: lists of F entries (H_pre or an entry of it None: the tracker's own H).  Returns the F per-tracker codes; raises on the first non-zero one
+    unless check=False."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    assert len(vis) == F and len(vext) == F and (H_pre is None or len(H_pre) == F)
+    v = [np.ascontiguousarray(x, dtype=np.int32) for x in vis]
+    ve = [np.ascontiguousarray(x, dtype=np.int32) for x in vext]
+    Hm = None if H_pre is None else [None if h is None else _f64(h) for h in H_pre]
+    pv = (C.c_void_p * F)(*[x.ctypes.data for x in v]); pe = (C.c_void_p * F)(*[x.ctypes.data for x in ve])
+    nv = np.array([len(x) for x in v], dtype=np.int32); ne = np.array([len(x) for x in ve], dtype=np.int32)
+    ph = None if Hm is None else (C.c_void_p * F)(*[None if h is None else h.ctypes.data for h in Hm])
+    rc = trackers[0].ctx.lib.tdlo_tracker_tracking_step_batch(C.cast(tab, C.c_void_p), F, C.cast(pv, C.c_void_p), _ptr(nv), C.cast(pe, C.c_void_p), _ptr(ne),
+                                                              C.cast(ph, C.c_void_p) if ph is not None else None, C.cast(st, C.c_void_p), _ptr(rcs))
+    return _batch_done(trackers, st, rcs, rc, check)
+
+
+def frame_batch(trackers, d_vis, check=True):
+    """tdlo_tracker_frame_batch: the visibility pre-pass of all trackers in one launch, then tracking_step_batch.  Returns (codes, [visible_nodes],
+    [visible_nodes_extended])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    M = trackers[0].M
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frame_batch(C.cast(tab, C.c_void_p), F, float(d_vis), _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), C.cast(st, C.c_void_p), _ptr(rcs))
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)]
 
 
 def calc_LLE_weights(k, Y):

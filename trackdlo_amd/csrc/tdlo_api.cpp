@@ -190,6 +190,13 @@ struct tdlo_ctx {
     // the same bits; init_route: tdlo_debug_route_count 25 / 26 -- calls ordered by k_sort_pts (tdlo_sort_pts among them) / by the host twin
     bool init_sort_host = getenv("TDLO_INIT_SORT") && getenv("TDLO_INIT_SORT")[0] == 'h';
     long long init_route[2] = {0, 0};
+    // the pre-pass of F slots in one launch (k_node_min_dist_batch, tdlo_batch.hip): a state of its own -- [vbat_cap minima | ticket], grown on demand and armed
+    // when allocated, kept armed by the kernel -- and [word | F M minima] in pinned host memory
+    unsigned long long *vbat_state = nullptr, *vbat_res = nullptr;
+    size_t vbat_cap = 0;
+    unsigned vbat_epoch = 0;
+    bool vbat_armed = false;
+    long long vbat_route[2] = {0, 0};    // tdlo_debug_route_count 30 / 31: tdlo_visibility_prepass_batch calls served by the one launch / passed on to tdlo_visibility_prepass per slot
     long long vis_route[2] = {0, 0};     // tdlo_debug_route_count 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel / by the copies + k_node_min_dist
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
@@ -681,6 +688,9 @@ static void estep2_geometry(tdlo_ctx *c, FrameDev &f, bool share) {
     f.nblkE = std::max(1, std::min(nblk, std::min(cap, kMaxEstepBlocks)));
 }
 
+// trackdlo.cpp:358: visible_nodes.size() != Y.rows() && !visible_nodes.empty() && k_vis != 0 -- the registration weighs the memberships by visibility
+static bool frame_vis_branch(int n_vis, int M, const tdlo_params *p) { return n_vis != M && n_vis != 0 && p->k_vis != 0; }
+
 int prepare_frame(tdlo_ctx *c, int slot, const double *Y, int M, double sigma2, const tdlo_params *p,
                   const double *priors, int K, const int *vis, int n_vis, const double *H_override,
                   double *stage, FrameDev &f, bool second_block = false, bool hb_may_stay = true) {      // hb_may_stay: f.Hb may point at Slot::hb_next (a batch moves every frame's Hb into its transfer buffer instead)
@@ -784,7 +794,7 @@ int prepare_frame(tdlo_ctx *c, int slot, const double *Y, int M, double sigma2, 
     f.nblkE = std::max(1, std::min(nblk, cap));
     f.max_iter = p->max_iter; f.include_lle = p->include_lle ? 1 : 0; f.has_priors = K > 0 ? 1 : 0;
     // trackdlo.cpp:358: visible_nodes.size() != Y.rows() && !visible_nodes.empty() && k_vis != 0
-    f.vis_branch = (n_vis != M && n_vis != 0 && p->k_vis != 0) ? 1 : 0;
+    f.vis_branch = frame_vis_branch(n_vis, M, p) ? 1 : 0;
     (void)vis;
     f.precision = p->precision;
     // which M-step: decided here, once per frame (the launchers dispatch on the descriptor, not on the process-wide toggles)
@@ -969,7 +979,7 @@ static bool any_frame_ended_with(int status, const double *blocks, size_t stride
 
 int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
                const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats,
-               const LatePriors *late = nullptr);
+               const LatePriors *late = nullptr, const tdlo_frame_args *each = nullptr);
 
 // a paired registration's first M-step may already be waiting on the stream (launched by the previous call): released when the priors are staged,
 // told to leave on every other way out of run_frames
@@ -984,7 +994,9 @@ struct SpecGuard {
 struct FramesCall {
     // the arguments
     tdlo_ctx *const c; const int F; const int *const slots; double *const Y; const int M; double *const sigma2; const tdlo_params *const p;
-    const double *const priors; const int K; const int *const vis; const int n_vis; const double *const H_override; tdlo_stats *const stats;
+    // priors / visible set / H per frame (F entries): the caller's own (tdlo_cpd_lle_batch_each, a batch of trackers), or the call's shared ones F times
+    std::vector<tdlo_frame_args> fa;
+    tdlo_stats *const stats;
     const LatePriors *const late;
     const int iter_hint;          // tdlo_ctx::iter_hint as this call found it
     const bool timing;
@@ -1026,8 +1038,10 @@ struct FramesCall {
     SpecGuard sg;
 
     FramesCall(tdlo_ctx *c_, int F_, const int *slots_, double *Y_, int M_, double *sigma2_, const tdlo_params *p_, const double *priors_, int K_,
-               const int *vis_, int n_vis_, const double *H_override_, tdlo_stats *stats_, const LatePriors *late_, int iter_hint_)
-        : c(c_), F(F_), slots(slots_), Y(Y_), M(M_), sigma2(sigma2_), p(p_), priors(priors_), K(K_), vis(vis_), n_vis(n_vis_), H_override(H_override_),
+               const int *vis_, int n_vis_, const double *H_override_, tdlo_stats *stats_, const LatePriors *late_, int iter_hint_,
+               const tdlo_frame_args *each_)
+        : c(c_), F(F_), slots(slots_), Y(Y_), M(M_), sigma2(sigma2_), p(p_),
+          fa(each_ ? std::vector<tdlo_frame_args>(each_, each_ + (F_ > 0 ? F_ : 0)) : std::vector<tdlo_frame_args>(F_ > 0 ? F_ : 0, tdlo_frame_args{priors_, K_, vis_, n_vis_, H_override_})),
           stats(stats_), late(late_), iter_hint(iter_hint_), timing(c_->timing), nc(M_), merged(F_ > 1),
           up(upload_doubles(nc, p_, p_->include_lle && mstep_band_enabled() && !c_->lle_dense_once)), ustride(merged ? up : nc.upload),
           fdd(((size_t)F_ * sizeof(FrameDev) + 15) / 16 * 2), sg{c_} {}
@@ -1074,7 +1088,7 @@ void FramesCall::recognise_pair() {
     if (late && c->pair.state == 2) {
         const tdlo_ctx::PairNext &pn = c->pair;
         const Slot &sl = slot0();
-        const bool same = F == 1 && !priors && !H_override && pn.slot == slots[0] && pn.M == M && pn.n_vis == n_vis && pn.sigma2 == sigma2[0] && same_params(pn.p, *p) &&
+        const bool same = F == 1 && !fa[0].priors && !fa[0].H_override && pn.slot == slots[0] && pn.M == M && pn.n_vis == fa[0].n_vis && pn.sigma2 == sigma2[0] && same_params(pn.p, *p) &&
                           std::memcmp(pn.Y.data(), Y, sizeof(double) * 3 * M) == 0 && pn.f.wide_tile != 0;
         if (pn.ahead) paired = ahead = same && c->stream2[0] != nullptr;
         else paired = same && sl.sorted_valid && sl.sorted_prec == p->precision &&
@@ -1095,7 +1109,8 @@ void FramesCall::recognise_pair() {
 int FramesCall::stage_frames() {
     for (int pass = 0; pass < 2 && !paired; ++pass) {
         for (int i = 0; i < F; ++i) {
-            const int rc = prepare_frame(c, slots[i], Y + (size_t)i * 3 * M, M, sigma2[i], p, priors, K, vis, n_vis, H_override,
+            const tdlo_frame_args &a = fa[i];
+            const int rc = prepare_frame(c, slots[i], Y + (size_t)i * 3 * M, M, sigma2[i], p, a.priors, a.K, a.visible_nodes, a.n_vis, a.H_override,
                                          c->pin + (size_t)i * ustride, c->fh[i], false, !merged);
             if (rc) return rc;
             if (merged) {
@@ -1142,6 +1157,9 @@ int FramesCall::choose_batch_kernels() {
         for (int i = 0; i < F; ++i) small = small && c->fh[i].nblkE <= 64 && !c->fh[i].mstep_dense && c->fh[i].M <= kChunk;
         if (small) for (int i = 0; i < F; ++i) c->fh[i].acc_rows = 2;
     }
+    // the E-step and k_dmin are instantiated per launch with or without the visibility weights (trackdlo.cpp:358): frames with per-frame visible sets that
+    // disagree here are split into two calls by the entry points (run_frames_each)
+    for (int i = 1; i < F; ++i) if (c->fh[i].vis_branch != c->fh[0].vis_branch) return fail(c, TDLO_E_INVALID, "internal: a batch's frames disagree about the visibility weights");
     if (!two) for (int i = 0; i < F; ++i) if (c->fh[i].estep2) return fail(c, TDLO_E_INVALID, "internal: a batch's frames disagree about the E-step kernel");   //  same M, precision and mode -- they cannot)
     return 0;
 }
@@ -1545,7 +1563,7 @@ bool FramesCall::repeat(int *rc) {
         drop_what_was_launched_ahead();
         c->lle_dense_once = true;
         ++c->band_retries;
-        *rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
+        *rc = run_frames(c, F, slots, Y, M, sigma2, p, nullptr, 0, nullptr, 0, nullptr, stats, nullptr, fa.data());
         c->lle_dense_once = false;
         return true;
     }
@@ -1558,7 +1576,7 @@ bool FramesCall::repeat(int *rc) {
         c->boost_off_once = true;
         ++c->boost_retries;
         for (int i = 0; i < F; ++i) c->slots[slots[i]].sorted_valid = false;
-        *rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late);      // (late priors: formed again from the same guide nodes)
+        *rc = run_frames(c, F, slots, Y, M, sigma2, p, nullptr, 0, nullptr, 0, nullptr, stats, late, fa.data());      // (late priors: formed again from the same guide nodes)
         c->boost_off_once = false;
         return true;
     }
@@ -1610,7 +1628,7 @@ int FramesCall::results_out(std::chrono::steady_clock::time_point t_host0) {
 // Shared driver of tdlo_cpd_lle_resident / _batch.
 int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
                const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats,
-               const LatePriors *late) {
+               const LatePriors *late, const tdlo_frame_args *each) {
     const auto t_host0 = std::chrono::steady_clock::now();
     int rc = check_params(c, M, p);
     if (rc) return rc;
@@ -1619,7 +1637,7 @@ int run_frames(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *s
     c->iter_hint = 0;
     if (late && F != 1) return fail(c, TDLO_E_INVALID, "late priors: one frame per call");
     if (F < 1 || F > c->cfg.max_frames) return fail(c, TDLO_E_INVALID, "bad frame count");
-    FramesCall k(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late, iter_hint);
+    FramesCall k(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, late, iter_hint, each);
     if ((rc = k.size_staging())) return rc;             // the pinned staging buffer, a batch's transfer buffer
     k.recognise_pair();                                 // tracking_step's second registration, set up (or begun) by the first one's call
     if ((rc = k.stage_frames())) return rc;             // upload blocks and descriptors; a batch's kernels
@@ -1724,6 +1742,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
     if (c->vis_nodes_pin) hipHostFree(c->vis_nodes_pin);
+    if (c->vbat_state) hipFree(c->vbat_state);
+    if (c->vbat_res) hipHostFree(c->vbat_res);
     if (c->cloud_res) hipHostFree(c->cloud_res);
     if (c->img_pin) hipHostFree(c->img_pin);
     if (c->col_pin) hipHostFree(c->col_pin);
@@ -1898,11 +1918,12 @@ int tdlo_get_cloud(tdlo_ctx *c, int slot, double *X_out, int x_capacity, int *n_
 // clouds -- the context is taken off the fused prologue (fuse_fallback: arrivals and barrier word reset, fuse_on = false) and the call repeated
 // ONCE on the copy + three-kernel route.  (tracking_step's main registration does the same around its own call: it forms its priors again.)
 static int run_frames_checked(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
-                              const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats) {
-    int rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
+                              const double *priors, int K, const int *vis, int n_vis, const double *H_override, tdlo_stats *stats,
+                              const tdlo_frame_args *each = nullptr) {
+    int rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, nullptr, each);
     if (rc == TDLO_E_FUSE) {
         fuse_fallback(c);
-        rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);
+        rc = run_frames(c, F, slots, Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats, nullptr, each);
         if (rc == TDLO_E_FUSE) rc = fail(c, TDLO_E_HIP, "the fused prologue reported a time-out on the route that does not use it");
     }
     return rc;
@@ -1935,6 +1956,56 @@ int tdlo_cpd_lle_batch(tdlo_ctx *c, int F, double *Y, int M, double *sigma2, con
     std::vector<int> slots(F);
     for (int i = 0; i < F; ++i) slots[i] = i;
     return run_frames_checked(c, F, slots.data(), Y, M, sigma2, p, priors, K, vis, n_vis, H_override, stats);      // (F == 1 takes the fused prologue like a single call)
+}
+
+// A batch whose frames bring their own priors, visible sets and H (args == NULL: none).  One frame is the one-frame route.  The E-step kernels
+// are instantiated per launch with or without the visibility weights (FrameDev::vis_branch), so frames that disagree there run as two batches, one behind the
+// other -- independent registrations: the results do not depend on the split.  Every frame's statistics are filled; returns the first non-zero code.
+static int run_frames_each(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p, const tdlo_frame_args *args, tdlo_stats *stats) {
+    if (F == 1) {
+        const tdlo_frame_args a = args ? args[0] : tdlo_frame_args{nullptr, 0, nullptr, 0, nullptr};
+        return run_frames_checked(c, 1, slots, Y, M, sigma2, p, a.priors, a.K, a.visible_nodes, a.n_vis, a.H_override, stats);
+    }
+    if (!p) return fail(c, TDLO_E_INVALID, "params is null");
+    std::vector<tdlo_frame_args> none;
+    if (!args) { none.assign(F, tdlo_frame_args{nullptr, 0, nullptr, 0, nullptr}); args = none.data(); }
+    std::vector<int> grp[2];
+    for (int i = 0; i < F; ++i) grp[frame_vis_branch(args[i].n_vis, M, p) ? 1 : 0].push_back(i);
+    if (grp[0].empty() || grp[1].empty()) return run_frames_checked(c, F, slots, Y, M, sigma2, p, nullptr, 0, nullptr, 0, nullptr, stats, args);
+    int first = 0;
+    for (const std::vector<int> &g : grp) {
+        const int Fg = (int)g.size();
+        std::vector<int> sl(Fg); std::vector<double> Yg(3 * (size_t)M * Fg), s2(Fg); std::vector<tdlo_frame_args> ag(Fg); std::vector<tdlo_stats> sg(Fg);
+        for (int k = 0; k < Fg; ++k) {
+            const int i = g[k];
+            sl[k] = slots[i]; s2[k] = sigma2[i]; ag[k] = args[i];
+            std::memcpy(&Yg[3 * (size_t)M * k], Y + 3 * (size_t)M * i, sizeof(double) * 3 * M);
+        }
+        const int rc = run_frames_each(c, Fg, sl.data(), Yg.data(), M, s2.data(), p, ag.data(), sg.data());
+        for (int k = 0; k < Fg; ++k) {
+            const int i = g[k];
+            sigma2[i] = s2[k];
+            std::memcpy(Y + 3 * (size_t)M * i, &Yg[3 * (size_t)M * k], sizeof(double) * 3 * M);
+            if (stats) stats[i] = sg[k];
+        }
+        if (rc && !first) first = rc;
+    }
+    return first;
+}
+
+int tdlo_cpd_lle_batch_each(tdlo_ctx *c, int F, const int *slots, double *Y, int M, double *sigma2, const tdlo_params *p,
+                            const tdlo_frame_args *args, tdlo_stats *stats) {
+    if (!c) return TDLO_E_INVALID;
+    if (F < 1 || F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad frame count");
+    if (!Y || !sigma2) return fail(c, TDLO_E_INVALID, "null Y / sigma2");
+    std::vector<int> own(F);
+    for (int i = 0; i < F; ++i) {
+        own[i] = slots ? slots[i] : i;
+        if (own[i] < 0 || own[i] >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+        for (int j = 0; j < i; ++j) if (own[j] == own[i]) return fail(c, TDLO_E_INVALID, "the slots of a batch must be distinct");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_frames_each(c, F, own.data(), Y, M, sigma2, p, args, stats);
 }
 
 // ---- N-split -------------------------------------------------------------------------------------
@@ -3202,6 +3273,103 @@ int tdlo_visibility_prepass(tdlo_ctx *c, int slot, const double *Y, int M, doubl
     return TDLO_OK;      // an empty visible set is reported as n_vis = 0 (the reference underflows at :351)
 }
 
+// the batch's own state for F M minima: replaced by a larger one (the stream drained first), armed when allocated or after a launch that did not report
+static int ensure_vbat_state(tdlo_ctx *c, size_t FM) {
+    if (FM > c->vbat_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->vbat_state) hipFree(c->vbat_state);
+        if (c->vbat_res) hipHostFree(c->vbat_res);
+        c->vbat_state = nullptr; c->vbat_res = nullptr; c->vbat_cap = 0;
+        const size_t cap = (FM + 1023) & ~(size_t)1023;
+        HIPCHK(c, hipMalloc((void **)&c->vbat_state, sizeof(unsigned long long) * (cap + 8)));
+        HIPCHK(c, hipHostMalloc((void **)&c->vbat_res, sizeof(unsigned long long) * (cap + 8), hipHostMallocDefault));
+        std::memset(c->vbat_res, 0, sizeof(unsigned long long) * (cap + 8));
+        c->vbat_cap = cap; c->vbat_armed = false; c->vbat_epoch = 0;
+    }
+    if (!c->vbat_armed) {
+        std::vector<unsigned long long> init(c->vbat_cap + 8, 0x7ff0000000000000ull);
+        for (size_t i = c->vbat_cap; i < c->vbat_cap + 8; ++i) init[i] = 0ull;
+        HIPCHK(c, hipMemcpy(c->vbat_state, init.data(), sizeof(unsigned long long) * init.size(), hipMemcpyHostToDevice));
+        c->vbat_armed = true;
+    }
+    return TDLO_OK;
+}
+
+// tdlo_visibility_prepass for F slots: ONE launch and one wait (k_node_min_dist_batch), then the thresholding and gap fill per frame.  Where the single call
+// does not take its one-launch kernel (TDLO_DIRECT_UPLOAD=0, M > 1024), and for one slot, the call loops over it.  The bits are the single call's on every route.
+int tdlo_visibility_prepass_batch(tdlo_ctx *c, int F, const int *slots, const double *Y, int M, double visibility_threshold, double d_vis,
+                                  const double *geodesic_coord, double *node_dist, int *visible_nodes, int *n_vis,
+                                  int *visible_nodes_extended, int *n_vis_ext) {
+    if (!c) return TDLO_E_INVALID;
+    if (F < 1 || F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad frame count");
+    if (!slots || !Y || M < 1 || !geodesic_coord) return fail(c, TDLO_E_INVALID, "null slots / Y / geodesic_coord");
+    for (int i = 0; i < F; ++i) {
+        if (slots[i] < 0 || slots[i] >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+        for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(c, TDLO_E_INVALID, "the slots of a batch must be distinct");
+        if (c->slots[slots[i]].N0 <= 0) return fail(c, TDLO_E_INVALID, "no cloud resident in slot (call tdlo_set_cloud)");
+    }
+    auto at = [&](auto *p, int i) { return p ? p + (size_t)i * M : nullptr; };
+    auto at1 = [&](int *p, int i) { return p ? p + i : nullptr; };
+    if (F == 1 || !c->direct_in || M > kMaxNodes) {      // (one slot: the single call's kernel has no frame table to fetch first -- 0.035 against 0.044 ms for one slot, profiles/tracker_batch_ab.txt)
+        ++c->vbat_route[1];
+        for (int i = 0; i < F; ++i) {
+            const int rc = tdlo_visibility_prepass(c, slots[i], Y + (size_t)i * 3 * M, M, visibility_threshold, d_vis, geodesic_coord + (size_t)i * M, at(node_dist, i),
+                                                   at(visible_nodes, i), at1(n_vis, i), at(visible_nodes_extended, i), at1(n_vis_ext, i));
+            if (rc) return rc;
+        }
+        return TDLO_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    const size_t FM = (size_t)F * M;
+    // the pinned staging block: [VisBatchFrame x F | wg0 x (F + 1) | F node blocks]
+    const size_t tab_doubles = ((size_t)F * sizeof(VisBatchFrame) + 7) / 8, wg_doubles = ((size_t)(F + 1) * sizeof(int) + 7) / 8;
+    if ((rc = ensure_pin(c, tab_doubles + wg_doubles + 3 * FM + 8))) return rc;
+    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+    if ((rc = ensure_vbat_state(c, FM))) return rc;
+    VisBatchFrame *tab = (VisBatchFrame *)c->pin;
+    int *wg0 = (int *)(c->pin + tab_doubles);
+    double *Yp = c->pin + tab_doubles + wg_doubles;
+    int nwg = 0;
+    for (int i = 0; i < F; ++i) {
+        const Slot &s = c->slots[slots[i]];
+        tab[i].X = s.Xraw; tab[i].N0 = s.N0; tab[i].pad = 0;
+        wg0[i] = nwg;
+        nwg += node_min_dist_batch_wgs(s.N0);
+    }
+    wg0[F] = nwg;
+    std::memcpy(Yp, Y, sizeof(double) * 3 * FM);
+    hipStream_t st = c->stream;
+    if (++c->vbat_epoch == 0) ++c->vbat_epoch;
+    ++c->vbat_route[0];
+    HIPCHK(c, launch_node_min_dist_batch(tab, wg0, Yp, F, M, nwg, c->vbat_state, c->vbat_state + c->vbat_cap, c->vbat_res, c->vbat_epoch, st));
+    auto t_chk = std::chrono::steady_clock::now();
+    for (unsigned spins = 1;; ++spins) {
+        if ((unsigned)__atomic_load_n(c->vbat_res, __ATOMIC_ACQUIRE) == c->vbat_epoch) break;
+        if ((spins & 255u) == 0) {
+            const auto now = std::chrono::steady_clock::now();
+            if (std::chrono::duration<double, std::micro>(now - t_chk).count() > 500.0) {
+                t_chk = now;
+                const hipError_t e = hipStreamQuery(st);
+                if (e == hipSuccess) {
+                    if ((unsigned)__atomic_load_n(c->vbat_res, __ATOMIC_ACQUIRE) == c->vbat_epoch) break;
+                    c->vbat_armed = false;
+                    return fail(c, TDLO_E_HIP, "the stream drained, but the batched visibility pre-pass did not report");
+                }
+                if (e != hipErrorNotReady) { c->vbat_armed = false; return fail(c, TDLO_E_HIP, std::string("stream: ") + hipGetErrorString(e)); }
+            }
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    const double *mins = (const double *)(c->vbat_res + 1);
+    for (int i = 0; i < F; ++i)
+        vis_threshold_and_fill(mins + (size_t)i * M, M, visibility_threshold, d_vis, geodesic_coord + (size_t)i * M, at(node_dist, i), at(visible_nodes, i), at1(n_vis, i),
+                               at(visible_nodes_extended, i), at1(n_vis_ext, i));
+    return TDLO_OK;
+}
+
 // trackdlo_node.cpp:348-360: occluded runs shorter than d_vis (in the geodesic coordinate) between two visible nodes are filled in
 static void fill_visible_gaps(const std::vector<int> &vis, const double *geodesic_coord, double d_vis, std::vector<int> &ext) {
     ext.clear();
@@ -3637,7 +3805,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 29) return -1;
+    if (!c || which < 0 || which > 31) return -1;
+    if (which >= 30) return c->vbat_route[which - 30];
     if (which >= 27) return c->view_team_route[which - 27];
     if (which >= 25) return c->init_route[which - 25];
     if (which == 24) return c->fused_w0_calls;
@@ -3961,6 +4130,62 @@ int tdlo_tracker_get_correspondence_pairs(const tdlo_tracker *t, double *out, in
     return K;
 }
 
+// The priors of tracking_step's main registration (trackdlo.cpp:929-995), formed from the pre-processing registration's result in t->guide_nodes for the
+// visible nodes in t->vis_ext; vis / n_vis: the frame's visible_nodes (the anchor search of :980-995).  Appends to / replaces t->priors as the reference does.
+static int tracker_form_priors(tdlo_tracker *t, const int *vis, int n_vis) {
+    tdlo_ctx *c = t->ctx;
+    const int M = t->M, Mg = t->Mg;
+    std::vector<int> &ve = t->vis_ext;
+    std::vector<double> &p1 = t->trav1, &p2 = t->trav2;
+    const double *guide = t->guide_nodes.data();
+    auto trav = [&](int alignment, int anchor, std::vector<double> &out) {
+        return traverse_euclidean(t->geodesic_coord, guide, Mg, ve, alignment, anchor, out);
+    };
+    const char *oob = "traverse_euclidean: the reference would index out of bounds for these visible nodes";
+    if (Mg == M) {                                                       // all visible / minor occlusion (:929-957)
+        const int n1 = trav(0, -1, p1), n2 = trav(1, -1, p2);
+        if (n1 <= 0 || n2 <= 0) return fail(c, TDLO_E_TRAVERSE, oob);
+        // p2 runs tail -> head; bring it to ascending order (:942)
+        std::vector<double> &r2 = t->trav2r;
+        r2.resize(p2.size());
+        for (int i = 0; i < n2; ++i) std::memcpy(&r2[4 * i], &p2[4 * (n2 - 1 - i)], 4 * sizeof(double));
+        t->priors.reserve(t->priors.size() + 4 * (size_t)M);
+        for (int i = 0; i < M; ++i) {
+            const long long j2 = (long long)i - ((long long)M - n2);     // unsigned in the reference: negative == huge
+            const bool j2_ok = j2 >= 0 && j2 < n2;
+            if ((double)i < r2[0] && i < n1) {
+                t->priors.insert(t->priors.end(), &p1[4 * i], &p1[4 * i] + 4);
+            } else if ((double)i > p1[4 * (n1 - 1)] && j2_ok) {
+                t->priors.insert(t->priors.end(), &r2[4 * j2], &r2[4 * j2] + 4);
+            } else {
+                if (i >= n1 || !j2_ok) return fail(c, TDLO_E_TRAVERSE, oob);
+                for (int k = 0; k < 4; ++k) t->priors.push_back((p1[4 * i + k] + r2[4 * j2 + k]) / 2.0);    // :954
+            }
+        }
+    } else if (ve.front() == 0 && ve.back() == M - 1) {                  // mid-section occluded (:958-967)
+        if (trav(0, -1, p1) < 0 || trav(1, -1, p2) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
+        t->priors = p1;
+        t->priors.insert(t->priors.end(), p2.begin(), p2.end());
+    } else if (ve.front() == 0) {                                        // tail occluded (:968-973)
+        if (trav(0, -1, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
+        t->priors = p1;
+    } else if (ve.back() == M - 1) {                                     // head occluded (:974-979)
+        if (trav(1, -1, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
+        t->priors = p1;
+    } else {                                                             // both ends occluded (:980-995)
+        int anchor = -1; double moved = 999999;
+        for (int i = 0; i < n_vis && i < Mg; ++i) {                      // reference pairs visible_nodes[i] with guide row i
+            double s = 0;
+            for (int d = 0; d < 3; ++d) { const double e = t->Y[d * M + vis[i]] - t->guide_nodes[d * Mg + i]; s += e * e; }
+            const double dd = std::sqrt(s);
+            if (dd < moved) { moved = dd; anchor = i; }
+        }
+        if (trav(2, anchor, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
+        t->priors = p1;
+    }
+    return 0;
+}
+
 // tdlo_tracker_tracking_step / _view: the frame's cloud is X (N x 3 column-major doubles), the view v, or -- both null -- what is resident in the slot
 static int tracking_step_impl(tdlo_tracker *t, const double *X, const tdlo_cloud_view *v, int N, const int *vis, int n_vis,
                               const int *vis_ext, int n_ext, const double *H_pre, tdlo_stats *stats) {
@@ -4056,60 +4281,13 @@ static int tracking_step_impl(tdlo_tracker *t, const double *X, const tdlo_cloud
         return rc;
     }
 
-    std::vector<int> &ve = t->vis_ext;
-    ve.assign(vis_ext, vis_ext + n_ext);
-    std::vector<double> &p1 = t->trav1, &p2 = t->trav2;
-    const double *guide = t->guide_nodes.data();
-    auto trav = [&](int alignment, int anchor, std::vector<double> &out) {
-        return traverse_euclidean(t->geodesic_coord, guide, Mg, ve, alignment, anchor, out);
-    };
-    const char *oob = "traverse_euclidean: the reference would index out of bounds for these visible nodes";
+    t->vis_ext.assign(vis_ext, vis_ext + n_ext);
     // The priors of the main registration (:929-995), formed from the pre-processing registration's result.  As a function: the main registration's
     // set-up kernel does not need them, so run_frames launches it first and calls this while it runs (LatePriors).
     const LatePriors form_priors = [&](const double *&lp, int &lk) -> int {
-    if (Mg == M) {                                                       // all visible / minor occlusion (:929-957)
-        const int n1 = trav(0, -1, p1), n2 = trav(1, -1, p2);
-        if (n1 <= 0 || n2 <= 0) return fail(c, TDLO_E_TRAVERSE, oob);
-        // p2 runs tail -> head; bring it to ascending order (:942)
-        std::vector<double> &r2 = t->trav2r;
-        r2.resize(p2.size());
-        for (int i = 0; i < n2; ++i) std::memcpy(&r2[4 * i], &p2[4 * (n2 - 1 - i)], 4 * sizeof(double));
-        t->priors.reserve(t->priors.size() + 4 * (size_t)M);
-        for (int i = 0; i < M; ++i) {
-            const long long j2 = (long long)i - ((long long)M - n2);     // unsigned in the reference: negative == huge
-            const bool j2_ok = j2 >= 0 && j2 < n2;
-            if ((double)i < r2[0] && i < n1) {
-                t->priors.insert(t->priors.end(), &p1[4 * i], &p1[4 * i] + 4);
-            } else if ((double)i > p1[4 * (n1 - 1)] && j2_ok) {
-                t->priors.insert(t->priors.end(), &r2[4 * j2], &r2[4 * j2] + 4);
-            } else {
-                if (i >= n1 || !j2_ok) return fail(c, TDLO_E_TRAVERSE, oob);
-                for (int k = 0; k < 4; ++k) t->priors.push_back((p1[4 * i + k] + r2[4 * j2 + k]) / 2.0);    // :954
-            }
-        }
-    } else if (ve.front() == 0 && ve.back() == M - 1) {                  // mid-section occluded (:958-967)
-        if (trav(0, -1, p1) < 0 || trav(1, -1, p2) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
-        t->priors = p1;
-        t->priors.insert(t->priors.end(), p2.begin(), p2.end());
-    } else if (ve.front() == 0) {                                        // tail occluded (:968-973)
-        if (trav(0, -1, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
-        t->priors = p1;
-    } else if (ve.back() == M - 1) {                                     // head occluded (:974-979)
-        if (trav(1, -1, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
-        t->priors = p1;
-    } else {                                                             // both ends occluded (:980-995)
-        int anchor = -1; double moved = 999999;
-        for (int i = 0; i < n_vis && i < Mg; ++i) {                      // reference pairs visible_nodes[i] with guide row i
-            double s = 0;
-            for (int d = 0; d < 3; ++d) { const double e = t->Y[d * M + vis[i]] - t->guide_nodes[d * Mg + i]; s += e * e; }
-            const double dd = std::sqrt(s);
-            if (dd < moved) { moved = dd; anchor = i; }
-        }
-        if (trav(2, anchor, p1) < 0) return fail(c, TDLO_E_TRAVERSE, oob);
-        t->priors = p1;
-    }
-    lp = t->priors.data(); lk = (int)(t->priors.size() / 4);
-    return 0;
+        if (const int prc = tracker_form_priors(t, vis, n_vis)) return prc;
+        lp = t->priors.data(); lk = (int)(t->priors.size() / 4);
+        return 0;
     };
 
     // main registration (:998): include_lle = false, priors, alpha, visible_nodes_extended, k_vis (mp, above)
@@ -4254,6 +4432,224 @@ int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v
     if (n == 0) return fail(c, TDLO_E_EMPTY, "no point of the view is kept: no cloud for this frame");
     if (ne == 0) return fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)");
     return tdlo_tracker_tracking_step(t, nullptr, 0, vv.data(), nv, ve.data(), ne, nullptr, stats);
+}
+
+// ---- F trackers in one call ----------------------------------------------------------------------
+// Below this many trackers tdlo_tracker_tracking_step_batch / tdlo_tracker_frame_batch step them one by one with the single calls (which keep their short
+// cuts: paired set-up, handed-over sums, the M-step launched ahead); from here on the registrations run as run_frames batches.
+// Measured at production size, steady state (profiles/tracker_batch_ab.txt): two trackers 0.128 ms as batches against 0.105 ms one by one, three 0.143 against 0.158.
+// TDLO_TRACKER_BATCH_MIN=n overrides (the measurement forces 2 to show both sides at every size).
+constexpr int kTrackerBatchMin = 3;
+static int tracker_batch_min() {
+    static const int env = getenv("TDLO_TRACKER_BATCH_MIN") ? atoi(getenv("TDLO_TRACKER_BATCH_MIN")) : 0;
+    return env >= 1 ? env : kTrackerBatchMin;
+}
+
+// what a batch of trackers must share (one context, distinct slots with a cloud each, node count, precision, the eleven reference parameters, nodes and
+// geodesic coordinates initialised): the reason it does not, or nullptr
+static const char *tracker_batch_refusal(tdlo_tracker *const *tr, int F) {
+    if (!tr || F < 1 || !tr[0]) return "no trackers";
+    const tdlo_tracker *a = tr[0];
+    if (F > (int)a->ctx->slots.size()) return "more trackers than the context has slots";
+    for (int i = 0; i < F; ++i) {
+        const tdlo_tracker *t = tr[i];
+        if (!t) return "a tracker is null";
+        if (t->ctx != a->ctx) return "the trackers of a batch share one context";
+        for (int j = 0; j < i; ++j) if (tr[j]->slot == t->slot) return "the trackers of a batch have distinct slots";
+        if (t->M != a->M || t->precision != a->precision) return "the trackers of a batch share num_of_nodes and precision";
+        if (t->visibility_threshold != a->visibility_threshold || t->beta != a->beta || t->lambda != a->lambda || t->alpha != a->alpha || t->k_vis != a->k_vis ||
+            t->mu != a->mu || t->max_iter != a->max_iter || t->tol != a->tol || t->beta_pre_proc != a->beta_pre_proc || t->lambda_pre_proc != a->lambda_pre_proc ||
+            t->lle_weight != a->lle_weight) return "the trackers of a batch share the reference's parameters";
+        if (t->geodesic_coord.size() != (size_t)t->M || t->Y.size() != 3 * (size_t)t->M) return "a tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)";
+        if (t->ctx->slots[t->slot].N0 <= 0) return "no cloud is resident in a tracker's slot";
+    }
+    return nullptr;
+}
+
+int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F, const int *const *visible_nodes, const int *n_vis,
+                                     const int *const *visible_nodes_extended, const int *n_vis_ext, const double *const *H_pre,
+                                     tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
+    if (!visible_nodes_extended || !n_vis_ext) return fail(c, TDLO_E_INVALID, "null visible_nodes_extended / n_vis_ext");
+    const int M = trackers[0]->M;
+    auto nv = [&](int i) { return (visible_nodes && n_vis && visible_nodes[i]) ? n_vis[i] : 0; };
+    for (int i = 0; i < F; ++i) {
+        const int ne = n_vis_ext[i];
+        if (!visible_nodes_extended[i] || ne <= 0 || ne > M) return fail(c, TDLO_E_INVALID, "visible_nodes_extended must hold 1..M indices (empty is undefined in the reference, trackdlo_node.cpp:351)");
+        for (int k = 0; k < ne; ++k) if (visible_nodes_extended[i][k] < 0 || visible_nodes_extended[i][k] >= M) return fail(c, TDLO_E_INVALID, "visible_nodes_extended index out of range");
+        if (nv(i) < 0) return fail(c, TDLO_E_INVALID, "n_vis < 0");
+        for (int k = 0; k < nv(i); ++k) if (visible_nodes[i][k] < 0 || visible_nodes[i][k] >= M) return fail(c, TDLO_E_INVALID, "visible_nodes index out of range");
+    }
+    std::vector<int> rcs(F, 0);
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    auto finish = [&]() {
+        if (stats) std::copy(st.begin(), st.end(), stats);
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int i = 0; i < F; ++i) if (rcs[i]) return rcs[i];
+        return (int)TDLO_OK;
+    };
+    if (F < tracker_batch_min()) {
+        for (int i = 0; i < F; ++i)
+            rcs[i] = tracking_step_impl(trackers[i], nullptr, nullptr, 0, visible_nodes ? visible_nodes[i] : nullptr, nv(i), visible_nodes_extended[i], n_vis_ext[i],
+                                        H_pre ? H_pre[i] : nullptr, &st[2 * (size_t)i]);
+        return finish();
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->cloud_pending >= 0) { if (const int frc = flush_pending_cloud(c)) return frc; }
+    // none of the single tracker's short cuts (PairNext, the M-step launched ahead, lle_next, the mailbox of one frame): a batch's registrations take run_frames' batch route
+    c->pair.state = 0; c->pair.ahead = false; c->iter_hint = 0; c->iter_hint_next = 0;
+    const tdlo_tracker *a = trackers[0];
+    tdlo_params pp{};
+    pp.beta = a->beta_pre_proc; pp.lambda = a->lambda_pre_proc; pp.lle_weight = a->lle_weight; pp.mu = a->mu;
+    pp.max_iter = a->max_iter; pp.tol = a->tol; pp.include_lle = 1; pp.alpha = 0; pp.k_vis = 0; pp.visibility_threshold = 0.01;
+    pp.precision = a->precision;
+    tdlo_params mp{};
+    mp.beta = a->beta; mp.lambda = a->lambda; mp.lle_weight = a->lle_weight; mp.mu = a->mu; mp.max_iter = a->max_iter;
+    mp.tol = a->tol; mp.include_lle = 0; mp.alpha = a->alpha; mp.k_vis = a->k_vis; mp.visibility_threshold = a->visibility_threshold;
+    mp.precision = a->precision;
+    // guide nodes = visible sub-chain (:913-921), per tracker
+    for (int i = 0; i < F; ++i) {
+        tdlo_tracker *t = trackers[i];
+        const int Mg = n_vis_ext[i];
+        const int *ve = visible_nodes_extended[i];
+        t->priors.clear();                                                   // :908
+        t->Mg = Mg;
+        t->guide_nodes.assign(3 * (size_t)Mg, 0.0);
+        if (Mg != M) { for (int k = 0; k < Mg; ++k) for (int d = 0; d < 3; ++d) t->guide_nodes[d * Mg + k] = t->Y[d * M + ve[k]]; }
+        else t->guide_nodes = t->Y;
+    }
+    // a registration's verdict per frame: the frame's own status, or -- the call failed before any frame had one -- the call's code
+    auto verdicts = [&](int rc, const std::vector<int> &who, const std::vector<tdlo_stats> &sg, int which) {
+        bool any = false;
+        for (size_t k = 0; k < who.size(); ++k) any = any || sg[k].status != 0;
+        for (size_t k = 0; k < who.size(); ++k) {
+            const int i = who[k];
+            rcs[i] = (rc != 0 && !any) ? rc : sg[k].status;
+            st[2 * (size_t)i + which] = sg[k];
+            trackers[i]->last_iters[which] = rcs[i] ? 0 : sg[k].iters;
+        }
+    };
+    // the pre-processing registrations (:925-927), one batch per chain length n_vis_ext (steady state: one)
+    std::vector<char> placed(F, 0);
+    for (int i0 = 0; i0 < F; ++i0) {
+        if (placed[i0]) continue;
+        const int Mg = n_vis_ext[i0];
+        std::vector<int> who;
+        for (int i = i0; i < F; ++i) if (!placed[i] && n_vis_ext[i] == Mg) { who.push_back(i); placed[i] = 1; }
+        const int Fg = (int)who.size();
+        std::vector<int> sl(Fg); std::vector<double> Yg(3 * (size_t)Mg * Fg), s2(Fg); std::vector<tdlo_frame_args> ag(Fg); std::vector<tdlo_stats> sg(Fg);
+        std::memset(sg.data(), 0, sizeof(tdlo_stats) * Fg);
+        for (int k = 0; k < Fg; ++k) {
+            const tdlo_tracker *t = trackers[who[k]];
+            sl[k] = t->slot; s2[k] = t->sigma2;                              // (a copy: the pre-processing registration's sigma2 is dropped, :925)
+            ag[k] = tdlo_frame_args{nullptr, 0, nullptr, 0, H_pre ? H_pre[who[k]] : nullptr};
+            std::memcpy(&Yg[3 * (size_t)Mg * k], t->guide_nodes.data(), sizeof(double) * 3 * Mg);
+        }
+        if (Fg == 1) c->iter_hint = trackers[who[0]]->last_iters[0];
+        const int rc = run_frames_each(c, Fg, sl.data(), Yg.data(), Mg, s2.data(), &pp, ag.data(), sg.data());
+        c->iter_hint = 0; c->iter_hint_next = 0;
+        for (int k = 0; k < Fg; ++k) std::memcpy(trackers[who[k]]->guide_nodes.data(), &Yg[3 * (size_t)Mg * k], sizeof(double) * 3 * Mg);
+        verdicts(rc, who, sg, 0);
+    }
+    // priors per tracker (:929-995), on the host
+    std::vector<int> live;
+    for (int i = 0; i < F; ++i) {
+        if (rcs[i]) continue;
+        tdlo_tracker *t = trackers[i];
+        t->vis_ext.assign(visible_nodes_extended[i], visible_nodes_extended[i] + n_vis_ext[i]);
+        rcs[i] = tracker_form_priors(t, visible_nodes ? visible_nodes[i] : nullptr, nv(i));
+        if (rcs[i]) t->last_iters[1] = 0; else live.push_back(i);
+    }
+    // the main registrations (:998) as one batch of M nodes: per-frame priors and visible_nodes_extended
+    if (!live.empty()) {
+        const int Fg = (int)live.size();
+        std::vector<int> sl(Fg); std::vector<double> Yg(3 * (size_t)M * Fg), s2(Fg); std::vector<tdlo_frame_args> ag(Fg); std::vector<tdlo_stats> sg(Fg);
+        std::memset(sg.data(), 0, sizeof(tdlo_stats) * Fg);
+        for (int k = 0; k < Fg; ++k) {
+            const int i = live[k];
+            const tdlo_tracker *t = trackers[i];
+            sl[k] = t->slot; s2[k] = t->sigma2;
+            ag[k] = tdlo_frame_args{t->priors.data(), (int)(t->priors.size() / 4), visible_nodes_extended[i], n_vis_ext[i], nullptr};
+            std::memcpy(&Yg[3 * (size_t)M * k], t->Y.data(), sizeof(double) * 3 * M);
+        }
+        if (Fg == 1) c->iter_hint = trackers[live[0]]->last_iters[1];
+        const int rc = run_frames_each(c, Fg, sl.data(), Yg.data(), M, s2.data(), &mp, ag.data(), sg.data());
+        for (int k = 0; k < Fg; ++k) {
+            tdlo_tracker *t = trackers[live[k]];
+            std::memcpy(t->Y.data(), &Yg[3 * (size_t)M * k], sizeof(double) * 3 * M);
+            t->sigma2 = s2[k];
+        }
+        verdicts(rc, live, sg, 1);
+    }
+    c->iter_hint = 0; c->iter_hint_next = 0;
+    c->pair.state = 0; c->pair.ahead = false; spec_abort(c);
+    return finish();
+}
+
+int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                             tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
+    const int M = trackers[0]->M;
+    std::vector<int> sl(F), nv(F, 0), ne(F, 0), vis((size_t)F * M), ext((size_t)F * M);
+    std::vector<double> Yall(3 * (size_t)M * F), coord((size_t)M * F), dist((size_t)M * F);
+    for (int i = 0; i < F; ++i) {
+        const tdlo_tracker *t = trackers[i];
+        sl[i] = t->slot;
+        std::memcpy(&Yall[3 * (size_t)M * i], t->Y.data(), sizeof(double) * 3 * M);
+        std::memcpy(&coord[(size_t)M * i], t->geodesic_coord.data(), sizeof(double) * M);
+    }
+    int rc = tdlo_visibility_prepass_batch(c, F, sl.data(), Yall.data(), M, trackers[0]->visibility_threshold, d_vis, coord.data(), dist.data(), vis.data(), nv.data(),
+                                           ext.data(), ne.data());
+    if (rc) return rc;
+    std::vector<tdlo_tracker *> sub;
+    std::vector<const int *> pv, pe;
+    std::vector<int> snv, sne, who;
+    for (int i = 0; i < F; ++i) {
+        tdlo_tracker *t = trackers[i];
+        int *v = &vis[(size_t)M * i], *e = &ext[(size_t)M * i];
+        t->frame_dist.assign(&dist[(size_t)M * i], &dist[(size_t)M * i] + M);
+        if (t->painter_on) t->frame_Y0 = t->Y; else t->frame_Y0.clear();
+        if (t->painter_on) {      // the self-occlusion switch, as in tracker_frame_impl
+            std::vector<int> qv, qe;
+            self_occlusion_visible(t->Y.data(), M, t->painter_proj, t->painter_width, t->frame_dist.data(), t->visibility_threshold, qv);
+            fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
+            nv[i] = (int)qv.size(); ne[i] = (int)qe.size();
+            std::copy(qv.begin(), qv.end(), v); std::copy(qe.begin(), qe.end(), e);
+        }
+        t->frame_vis.assign(v, v + M); t->frame_vis_ext.assign(e, e + M);
+        if (ne[i] > 0) { sub.push_back(t); pv.push_back(v); pe.push_back(e); snv.push_back(nv[i]); sne.push_back(ne[i]); who.push_back(i); }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    std::vector<int> rcs(F, 0), src(sub.size(), 0);
+    std::vector<tdlo_stats> st(2 * (size_t)F), sst(2 * sub.size() + 2);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+    // (the reference's callback indexes visible_nodes[size() - 1] without a test, trackdlo_node.cpp:351-361: a frame without a visible node is an error here)
+    for (int i = 0; i < F; ++i) if (ne[i] == 0) rcs[i] = TDLO_E_EMPTY;
+    if (!sub.empty()) {
+        const int brc = tdlo_tracker_tracking_step_batch(sub.data(), (int)sub.size(), pv.data(), snv.data(), pe.data(), sne.data(), nullptr, sst.data(), src.data());
+        for (size_t k = 0; k < sub.size(); ++k) {
+            rcs[who[k]] = src[k] ? src[k] : 0;
+            st[2 * (size_t)who[k]] = sst[2 * k]; st[2 * (size_t)who[k] + 1] = sst[2 * k + 1];
+        }
+        bool any = false;
+        for (int r : src) any = any || r != 0;
+        if (brc && !any) return brc;      // (refused as a whole: nothing was stepped)
+    }
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return rcs[i] == TDLO_E_EMPTY && ne[i] == 0
+                               ? fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)") : rcs[i];
+    return TDLO_OK;
 }
 
 // The picture of the tracker's current nodes over the last colour frame (trackdlo_node.cpp:377-452).  vis = the reference's not_self_occluded_nodes (:401):

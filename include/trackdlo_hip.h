@@ -667,6 +667,48 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
                                    int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                    int *n_out, int *n_raw_out, tdlo_stats *stats);
 
+/* ---- clouds for many slots in one call ---------------------------------------------------------------- */
+/* The front end of a batch of trackers (several ropes in a work cell, one rope seen by several cameras, many recorded sequences at once): F frames of one
+ * image size become the resident clouds of F slots in one call.  An IMAGE is a set of planes of rows x cols pixels, packed and row-major as in the single
+ * calls -- depth, and a mask, or a colour image (with an optional occluder image), or both; a FRAME names a slot, an image and how the image is segmented:
+ * colour_params == NULL takes the image's mask, otherwise the segmentation is formed from its colour image under these ranges.  Any number of frames may
+ * share an image (one camera, several ropes, each with its own ranges).  Plane pointers may be host memory or device memory of the context's GPU (the runtime
+ * is asked); every distinct plane is copied once per call into the context's batch arena, device planes device to device.
+ *   The frames that take a mask and the frames that take colour ranges are one launch each of k_cloud_fused_batch (grid: tiles x frames; every frame with
+ * its own state words, workspace and pinned result words; no workgroup waits for another), on one stream behind the copies, followed by ONE host wait.
+ * A frame the kernel does not take -- more than 32 704 masked pixels, cell-index bits + rank bits beyond 32, PCL's pass-through -- then goes through the
+ * single call for its slot alone.  tdlo_debug_route_count 32 counts the frames the batch launch served, 33 the frames it passed on; 6 / 7 / 15 / 16 keep
+ * counting what the single route does.
+ *   BITS: every slot's cloud, n_out[f] and n_raw_out[f] are those of tdlo_depth_to_cloud / tdlo_colour_depth_to_cloud on that frame alone, the sign of a
+ * zero included, whatever else shares the call and in whatever order.  A frame that selects no pixel leaves an empty cloud (n = 0), as the single call does.
+ *   Refused as a whole with TDLO_E_INVALID before anything is touched (resident clouds intact): F < 1 or F greater than the context's slot count, a slot out
+ * of range or named twice, an image index out of range, an image without depth or with neither mask nor colour, colour ranges on an image without colour,
+ * no ranges on an image without mask, bad tdlo_colour_params, and what the single call refuses of size, leaf and intrinsics.
+ *   rc_each (NULL or F codes): a frame that fails on its own (passed on, then refused by the single route) gets its code; the call returns the first one.
+ *   Fewer than kCloudBatchMin frames (csrc/tdlo_api.cpp) loop over the single calls: the same bits.  MEASURED (profiles/cloud_batch_ab.txt, rope frames,
+ * F = 1 .. 32): from pageable images the batch call wins from 2 frames at 640 x 480 (0.155 against 0.175 ms; 1.40 against 2.82 ms at 32) and from 3 at
+ * 1280 x 720 (3.31 against 4.81 ms at 32); frames that share one image cost 0.19 ms at 32 frames of 640 x 480; but F single calls on the context's pinned
+ * image buffers, read in place, beat a batch that copies caller-pinned images up at every F at 1280 x 720 (2.13 against 2.63 ms at 32) and up to 8 frames at
+ * 640 x 480.  The rule "every batch value below every single-calls value at both sizes" is met by no F up to 32, so kCloudBatchMin is 33: BY DEFAULT THE
+ * CALLS LOOP OVER THE SINGLE CALLS.  TDLO_CLOUD_BATCH_MIN=n (read when the context is made) turns the batch launch on from n frames -- worth it for callers
+ * whose images lie in ordinary host or device memory, or who segment several ropes out of one image. */
+typedef struct { const unsigned short *depth; const unsigned char *mask;      /* mask, or: */
+                 const unsigned char *colour; const unsigned char *occluder;  /* colour (+ optional occluder) */
+                 double fx, fy, cx, cy; } tdlo_batch_image;
+typedef struct { int slot; int image; const tdlo_colour_params *colour_params; /* NULL: the image's mask */ } tdlo_batch_frame;
+int tdlo_depth_to_cloud_batch(tdlo_ctx *ctx, const tdlo_batch_image *images, int K, int rows, int cols,
+                              const tdlo_batch_frame *frames, int F, double leaf_size,
+                              int *n_out /* F */, int *n_raw_out /* F */, int *rc_each /* F or NULL */);
+/* The call above into the trackers' slots (frame i: tracker i's slot, image image_of[i], colour_params[i] or the mask), then tdlo_tracker_frame_batch on the
+ * trackers whose cloud is not empty.  A tracker whose frame selects no pixel gets TDLO_E_EMPTY in rc_each and is left untouched; the others go on.  Refused as
+ * tdlo_tracker_frame_batch and the call above refuse, except that no cloud need be resident.  visible_nodes / visible_nodes_extended: F rows of num_of_nodes
+ * entries; stats: 2 F entries; any output may be NULL.  Bits: those of tdlo_depth_to_cloud (or its colour form) per slot + tdlo_tracker_frame_batch. */
+int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_batch_image *images, int K, int rows, int cols,
+                              const int *image_of /* F */, const tdlo_colour_params *const *colour_params /* NULL or F entries, each NULL = mask */,
+                              double leaf_size, double d_vis,
+                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                              int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each);
+
 /* ---- frames as they arrive: image views in device or host memory ------------------------------------ */
 /* A view of one rows x cols image where its producer holds it; nothing is copied to build one.  The packed calls above take one shape only (packed
  * rows, 3-channel colour, uint16 millimetres, a host pointer); a renderer, simulator or decoder on the same GPU, or a torch tensor, delivers RGBA8 /
@@ -917,6 +959,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * one-launch kernel / passed on by it to the multi-launch form, a team that gave up included; calls that the host never hands to it (TDLO_CLOUD_FUSED=0,
  * TDLO_CLOUD_TEAM=0, more than 4095 tiles) count in 21 alone.  29: view frames whose visibility pre-pass rode in that launch.  6 / 7 / 8 count depth frames only.
  * 30 / 31: tdlo_visibility_prepass_batch calls served by the one launch k_node_min_dist_batch / passed on to tdlo_visibility_prepass slot by slot.
+ * 32 / 33: frames of tdlo_depth_to_cloud_batch (tdlo_tracker_frames_batch's among them) served by the batch launch k_cloud_fused_batch / passed on by it to the
+ * single call for their slot; frames of a batch below the crossover, which loops over the single calls, count in 6 / 7 alone.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

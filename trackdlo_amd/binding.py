@@ -78,6 +78,15 @@ class FrameArgs(C.Structure):                      # tdlo_frame_args: a frame's 
     _fields_ = [("priors", C.c_void_p), ("K", C.c_int), ("visible_nodes", C.c_void_p), ("n_vis", C.c_int), ("H_override", C.c_void_p)]
 
 
+class BatchImage(C.Structure):                     # tdlo_batch_image: the planes of one image of a cloud batch (host or device pointers) and its camera
+    _fields_ = [("depth", C.c_void_p), ("mask", C.c_void_p), ("colour", C.c_void_p), ("occluder", C.c_void_p),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class BatchFrame(C.Structure):                     # tdlo_batch_frame: a slot, the image it takes, and colour ranges (NULL: the image's mask)
+    _fields_ = [("slot", C.c_int), ("image", C.c_int), ("colour_params", C.c_void_p)]
+
+
 class FrameView(C.Structure):
     """tdlo_frame_view: the images of one frame; an image whose data is NULL is absent."""
     _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
@@ -106,6 +115,7 @@ SYMBOLS = [
     "tdlo_voxel_grid_dims", "tdlo_cloud_view_voxel_grid", "tdlo_tracker_frame_from_cloud_view", "tdlo_cloud_view_voxel_grid_visibility",
     "tdlo_sort_pts", "tdlo_sort_pts_host", "tdlo_tracker_initialize_from_cloud", "tdlo_tracker_initialize_from_cloud_view",
     "tdlo_visibility_prepass_batch", "tdlo_cpd_lle_batch_each", "tdlo_tracker_tracking_step_batch", "tdlo_tracker_frame_batch",
+    "tdlo_depth_to_cloud_batch", "tdlo_tracker_frames_batch",
 ]
 
 _lib = None
@@ -302,6 +312,9 @@ def load_library(path: str | None = None):
         lib.tdlo_sort_pts_host.argtypes = [vp, ci, vp, vp, vp]
         lib.tdlo_tracker_initialize_from_cloud.argtypes = [vp, vp, ci, cd, ci, C.POINTER(cd)]
         lib.tdlo_tracker_initialize_from_cloud_view.argtypes = [vp, cvp, ci, cd, ci, C.POINTER(cd)]
+    if hasattr(lib, "tdlo_depth_to_cloud_batch"):
+        lib.tdlo_depth_to_cloud_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, cd, vp, vp, vp]
+        lib.tdlo_tracker_frames_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -569,6 +582,40 @@ def _colour_images(depth, colour, occluder):
         if occluder.shape != colour.shape[:2]:
             raise ValueError("occluder must be rows x cols")
     return depth, colour, occluder, (occluder.ctypes.data_as(C.c_void_p) if occluder is not None else None)
+
+
+def _batch_plane(p, dtype, shape, what):
+    """(address, owner) of one plane of a batch image: anything numpy takes (host memory), or an object with data_ptr() -- a torch tensor, in host or device
+    memory -- which must already be packed, of the right element size and shape."""
+    if p is None:
+        return None, None
+    if hasattr(p, "data_ptr"):
+        if tuple(p.shape) != tuple(shape) or p.element_size() != np.dtype(dtype).itemsize or not p.is_contiguous():
+            raise ValueError(f"{what}: a packed tensor of shape {tuple(shape)} and {np.dtype(dtype).itemsize}-byte elements is needed")
+        return int(p.data_ptr()), p
+    a = np.ascontiguousarray(p, dtype=dtype)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}")
+    return a.ctypes.data, a
+
+
+def _batch_images(images):
+    """tdlo_batch_image table of a list of dicts {depth, mask | colour (+ occluder), cam: (fx, fy, cx, cy)}.  Returns (table, K, rows, cols, owners)."""
+    K = len(images)
+    assert K >= 1
+    rows, cols = (int(v) for v in images[0]["depth"].shape)
+    tab = (BatchImage * K)(); keep = []
+    for k, im in enumerate(images):
+        for name, dt, shape in (("depth", np.uint16, (rows, cols)), ("mask", np.uint8, (rows, cols)), ("colour", np.uint8, (rows, cols, 3)),
+                                ("occluder", np.uint8, (rows, cols))):
+            adr, owner = _batch_plane(im.get(name), dt, shape, f"image {k}: {name}")
+            setattr(tab[k], name, adr); keep.append(owner)
+        tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = (float(v) for v in im["cam"])
+    return tab, K, rows, cols, keep
+
+
+def _params_address(p):
+    return None if p is None else C.addressof(p)
 
 
 class Context:
@@ -1034,6 +1081,27 @@ class Context:
         X = buf[:3 * n.value].reshape(3, n.value).T.copy() if fetch else None
         return X, n.value, nraw.value
 
+    def cloud_batch_route_counts(self):
+        """[frames served by the batch launch k_cloud_fused_batch, frames it passed on to the single call] (tdlo_debug_route_count 32 / 33)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (32, 33)]
+
+    def depth_to_cloud_batch(self, images, frames, leaf_size, check=True):
+        """tdlo_depth_to_cloud_batch: the clouds of F slots from images of one size in one call.  images: dicts {depth, mask and / or colour (+ occluder),
+        cam: (fx, fy, cx, cy)}, the planes numpy arrays or packed torch tensors (host or device); frames: (slot, image index, ColourParams or None = the
+        image's mask).  The clouds stay resident in the slots (get_cloud).  Returns (n [F], n_raw [F], codes [F]); raises on the first non-zero code unless
+        check=False."""
+        tab, K, rows, cols, keep = _batch_images(images)
+        F = len(frames)
+        fr = (BatchFrame * max(F, 1))()
+        for i, (slot, image, params) in enumerate(frames):
+            fr[i].slot, fr[i].image, fr[i].colour_params = int(slot), int(image), _params_address(params)
+        n = np.zeros(max(F, 1), dtype=np.int32); nraw = np.zeros(max(F, 1), dtype=np.int32); rcs = np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.tdlo_depth_to_cloud_batch(self.h, C.cast(tab, C.c_void_p), K, rows, cols, C.cast(fr, C.c_void_p), F, float(leaf_size), _ptr(n), _ptr(nraw), _ptr(rcs))
+        del keep
+        if rc and check:
+            self._chk(rc)
+        return [int(v) for v in n[:F]], [int(v) for v in nraw[:F]], [int(v) for v in rcs[:F]]
+
     def depth_to_cloud_visibility(self, slot, depth, mask, fx, fy, cx, cy, leaf_size, Y, visibility_threshold, d_vis, geodesic_coord):
         """One frame of the ROS node up to tracking_step (trackdlo_node.cpp:195-277, :345-360): depth_to_cloud (the cloud stays resident in the slot) and
         the visibility pre-pass of the nodes Y against it, in one launch where the library can (tdlo_depth_to_cloud_visibility).
@@ -1396,6 +1464,26 @@ def frame_batch(trackers, d_vis, check=True):
     rc = trackers[0].ctx.lib.tdlo_tracker_frame_batch(C.cast(tab, C.c_void_p), F, float(d_vis), _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), C.cast(st, C.c_void_p), _ptr(rcs))
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)]
+
+
+def frames_batch(trackers, images, image_of, colour_params, leaf_size, d_vis, check=True):
+    """tdlo_tracker_frames_batch: the trackers' frames from their images -- depth_to_cloud_batch into the trackers' slots (tracker i: image image_of[i], segmented
+    by colour_params[i], or by the image's mask where that is None or colour_params is None), then frame_batch on the trackers that got a cloud.
+    Returns (codes, [visible_nodes], [visible_nodes_extended], n [F], n_raw [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    itab, K, rows, cols, keep = _batch_images(images)
+    M = trackers[0].M
+    io = np.ascontiguousarray(image_of, dtype=np.int32)
+    assert len(io) == F and (colour_params is None or len(colour_params) == F)
+    cp = None if colour_params is None else (C.c_void_p * F)(*[_params_address(p) for p in colour_params])
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_batch(C.cast(tab, C.c_void_p), F, C.cast(itab, C.c_void_p), K, rows, cols, _ptr(io),
+                                                       C.cast(cp, C.c_void_p) if cp is not None else None, float(leaf_size), float(d_vis),
+                                                       _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
+    del keep
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
 
 
 def calc_LLE_weights(k, Y):

@@ -199,6 +199,17 @@ struct tdlo_ctx {
     long long vbat_route[2] = {0, 0};    // tdlo_debug_route_count 30 / 31: tdlo_visibility_prepass_batch calls served by the one launch / passed on to tdlo_visibility_prepass per slot
     long long vis_route[2] = {0, 0};     // tdlo_debug_route_count 22 / 23: tdlo_visibility_prepass calls served by the one-launch kernel / by the copies + k_node_min_dist
     long long cloud_route[2] = {0, 0};   // tdlo_debug_route_count 6 / 7: depth -> cloud calls served by the one-launch kernel / sent on to the multi-launch form by it
+    // clouds for F slots in one call (tdlo_depth_to_cloud_batch, k_cloud_fused_batch): the arena -- cbat_dev: the frame blocks (tile regions, state words,
+    // workspace; frame f's at f x cloud_batch_frame_bytes(P) whatever F is), cbat_img: [descriptor table | image planes] -- in device memory and
+    // [2 F result words | descriptor table] in pinned host memory, all grown on demand; the first cbat_armed_F frame blocks' state words are armed for images
+    // of cbat_armed_P pixels (the kernel keeps them so; a call that did not complete, another size or a reallocation has them initialised again)
+    void *cbat_dev = nullptr, *cbat_img = nullptr;
+    size_t cbat_dev_cap = 0, cbat_img_cap = 0;
+    char *cbat_pin = nullptr;
+    size_t cbat_pin_cap = 0;
+    int cbat_armed_F = 0, cbat_armed_P = 0;
+    int cloud_batch_min = (getenv("TDLO_CLOUD_BATCH_MIN") && atoi(getenv("TDLO_CLOUD_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_CLOUD_BATCH_MIN")) : 0;      // 0: kCloudBatchMin
+    long long cbat_route[2] = {0, 0};    // tdlo_debug_route_count 32 / 33: frames served by the batch launch / passed on by it to the single call
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1739,6 +1750,9 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->fd) hipFree(c->fd);
     if (c->cloud_ws) hipFree(c->cloud_ws);
     if (c->cloud_fws) hipFree(c->cloud_fws);
+    if (c->cbat_dev) hipFree(c->cbat_dev);
+    if (c->cbat_img) hipFree(c->cbat_img);
+    if (c->cbat_pin) hipHostFree(c->cbat_pin);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
     if (c->vis_nodes_pin) hipHostFree(c->vis_nodes_pin);
@@ -3078,6 +3092,221 @@ int tdlo_colour_depth_to_cloud(tdlo_ctx *c, int slot, const unsigned short *dept
     return depth_to_cloud_impl(c, slot, depth, nullptr, rows, cols, fx, fy, cx, cy, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr, &ci);
 }
 
+// ---- clouds for F slots in one call (include/trackdlo_hip.h: tdlo_depth_to_cloud_batch) ----------------------------------------------------------
+// From this many frames on the call is the batch launch; below it loops over the single calls (the same bits).  Set from profiles/cloud_batch_ab.txt by the
+// rule "the smallest F from which every batch value lies below every single-calls value, at both image sizes".  Measured: there is no such F up to 32 -- the
+// batch wins from pageable images (from 2 frames at 640 x 480, from 3 at 1280 x 720; half the time at 32) and in the tracker call, and by far when frames
+// share an image, but F single calls that read the context's pinned image buffers in place stay ahead of a batch that copies caller-pinned images up
+// (1.43 against 1.35 ms at 32 frames of 640 x 480 is the batch's only win there; 2.13 against 2.63 ms at 1280 x 720).  So the route is OFF by default (the
+// constant lies above any F the measurement covers); TDLO_CLOUD_BATCH_MIN=n, read when the context is made, turns it on from n frames.
+constexpr int kCloudBatchMin = 33;
+
+// a batch image's planes: which are in device memory (of the context's GPU)
+struct BatchPlanes { bool dev[4] = {false, false, false, false}; };      // depth, mask, colour, occluder
+
+// Everything that refuses the call as a whole; nothing of the context or the slots is touched.  where: per image, where its planes lie.
+static int cloud_batch_refusal(tdlo_ctx *c, const tdlo_batch_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                               std::vector<BatchPlanes> &where) {
+    if (!images || !frames || K < 1 || F < 1) return fail(c, TDLO_E_INVALID, "cloud batch: no images / no frames");
+    if (F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "cloud batch: more frames than the context has slots");
+    if (rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26)) return fail(c, TDLO_E_INVALID, "bad image");
+    if (!(leaf_size > 0)) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
+    where.assign(K, BatchPlanes{});
+    for (int k = 0; k < K; ++k) {
+        const tdlo_batch_image &im = images[k];
+        if (!im.depth || (!im.mask && !im.colour)) return fail(c, TDLO_E_INVALID, "cloud batch: an image needs depth and a mask or a colour image");
+        if (im.fx == 0 || im.fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
+        const void *pl[4] = {im.depth, im.mask, im.colour, im.colour ? im.occluder : nullptr};
+        for (int q = 0; q < 4; ++q)
+            if (pl[q]) { if (int rc = pointer_location(c, pl[q], TDLO_MEM_AUTO, "cloud batch image", &where[k].dev[q])) return rc; }
+    }
+    for (int f = 0; f < F; ++f) {
+        const tdlo_batch_frame &fr = frames[f];
+        if (fr.slot < 0 || fr.slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+        for (int g = 0; g < f; ++g) if (frames[g].slot == fr.slot) return fail(c, TDLO_E_INVALID, "cloud batch: a slot is named twice");
+        if (fr.image < 0 || fr.image >= K) return fail(c, TDLO_E_INVALID, "cloud batch: image index out of range");
+        if (fr.colour_params) {
+            CloudColour cc;
+            if (!colour_pack(fr.colour_params, cc)) return fail(c, TDLO_E_INVALID, "tdlo_colour_params: 1 .. 4 ranges");
+            if (!images[fr.image].colour) return fail(c, TDLO_E_INVALID, "cloud batch: colour ranges for an image without a colour image");
+        } else if (!images[fr.image].mask) return fail(c, TDLO_E_INVALID, "cloud batch: no colour ranges for an image without a mask");
+    }
+    return TDLO_OK;
+}
+
+// one frame of a batch through the single call (a batch below the crossover, a frame the batch launch passed on): device planes are brought to the host
+// first, as the single call takes host images
+static int cloud_batch_single(tdlo_ctx *c, const tdlo_batch_image &im, const BatchPlanes &w, const tdlo_batch_frame &fr, int rows, int cols, double leaf_size,
+                              int *n_out, int *n_raw_out) {
+    const size_t P = (size_t)rows * cols;
+    std::vector<unsigned char> hold[4];
+    auto host = [&](const void *p, int q, size_t bytes, const void **out) -> int {
+        *out = p;
+        if (!p || !w.dev[q]) return TDLO_OK;
+        hold[q].resize(bytes);
+        HIPCHK(c, hipMemcpy(hold[q].data(), p, bytes, hipMemcpyDeviceToHost));
+        *out = hold[q].data();
+        return TDLO_OK;
+    };
+    const void *d = nullptr, *m = nullptr, *col = nullptr, *occ = nullptr;
+    int rc = host(im.depth, 0, 2 * P, &d);
+    if (rc) return rc;
+    if (!fr.colour_params) {
+        if ((rc = host(im.mask, 1, P, &m))) return rc;
+        return depth_to_cloud_impl(c, fr.slot, (const unsigned short *)d, (const unsigned char *)m, rows, cols, im.fx, im.fy, im.cx, im.cy, leaf_size, nullptr, 0, n_out,
+                                   n_raw_out, nullptr, 0, nullptr);
+    }
+    if ((rc = host(im.colour, 2, 3 * P, &col)) || (rc = host(im.occluder, 3, P, &occ))) return rc;
+    const ColourIn ci{(const unsigned char *)col, fr.colour_params, (const unsigned char *)occ};
+    return depth_to_cloud_impl(c, fr.slot, (const unsigned short *)d, nullptr, rows, cols, im.fx, im.fy, im.cx, im.cy, leaf_size, nullptr, 0, n_out, n_raw_out, nullptr, 0,
+                               nullptr, &ci);
+}
+
+int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                              int *n_out, int *n_raw_out, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    std::vector<BatchPlanes> where;
+    int rc = cloud_batch_refusal(c, images, K, rows, cols, frames, F, leaf_size, where);
+    if (rc) return rc;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    auto finish = [&]() {
+        if (n_out) std::copy(n.begin(), n.end(), n_out);
+        if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int f = 0; f < F; ++f) if (rcs[f]) return rcs[f];
+        return (int)TDLO_OK;
+    };
+    const int P = rows * cols;
+    if (F < (c->cloud_batch_min ? c->cloud_batch_min : kCloudBatchMin) || !c->cloud_fused_on || !cloud_fused_ok(P)) {
+        for (int f = 0; f < F; ++f)
+            rcs[f] = cloud_batch_single(c, images[frames[f].image], where[frames[f].image], frames[f], rows, cols, leaf_size, &n[f], &nraw[f]);
+        return finish();
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+    // ---- the arena: F frame blocks; the descriptor table and the planes of the images in use
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t fb = cloud_batch_frame_bytes(P), tab = r256(cloud_batch_desc_bytes() * (size_t)F);
+    const size_t plane_bytes[4] = {img_depth_bytes(P), img_mask_bytes(P), img_colour_bytes(P), img_occ_bytes(P)}, plane_copy[4] = {2 * (size_t)P, (size_t)P, 3 * (size_t)P, (size_t)P};
+    std::vector<char> use(4 * (size_t)K, 0);                  // plane q of image k is read by a frame
+    for (int f = 0; f < F; ++f) {
+        const int k = frames[f].image;
+        use[4 * k] = 1;
+        if (frames[f].colour_params) { use[4 * k + 2] = 1; if (images[k].occluder) use[4 * k + 3] = 1; }
+        else use[4 * k + 1] = 1;
+    }
+    struct Plane { const void *src; int kind; size_t off; bool dev; };
+    std::vector<Plane> planes;                                // every distinct (pointer, kind) once
+    std::vector<size_t> at(4 * (size_t)K, 0);
+    size_t img_bytes = 0;
+    for (int k = 0; k < K; ++k) {
+        const void *pl[4] = {images[k].depth, images[k].mask, images[k].colour, images[k].occluder};
+        for (int q = 0; q < 4; ++q) {
+            if (!use[4 * k + q]) continue;
+            size_t j = 0;
+            while (j < planes.size() && !(planes[j].src == pl[q] && planes[j].kind == q)) ++j;
+            if (j == planes.size()) { planes.push_back(Plane{pl[q], q, img_bytes, where[k].dev[q]}); img_bytes += plane_bytes[q]; }
+            at[4 * k + q] = planes[j].off;
+        }
+    }
+    // (two device blocks: a frame block's place must not depend on what else a call brings -- its state words stay armed from call to call -- so the table
+    // and the planes, whose sizes change with every call, live apart from the frame blocks)
+    if (fb * (size_t)F > c->cbat_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_dev) hipFree(c->cbat_dev);
+        c->cbat_dev = nullptr; c->cbat_dev_cap = 0; c->cbat_armed_F = 0;
+        HIPCHK(c, hipMalloc(&c->cbat_dev, fb * (size_t)F));
+        c->cbat_dev_cap = fb * (size_t)F;
+    }
+    if (tab + img_bytes > c->cbat_img_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_img) hipFree(c->cbat_img);
+        c->cbat_img = nullptr; c->cbat_img_cap = 0;
+        HIPCHK(c, hipMalloc(&c->cbat_img, tab + img_bytes));
+        c->cbat_img_cap = tab + img_bytes;
+    }
+    const size_t pin_need = 2 * sizeof(unsigned long long) * (size_t)F + tab;
+    if (pin_need > c->cbat_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_pin) hipHostFree(c->cbat_pin);
+        c->cbat_pin = nullptr; c->cbat_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->cbat_pin, pin_need, hipHostMallocDefault));
+        std::memset(c->cbat_pin, 0, pin_need);
+        c->cbat_pin_cap = pin_need;
+    }
+    char *base = (char *)c->cbat_dev, *d_tab = (char *)c->cbat_img, *d_img = d_tab + tab;
+    unsigned long long *res = (unsigned long long *)c->cbat_pin;
+    char *h_tab = c->cbat_pin + 2 * sizeof(unsigned long long) * (size_t)F;
+    std::memset(res, 0, 2 * sizeof(unsigned long long) * (size_t)F);      // (where another F had its table: no word may look like this call's epoch)
+    // ---- the slots: room for a point per masked pixel the kernel takes; whatever was resident is gone from here on
+    for (int f = 0; f < F; ++f) {
+        Slot &s = c->slots[frames[f].slot];
+        if ((rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;
+        s.N0 = 0; s.sorted_valid = false;
+    }
+    // ---- state words
+    if (c->cbat_armed_P != P || F > c->cbat_armed_F) {
+        std::vector<void *> blocks(F);
+        for (int f = 0; f < F; ++f) blocks[f] = base + fb * (size_t)f;
+        c->cbat_armed_F = 0;
+        HIPCHK(c, cloud_batch_arm(blocks.data(), F, P, st));
+        c->cbat_armed_F = F; c->cbat_armed_P = P;
+    }
+    // ---- every distinct plane once (device planes device to device: the kernel's loads want the padding behind the image)
+    for (const Plane &pl : planes)
+        HIPCHK(c, hipMemcpyAsync(d_img + pl.off, pl.src, plane_copy[pl.kind], pl.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    // ---- the table: the frames that bring a mask, then the frames that form it from the colour image
+    std::vector<int> order;
+    for (int f = 0; f < F; ++f) if (!frames[f].colour_params) order.push_back(f);
+    const int Fm = (int)order.size();
+    for (int f = 0; f < F; ++f) if (frames[f].colour_params) order.push_back(f);
+    std::vector<CloudBatchFrame> bf(F);
+    for (int j = 0; j < F; ++j) {
+        const tdlo_batch_frame &fr = frames[order[j]];
+        const tdlo_batch_image &im = images[fr.image];
+        const int k = fr.image;
+        CloudBatchFrame &b = bf[j];
+        b = CloudBatchFrame{};
+        b.depth = (const unsigned short *)(d_img + at[4 * k]);
+        if (fr.colour_params) {
+            colour_pack(fr.colour_params, b.colour);
+            b.colour.colour = (const unsigned char *)(d_img + at[4 * k + 2]);
+            b.colour.occluder = im.occluder ? (const unsigned char *)(d_img + at[4 * k + 3]) : nullptr;
+        } else b.mask = (const unsigned char *)(d_img + at[4 * k + 1]);
+        b.cam[0] = im.fx; b.cam[1] = im.fy; b.cam[2] = im.cx; b.cam[3] = im.cy;
+        b.ws = base + fb * (size_t)j;
+        Slot &s = c->slots[fr.slot];
+        b.X = s.Xraw; b.cap = s.cap_points; b.res = res + 2 * (size_t)j;
+    }
+    if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+    const unsigned epoch = c->cloud_epoch;
+    const float leaf = (float)leaf_size, inv = 1.0f / leaf;
+    {
+        const hipError_t e = launch_cloud_fused_batch(bf.data(), Fm, F - Fm, P, cols, inv, epoch, h_tab, d_tab, st);
+        if (e != hipSuccess) { c->cbat_armed_F = 0; HIPCHK(c, e); }
+    }
+    {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { c->cbat_armed_F = 0; HIPCHK(c, e); }
+    }
+    // ---- the frames' words; a frame the kernel did not take goes through the single call for its slot alone
+    std::vector<int> passed;
+    for (int j = 0; j < F; ++j) {
+        const int f = order[j];
+        const unsigned long long w0 = __atomic_load_n(res + 2 * (size_t)j, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(res + 2 * (size_t)j + 1, __ATOMIC_RELAXED);
+        const unsigned status = (unsigned)w0;
+        if ((unsigned)(w0 >> 32) != epoch) { c->cbat_armed_F = 0; rcs[f] = fail(c, TDLO_E_HIP, "the stream drained, but a frame of the depth -> cloud batch did not report"); continue; }
+        nraw[f] = (int)(unsigned)(w1 >> 32);
+        if (status == 1u) { n[f] = (int)(unsigned)w1; c->slots[frames[f].slot].N0 = n[f]; ++c->cbat_route[0]; }
+        else if (status == 2u) { passed.push_back(f); ++c->cbat_route[1]; }
+        else rcs[f] = fail(c, TDLO_E_HIP, "voxel grid produced more points than the slot holds");
+    }
+    for (int f : passed)
+        rcs[f] = cloud_batch_single(c, images[frames[f].image], where[frames[f].image], frames[f], rows, cols, leaf_size, &n[f], &nraw[f]);
+    return finish();
+}
+
 // ---- the voxel grid on a cloud view (include/trackdlo_hip.h: V(view, N, select, leaf)) ---------------------------------------------------------
 // Everything that can refuse the call without a look at the points; nothing of the context or the slot is touched.
 static int voxel_view_refusal(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, double leaf_size) {
@@ -3805,7 +4034,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 31) return -1;
+    if (!c || which < 0 || which > 33) return -1;
+    if (which >= 32) return c->cbat_route[which - 32];
     if (which >= 30) return c->vbat_route[which - 30];
     if (which >= 27) return c->view_team_route[which - 27];
     if (which >= 25) return c->init_route[which - 25];
@@ -4447,7 +4677,7 @@ static int tracker_batch_min() {
 
 // what a batch of trackers must share (one context, distinct slots with a cloud each, node count, precision, the eleven reference parameters, nodes and
 // geodesic coordinates initialised): the reason it does not, or nullptr
-static const char *tracker_batch_refusal(tdlo_tracker *const *tr, int F) {
+static const char *tracker_batch_refusal(tdlo_tracker *const *tr, int F, bool need_cloud = true) {
     if (!tr || F < 1 || !tr[0]) return "no trackers";
     const tdlo_tracker *a = tr[0];
     if (F > (int)a->ctx->slots.size()) return "more trackers than the context has slots";
@@ -4461,7 +4691,7 @@ static const char *tracker_batch_refusal(tdlo_tracker *const *tr, int F) {
             t->mu != a->mu || t->max_iter != a->max_iter || t->tol != a->tol || t->beta_pre_proc != a->beta_pre_proc || t->lambda_pre_proc != a->lambda_pre_proc ||
             t->lle_weight != a->lle_weight) return "the trackers of a batch share the reference's parameters";
         if (t->geodesic_coord.size() != (size_t)t->M || t->Y.size() != 3 * (size_t)t->M) return "a tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)";
-        if (t->ctx->slots[t->slot].N0 <= 0) return "no cloud is resident in a tracker's slot";
+        if (need_cloud && t->ctx->slots[t->slot].N0 <= 0) return "no cloud is resident in a tracker's slot";
     }
     return nullptr;
 }
@@ -4649,6 +4879,66 @@ int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return rcs[i] == TDLO_E_EMPTY && ne[i] == 0
                                ? fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)") : rcs[i];
+    return TDLO_OK;
+}
+
+// The frames of F trackers from their images: tdlo_depth_to_cloud_batch into the trackers' slots, then tdlo_tracker_frame_batch on the trackers that got a cloud
+int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_batch_image *images, int K, int rows, int cols, const int *image_of,
+                              const tdlo_colour_params *const *colour_params, double leaf_size, double d_vis,
+                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (!image_of) return fail(c, TDLO_E_INVALID, "null image_of");
+    const int M = trackers[0]->M;
+    std::vector<tdlo_batch_frame> fr(F);
+    for (int i = 0; i < F; ++i) fr[i] = tdlo_batch_frame{trackers[i]->slot, image_of[i], colour_params ? colour_params[i] : nullptr};
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    int rc = tdlo_depth_to_cloud_batch(c, images, K, rows, cols, fr.data(), F, leaf_size, n.data(), nraw.data(), rcs.data());
+    if (n_out) std::copy(n.begin(), n.end(), n_out);
+    if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+    bool any = false;
+    for (int r : rcs) any = any || r != 0;
+    if (rc && !any) return rc;                     // (refused as a whole: nothing was touched)
+    std::vector<tdlo_tracker *> sub;
+    std::vector<int> who;
+    for (int i = 0; i < F; ++i) {
+        if (!rcs[i] && n[i] == 0) rcs[i] = TDLO_E_EMPTY;      // the frame selects no pixel: no cloud, the tracker is left as it is
+        if (!rcs[i]) {
+            tdlo_tracker *t = trackers[i];
+            const tdlo_batch_image &im = images[image_of[i]];
+            t->frame_cam[0] = im.fx; t->frame_cam[1] = im.fy; t->frame_cam[2] = im.cx; t->frame_cam[3] = im.cy; t->frame_seen = true;
+            sub.push_back(t); who.push_back(i);
+        }
+    }
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
+    if (!sub.empty()) {
+        const int Fs = (int)sub.size();
+        std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
+        std::vector<tdlo_stats> sst(2 * (size_t)Fs);
+        std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+        const int brc = tdlo_tracker_frame_batch(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data());
+        bool sany = false;
+        for (int r : src) sany = sany || r != 0;
+        for (int k = 0; k < Fs; ++k) {
+            const int i = who[k];
+            rcs[i] = (brc && !sany) ? brc : src[k];
+            nv[i] = snv[k]; ne[i] = sne[k];
+            std::copy(&svis[(size_t)M * k], &svis[(size_t)M * k] + M, &vis[(size_t)M * i]);
+            std::copy(&sext[(size_t)M * k], &sext[(size_t)M * k] + M, &ext[(size_t)M * i]);
+            st[2 * (size_t)i] = sst[2 * (size_t)k]; st[2 * (size_t)i + 1] = sst[2 * (size_t)k + 1];
+        }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "the mask selects no pixel: no cloud for this frame") : rcs[i];
     return TDLO_OK;
 }
 

@@ -659,8 +659,10 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
 
 
 
+// the whole of k_cloud_fused for the frame `a` describes, called by every thread of a workgroup whose blockIdx.x is one of the frame's tiles: the single-frame
+// kernel and the batch kernel (one frame per blockIdx.y) are this body behind two ways of finding the descriptor
 template <bool kColour>
-__global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
+__device__ __forceinline__ void cloud_fused_body(const FusedCloud &a) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     unsigned *E = (unsigned *)fsm;                                           // kFNmax sort words (through sw(): bank swizzle)
     unsigned *cnt32 = (unsigned *)(fsm + kFLdsE);                            // 32 KB: per (digit, thread) counts as bytes, then start offsets as 16-bit words
@@ -942,6 +944,20 @@ __global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) {
     FSTAMP(6);
     finish(1u, ncell);
 #undef FSTAMP
+}
+
+template <bool kColour>
+__global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) { cloud_fused_body<kColour>(a); }
+
+// F frames in one launch (tdlo_depth_to_cloud_batch): grid (T, F), blockIdx.y picks the frame's descriptor out of a table in device memory.  Every frame has
+// its own state words, tile regions, compacted points, tile counts, destination and pinned result words, so the frames share nothing: each one's last ticket
+// starts its phase B on whatever compute unit that workgroup runs on -- F of them at once where the single frame had one.  NO wait of any kind: the
+// last-ticket rule of the body is the only hand-over between workgroups, a workgroup beyond the frame's tiles leaves at once.
+template <bool kColour>
+__global__ __launch_bounds__(kFT) void k_cloud_fused_batch(const FusedCloud *__restrict__ table) {
+    const FusedCloud a = table[blockIdx.y];
+    if ((int)blockIdx.x >= a.T) return;
+    cloud_fused_body<kColour>(a);
 }
 
 }  // namespace
@@ -1419,6 +1435,56 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
     } else {
         if (colour) hipLaunchKernelGGL(k_cloud_fused<true>, dim3(a.T), dim3(kFT), kFLds, s, a);
         else hipLaunchKernelGGL(k_cloud_fused<false>, dim3(a.T), dim3(kFT), kFLds, s, a);
+    }
+    return hipGetLastError();
+}
+
+// ---- k_cloud_fused_batch: a frame's share of the batch arena is [tile regions: 3 P floats | state words 256 B | compacted points 3 kFNmax floats | T tile counts]
+static size_t batch_tiles_bytes(int P) { return (3 * (size_t)P * sizeof(float) + 255) & ~(size_t)255; }
+size_t cloud_batch_frame_bytes(int P) {
+    const size_t T = ((size_t)P + kFPix - 1) / kFPix;
+    return batch_tiles_bytes(P) + 256 + ((3 * (size_t)kFNmax * sizeof(float) + 255) & ~(size_t)255) + ((T * sizeof(int) + 255) & ~(size_t)255);
+}
+size_t cloud_batch_desc_bytes() { return sizeof(FusedCloud); }
+
+hipError_t cloud_batch_arm(void *const *frame_ws, int F, int P, hipStream_t s) {
+    static const unsigned init[16] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (int f = 0; f < F; ++f)
+        if (const hipError_t e = hipMemcpyAsync((char *)frame_ws[f] + batch_tiles_bytes(P), init, sizeof init, hipMemcpyHostToDevice, s)) return e;
+    return hipSuccess;
+}
+
+hipError_t launch_cloud_fused_batch(const CloudBatchFrame *fr, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev,
+                                    hipStream_t s) {
+    const int F = Fm + Fc;
+    if (F < 1 || P <= 0 || !cloud_fused_ok(P)) return hipErrorInvalidValue;
+    FusedCloud *tab = (FusedCloud *)table_pinned;
+    for (int f = 0; f < F; ++f) {
+        FusedCloud a{};
+        if (f >= Fm) a.col = fr[f].colour;
+        a.depth = fr[f].depth; a.mask = fr[f].mask; a.cols = cols;
+        a.cam = Cam{fr[f].cam[0], fr[f].cam[1], fr[f].cam[2], fr[f].cam[3]};
+        a.P = P; a.T = (P + kFPix - 1) / kFPix;
+        a.inv_leaf = inv_leaf;
+        char *w = (char *)fr[f].ws;
+        a.ex = (float *)w; a.ey = a.ex + P; a.ez = a.ey + P;
+        w += batch_tiles_bytes(P);
+        a.state = (unsigned *)w;
+        a.cx = (float *)(w + 256); a.cy = a.cx + kFNmax; a.cz = a.cy + kFNmax;
+        a.tcnt = (int *)(w + 256 + ((3 * (size_t)kFNmax * sizeof(float) + 255) & ~(size_t)255));
+        a.X = fr[f].X; a.cap = fr[f].cap; a.res = fr[f].res; a.epoch = epoch;
+        tab[f] = a;
+    }
+    if (const hipError_t e = hipMemcpyAsync(table_dev, tab, sizeof(FusedCloud) * (size_t)F, hipMemcpyHostToDevice, s)) return e;
+    const int T = (P + kFPix - 1) / kFPix;
+    if (Fm > 0) {
+        if (const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_fused_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;      // (per device: see launch_cloud_fused)
+        hipLaunchKernelGGL(k_cloud_fused_batch<false>, dim3(T, Fm), dim3(kFT), kFLds, s, (const FusedCloud *)table_dev);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    if (Fc > 0) {
+        if (const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_fused_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;
+        hipLaunchKernelGGL(k_cloud_fused_batch<true>, dim3(T, Fc), dim3(kFT), kFLds, s, (const FusedCloud *)table_dev + Fm);
     }
     return hipGetLastError();
 }

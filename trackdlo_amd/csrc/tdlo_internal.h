@@ -314,6 +314,16 @@ hipError_t launch_cloud_fused(const unsigned short *depth, const unsigned char *
                               bool first, bool team, double *Xraw, int cap, unsigned long long *res_pinned, unsigned epoch, hipStream_t s,
                               const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr, unsigned long long *vis_out_pinned = nullptr,
                               const CloudColour *colour = nullptr);
+// k_cloud_fused for F frames of one image size in at most two launches (k_cloud_fused_batch: grid (tiles, frames); the Fm frames that bring a mask first,
+// then the Fc frames that form it from their colour image).  Per frame: the images as launch_cloud_fused takes them, ws = cloud_batch_frame_bytes(P) bytes
+// of device memory that belong to the frame alone (cloud_batch_arm initialises its state words; the kernel re-arms them), the slot's raw cloud, and two pinned
+// words res[0] = epoch << 32 | status, res[1] = n_raw << 32 | n.  table_pinned / table_dev: (Fm + Fc) x cloud_batch_desc_bytes() bytes each.
+struct CloudBatchFrame { const unsigned short *depth; const unsigned char *mask; CloudColour colour; double cam[4]; void *ws; double *X; int cap; unsigned long long *res; };
+size_t cloud_batch_frame_bytes(int P);
+size_t cloud_batch_desc_bytes();
+hipError_t cloud_batch_arm(void *const *frame_ws, int F, int P, hipStream_t s);
+hipError_t launch_cloud_fused_batch(const CloudBatchFrame *frames, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev,
+                                    hipStream_t s);
 // the team kernel with a cloud view as its point source (k_cloud_team's view instantiations; CloudViewSrc as for the multi-launch form): reports like
 // launch_cloud_fused's team launch -- 1 done, 2 not taken, 3 the slot's capacity `cap` does not hold the result (nothing of Xraw is written), 4 given up
 hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,

@@ -840,6 +840,56 @@ int tdlo_last_colour_shape(tdlo_ctx *ctx, int *rows, int *cols);
  * touched: a tracker that renders and one that does not give the same nodes, bit for bit. */
 int tdlo_tracker_render_result(tdlo_tracker *t, const double proj[12], const tdlo_render_params *p, unsigned char *image_out, int corners[4]);
 
+/* Result images for many ropes: any number of ropes over each image, K images of one size in ONE launch (k_render_batch, csrc/tdlo_render_batch.hip).
+ * tdlo_render_result blends the whole image and paints its one rope, so a picture of several ropes over one camera image cannot be made from single calls
+ * (a second call over the first one's output blends twice, over the original it loses the first rope).  Per image k, in terms of the single call:
+ *     img = blend(colour_k, occluder_k)
+ *     for every rope whose .image == k, in the order of the caller's rope list: if rope.M > 1, paint its primitives (tdlo_render_primitives) over img
+ *     corners_k = the occlusion corners of occluder_k
+ * i.e. the blend ONCE, then each rope exactly as tdlo_render_result draws its one rope (edges farthest first: line, disc, disc; the same pixel rule, the
+ * same guards); ropes in list order, so a later rope paints over an earlier one -- what R successive drawing passes over one blended image give, and
+ * the caller controls it.  An image without a rope is the blend alone; an image with exactly one rope is byte for byte tdlo_render_result's.
+ * PARITY UNPINNED against OpenCV's own rasterisers, exactly as for the single call; tests/render_batch_ref.py is the numpy statement.
+ *   limits     1 .. 256 images of 1 .. 8192 rows and columns, 0 .. 1024 ropes of 1 .. 1024 nodes; the device and pinned tables grow on demand.
+ *   sources    as the single call's: the context's pinned colour buffers (tdlo_colour_buffers) and 4-byte aligned device memory of the context's GPU are read
+ *              in place; pageable host memory and unaligned device memory are staged into a device arena of the context.  colour == NULL: the images of
+ *              the context's most recent colour call, as tdlo_render_result (occluder is ignored then).
+ *   image_out  per image: 4-byte aligned device memory of the context's GPU and tdlo_result_image_buffer's pointer are written by the kernel; anything else
+ *              is written into the arena and copied out behind the launch.  With 3 rows cols not a multiple of 4, consecutive images of one device tensor
+ *              alternate between the two routes.  TDLO_RENDER_INPLACE=0: the arena and a copy for every image.  tdlo_debug_route_count 34 counts the images
+ *              the kernel wrote in place, 35 the images copied out of the arena (19 / 20 stay the single call's).
+ *   corners    4 K ints (image k: corners[4 k ..]) or NULL.
+ * All or nothing: TDLO_E_INVALID, tdlo_last_error names the rope or image, and NO byte of any image_out and no entry of corners is written -- a rope
+ * whose image is outside 0 .. K - 1, a rope tdlo_render_primitives refuses, a NULL image_out, two images with the same image_out, colour == NULL without
+ * a colour call of the same shape before it, device memory of another GPU.
+ * One launch per call, plus the table upload, the corner words' memset, the copies of staged sources and arena images, one read-back of the corner words
+ * and one stream wait.  Cost (profiles/render_batch_ab.txt, measured against K x tdlo_render_result, medians): one image costs what the single call
+ * costs (640 x 480: 0.068 against 0.068 ms device-resident, 0.201 against 0.199 pageable both ways); from K = 2 on the batch is cheaper on every line
+ * (K = 32: 0.53 against 2.01 ms and 3.87 against 7.00 ms; 1280 x 720: 0.70 against 1.89 and 4.54 against 7.54 ms).  There is no routing threshold: the calls
+ * always take k_render_batch. */
+typedef struct { const unsigned char *colour;    /* rows x cols x 3, or NULL: the context's most recent colour frame (as tdlo_render_result) */
+                 const unsigned char *occluder;  /* rows x cols or NULL; ignored when colour == NULL */
+                 unsigned char *image_out;       /* rows x cols x 3 */ } tdlo_render_image;
+typedef struct { int image, M; const double *Y /* column-major, 3 M */; const double *proj /* 12 */;
+                 const int *vis; int n_vis; const tdlo_render_params *params /* NULL: defaults */; } tdlo_render_rope;
+/* The host half, no device work: the table the kernel reads.  Ropes are ordered stably by image: positions rope_first[k] .. rope_first[k + 1] - 1 are image
+ * k's ropes in list order (rope_first: K + 1 ints).  heads: eight ints per rope, in that order: {c_lo, r_lo, c_hi, r_hi, first primitive, number of
+ * primitives, 0, 0} -- the union of its primitives' bounding boxes, a disc inflated by its radius, a line by (width + 1) >> 1; a one-node rope has no
+ * primitive and the empty box {0, 0, -1, -1}.  prims: tdlo_render_primitives' records, rope after rope in the same order; *n_prims their number.
+ * TDLO_E_INVALID (every output untouched): R outside 0 .. 1024, K outside 1 .. 256, a rope's image outside 0 .. K - 1, a rope of fewer than 1 or more
+ * than 1024 nodes or one that tdlo_render_primitives refuses, more than prims_cap records. */
+int tdlo_render_batch_table(const tdlo_render_rope *ropes, int R, int K,
+                            int *heads /* 8 R ints */, int *prims /* 8 ints per primitive */, int prims_cap, int *n_prims, int *rope_first /* K + 1 */);
+int tdlo_render_result_batch(tdlo_ctx *ctx, const tdlo_render_image *images, int K, int rows, int cols,
+                             const tdlo_render_rope *ropes, int R, int *corners /* 4 K or NULL */);
+/* Rope i: tracker i's current nodes over image image_of[i], vis formed exactly as tdlo_tracker_render_result forms it; proj_each / params_each: NULL, or F
+ * entries of which any may be NULL (the tracker's matrix as tdlo_tracker_render_result chooses it / the default parameters).  The images are passed
+ * explicitly, as tdlo_tracker_frames_batch takes them: a batch of cloud calls leaves no per-image colour residency to lean on.  Refused as above, and for
+ * trackers of different contexts or a tracker without nodes.  No tracker's state is touched. */
+int tdlo_tracker_render_result_batch(tdlo_tracker *const *trackers, int F, const tdlo_render_image *images, int K, int rows, int cols,
+                                     const int *image_of /* F */, const double *const *proj_each /* F entries or NULL; an entry may be NULL */,
+                                     const tdlo_render_params *const *params_each /* likewise */, int *corners /* 4 K or NULL */);
+
 /* The callback's self-occlusion ("painter") test, trackdlo/src/trackdlo_node.cpp:279-343: the edges between consecutive nodes are taken nearest the camera
  * first (:279-290, by the camera distance of their mid-points) and each is drawn as a line of dlo_pixel_width pixels (:337-341) after its two end nodes
  * were looked up in what had been drawn before (:304-334): a node whose projected pixel (proj: 3 x 4 row-major, the reference's proj_matrix; pixel
@@ -961,6 +1011,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 30 / 31: tdlo_visibility_prepass_batch calls served by the one launch k_node_min_dist_batch / passed on to tdlo_visibility_prepass slot by slot.
  * 32 / 33: frames of tdlo_depth_to_cloud_batch (tdlo_tracker_frames_batch's among them) served by the batch launch k_cloud_fused_batch / passed on by it to the
  * single call for their slot; frames of a batch below the crossover, which loops over the single calls, count in 6 / 7 alone.
+ * 34 / 35: images of tdlo_render_result_batch (tdlo_tracker_render_result_batch's among them) that k_render_batch wrote where the caller wanted them / that
+ * were copied out of the context's arena; 19 / 20 count the single call's images only.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -23,6 +23,7 @@ cd $S
 /opt/rocm/bin/hipcc $F -c tdlo_batch.hip -o $B/tdlo_batch.o &
 /opt/rocm/bin/hipcc $F -c tdlo_image.hip -o $B/tdlo_image.o &
 /opt/rocm/bin/hipcc $F -c tdlo_render.hip -o $B/tdlo_render.o &
+/opt/rocm/bin/hipcc $F -c tdlo_render_batch.hip -o $B/tdlo_render_batch.o &
 /opt/rocm/bin/hipcc $F -x hip -c tdlo_api.cpp -o $B/tdlo_api.o &
 /opt/rocm/bin/hipcc $F -x hip -c tdlo_rccl.cpp -o $B/tdlo_rccl.o &
 g++ -O3 -std=c++17 -fPIC -ffp-contract=off $* -c tdlo_host.cpp -o $B/tdlo_host.o &

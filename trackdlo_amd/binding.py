@@ -53,6 +53,14 @@ class RenderParams(C.Structure):
                 ("edge_visible", C.c_ubyte * 3), ("edge_hidden", C.c_ubyte * 3)]
 
 
+class RenderImage(C.Structure):                    # tdlo_render_image: the planes of one image of a render batch (host or device pointers) and where its picture goes
+    _fields_ = [("colour", C.c_void_p), ("occluder", C.c_void_p), ("image_out", C.c_void_p)]
+
+
+class RenderRope(C.Structure):                     # tdlo_render_rope: one rope of a render batch -- the image it is drawn over, its nodes, matrix, index set and colours
+    _fields_ = [("image", C.c_int), ("M", C.c_int), ("Y", C.c_void_p), ("proj", C.c_void_p), ("vis", C.c_void_p), ("n_vis", C.c_int), ("params", C.c_void_p)]
+
+
 F32, F64 = 0, 1                                     # tdlo_cloud_view.dtype
 MEM_AUTO, MEM_HOST, MEM_DEVICE = 0, 1, 2            # tdlo_cloud_view.location
 VIEW_ASYNC = 1                                      # tdlo_cloud_view.flags
@@ -116,6 +124,7 @@ SYMBOLS = [
     "tdlo_sort_pts", "tdlo_sort_pts_host", "tdlo_tracker_initialize_from_cloud", "tdlo_tracker_initialize_from_cloud_view",
     "tdlo_visibility_prepass_batch", "tdlo_cpd_lle_batch_each", "tdlo_tracker_tracking_step_batch", "tdlo_tracker_frame_batch",
     "tdlo_depth_to_cloud_batch", "tdlo_tracker_frames_batch",
+    "tdlo_render_batch_table", "tdlo_render_result_batch", "tdlo_tracker_render_result_batch",
 ]
 
 _lib = None
@@ -315,6 +324,10 @@ def load_library(path: str | None = None):
     if hasattr(lib, "tdlo_depth_to_cloud_batch"):
         lib.tdlo_depth_to_cloud_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, cd, vp, vp, vp]
         lib.tdlo_tracker_frames_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "tdlo_render_result_batch"):
+        lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
+        lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
+        lib.tdlo_tracker_render_result_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -616,6 +629,64 @@ def _batch_images(images):
 
 def _params_address(p):
     return None if p is None else C.addressof(p)
+
+
+def _render_ropes(ropes):
+    """tdlo_render_rope table of a list of dicts {image, Y [M x 3], proj (12), vis, params (RenderParams or None)}.  Returns (table, R, owners)."""
+    R = len(ropes)
+    tab = (RenderRope * max(R, 1))(); keep = []
+    for i, r in enumerate(ropes):
+        Y = _f64(r["Y"])
+        if Y.ndim != 2 or Y.shape[1] != 3:
+            raise ValueError(f"rope {i}: Y must be M x 3")
+        pj = np.ascontiguousarray(r["proj"], dtype=np.float64).reshape(12)
+        v = np.ascontiguousarray(r["vis"], dtype=np.int32).reshape(-1)
+        prm = r.get("params")
+        tab[i].image = int(r["image"]); tab[i].M = Y.shape[0]
+        tab[i].Y = Y.ctypes.data; tab[i].proj = pj.ctypes.data; tab[i].vis = v.ctypes.data if len(v) else None; tab[i].n_vis = len(v)
+        tab[i].params = _params_address(prm)
+        keep += [Y, pj, v, prm]
+    return tab, R, keep
+
+
+def _render_images(images, rows, cols):
+    """tdlo_render_image table of a list of dicts {colour, occluder, out}: colour / occluder as _batch_plane takes a plane (colour None: the context's last colour
+    frame), out as Context._render_out takes it.  Returns (table, K, [out arrays], owners)."""
+    K = len(images)
+    if K < 1:
+        raise ValueError("at least one image")
+    tab = (RenderImage * K)(); outs = []; keep = []
+    for k, im in enumerate(images):
+        cadr, cown = _batch_plane(im.get("colour"), np.uint8, (rows, cols, 3), f"image {k}: colour")
+        oadr, oown = _batch_plane(im.get("occluder"), np.uint8, (rows, cols), f"image {k}: occluder")
+        out, adr = Context._render_out(im.get("out"), rows, cols)
+        tab[k].colour = cadr; tab[k].occluder = oadr; tab[k].image_out = adr
+        outs.append(out); keep += [cown, oown]
+    return tab, K, outs, keep
+
+
+def _render_shape(ctx, images, shape):
+    if shape is not None:
+        return tuple(int(v) for v in shape)
+    for im in images:
+        if im.get("colour") is not None:
+            return tuple(int(v) for v in im["colour"].shape[:2])
+    return ctx.last_colour_shape()
+
+
+def render_batch_table(ropes, K):
+    """The host half of the batched result image (tdlo_render_batch_table; no GPU): (heads [R x 8], prims [n x 8], rope_first [K + 1]) -- the ropes ordered
+    stably by image, per rope {c_lo, r_lo, c_hi, r_hi, first primitive, number of primitives, 0, 0}, and the ropes' primitive records one after the other.
+    Raises TdloError(TDLO_E_INVALID) for a rope that cannot be drawn."""
+    tab, R, keep = _render_ropes(ropes)
+    cap = sum(3 * max(int(tab[i].M) - 1, 0) for i in range(R))
+    heads = np.zeros((R, 8), dtype=np.int32); prims = np.zeros((cap, 8), dtype=np.int32); first = np.zeros(int(K) + 1 if K >= 0 else 1, dtype=np.int32)
+    n = C.c_int(-1)
+    rc = load_library().tdlo_render_batch_table(C.cast(tab, C.c_void_p), R, int(K), _ptr(heads), _ptr(prims), cap, C.byref(n), _ptr(first))
+    del keep
+    if rc:
+        raise TdloError(rc, "tdlo_render_batch_table: a rope that cannot be drawn, or an image index out of range")
+    return heads, prims[:n.value], first
 
 
 class Context:
@@ -976,6 +1047,24 @@ class Context:
     def render_route_counts(self):
         """[result images the kernel wrote where the caller wanted them, result images copied out of the device image] (tdlo_debug_route_count 19 / 20)."""
         return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (19, 20)]
+
+    def render_batch_route_counts(self):
+        """[images of render_result_batch the kernel wrote where the caller wanted them, images copied out of the arena] (tdlo_debug_route_count 34 / 35)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (34, 35)]
+
+    def render_result_batch(self, images, ropes, *, shape=None, corners=True):
+        """Result images for many ropes (tdlo_render_result_batch): per image the blend once, then the image's ropes in list order, each as render_result draws
+        its one rope; all images in one launch.  images: dicts {colour, occluder, out} -- colour / occluder numpy arrays or packed tensors (host or device;
+        colour None: the context's last colour frame, shape = (rows, cols) is needed then), out as render_result's.  ropes: dicts {image, Y, proj, vis, params}.
+        Returns ([image], [[row, col, row, col] per image] or None)."""
+        rows, cols = _render_shape(self, images, shape)
+        itab, K, outs, keep = _render_images(images, rows, cols)
+        rtab, R, rkeep = _render_ropes(ropes)
+        cor = np.zeros((K, 4), dtype=np.int32)
+        rc = self.lib.tdlo_render_result_batch(self.h, C.cast(itab, C.c_void_p), K, rows, cols, C.cast(rtab, C.c_void_p), R, _ptr(cor) if corners else None)
+        del keep, rkeep
+        self._chk(rc)
+        return outs, ([[int(x) for x in row] for row in cor] if corners else None)
 
     def result_image_buffer(self, rows, cols):
         """The context's pinned result image as a numpy view (uint8 [rows x cols x 3]): passed as render_result's `out`, the kernel writes it in place
@@ -1484,6 +1573,33 @@ def frames_batch(trackers, images, image_of, colour_params, leaf_size, d_vis, ch
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def render_result_batch(trackers, images, image_of, proj=None, params=None, corners=True, check=True):
+    """tdlo_tracker_render_result_batch: the trackers' current nodes (one context) in one launch -- tracker i over image image_of[i], its vis and matrix as
+    trackdlo.render_result forms them; proj / params: None, or F entries of which any may be None.  images as Context.render_result_batch takes them, with a
+    colour image each.  Returns ([image], corners or None); check=False: ([image], corners or None, code) instead of raising on a refusal."""
+    F = len(trackers)
+    assert F >= 1
+    ctx = trackers[0].ctx
+    rows, cols = _render_shape(ctx, images, None)
+    itab, K, outs, keep = _render_images(images, rows, cols)
+    io = np.ascontiguousarray(image_of, dtype=np.int32)
+    assert len(io) == F and (proj is None or len(proj) == F) and (params is None or len(params) == F)
+    pjs = None if proj is None else [None if p is None else np.ascontiguousarray(p, dtype=np.float64).reshape(12) for p in proj]
+    pp = None if pjs is None else (C.c_void_p * F)(*[None if p is None else p.ctypes.data for p in pjs])
+    pr = None if params is None else (C.c_void_p * F)(*[_params_address(p) for p in params])
+    tab = (C.c_void_p * F)(*[t.h for t in trackers])
+    cor = np.zeros((K, 4), dtype=np.int32)
+    rc = ctx.lib.tdlo_tracker_render_result_batch(C.cast(tab, C.c_void_p), F, C.cast(itab, C.c_void_p), K, rows, cols, _ptr(io),
+                                                  C.cast(pp, C.c_void_p) if pp is not None else None, C.cast(pr, C.c_void_p) if pr is not None else None,
+                                                  _ptr(cor) if corners else None)
+    del keep
+    cl = [[int(x) for x in row] for row in cor] if corners else None
+    if not check:
+        return outs, cl, int(rc)
+    ctx._chk(rc)
+    return outs, cl
 
 
 def calc_LLE_weights(k, Y):

@@ -240,6 +240,12 @@ struct tdlo_ctx {
     char *rnd_pin = nullptr, *rnd_dev = nullptr;
     bool render_inplace = !(getenv("TDLO_RENDER_INPLACE") && atoi(getenv("TDLO_RENDER_INPLACE")) == 0);
     long long render_route[2] = {0, 0};  // images the kernel wrote where the caller wanted them / images copied out of res_dev
+    // result images for many ropes and images in one launch (tdlo_render_result_batch, k_render_batch): rbat_dev = [image records | rope heads | primitive
+    // records | corner words | staged sources | images to be copied out] in device memory, rbat_pin = [the table as it is uploaded | the corner words as they
+    // are read back] in pinned host memory, both grown on demand.  rbat_route: tdlo_debug_route_count 34 / 35
+    char *rbat_dev = nullptr, *rbat_pin = nullptr;
+    size_t rbat_dev_cap = 0, rbat_pin_cap = 0;
+    long long rbat_route[2] = {0, 0};    // images k_render_batch wrote where the caller wanted them / images copied out of rbat_dev
     size_t pin_doubles = 0;
     std::string err;
     int last_F = 0;
@@ -1766,6 +1772,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->res_dev) hipFree(c->res_dev);
     if (c->rnd_pin) hipHostFree(c->rnd_pin);
     if (c->rnd_dev) hipFree(c->rnd_dev);
+    if (c->rbat_pin) hipHostFree(c->rbat_pin);
+    if (c->rbat_dev) hipFree(c->rbat_dev);
     if (c->reg_ws) hipFree(c->reg_ws);
     if (c->pin) hipHostFree(c->pin);
     if (c->pin2) hipHostFree(c->pin2);
@@ -2846,6 +2854,160 @@ int tdlo_render_result(tdlo_ctx *c, const unsigned char *colour, const unsigned 
             corners[2] = (int)(h_corner[1] / (unsigned)cols); corners[3] = (int)(h_corner[1] % (unsigned)cols);
         }
     }
+    return TDLO_OK;
+}
+
+// ---- result images for many ropes: several ropes per image, K images per launch (tdlo_render_batch.hip) -------------------------------------------------
+int tdlo_render_batch_table(const tdlo_render_rope *ropes, int R, int K, int *heads, int *prims, int prims_cap, int *n_prims, int *rope_first) {
+    if (R < 0 || R > 1024 || K < 1 || K > 256 || (R > 0 && (!ropes || !heads)) || prims_cap < 0 || !n_prims || !rope_first) return TDLO_E_INVALID;
+    tdlo_render_params d;
+    tdlo_default_render_params(&d);
+    std::vector<int> order, hd, pr, first;
+    if (render_batch_table(ropes, R, K, d, order, hd, pr, first) >= 0) return TDLO_E_INVALID;
+    if (pr.size() / 8 > (size_t)prims_cap || (!pr.empty() && !prims)) return TDLO_E_INVALID;
+    std::copy(hd.begin(), hd.end(), heads);
+    std::copy(pr.begin(), pr.end(), prims);
+    std::copy(first.begin(), first.end(), rope_first);
+    *n_prims = (int)(pr.size() / 8);
+    return TDLO_OK;
+}
+
+int tdlo_render_result_batch(tdlo_ctx *c, const tdlo_render_image *images, int K, int rows, int cols, const tdlo_render_rope *ropes, int R, int *corners) {
+    if (!c) return TDLO_E_INVALID;
+    // everything that can be refused is refused before the first byte of any image_out is written
+    if (K < 1 || K > 256 || !images) return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: 1 .. 256 images");
+    if (rows <= 0 || cols <= 0 || rows > 8192 || cols > 8192) return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: images of 1 .. 8192 rows and columns");
+    if (R < 0 || R > 1024 || (R > 0 && !ropes)) return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: 0 .. 1024 ropes");
+    HIPCHK(c, hipSetDevice(c->device));
+    tdlo_render_params dflt;
+    tdlo_default_render_params(&dflt);
+    std::vector<int> order, heads, prims, rope_first;
+    {
+        const int bad = render_batch_table(ropes, R, K, dflt, order, heads, prims, rope_first);
+        if (bad >= 0)
+            return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: rope " + std::to_string(bad) + ": an image outside 0 .. K - 1, not 1 .. 1024 nodes with a projection "
+                                           "matrix, a node that cannot be drawn (w <= 0, a non-finite pixel, a pixel beyond +-8192), vis out of range, or a line width / "
+                                           "node radius outside 1 .. 255");
+    }
+    const size_t P = (size_t)rows * cols, n_prims = prims.size() / 8;
+    // ---- where every plane lies.  Sources: the context's pinned colour buffers and 4-byte aligned device memory are read in place, anything else is
+    // staged; destinations: the pinned result buffer and 4-byte aligned device memory are written by the kernel, anything else receives a copy
+    enum { kHost = 0, kDevice = 1, kOtherGpu = 2 };
+    auto where = [&](const void *p) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return (int)kHost; }      // (a pointer the runtime does not know: host memory)
+        if (at.type != hipMemoryTypeDevice) return (int)kHost;
+        return at.device == c->device ? (int)kDevice : (int)kOtherGpu;
+    };
+    const bool pin_shape = c->col_pin != nullptr && c->col_pin_rows == rows && c->col_pin_cols == cols;
+    struct Src { const unsigned char *p; bool occ, dev; size_t off; };
+    std::vector<Src> staged;                                   // every distinct (pointer, kind) once
+    struct Img { const unsigned char *colour, *occluder; long long colour_at, occ_at, out_at; bool out_dev; };      // *_at >= 0: an offset into the arena
+    std::vector<Img> im(K);
+    size_t stage_bytes = 0, out_bytes = 0;
+    int n_direct = 0;
+    auto source = [&](const unsigned char *p, bool occ, int k, const unsigned char *&in_place, long long &at) -> int {
+        in_place = nullptr; at = -1;
+        const bool pinned = pin_shape && (const char *)p == (occ ? c->col_pin + img_colour_bytes(P) : c->col_pin);
+        int w = kHost;
+        if (!pinned && (w = where(p)) == kOtherGpu)
+            return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: image " + std::to_string(k) + (occ ? ": occluder" : ": colour") + " is device memory of another GPU");
+        if (pinned || (w == kDevice && (uintptr_t)p % 4 == 0)) { in_place = p; return TDLO_OK; }
+        size_t j = 0;
+        while (j < staged.size() && !(staged[j].p == p && staged[j].occ == occ)) ++j;
+        if (j == staged.size()) { staged.push_back(Src{p, occ, w == kDevice, stage_bytes}); stage_bytes += occ ? img_occ_bytes(P) : img_colour_bytes(P); }
+        at = (long long)staged[j].off;
+        return TDLO_OK;
+    };
+    for (int k = 0; k < K; ++k) {
+        const tdlo_render_image &g = images[k];
+        Img &m = im[k];
+        m = Img{nullptr, nullptr, -1, -1, -1, false};
+        if (!g.image_out) return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: image " + std::to_string(k) + " has no image_out");
+        for (int j = 0; j < k; ++j)
+            if (images[j].image_out == g.image_out)
+                return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: images " + std::to_string(j) + " and " + std::to_string(k) + " have the same image_out");
+        if (!g.colour) {
+            if (!(c->last_colour && c->last_col_rows == rows && c->last_col_cols == cols))
+                return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: image " + std::to_string(k) + ": colour == NULL needs a colour call of this context on an image of "
+                                               "the same shape before it");
+            m.colour = c->last_colour; m.occluder = c->last_occluder;
+        } else {
+            if (int rc = source(g.colour, false, k, m.colour, m.colour_at)) return rc;
+            if (g.occluder) { if (int rc = source(g.occluder, true, k, m.occluder, m.occ_at)) return rc; }
+        }
+        const bool out_pinned = c->res_pin != nullptr && (char *)g.image_out == c->res_pin && c->res_pin_rows == rows && c->res_pin_cols == cols;
+        if (!out_pinned) {
+            const int w = where(g.image_out);
+            if (w == kOtherGpu) return fail(c, TDLO_E_INVALID, "tdlo_render_result_batch: image " + std::to_string(k) + ": image_out is device memory of another GPU");
+            m.out_dev = w == kDevice;
+        }
+        if (c->render_inplace && (out_pinned || (m.out_dev && (uintptr_t)g.image_out % 4 == 0))) ++n_direct;
+        else { m.out_at = (long long)out_bytes; out_bytes += img_colour_bytes(P); }
+    }
+    // ---- the arena (grown on demand)
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t tab_img = r256(sizeof(RenderBatchImage) * (size_t)K), tab_head = r256(32 * (size_t)R), tab_prim = r256(32 * n_prims);
+    const size_t tab = tab_img + tab_head + tab_prim, corner_bytes = r256(8 * (size_t)K);
+    const size_t dev_need = tab + corner_bytes + stage_bytes + out_bytes, pin_need = tab + corner_bytes;
+    hipStream_t st = c->stream;
+    if (dev_need > c->rbat_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->rbat_dev) hipFree(c->rbat_dev);
+        c->rbat_dev = nullptr; c->rbat_dev_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->rbat_dev, dev_need));
+        c->rbat_dev_cap = dev_need;
+    }
+    if (pin_need > c->rbat_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->rbat_pin) hipHostFree(c->rbat_pin);
+        c->rbat_pin = nullptr; c->rbat_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->rbat_pin, pin_need, hipHostMallocDefault));
+        std::memset(c->rbat_pin, 0, pin_need);
+        c->rbat_pin_cap = pin_need;
+    }
+    char *d_tab = c->rbat_dev, *d_corner = d_tab + tab, *d_stage = d_corner + corner_bytes, *d_out = d_stage + stage_bytes;
+    char *h_tab = c->rbat_pin;                                 // (free: every call returns with the stream drained)
+    const unsigned *h_corner = (const unsigned *)(c->rbat_pin + tab);
+    bool any_corner = false;
+    {
+        RenderBatchImage *rec = (RenderBatchImage *)h_tab;
+        for (int k = 0; k < K; ++k) {
+            const Img &m = im[k];
+            rec[k].colour = m.colour_at >= 0 ? (const unsigned char *)(d_stage + m.colour_at) : m.colour;
+            rec[k].occluder = m.occ_at >= 0 ? (const unsigned char *)(d_stage + m.occ_at) : m.occluder;
+            rec[k].out = m.out_at >= 0 ? (unsigned char *)(d_out + m.out_at) : images[k].image_out;
+            rec[k].rope_lo = rope_first[k]; rec[k].rope_hi = rope_first[k + 1];
+            rec[k].corner = (corners && rec[k].occluder) ? k : -1;
+            rec[k].pad = 0;
+            any_corner = any_corner || rec[k].corner >= 0;
+        }
+        if (R) std::memcpy(h_tab + tab_img, heads.data(), 32 * (size_t)R);
+        if (n_prims) std::memcpy(h_tab + tab_img + tab_head, prims.data(), 32 * n_prims);
+    }
+    // ---- uploads, one launch, the copies out, one read-back, one wait
+    HIPCHK(c, hipMemcpyAsync(d_tab, h_tab, tab_img + tab_head + 32 * n_prims, hipMemcpyHostToDevice, st));
+    for (const Src &s : staged)
+        HIPCHK(c, hipMemcpyAsync(d_stage + s.off, s.p, s.occ ? P : 3 * P, s.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (any_corner) HIPCHK(c, hipMemsetAsync(d_corner, 0xff, 8 * (size_t)K, st));                  // {0xffffffff, -1} per image: no zero byte seen
+    HIPCHK(c, launch_render_batch((const RenderBatchImage *)d_tab, K, (const int *)(d_tab + tab_img), (const int *)(d_tab + tab_img + tab_head), (int)P, cols,
+                                  (unsigned *)d_corner, st));
+    for (int k = 0; k < K; ++k)
+        if (im[k].out_at >= 0)
+            HIPCHK(c, hipMemcpyAsync(images[k].image_out, d_out + im[k].out_at, 3 * P, im[k].out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    if (any_corner) HIPCHK(c, hipMemcpyAsync((void *)h_corner, d_corner, 8 * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, wait_stream(st));
+    c->rbat_route[0] += n_direct; c->rbat_route[1] += K - n_direct;
+    if (corners)
+        for (int k = 0; k < K; ++k) {
+            int *q = corners + 4 * (size_t)k;
+            q[0] = q[1] = q[2] = q[3] = -1;
+            const unsigned *h = h_corner + 2 * (size_t)k;
+            if (((const RenderBatchImage *)h_tab)[k].corner >= 0 && h[0] != 0xffffffffu) {
+                q[0] = (int)(h[0] / (unsigned)cols); q[1] = (int)(h[0] % (unsigned)cols);
+                q[2] = (int)(h[1] / (unsigned)cols); q[3] = (int)(h[1] % (unsigned)cols);
+            }
+        }
     return TDLO_OK;
 }
 
@@ -4034,7 +4196,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 33) return -1;
+    if (!c || which < 0 || which > 35) return -1;
+    if (which >= 34) return c->rbat_route[which - 34];
     if (which >= 32) return c->cbat_route[which - 32];
     if (which >= 30) return c->vbat_route[which - 30];
     if (which >= 27) return c->view_team_route[which - 27];
@@ -4942,6 +5105,22 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
     return TDLO_OK;
 }
 
+// The rope tdlo_tracker_render_result draws: the projection matrix it chooses and the reference's not_self_occluded_nodes.  false: no matrix to be had.
+static bool tracker_render_rope(const tdlo_tracker *t, const double *proj, double pj[12], std::vector<int> &vis) {
+    const int M = t->M;
+    std::fill(pj, pj + 12, 0.0);
+    if (proj) std::copy(proj, proj + 12, pj);
+    else if (t->painter_on) std::copy(t->painter_proj, t->painter_proj + 12, pj);
+    else if (t->frame_seen) { pj[0] = t->frame_cam[0]; pj[2] = t->frame_cam[2]; pj[5] = t->frame_cam[1]; pj[6] = t->frame_cam[3]; pj[10] = 1.0; }
+    else return false;
+    vis.clear();
+    if (t->painter_on && t->frame_Y0.size() == 3 * (size_t)M) {
+        const std::vector<double> zero(M, 0.0);
+        self_occlusion_visible(t->frame_Y0.data(), M, t->painter_proj, t->painter_width, zero.data(), std::numeric_limits<double>::infinity(), vis);
+    } else { vis.resize(M); for (int m = 0; m < M; ++m) vis[m] = m; }
+    return true;
+}
+
 // The picture of the tracker's current nodes over the last colour frame (trackdlo_node.cpp:377-452).  vis = the reference's not_self_occluded_nodes (:401):
 // the nodes the self-occlusion test leaves when no node is too far from the cloud, formed from the nodes the frame STARTED from (:279-343 run before
 // tracking_step); every node when the test is off.  Reads the tracker, changes nothing of it.
@@ -4950,16 +5129,32 @@ int tdlo_tracker_render_result(tdlo_tracker *t, const double *proj, const tdlo_r
     tdlo_ctx *c = t->ctx;
     const int M = t->M;
     double pj[12] = {0};
-    if (proj) std::copy(proj, proj + 12, pj);
-    else if (t->painter_on) std::copy(t->painter_proj, t->painter_proj + 12, pj);
-    else if (t->frame_seen) { pj[0] = t->frame_cam[0]; pj[2] = t->frame_cam[2]; pj[5] = t->frame_cam[1]; pj[6] = t->frame_cam[3]; pj[10] = 1.0; }
-    else return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result: no projection matrix (none given, no tdlo_tracker_set_self_occlusion, no frame call yet)");
     std::vector<int> vis;
-    if (t->painter_on && t->frame_Y0.size() == 3 * (size_t)M) {
-        const std::vector<double> zero(M, 0.0);
-        self_occlusion_visible(t->frame_Y0.data(), M, t->painter_proj, t->painter_width, zero.data(), std::numeric_limits<double>::infinity(), vis);
-    } else { vis.resize(M); for (int m = 0; m < M; ++m) vis[m] = m; }
+    if (!tracker_render_rope(t, proj, pj, vis))
+        return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result: no projection matrix (none given, no tdlo_tracker_set_self_occlusion, no frame call yet)");
     return tdlo_render_result(c, nullptr, nullptr, c->last_col_rows, c->last_col_cols, t->Y.data(), M, pj, vis.data(), (int)vis.size(), p, image_out, corners);
+}
+
+// Rope i = tracker i's current nodes over image image_of[i], drawn by tdlo_render_result_batch.  Reads the trackers, changes nothing of them.
+int tdlo_tracker_render_result_batch(tdlo_tracker *const *trackers, int F, const tdlo_render_image *images, int K, int rows, int cols, const int *image_of,
+                                     const double *const *proj_each, const tdlo_render_params *const *params_each, int *corners) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (F > 1024 || !image_of) return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result_batch: 1 .. 1024 trackers and an image for each");
+    std::vector<tdlo_render_rope> ropes(F);
+    std::vector<std::vector<int>> vis(F);
+    std::vector<double> pj(12 * (size_t)F);
+    for (int i = 0; i < F; ++i) {
+        const tdlo_tracker *t = trackers[i];
+        if (!t || t->M < 1 || t->Y.size() != 3 * (size_t)t->M)
+            return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result_batch: tracker " + std::to_string(i) + " has no nodes");
+        if (t->ctx != c) return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result_batch: tracker " + std::to_string(i) + " belongs to another context: the trackers of a batch share one");
+        if (!tracker_render_rope(t, proj_each ? proj_each[i] : nullptr, pj.data() + 12 * (size_t)i, vis[i]))
+            return fail(c, TDLO_E_INVALID, "tdlo_tracker_render_result_batch: tracker " + std::to_string(i) + ": no projection matrix (none given, no tdlo_tracker_set_self_occlusion, "
+                                           "no frame call yet)");
+        ropes[i] = tdlo_render_rope{image_of[i], t->M, t->Y.data(), pj.data() + 12 * (size_t)i, vis[i].data(), (int)vis[i].size(), params_each ? params_each[i] : nullptr};
+    }
+    return tdlo_render_result_batch(c, images, K, rows, cols, ropes.data(), F, corners);
 }
 
 // trackdlo_node.cpp:279-343 on the host (tdlo_host.cpp, self_occlusion_visible): O(M^2) integer tests, no kernel warranted

@@ -496,6 +496,48 @@ int render_primitives(const double *Y, int M, const double proj[12], const int *
     return 0;
 }
 
+// ---- the table of k_render_batch (tdlo_render_batch.hip): many ropes over many images ------------------------------------------------------------------
+// The ropes ordered stably by image (list order within an image: the drawing order), per rope a head {c_lo, r_lo, c_hi, r_hi, first primitive, number of
+// primitives, 0, 0} whose box is the union of its primitives' boxes inflated exactly as the kernels inflate them (disc: radius, line: (width + 1) >> 1),
+// and render_primitives' records rope after rope.  Nothing is written unless every rope can be drawn.
+int render_batch_table(const tdlo_render_rope *ropes, int R, int K, const tdlo_render_params &dflt, std::vector<int> &order, std::vector<int> &heads, std::vector<int> &prims,
+                       std::vector<int> &rope_first) {
+    size_t total = 0;
+    for (int i = 0; i < R; ++i) {
+        if (ropes[i].image < 0 || ropes[i].image >= K || ropes[i].M < 1 || ropes[i].M > 1024) return i;
+        total += 3 * (size_t)(ropes[i].M - 1);
+    }
+    std::vector<int> ord(R), first(K + 1, 0), hd(8 * (size_t)R, 0), pr(8 * total);
+    for (int i = 0; i < R; ++i) ++first[ropes[i].image + 1];
+    for (int k = 0; k < K; ++k) first[k + 1] += first[k];
+    {
+        std::vector<int> at(first.begin(), first.end() - 1);
+        for (int i = 0; i < R; ++i) ord[at[ropes[i].image]++] = i;
+    }
+    int at = 0;
+    for (int j = 0; j < R; ++j) {
+        const tdlo_render_rope &r = ropes[ord[j]];
+        const tdlo_render_params *p = r.params ? r.params : &dflt;
+        int *q = pr.data() + 8 * (size_t)at;
+        const int np = 3 * (r.M - 1);
+        if (render_primitives(r.Y, r.M, r.proj, r.vis, r.n_vis, p->line_width, p->node_radius, p->node_visible, p->node_hidden, p->edge_visible, p->edge_hidden,
+                              np ? q : hd.data()))      // (one node: validated, nothing written)
+            return ord[j];
+        int *h = hd.data() + 8 * (size_t)j;
+        h[0] = 0; h[1] = 0; h[2] = -1; h[3] = -1; h[4] = at; h[5] = np; h[6] = 0; h[7] = 0;
+        for (int i = 0; i < np; ++i) {
+            const int *rec = q + 8 * (size_t)i;
+            const int ext = rec[0] ? rec[5] : (rec[5] + 1) >> 1;
+            const int x0 = std::min(rec[1], rec[3]) - ext, x1 = std::max(rec[1], rec[3]) + ext, y0 = std::min(rec[2], rec[4]) - ext, y1 = std::max(rec[2], rec[4]) + ext;
+            if (i == 0) { h[0] = x0; h[1] = y0; h[2] = x1; h[3] = y1; }
+            else { h[0] = std::min(h[0], x0); h[1] = std::min(h[1], y0); h[2] = std::max(h[2], x1); h[3] = std::max(h[3], y1); }
+        }
+        at += np;
+    }
+    order.swap(ord); heads.swap(hd); prims.swap(pr); rope_first.swap(first);
+    return -1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // sort_pts (trackdlo/src/utils.cpp:95-170) and the chain coordinate of trackdlo_node.cpp:135-141: the host twin of k_sort_pts
 // (tdlo_init.hip), the same rule in the same arithmetic.  The reference's triple loop takes, in each of its M - 1 rounds, the pair

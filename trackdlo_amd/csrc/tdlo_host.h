@@ -1,6 +1,8 @@
 // tdlo_host.h -- host-side helpers of the path (see tdlo_host.cpp).
 #pragma once
+#include <stddef.h>
 #include <vector>
+#include "../../include/trackdlo_hip.h"
 
 namespace tdlo {
 
@@ -28,6 +30,13 @@ void self_occlusion_visible(const double *Y, int M, const double proj[12], int d
 int render_primitives(const double *Y, int M, const double proj[12], const int *vis, int n_vis, int line_width, int node_radius,
                       const unsigned char node_visible[3], const unsigned char node_hidden[3], const unsigned char edge_visible[3],
                       const unsigned char edge_hidden[3], int *prims);
+
+// The table k_render_batch reads (tdlo_render_batch_table, include/trackdlo_hip.h): the ropes ordered stably by image, a head record per rope, the ropes'
+// primitive records one after the other.  order[j]: the list index of the rope at position j.  Returns -1 when every rope can be drawn, else the list index
+// of the first rope that cannot (its image outside 0 .. K - 1, its node count outside 1 .. 1024, or refused by render_primitives).  dflt: the parameters
+// of a rope that brings none.
+int render_batch_table(const tdlo_render_rope *ropes, int R, int K, const tdlo_render_params &dflt, std::vector<int> &order, std::vector<int> &heads, std::vector<int> &prims,
+                       std::vector<int> &rope_first);
 
 // evaluator::get_piecewise_error (evaluator.cpp:258-283); chains are n x 3 column-major.
 double piecewise_error(const double *Ytrack, int n1, const double *Ytrue, int n2);

@@ -337,6 +337,11 @@ int check_device_image();
 // aligned; prims: n_prims records of eight ints in device memory (tdlo_host.cpp, render_primitives); corner: nullptr, or two device words set to {0xffffffff, -1}
 hipError_t launch_render(const unsigned char *colour, const unsigned char *occluder, unsigned char *out, const int *prims, int n_prims, int P, int cols,
                          unsigned *corner, hipStream_t s);
+// tdlo_render_batch.hip: the same for K images of P pixels with any number of ropes each, in one launch (k_render_batch: grid (tiles, images)).  images: K
+// records in device memory -- colour / occluder (may be null) / out as above, the image's ropes [rope_lo, rope_hi) among `heads` (eight ints per rope:
+// tdlo_render_batch_table), corner: which pair of `corners` words is the image's (< 0: none; the caller has set the pairs to {0xffffffff, -1})
+struct RenderBatchImage { const unsigned char *colour, *occluder; unsigned char *out; int rope_lo, rope_hi, corner, pad; };
+hipError_t launch_render_batch(const RenderBatchImage *images, int K, const int *heads, const int *prims, int P, int cols, unsigned *corners, hipStream_t s);
 // tdlo_import.hip: a cloud view (float32 / float64 elements at src, strides in elements) -> Xraw (N x 3 column-major doubles); the form -- 0 generic,
 // 1 one 12-byte load per point, 2 column-major pairs -- follows from the strides and the alignment of src only
 int cloud_import_form(const void *src, bool f64, long long stride_point, long long stride_comp);

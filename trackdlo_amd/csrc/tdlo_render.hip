@@ -15,28 +15,14 @@
 // The occlusion corners (:198-208: first and last pixel in row-major order whose occluder byte is 0) ride along: one atomicMin and one atomicMax per
 // wave that saw such a byte.
 #include "tdlo_internal.h"
-#include "tdlo_thick_line.h"
+#include "tdlo_render_px.h"
 
 namespace tdlo {
 namespace {
 
 constexpr int kRB = 256;                 // threads per workgroup: 4 waves, 1024 pixels
 
-// 0.5 a + 0.5 b on four bytes at once, b = a & m, rounded half to even: s = a + b, out = (s >> 1) + ((s & 1) & ((s >> 1) & 1)).
-// h = floor(s / 2) = (a & b) + ((a ^ b) >> 1) per byte; s & 1 = (a ^ b) & 1; an odd s is at most 509, so h + 1 <= 255: no carry leaves a byte.
-__device__ __forceinline__ unsigned blend4(unsigned a, unsigned m) {
-    const unsigned b = a & m, x = a ^ b;
-    const unsigned h = (a & b) + ((x >> 1) & 0x7f7f7f7fu);
-    return h + (x & h & 0x01010101u);
-}
-
-// one primitive against one pixel (bounding box first: the exact line test is 64-bit)
-__device__ __forceinline__ bool covers(int kind, int c0, int r0, int c1, int r1, int size, int pc, int pr) {
-    if (kind) { const int dx = pc - c0, dy = pr - r0; return dx * dx + dy * dy <= size * size; }
-    const int hw = (size + 1) >> 1;
-    if (pc < min(c0, c1) - hw || pc > max(c0, c1) + hw || pr < min(r0, r1) - hw || pr > max(r0, r1) + hw) return false;
-    return within_half_width(Px{pc, pr}, Px{c0, r0}, Px{c1, r1}, size);
-}
+// (blend4 and covers: tdlo_render_px.h, shared with k_render_batch)
 
 __global__ __launch_bounds__(kRB) void k_render(const unsigned char *__restrict__ colour, const unsigned char *__restrict__ occluder,
                                                 unsigned char *__restrict__ out, const int *__restrict__ prims, int n_prims, int P, int cols,

@@ -457,6 +457,39 @@ int tdlo_tracker_initialize_from_cloud(tdlo_tracker *t, const double *X, int N, 
 /* tdlo_set_cloud_view (enqueued without a host wait; a device source must stay valid until this call returns), then the X == NULL route above. */
 int tdlo_tracker_initialize_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v, int N, double mu, int max_iter, double *sigma2_out);
 
+/* ---- many trackers started in one call ------------------------------------------------------------- */
+/* tdlo_reg, tdlo_sort_pts and tdlo_tracker_initialize_from_cloud for F frames at once.  A tracker's start is 2 + 2 max_iter launches of a few workgroups
+ * each; here the F loops are the second grid dimension of the SAME 2 + 2 max_iter launches (k_reg_estep_batch / k_reg_mstep_batch, csrc/tdlo_reg_batch.hip:
+ * every frame its own state and partial sums, no workgroup waits for another), k_sort_pts runs once with one workgroup per frame, and one upload, one
+ * read-back and one wait serve them all.  All three work on the clouds RESIDENT in the slots -- what tdlo_set_cloud, tdlo_set_cloud_view,
+ * tdlo_depth_to_cloud_batch / tdlo_tracker_frames_batch or the single cloud calls left there (a cloud tracking_step staged is flushed first).
+ * Bits: for every frame reg's Y and sigma2, the permutation, the sorted nodes and the chain coordinate are the single calls' bit for bit, a centroid that
+ * attracts no mass NaN in the same places; a single call made afterwards on the same context gives what it always gave.
+ * Refused as a whole with TDLO_E_INVALID before anything is enqueued or touched (the reason in tdlo_last_error): F < 1 or a null pointer, trackers of
+ * different contexts, a slot out of range or named twice, a slot without a cloud, node counts that differ, fewer than 4 or more than 890 nodes
+ * (tdlo_reg_batch: M < 1; tdlo_sort_pts_batch: M outside 2 .. 1024), bad mu / max_iter.
+ * One frame fails with TDLO_E_NUMERIC where the single call would (a NaN centroid, tdlo_sort_pts' three refusals): it gets the code in rc_each, its
+ * tracker and its outputs stay exactly as they were, the other frames complete as if alone; the call returns the first non-zero code and
+ * tdlo_last_error names that frame with the single call's reason.
+ * Cost (profiles/init_batch_ab.txt; N = 5 000, M = 45, 100 iterations): two trackers 5.69 against 11.61 ms for two single calls, 32 trackers 11.79 against
+ * 186.0 ms; with voxel-grid-sized clouds (N = 500) 32 trackers 5.31 against 167.8 ms.  One frame is level with the single call (5.72 against 5.81 ms).
+ * TDLO_INIT_BATCH_MIN=n (read when the context is made): below n frames the call loops over the single calls -- the comparator; the default is 1, the
+ * smallest F from which the batch launches won by the rule set before they were measured, so by default every call takes them.
+ * tdlo_debug_route_count 36 / 37 count the frames of the two routes; TDLO_INIT_SORT=host applies as to the single call (the F centroid sets are read
+ * back once and ordered by tdlo_sort_pts_host).
+ *   tdlo_reg_batch        slots: F distinct slots; Y: F blocks of M x 3 column-major, sigma2: F -- pure outputs as tdlo_reg's.
+ *   tdlo_sort_pts_batch   Y: F blocks of M x 3 column-major in host memory; Y_sorted / perm / coord: NULL or F blocks; rc_each: NULL or F codes.
+ *   tdlo_tracker_initialize_from_cloud_batch   every tracker gets its nodes and guide nodes, its geodesic coordinate is REPLACED, its own sigma2 is left
+ *                         alone; sigma2_out: NULL or F (reg's sigma2 of the frames that succeeded), rc_each: NULL or F codes. */
+int tdlo_reg_batch(tdlo_ctx *ctx, const int *slots, int F, double *Y, double *sigma2, int M, double mu, int max_iter);
+int tdlo_sort_pts_batch(tdlo_ctx *ctx, const double *Y, int F, int M, double *Y_sorted, int *perm, double *coord, int *rc_each);
+int tdlo_tracker_initialize_from_cloud_batch(tdlo_tracker *const *trackers, int F, double mu, int max_iter, double *sigma2_out, int *rc_each);
+/* Test aid, no device and no context: where the F frames of such a call keep their doubles in the workspace (csrc/tdlo_reg_plan.h).  N: the F cloud
+ * sizes (>= 1).  nblk: E-step workgroups per frame, max(1, min(ceil(N / 256), 256)) as tdlo_reg's; state_off / part_off / out_off: each frame's state
+ * block (8 + 3 M doubles), partial sums (nblk x (5 M + 1)) and output block (2 + 4 M + ceil(M / 2), on 16 bytes), in doubles; total: doubles in all --
+ * for F = 1 what the single call asks for.  Any output may be NULL.  TDLO_E_INVALID for F < 1, M < 1, a null N or an empty cloud. */
+int tdlo_debug_reg_batch_plan(const int *N, int F, int M, int *nblk, long long *state_off, long long *part_off, long long *out_off, long long *total);
+
 /* ---- depth image -> cloud -> voxel-grid down-sample ------------------------ */
 /* The step right upstream of tracking_step in the ROS node (trackdlo/src/trackdlo_node.cpp:195-241): every pixel
  * with mask != 0 is back-projected ((u - cx) z / fx, (v - cy) z / fy, z = depth / 1000; float storage like
@@ -1013,6 +1046,9 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * single call for their slot; frames of a batch below the crossover, which loops over the single calls, count in 6 / 7 alone.
  * 34 / 35: images of tdlo_render_result_batch (tdlo_tracker_render_result_batch's among them) that k_render_batch wrote where the caller wanted them / that
  * were copied out of the context's arena; 19 / 20 count the single call's images only.
+ * 36 / 37: frames of tdlo_reg_batch, tdlo_sort_pts_batch and tdlo_tracker_initialize_from_cloud_batch served by the batch launches (k_reg_estep_batch /
+ * k_reg_mstep_batch, k_sort_pts_batch; a frame that ends on TDLO_E_NUMERIC included) / handed to the single call because the batch was smaller than
+ * TDLO_INIT_BATCH_MIN; 25 / 26 keep counting the single calls only, those of the second route among them.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

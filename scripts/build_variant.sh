@@ -18,6 +18,7 @@ cd $S
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-mfma-vgpr-form -c tdlo_mstep_band.hip -o $B/tdlo_mstep_band.o &
 /opt/rocm/bin/hipcc $F -c tdlo_cloud.hip -o $B/tdlo_cloud.o &
 /opt/rocm/bin/hipcc $F -c tdlo_reg.hip -o $B/tdlo_reg.o &
+/opt/rocm/bin/hipcc $F -c tdlo_reg_batch.hip -o $B/tdlo_reg_batch.o &
 /opt/rocm/bin/hipcc $F -ffp-contract=off -c tdlo_init.hip -o $B/tdlo_init.o &
 /opt/rocm/bin/hipcc $F -c tdlo_import.hip -o $B/tdlo_import.o &
 /opt/rocm/bin/hipcc $F -c tdlo_batch.hip -o $B/tdlo_batch.o &

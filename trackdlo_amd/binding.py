@@ -125,6 +125,7 @@ SYMBOLS = [
     "tdlo_visibility_prepass_batch", "tdlo_cpd_lle_batch_each", "tdlo_tracker_tracking_step_batch", "tdlo_tracker_frame_batch",
     "tdlo_depth_to_cloud_batch", "tdlo_tracker_frames_batch",
     "tdlo_render_batch_table", "tdlo_render_result_batch", "tdlo_tracker_render_result_batch",
+    "tdlo_reg_batch", "tdlo_sort_pts_batch", "tdlo_tracker_initialize_from_cloud_batch", "tdlo_debug_reg_batch_plan",
 ]
 
 _lib = None
@@ -328,6 +329,11 @@ def load_library(path: str | None = None):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
         lib.tdlo_tracker_render_result_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp]
+    if hasattr(lib, "tdlo_reg_batch"):
+        lib.tdlo_reg_batch.argtypes = [vp, vp, ci, vp, vp, ci, cd, ci]
+        lib.tdlo_sort_pts_batch.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+        lib.tdlo_tracker_initialize_from_cloud_batch.argtypes = [vp, ci, cd, ci, vp, vp]
+        lib.tdlo_debug_reg_batch_plan.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
     if path is None:
         _lib = lib
     return lib
@@ -1022,6 +1028,31 @@ class Context:
         """[node sets ordered by k_sort_pts, initialize_from_cloud calls ordered by the host twin (TDLO_INIT_SORT=host)] (tdlo_debug_route_count 25 / 26)."""
         return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (25, 26)]
 
+    def init_batch_route_counts(self):
+        """[frames of reg_batch / sort_pts_batch / initialize_from_cloud_batch served by the batch launches, frames handed to the single call]
+        (tdlo_debug_route_count 36 / 37)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (36, 37)]
+
+    def reg_batch(self, slots, M, mu=0.05, max_iter=50):
+        """reg on the clouds resident in the F slots, the F loops in the same launches (tdlo_reg_batch).  Returns (Y [F x M x 3], sigma2 [F]): per slot
+        what reg(None, M, mu, max_iter, slot) returns, bit for bit."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32); F = len(sl)
+        Yb = np.zeros((F, 3, M)); s2 = np.zeros(F)
+        self._chk(self.lib.tdlo_reg_batch(self.h, _ptr(sl), F, _ptr(Yb), _ptr(s2), int(M), float(mu), int(max_iter)))
+        return np.ascontiguousarray(Yb.transpose(0, 2, 1)), s2
+
+    def sort_pts_batch(self, Ys, check=True):
+        """sort_pts for F node sets of one size in one launch (tdlo_sort_pts_batch): Ys [F x M x 3].  Returns (Y_sorted [F x M x 3], perm [F x M],
+        coord [F x M], codes [F]); a set that is refused (TDLO_E_NUMERIC) keeps zeros in its outputs and raises unless check=False."""
+        Ya = np.ascontiguousarray(Ys, dtype=np.float64); F, M = Ya.shape[0], Ya.shape[1]
+        assert Ya.shape == (F, M, 3)
+        Yin = np.ascontiguousarray(Ya.transpose(0, 2, 1))                   # F blocks of M x 3 column-major
+        Yo = np.zeros((F, 3, M)); perm = np.zeros((F, M), dtype=np.int32); coord = np.zeros((F, M)); rcs = np.zeros(F, dtype=np.int32)
+        rc = self.lib.tdlo_sort_pts_batch(self.h, _ptr(Yin), F, M, _ptr(Yo), _ptr(perm), _ptr(coord), _ptr(rcs))
+        if rc and check:
+            self._chk(rc)
+        return np.ascontiguousarray(Yo.transpose(0, 2, 1)), perm, coord, [int(r) for r in rcs]
+
     def image_buffers(self, rows, cols):
         """The context's pinned image buffers as numpy views (depth uint16 [rows x cols], mask uint8 [rows x cols]): images written into them and
         handed to depth_to_cloud as they are get read by the kernel where they lie (tdlo_image_buffers)."""
@@ -1541,6 +1572,20 @@ def tracking_step_batch(trackers, vis, vext, H_pre=None, check=True):
     rc = trackers[0].ctx.lib.tdlo_tracker_tracking_step_batch(C.cast(tab, C.c_void_p), F, C.cast(pv, C.c_void_p), _ptr(nv), C.cast(pe, C.c_void_p), _ptr(ne),
                                                               C.cast(ph, C.c_void_p) if ph is not None else None, C.cast(st, C.c_void_p), _ptr(rcs))
     return _batch_done(trackers, st, rcs, rc, check)
+
+
+def initialize_from_cloud_batch(trackers, mu=0.05, max_iter=100, check=True):
+    """tdlo_tracker_initialize_from_cloud_batch: initialize_from_cloud(None, mu, max_iter) of every tracker (one context, distinct slots, one node count) on
+    the cloud resident in its slot, the F starts in the same launches.  Returns (codes [F], sigma2 [F]: reg's, NaN where a tracker's start was refused);
+    raises on the first non-zero code unless check=False."""
+    F = len(trackers)
+    assert F >= 1
+    tab = (C.c_void_p * F)(*[t.h for t in trackers])
+    s2 = np.full(F, np.nan); rcs = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_initialize_from_cloud_batch(C.cast(tab, C.c_void_p), F, float(mu), int(max_iter), _ptr(s2), _ptr(rcs))
+    if rc and check:
+        trackers[0].ctx._chk(rc)
+    return [int(r) for r in rcs], s2
 
 
 def frame_batch(trackers, d_vis, check=True):

@@ -6,6 +6,7 @@
 #include "tdlo_host.h"
 #include "tdlo_image.h"
 #include "tdlo_rccl.h"
+#include "tdlo_reg_plan.h"
 
 #include <algorithm>
 #include <limits>
@@ -190,6 +191,11 @@ struct tdlo_ctx {
     // the same bits; init_route: tdlo_debug_route_count 25 / 26 -- calls ordered by k_sort_pts (tdlo_sort_pts among them) / by the host twin
     bool init_sort_host = getenv("TDLO_INIT_SORT") && getenv("TDLO_INIT_SORT")[0] == 'h';
     long long init_route[2] = {0, 0};
+    // tdlo_reg_batch / tdlo_sort_pts_batch / tdlo_tracker_initialize_from_cloud_batch: from init_batch_min frames on the frames share the launches
+    // (tdlo_reg_batch.hip, k_sort_pts_batch), below it the call loops over the single calls (kInitBatchMin = 1: never, unless TDLO_INIT_BATCH_MIN=n, read here, says so).
+    // ibat_route: tdlo_debug_route_count 36 / 37 -- frames served by the batch launches / handed to the single call
+    int init_batch_min = (getenv("TDLO_INIT_BATCH_MIN") && atoi(getenv("TDLO_INIT_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_INIT_BATCH_MIN")) : 0;      // 0: kInitBatchMin
+    long long ibat_route[2] = {0, 0};
     // the pre-pass of F slots in one launch (k_node_min_dist_batch, tdlo_batch.hip): a state of its own -- [vbat_cap minima | ticket], grown on demand and armed
     // when allocated, kept armed by the kernel -- and [word | F M minima] in pinned host memory
     unsigned long long *vbat_state = nullptr, *vbat_res = nullptr;
@@ -2598,6 +2604,141 @@ int tdlo_sort_pts(tdlo_ctx *c, const double *Y, int M, double *Y_sorted, int *pe
     return TDLO_OK;
 }
 
+// ---- reg and sort_pts for F frames in one call (csrc/tdlo_reg_batch.hip, k_sort_pts_batch; the layout: csrc/tdlo_reg_plan.h) ---------------------
+// From this many frames on tdlo_reg_batch, tdlo_sort_pts_batch and tdlo_tracker_initialize_from_cloud_batch let the frames share the launches; below it
+// they loop over the single calls.  By the rule set beforehand -- the smallest F from which on the batch's median lies below the single calls' by more than
+// both spreads, at N = 5 000 and N = 500 -- measured (profiles/init_batch_ab.txt): 1.  Two trackers start in 5.69 against 11.61 ms, 32 in 11.79 against
+// 186.0 ms, and one frame through the batch launches is level with the single call (5.72 against 5.81 ms), so every batch call takes them.
+// TDLO_INIT_BATCH_MIN=n, read when the context is made, overrides: below n frames the call loops over the single calls (the comparator).
+constexpr int kInitBatchMin = 1;
+static int init_batch_min(const tdlo_ctx *c) { return c->init_batch_min ? c->init_batch_min : kInitBatchMin; }
+
+static_assert(sizeof(RegBatchFrame) == 4 * sizeof(double), "the frame table is carved out of the workspace in doubles");
+
+// what the slots of a batch must be (in range, distinct, a cloud resident in each): the reason they are not, or nullptr
+static const char *batch_slots_refusal(const tdlo_ctx *c, const int *slots, int F) {
+    for (int f = 0; f < F; ++f) {
+        if (slots[f] < 0 || slots[f] >= (int)c->slots.size()) return "a slot is out of range";
+        for (int g = 0; g < f; ++g) if (slots[g] == slots[f]) return "a slot is named twice";
+        if (c->slots[slots[f]].N0 <= 0) return "no cloud is resident in a slot";
+    }
+    return nullptr;
+}
+
+// Where a batched start keeps things.  Device (reg_ws): [frame table 4 F | plan: F states | partials | F output blocks]; pinned staging: [frame table |
+// F start states | read-back: F states or F output blocks]
+struct RegBatchRun {
+    long long S = 0, O = 0;              // strides of the state and of the output blocks
+    double *states_dev = nullptr, *outs_dev = nullptr;
+    double *readback = nullptr;          // pinned
+};
+
+// reg's whole loop for the clouds resident in F slots, enqueued: one upload (table and start states), then the 2 + 2 max_iter launches.  The arguments
+// have been checked (batch_slots_refusal, M, mu, max_iter).
+static int reg_batch_enqueue(tdlo_ctx *c, const int *slots, int F, int M, double mu, int max_iter, RegBatchRun &run) {
+    std::vector<int> N(F), nblk(F);
+    std::vector<long long> state_off(F), part_off(F), out_off(F);
+    long long total = 0;
+    for (int f = 0; f < F; ++f) N[f] = c->slots[slots[f]].N0;
+    if (reg_batch_plan(N.data(), F, M, nblk.data(), state_off.data(), part_off.data(), out_off.data(), &total)) return fail(c, TDLO_E_INVALID, "reg batch: no plan");
+    const size_t T = 4 * (size_t)F;
+    run.S = reg_plan_state_stride(M); run.O = reg_plan_out_stride(M);
+    const size_t up = T + (size_t)run.S * F;
+    int rc;
+    if ((rc = ensure_reg_ws(c, T + (size_t)total)) || (rc = ensure_pin(c, up + (size_t)std::max(run.S, run.O) * F))) return rc;
+    double *base = c->reg_ws + T;
+    run.states_dev = base; run.outs_dev = base + out_off[0]; run.readback = c->pin + up;
+    RegBatchFrame *tab = reinterpret_cast<RegBatchFrame *>(c->pin);
+    int max_nblk = 1;
+    for (int f = 0; f < F; ++f) {
+        tab[f] = RegBatchFrame{c->slots[slots[f]].Xraw, base + state_off[f], base + part_off[f], N[f], nblk[f]};
+        max_nblk = std::max(max_nblk, nblk[f]);
+        double *h = c->pin + T + (size_t)run.S * f;
+        for (long long i = 0; i < run.S; ++i) h[i] = 0.0;
+        for (int i = 0; i < M; ++i) h[8 + M + i] = 0.1 / static_cast<double>(M) * static_cast<double>(i);      // utils.cpp:24-29, as reg_enqueue
+    }
+    HIPCHK(c, hipMemcpyAsync(c->reg_ws, c->pin, sizeof(double) * up, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_reg_batch(reinterpret_cast<const RegBatchFrame *>(c->reg_ws), F, max_nblk, M, mu, max_iter, c->stream));
+    return TDLO_OK;
+}
+
+int tdlo_reg_batch(tdlo_ctx *c, const int *slots, int F, double *Y, double *sigma2, int M, double mu, int max_iter) {
+    if (!c) return TDLO_E_INVALID;
+    if (!slots || F < 1 || !Y || !sigma2 || M < 1 || max_iter < 0 || !(mu >= 0 && mu < 1)) return fail(c, TDLO_E_INVALID, "reg batch: bad reg arguments");
+    if (M > reg_max_nodes()) return fail(c, TDLO_E_INVALID, "reg batch: more than " + std::to_string(reg_max_nodes()) + " centroids do not fit the E-step's per-wave accumulators in 160 KB of LDS");
+    if (const char *why = batch_slots_refusal(c, slots, F)) return fail(c, TDLO_E_INVALID, std::string("reg batch: ") + why);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = flush_pending_cloud(c))) return rc;
+    const size_t YM = 3 * (size_t)M;
+    if (F < init_batch_min(c)) {
+        for (int f = 0; f < F; ++f) {
+            if ((rc = tdlo_reg(c, slots[f], nullptr, 0, Y + YM * f, sigma2 + f, M, mu, max_iter))) return rc;
+            ++c->ibat_route[1];
+        }
+        return TDLO_OK;
+    }
+    RegBatchRun run;
+    if ((rc = reg_batch_enqueue(c, slots, F, M, mu, max_iter, run))) return rc;
+    HIPCHK(c, hipMemcpyAsync(run.readback, run.states_dev, sizeof(double) * (size_t)run.S * F, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ibat_route[0] += F;
+    for (int f = 0; f < F; ++f) {
+        const double *h = run.readback + (size_t)run.S * f;
+        sigma2[f] = h[0];
+        std::memcpy(Y + YM * f, h + 8, sizeof(double) * YM);
+    }
+    return TDLO_OK;
+}
+
+int tdlo_sort_pts_batch(tdlo_ctx *c, const double *Y, int F, int M, double *Y_sorted, int *perm, double *coord, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    if (!Y || F < 1) return fail(c, TDLO_E_INVALID, "sort_pts batch: no node sets");
+    if (M < 2 || M > kMaxNodes) return fail(c, TDLO_E_INVALID, "sort_pts batch: 2 .. " + std::to_string(kMaxNodes) + " nodes");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t YM = 3 * (size_t)M;
+    std::vector<int> rcs(F, 0);
+    std::string why;
+    int first = -1;
+    auto failed = [&](int f, int code, const std::string &text) {
+        rcs[f] = code;
+        if (first < 0) { first = f; why = text; }
+    };
+    int rc;
+    if (F < init_batch_min(c)) {
+        for (int f = 0; f < F; ++f) {
+            rc = tdlo_sort_pts(c, Y + YM * f, M, Y_sorted ? Y_sorted + YM * f : nullptr, perm ? perm + (size_t)M * f : nullptr, coord ? coord + (size_t)M * f : nullptr);
+            if (rc && rc != TDLO_E_NUMERIC) return rc;
+            if (rc) failed(f, rc, c->err);
+            ++c->ibat_route[1];
+        }
+    } else {
+        const size_t I = YM + (YM & 1), O = (size_t)reg_plan_out_stride(M);       // every node set and every output block on 16 bytes
+        if ((rc = ensure_reg_ws(c, (I + O) * F)) || (rc = ensure_pin(c, (I + O) * F))) return rc;
+        double *h = c->pin, *ho = h + I * F, *out_dev = c->reg_ws + I * F;
+        for (int f = 0; f < F; ++f) std::memcpy(h + I * f, Y + YM * f, sizeof(double) * YM);
+        HIPCHK(c, hipMemcpyAsync(c->reg_ws, h, sizeof(double) * I * F, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_sort_pts_batch(c->reg_ws, (long long)I, false, F, M, out_dev, (long long)O, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ho, out_dev, sizeof(double) * O * F, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ibat_route[0] += F;
+        for (int f = 0; f < F; ++f) {
+            const double *o = ho + O * f;
+            if (o[1] != 0.0) { failed(f, TDLO_E_NUMERIC, sort_pts_reason((int)o[1])); continue; }
+            if (Y_sorted) std::memcpy(Y_sorted + YM * f, o + 2, sizeof(double) * YM);
+            if (coord) std::memcpy(coord + (size_t)M * f, o + 2 + YM, sizeof(double) * M);
+            if (perm) std::memcpy(perm + (size_t)M * f, o + 2 + 4 * (size_t)M, sizeof(int) * M);
+        }
+    }
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    if (first >= 0) return fail(c, rcs[first], "sort_pts batch: frame " + std::to_string(first) + ": " + why);
+    return TDLO_OK;
+}
+
+int tdlo_debug_reg_batch_plan(const int *N, int F, int M, int *nblk, long long *state_off, long long *part_off, long long *out_off, long long *total) {
+    return reg_batch_plan(N, F, M, nblk, state_off, part_off, out_off, total) ? TDLO_E_INVALID : TDLO_OK;
+}
+
 // Waits for the one-launch kernel's word in pinned host memory (epoch << 32 | status); like mbox_wait, the stream is looked at every 0.5 ms so that
 // a faulting kernel cannot hang the caller.  Returns the status (1, 2, 3), 0 when the stream drained without the word, or a negative code.
 static int cloud_wait(tdlo_ctx *c, hipStream_t st, unsigned epoch) {
@@ -4196,7 +4337,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 35) return -1;
+    if (!c || which < 0 || which > 37) return -1;
+    if (which >= 36) return c->ibat_route[which - 36];
     if (which >= 34) return c->rbat_route[which - 34];
     if (which >= 32) return c->cbat_route[which - 32];
     if (which >= 30) return c->vbat_route[which - 30];
@@ -4488,6 +4630,87 @@ int tdlo_tracker_initialize_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_vi
     if (!t) return TDLO_E_INVALID;
     if (const char *why = view_fault(v, N)) return fail(t->ctx, TDLO_E_INVALID, why);
     return initialize_from_cloud_impl(t, nullptr, v, N, mu, max_iter, sigma2_out);
+}
+
+// tdlo_tracker_initialize_from_cloud for F trackers on the clouds resident in their slots: reg's loops share their launches (reg_batch_enqueue), one
+// k_sort_pts_batch launch orders every frame's centroids where reg left them, one read-back, one wait.  A frame is installed exactly as
+// initialize_from_cloud_enqueued installs it, or -- its verdict non-zero -- not touched at all.
+int tdlo_tracker_initialize_from_cloud_batch(tdlo_tracker *const *trackers, int F, double mu, int max_iter, double *sigma2_out, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    const int M = trackers[0]->M;
+    std::vector<int> slots(F);
+    for (int i = 0; i < F; ++i) {
+        const tdlo_tracker *t = trackers[i];
+        if (!t) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: a tracker is null");
+        if (t->ctx != c) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: the trackers of a batch share one context");
+        if (t->M != M) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: the trackers of a batch share num_of_nodes");
+        slots[i] = t->slot;
+    }
+    if (M < 4) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: a tracker has at least 4 nodes");
+    if (M > reg_max_nodes()) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: reg fits at most " + std::to_string(reg_max_nodes()) + " centroids (tdlo_reg)");
+    if (max_iter < 0 || !(mu >= 0 && mu < 1)) return fail(c, TDLO_E_INVALID, "initialize_from_cloud_batch: bad reg arguments");
+    if (const char *why = batch_slots_refusal(c, slots.data(), F)) return fail(c, TDLO_E_INVALID, std::string("initialize_from_cloud_batch: ") + why + " (the trackers' slots)");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int> rcs(F, 0);
+    std::string why;
+    int first = -1;
+    auto failed = [&](int i, int code, const std::string &text) {
+        rcs[i] = code;
+        if (first < 0) { first = i; why = text; }
+    };
+    auto finish = [&]() {
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        if (first >= 0) return fail(c, rcs[first], "initialize_from_cloud_batch: frame " + std::to_string(first) + ": " + why);
+        return (int)TDLO_OK;
+    };
+    int rc;
+    if (F < init_batch_min(c)) {
+        for (int i = 0; i < F; ++i) {
+            rc = initialize_from_cloud_impl(trackers[i], nullptr, nullptr, 0, mu, max_iter, sigma2_out ? sigma2_out + i : nullptr);
+            if (rc && rc != TDLO_E_NUMERIC) return rc;
+            if (rc) failed(i, rc, c->err);
+            ++c->ibat_route[1];
+        }
+        return finish();
+    }
+    auto enqueued = [&]() -> int {
+        if ((rc = flush_pending_cloud(c))) return rc;
+        RegBatchRun run;
+        if ((rc = reg_batch_enqueue(c, slots.data(), F, M, mu, max_iter, run))) return rc;
+        const size_t YM = 3 * (size_t)M;
+        std::vector<double> Ys(YM), coord(M);
+        if (!c->init_sort_host) {
+            HIPCHK(c, launch_sort_pts_batch(run.states_dev + 8, run.S, true, F, M, run.outs_dev, run.O, c->stream));
+            HIPCHK(c, hipMemcpyAsync(run.readback, run.outs_dev, sizeof(double) * (size_t)run.O * F, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(run.readback, run.states_dev, sizeof(double) * (size_t)run.S * F, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->ibat_route[0] += F;
+        for (int i = 0; i < F; ++i) {
+            double sigma2;
+            if (!c->init_sort_host) {
+                const double *ho = run.readback + (size_t)run.O * i;
+                if (ho[1] != 0.0) { failed(i, TDLO_E_NUMERIC, sort_pts_reason((int)ho[1])); continue; }
+                sigma2 = ho[0];
+                std::memcpy(Ys.data(), ho + 2, sizeof(double) * YM);
+                std::memcpy(coord.data(), ho + 2 + YM, sizeof(double) * M);
+            } else {
+                const double *h = run.readback + (size_t)run.S * i;
+                if (const int status = sort_pts_host(h + 8, M, Ys.data(), nullptr, coord.data())) { failed(i, TDLO_E_NUMERIC, sort_pts_reason(status)); continue; }
+                sigma2 = h[0];
+            }
+            tdlo_tracker *t = trackers[i];
+            t->Y = Ys;                                                       // as initialize_from_cloud_enqueued
+            t->guide_nodes = t->Y; t->Mg = M;
+            t->geodesic_coord = coord;                                       // replaced, not appended to
+            if (sigma2_out) sigma2_out[i] = sigma2;
+        }
+        return TDLO_OK;
+    };
+    if ((rc = enqueued())) { (void)hipStreamSynchronize(c->stream); return rc; }      // nothing of this call stays enqueued behind an error
+    return finish();
 }
 
 int tdlo_tracker_copy_state(tdlo_tracker *dst, const tdlo_tracker *src) {

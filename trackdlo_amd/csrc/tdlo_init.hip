@@ -38,9 +38,9 @@ __device__ __forceinline__ bool pair_before(double g, int a, int b, double h, in
     return g < h || (g == h && (a < c || (a == c && b < d)));
 }
 
+// one workgroup's whole job on one node set; k_sort_pts and k_sort_pts_batch below are this text
 template <bool kOneWave>
-__global__ __launch_bounds__(kOneWave ? 64 : 1024) void k_sort_pts(const double *__restrict__ Yin, const double *__restrict__ state, int M,
-                                                                  double *__restrict__ out) {
+__device__ __forceinline__ void sort_pts_body(const double *__restrict__ Yin, const double *__restrict__ state, int M, double *__restrict__ out) {
     constexpr int kCap = kOneWave ? kWave : kMaxNodes;
     __shared__ double xs[kCap], ys[kCap], zs[kCap], seg[kCap];
     __shared__ int place[kCap], order[kCap];      // place[node] (selected nodes), order[place] = node
@@ -141,6 +141,22 @@ __global__ __launch_bounds__(kOneWave ? 64 : 1024) void k_sort_pts(const double 
     }
 }
 
+template <bool kOneWave>
+__global__ __launch_bounds__(kOneWave ? 64 : 1024) void k_sort_pts(const double *__restrict__ Yin, const double *__restrict__ state, int M,
+                                                                  double *__restrict__ out) {
+    sort_pts_body<kOneWave>(Yin, state, M, out);
+}
+
+// F node sets in one launch, blockIdx.x = frame: frame f's nodes at Yin + f in_stride and its output block at out + f out_stride; with_state: the nodes
+// are those of a reg state block, where reg left them, and the block begins 8 doubles before them.  A kernel of its own beside k_sort_pts, whose
+// arguments, registers and LDS stay as they were.
+template <bool kOneWave>
+__global__ __launch_bounds__(kOneWave ? 64 : 1024) void k_sort_pts_batch(const double *__restrict__ Yin, long long in_stride, int with_state, int M,
+                                                                        double *__restrict__ out, long long out_stride) {
+    const double *Y = Yin + (size_t)blockIdx.x * in_stride;
+    sort_pts_body<kOneWave>(Y, with_state ? Y - 8 : nullptr, M, out + (size_t)blockIdx.x * out_stride);
+}
+
 }  // namespace
 
 size_t sort_pts_out_doubles(int M) { return 2 + 4 * (size_t)M + ((size_t)M + 1) / 2; }
@@ -148,6 +164,12 @@ size_t sort_pts_out_doubles(int M) { return 2 + 4 * (size_t)M + ((size_t)M + 1) 
 hipError_t launch_sort_pts(const double *Y, const double *state, int M, double *out, hipStream_t s) {
     if (M <= kWave) hipLaunchKernelGGL(k_sort_pts<true>, dim3(1), dim3(kWave), 0, s, Y, state, M, out);
     else hipLaunchKernelGGL(k_sort_pts<false>, dim3(1), dim3((M + kWave - 1) / kWave * kWave), 0, s, Y, state, M, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_pts_batch(const double *Y, long long in_stride, bool with_state, int F, int M, double *out, long long out_stride, hipStream_t s) {
+    if (M <= kWave) hipLaunchKernelGGL(k_sort_pts_batch<true>, dim3(F), dim3(kWave), 0, s, Y, in_stride, with_state ? 1 : 0, M, out, out_stride);
+    else hipLaunchKernelGGL(k_sort_pts_batch<false>, dim3(F), dim3((M + kWave - 1) / kWave * kWave), 0, s, Y, in_stride, with_state ? 1 : 0, M, out, out_stride);
     return hipGetLastError();
 }
 

@@ -285,11 +285,18 @@ int mstep_set_lle_dense(int on);  // 1: registrations with the LLE term take the
 size_t reg_ws_doubles(int M, int nblk);
 int reg_max_nodes();        // the E-step's per-wave accumulators must fit 160 KB of LDS
 hipError_t launch_reg(const double *X, int N, int M, double mu, int max_iter, int nblk, double *ws, hipStream_t s);
+// tdlo_reg_batch.hip: the same loop for F clouds in the same 2 + 2 max_iter launches (grid (max_nblk, F) / F).  RegBatchFrame: a frame's entry of the
+// table in device memory -- its cloud, its own state block (8 | Y 3 M, start values uploaded) and its own nblk x (5 M + 1) partials (tdlo_reg_plan.h)
+struct RegBatchFrame { const double *X; double *state; double *part; int N; int nblk; };
+hipError_t launch_reg_batch(const RegBatchFrame *tab_dev, int F, int max_nblk, int M, double mu, int max_iter, hipStream_t s);
 // tdlo_init.hip: `sort_pts` (utils.cpp:95-170) and the chain coordinate, one workgroup, 2 <= M <= kMaxNodes.  Y: M x 3 column-major in device memory (reg's
 // centroids: ws + 8); state: reg's state block (its sigma2 is copied into the output's header) or nullptr; out: sort_pts_out_doubles(M) doubles of device
 // memory: [sigma2 | status | Y sorted (3 M) | coord (M)] and M ints of perm -- status 1 .. 3: only the header is written
 size_t sort_pts_out_doubles(int M);
 hipError_t launch_sort_pts(const double *Y, const double *state, int M, double *out, hipStream_t s);
+// ... for F node sets in one launch, one workgroup each: set f at Y + f in_stride (with_state: the nodes of a reg state block that begins 8 doubles
+// before them), its output block at out + f out_stride
+hipError_t launch_sort_pts_batch(const double *Y, long long in_stride, bool with_state, int F, int M, double *out, long long out_stride, hipStream_t s);
 // tdlo_cloud.hip: depth image -> cloud -> voxel grid
 // colour segmentation in front of it (tdlo_colour_params as the kernels take it): the colour image (3 bytes a pixel) and the optional occluder image, readable by
 // the device and padded to 16 bytes beyond the image; per range the lower bounds H | S << 8 | V << 16 and upper - lower per channel (ranges that

@@ -5,7 +5,10 @@
   * fp64 restatements of every kernel family's algorithm -- partial-pivot LU of A W = B then V = G W (the dense eliminations),
     tests/chain_numpy.py (the chain smoother), tests/band_numpy.py (the banded L D L^T) -- sit inside the gate on every case of the
     GPU matrix (tests/test_mstep_sums_gpu.py): the gate is not tighter than honest fp64 arithmetic of the same algorithm;
-  * on every case the gate is at most 1/10 of the change rounding the sums to fp32 makes in T: it would see one fp32 slip."""
+  * on every case the gate is at most 1/10 of the change rounding the sums to fp32 makes in T: it would see one fp32 slip;
+  * the short-beta cells of the dense eliminations (beta = k h, tests/test_mstep_sums_gpu.py: short_beta_cases) can see a wrong kernel: the
+    restatement takes at most 1/10 of the gate, partial pivoting swaps rows, and T* moves by 100 gates and more without the LLE term, without
+    the priors and at the launch file's beta."""
 import numpy as np
 import pytest
 import scipy.linalg as sla
@@ -15,7 +18,7 @@ import chain_numpy as cn
 import estep_ref as R
 import mstep_ref as MR
 from conftest import case_kwargs, load_cases
-from test_mstep_sums_gpu import CASES, HANDOVER_BAND, band_handover_case, build_case, cid
+from test_mstep_sums_gpu import CASES, DEC, HANDOVER_BAND, band_handover_case, build_case, case_scene, cid, lle_H, params_of
 
 LD = np.longdouble
 
@@ -125,3 +128,60 @@ def test_band_hand_over_restatement_inside_the_dense_gate(regime):
     gT, _, _ = MR.gate(c, "dense", T)
     q = (np.abs(restated(c, "dense") - T.astype(np.float64)) / gT).max()
     assert q <= 1.0, (regime, float(q))
+
+
+# ---- the short-beta cells of the dense eliminations (beta = k h): conditions on the reference alone, so that a cell can see a wrong kernel ----------
+SHORT = [cs for cs in CPU_CASES if cs.get("beta_h")]
+PIVOTING = [cs for cs in SHORT if (cs["route"] == "lle_dense" and cs["M"] <= 300) or cs["regime"] == "p1zero"]
+TERMS = [(cs, "beta") for cs in SHORT] + [(cs, "lle") for cs in SHORT if cs["route"] == "lle_dense"] + [(cs, "priors") for cs in SHORT if cs["regime"] == "priors"]
+
+
+@pytest.mark.parametrize("case", SHORT, ids=cid)
+def test_short_beta_restatement_leaves_the_kernels_headroom(case):
+    """The kernels eliminate in another order than LAPACK: the fp64 restatement takes at most a tenth of the gate."""
+    c, T, gT, slip = case_data(case)
+    q = float((np.abs(restated(c, "dense") - T.astype(np.float64)) / gT).max())
+    print(f"{cid(case)}: beta {c.beta:.6g}, gate / slip {float(gT.max()) / slip:.3g}, restatement / gate {q:.3g}")
+    assert q <= 0.1, (cid(case), q)
+
+
+@pytest.mark.parametrize("case", PIVOTING, ids=cid)
+def test_short_beta_cells_swap_rows(case):
+    """Partial pivoting of A swaps at least one row: the cell exercises the kernels' pivot search."""
+    c = case_data(case)[0]
+    piv = sla.lu_factor(MR.system(c)[5])[1]
+    n = int((piv != np.arange(c.M)).sum())
+    print(f"{cid(case)}: {n} rows swapped")
+    assert n >= 1, cid(case)
+
+
+@pytest.mark.parametrize("case,term", TERMS, ids=[f"{cid(cs)}-{t}" for cs, t in TERMS])
+def test_short_beta_every_term_reaches_the_answer(case, term):
+    """T* moves by at least 100 gates (the largest move over the largest gate) when the LLE term or the priors are taken away or beta is the
+    launch file's: a kernel that ignored H G, alpha J or the beta it was given would fail the GPU cell."""
+    c, T, gT, _ = case_data(case)
+    kw = {"lle": dict(H=None, lle_weight=0.0), "priors": dict(priors=None, alpha=0.0), "beta": dict(beta=params_of(dict(case, beta_h=None))["beta"])}[term]
+    T2, _, _ = MR.reference(MR.Case(c.sums, c.Y0, c.y, c.s2, yp=c.yp, **dict(c.kw(), **kw)))
+    q = float(np.abs(T2 - T).max()) / float(gT.max())
+    print(f"{cid(case)} without {term}: T* moves by {q:.3g} gates")
+    assert q >= 100.0, (cid(case), term, q)
+
+
+@pytest.mark.parametrize("case", [cs for cs in DEC if cs.get("beta_h")], ids=cid)
+def test_short_beta_crit_gate_pins_the_stopping_decision(case):
+    """tests/test_mstep_sums_gpu.py::test_stopping_decision_and_refusals sets tol at crit (1 +- 1e-6): crit's gate is far below that."""
+    c, T, _, _ = case_data(case)
+    crit = MR.reference(c)[2]
+    gC = MR.gate(c, "dense", T)[2]
+    print(f"{cid(case)}: crit gate / crit {gC / float(crit):.3g}")
+    assert gC < 1e-7 * float(crit), (cid(case), gC, float(crit))
+
+
+def test_the_oracles_H_at_512_nodes_is_unbounded():
+    """Why the LLE cells of 512 nodes and more take uniform_H: on the straight 0.02 m chain calc_lle_weights' local Gram matrices are singular to
+    rounding and H = (I - L)^T (I - L) has entries above 1e12 -- the system's condition number is then 1e10 and more and no gate means anything.
+    Should this stop holding, the cells can go back to the oracle's H."""
+    case = next(cs for cs in SHORT if cs["route"] == "lle_dense" and cs["M"] == 512)
+    hmax = float(np.abs(lle_H(case_scene(case)[3], "typical")).max())
+    assert hmax > 1e12, hmax
+    assert float(np.abs(build_case(case).H).max()) < 10.0

@@ -248,6 +248,39 @@ def test_band_mstep_batch_equals_single(oracle):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("M,prec", [(300, 1), (300, 0), (512, 1), (512, 0)], ids=["M300-f64", "M300-f32", "M512-f64", "M512-f32"])
+def test_band_mstep_batch_equals_single_beyond_256_nodes(oracle, M, prec):
+    """The batch instantiation where a thread serves two nodes, the sums arrive as several elements per thread and the records pass the load loop
+    (300 nodes: two directions; 512: one, more than 64 KB of LDS): bit for bit the single calls."""
+    from trackdlo_amd import binding as B, synth
+    F, N = 3, 6000
+    L = np.zeros((M, M))                                 # an LLE regulariser with bounded entries, shared by the frames (the M-step takes H as an input;
+    for i in range(M):                                   # the reference's own weights on a chain this long and straight are rounding noise amplified)
+        nb = [j for j in range(i - 3, i + 4) if j != i and 0 <= j < M]
+        L[i, nb] = 1.0 / len(nb)
+    H = (np.eye(M) - L).T @ (np.eye(M) - L)
+    ctx = B.Context(device=0, max_frames=F, max_points=N, max_nodes=M)
+    try:
+        kw = _kw(3)
+        Ys, single = [], []
+        for fr in range(F):
+            X, Y0, _ = synth.scene(N, M, config=490, frame=fr, noise=0.003)
+            ctx.set_cloud(fr, X)
+            Ys.append(Y0)
+        for fr in range(F):
+            single.append(ctx.cpd_lle_resident(fr, Ys[fr], 2e-5, _params(kw, prec), H=H))
+            assert single[fr]["rc"] == 0 and single[fr]["iters"] == 3 and ctx.profile_iteration(1)[3] == "k_mstep_band"
+        out = ctx.cpd_lle_batch(Ys, [2e-5] * F, _params(kw, prec), H=H)
+        assert ctx.profile_iteration(1)[3] == "k_mstep_band"
+        for fr in range(F):
+            assert out["stats"][fr]["status"] == 0 and out["stats"][fr]["iters"] == 3
+            assert np.array_equal(np.asarray(out["Y"][fr]), single[fr]["Y"]) and out["stats"][fr]["sigma2"] == single[fr]["sigma2"]
+        assert any(not np.array_equal(single[0]["Y"], single[fr]["Y"]) for fr in range(1, F))      # (the frames differ: equal bits are not one frame thrice)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
 def test_band_mstep_hands_an_indefinite_system_to_the_dense_kernels(oracle):
     """The banded L D L^T takes no pivots.  An H_override that is banded and symmetric but NOT positive semi-definite (here
     (I - L)^T (I - L) - I with lle_weight 1e7: eigenvalues down to -110, condition number ~100) makes the M-step system indefinite: the reference's general solver

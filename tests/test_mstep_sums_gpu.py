@@ -6,7 +6,9 @@ sums [P1 | R | Q | N_kept] into the frame (from_sums = 1): that reaches every M-
 node, priors there, lambda sigma2 over eleven decades, an LLE regulariser whose rows do not sum to zero on a scene 12 m from the origin.  T and
 sigma2 must lie within `mstep_ref.gate`, and done / iters / converged must be the reference's decisions exactly.  Every case names the kernel it
 reached (Context.profile_iteration: mstep_kernel_name).  The dense eliminations from 129 nodes on and every dense LLE elimination are held at a
-beta of the order of the node spacing (short_beta_cases; the comment above DROPPED says why and with which ratios).
+beta of the order of the node spacing (short_beta_cases; the comment above DROPPED says why and with which ratios).  The banded solve is held by its
+backward error (mstep_ref.band_backward_error) at every chain length, above 129 nodes by that alone: 256 / 257 nodes (a thread's second node), both
+sides of BandPlan's edge, 480 and 512 (one direction, more than 64 KB of LDS), with the stopping decision at the kernel's own crit.
 
 After a successful M-step the next E-step must start from it: its sums match the E-step reference at the kernel's own (T, sigma2), and in fp64 mode
 their resolution follows the new sigma2 (IterState::sh_boost, set_iter_consts) -- every R x 2^sR an integer, not all of them even."""
@@ -20,6 +22,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
+import band_numpy as bn  # noqa: E402
 import chain_numpy as cn  # noqa: E402
 import estep_ref as R  # noqa: E402
 import mstep_ref as MR  # noqa: E402
@@ -36,10 +39,17 @@ def _direct_edge():
     return Ms[-1], Ms[-1] + 1
 
 
+def _plan_edge():
+    """The longest chain whose elimination runs from both ends (BandPlan: both directions' records fit the LDS) and the next one, one direction again."""
+    Ms = [M for M in range(19, 513) if bn.band_plan(M)["tw"]]
+    return Ms[-1], Ms[-1] + 1
+
+
 DE = _direct_edge()
+PE = _plan_edge()
 CHAIN_M = [4, 5, 7, 9, 13, 24, DE[0], DE[1], 255, 256, 257, 319, 320, 511, 512]
 LONG_M = [513, 777, 1024]
-BAND_M = [4, 5, 6, 7, 12, 13, 14, 19, 20, 26, 27, 45, 128, 129, 256, 257, 480, 512]
+BAND_M = [4, 5, 6, 7, 12, 13, 14, 19, 20, 26, 27, 45, 128, 129, 256, 257, PE[0], PE[1], 480, 512]
 DENSE_M = [8, 45, 60, 61, 64, 65, 129, 300, 512, 513]
 LLE_DENSE_M = [8, 45, 64, 65, 128, 129, 300, 512, 513]
 
@@ -66,12 +76,13 @@ def cases():
     cs.append(_c("chain", "long", 777, "p1zero"))
     for M in BAND_M:
         cs.append(_c("band", "band", M, "typical"))
-        if M >= 12:
+        if M >= 12 and M not in PE:
             cs.append(_c("band", "band", M, "p1zero"))
     for M in (45, 257):
         cs.append(_c("band", "band", M, "shifted_h"))
         cs.append(_c("band", "band", M, "priors"))
         cs.append(_c("band", "band", M, "typical", prec=0))
+    cs.append(_c("band", "band", 300, "priors"))             # (a prior on node 0 and none on node 256: the second round of the node loop has something to confuse)
     for M in DENSE_M:
         cs.append(_c("dense", "dense", M, "typical"))
         cs.append(_c("dense", "dense", M, "p1zero"))
@@ -120,10 +131,24 @@ def short_beta_cases():
 #
 # At the launch file's beta (0.35; pre-processing: 3) on chains whose nodes are 0.02 m apart G is nearly singular, |G| |W| / |V| reaches 1e5 - 1e9, and
 # the dense gate, which carries that amplification, is wider than a slip.  DROPPED takes those cells out:
-#   * band, 256+ nodes (pre-processing parameters, beta = 3): the banded solve's own fp64 error grows with the chain (its restatement is 3e-12 m off at
-#     257 nodes) and the gate that contains it is wider than an fp32 slip of the sums (gate / slip 1.3 at 257, 3e5 at 480); at 512 nodes the restatement
-#     is 8 - 160 gates out: the gate's state-precision term does not model the band there.  The band is held to the reference up to 129 nodes.  (This is
-#     the band's own fp64 error, not an amplification: a shorter beta leaves gate / slip at 1.3 - 1.5 and the restatement at 0.2 - 0.4 of the gate.)
+#   * (the band is no longer here.  Its FORWARD gate is wider than an fp32 slip from 256 nodes on -- gate / slip 1.3 at 257 nodes, 3e5 at 480, at any
+#     beta -- because the forward error of the state system grows with the chain and with H's entries; part of what was read as the band's own error
+#     was the quad reference's: under the oracle's H at 256 / 257 nodes (entries up to 9e10) mstep_ref.reference is 1e-12 - 2e-11 m from the system's
+#     answer at 256 bits.  The band solves (c G^-1 + D + g H) V = B as an SPD banded L D L^T, and such a solve promises a small BACKWARD error at any
+#     condition number: mstep_ref.band_backward_error, the longdouble residual of the state system at the returned T with f' rebuilt from f, against
+#     EPS_BAND u |A2| |x| + EPS_B u |B|'s terms + the read-back u |T|, times SAFETY.  Band cells above 129 nodes (by_backward_error) are held by it alone,
+#     sigma2 at the kernel's own T (mstep_ref.held_at_T); up to 129 nodes it is asserted beside the forward gate.  tests/test_mstep_ref.py, per cell --
+#     fp64 restatement / tolerance (<= 0.25 asked), answer of the fp32-rounded sums / tolerance (>= 10 asked), T* at 256 bits / tolerance (<= 0.25):
+#         256 typical 0.075, 2.2e4, 0.078   p1zero 0.083, 2.2e4, 0.066       257 typical 0.095, 1.5e4, 0.095   p1zero 0.072, 1.9e4, 0.069
+#         257 shifted_h 0.092, 820, 0.092   priors 0.072, 1.5e4, 0.070       257 typical fp32 mode 0.084, 2.1e4, 0.084     300 priors 0.074, 2.0e4, -
+#         474 typical 0.13, 1.7e4, -        475 typical 0.077, 1.9e4, -      480 typical 0.17, 2.5e4, -        p1zero 0.19, 1.3e4, -
+#         512 typical 0.086, 2.5e4, 0.072   p1zero 0.17, 2.5e4, -            (T* at 256 bits: every cell up to 257 nodes and one of 512)
+#     the kernel's own data flow (records, tile, both ends) 0.052 - 0.10 at 45 / 257 / 474 / 512; the 4 - 129 node cells 0.006 - 0.078 and 745 - 1.3e6.
+#     T* without the LLE term stands at 3.5e8 - 1.1e12 tolerances, without the priors at 1.9e11 - 4.5e11, at the launch file's beta at 3.3e11 - 1.4e13;
+#     node m - 256's P1, R, priors or H Y0 read at node m (the second round of the kernel's node loop) at 170 - 9e11 wherever it changes a value (at
+#     257 nodes only node 256 is in that round, and it shares P1 = R = 0 with node 0 in the P1-zeroed cell and the prior's offset in the priors cell:
+#     band-M300-priors is there for the priors).  All of them with the oracle's own H, made symmetric bit for bit (build_case); 474 / 475 are the two
+#     sides of BandPlan's edge (both ends / one direction again: the records of two directions no longer fit the LDS).  Nothing of the band is left out.)
 #   * dense eliminations without the LLE term from 129 nodes on (k_mstep_mcu at 129 / 300 / 512, k_mstep<1wg> at 513) and at lambda sigma2 = 1e-7: the
 #     dense gate carries |G| |A^-1| |A| |W| and the fp64 chain coordinate's worst-case running-sum error through G W; it is 0.2 - 5 (129 - 513 nodes),
 #     3e4 - 6e5 (lambda sigma2 = 1e-7) of an fp32 slip.  At that beta k_mstep_mcu is held at 61 - 65 nodes, k_mstep_fast<MFMA> up to 60.
@@ -155,9 +180,6 @@ def short_beta_cases():
 #   Still out at any beta: the LLE cells with P1 zeroed (condition number 1e6: the restatement sits at 0.12 - 1.16 of the gate, gate / slip up to 1.65)
 #   and the coincident LLE cells (gate 1e4 slips).
 DROPPED = {
-    "band-M256-typical-f64", "band-M256-p1zero-f64", "band-M257-typical-f64", "band-M257-p1zero-f64", "band-M480-typical-f64",
-    "band-M480-p1zero-f64", "band-M512-typical-f64", "band-M512-p1zero-f64", "band-M257-shifted_h-f64", "band-M257-priors-f64",
-    "band-M257-typical-f32",
     "dense-M129-typical-f64", "dense-M129-p1zero-f64", "dense-M300-typical-f64", "dense-M300-p1zero-f64", "dense-M512-typical-f64",
     "dense-M512-p1zero-f64", "dense-M513-typical-f64", "dense-M513-p1zero-f64", "dense-M45-dense_c-f64", "dense-M129-priors-f64",
     "dense-M129-dense_c-f64", "dense-M129-typical-f32",
@@ -167,6 +189,11 @@ DROPPED = {
 }
 ALL_CASES = cases()
 CASES = [c for c in ALL_CASES if f"{c['route']}-M{c['M']}-{c['regime']}-{'f64' if c['prec'] else 'f32'}" not in DROPPED] + short_beta_cases()
+
+
+def by_backward_error(case):
+    """The band cells above 129 nodes: held by mstep_ref.band_backward_error alone (their forward gate is wider than an fp32 slip, see above)."""
+    return case["family"] == "band" and case["M"] > 129
 
 
 def cid(c):
@@ -297,6 +324,10 @@ def build_case(case, with_scene=False):
                 P1[idx[1]] = 0; Rm[idx[1]] = 0                                         # a prior where no point is
                 s[:M] = P1; s[M:4 * M] = Rm.T.reshape(-1)
         H = (uniform_H(M) if case.get("beta_h") and M >= 512 else lle_H(Y0, reg)) if p["lle"] else None
+        if by_backward_error(case):
+            # prepare_frame gives an H_override to the banded solve only if it is symmetric bit for bit; the product (I - L)^T (I - L) as BLAS forms it
+            # is so on one machine and not on the next (entries up to 1e15 here): a + b == b + a makes it so everywhere, for both sides alike
+            H = 0.5 * (H + H.T)
         c = MR.Case(s, Yl, Yl, p["s2"], beta=p["beta"], lambda_=p["lambda_"], alpha=p["alpha"] if priors is not None else 0.0, priors=None
                     if priors is None else np.column_stack([priors[:, 0], priors[:, 1:] + (SHIFT if reg == "shifted_h" else 0)]),
                     lle_weight=p["lle_weight"] if p["lle"] else 0.0, H=H)
@@ -348,7 +379,8 @@ WORST = {}
 
 def _report():
     for k, (qt, qs) in sorted(WORST.items()):
-        print(f"  {k}: worst |dT| / gate {qt:.3g}, |d sigma2| / gate {qs:.3g}")
+        what = "backward error / tolerance" if k.endswith(" backward") else "|dT| / gate"
+        print(f"  {k}: worst {what} {qt:.3g}, |d sigma2| / gate {qs:.3g}")
 
 
 @pytest.mark.parametrize("case", CASES, ids=cid)
@@ -365,11 +397,25 @@ def test_mstep_from_sums_against_the_quad_solve(ctx, case):
         return
     assert rc == 0 and done, (cid(case), rc, done)
     assert o["iters"] == 1 and o["converged"] is False                  # max_iter = 1: done, not converged
+    Tk = np.asarray(o["Y"])
+    k = f"{name} {'f64' if case['prec'] else 'f32'}"
+    if case["family"] == "band":
+        # the banded solve by its backward error, every chain length; sigma2 at the kernel's own T (the plan on both sides of its edge)
+        if case["M"] in PE:
+            assert bn.band_plan(case["M"])["tw"] == (1 if case["M"] == PE[0] else 0) and bn.band_plan(case["M"])["lds_bytes"] > 64 * 1024
+        qb, where = MR.band_backward_error(c, Tk)
+        s2k, gSk, _, _ = MR.held_at_T(c, Tk)
+        qsk = abs(o["sigma2"] - float(s2k)) / gSk
+        a, b = WORST.get(k + " backward", (0.0, 0.0)); WORST[k + " backward"] = (max(a, qb), max(b, qsk))
+        print(f"{cid(case)} -> {name}: backward error / tolerance {qb:.3g} at node {where[0]} coordinate {where[1]}, |d sigma2| / gate at its own T {qsk:.3g}")
+        assert qb <= 1.0, (cid(case), qb, where)
+        assert qsk <= 1.0, (cid(case), qsk)
+        if by_backward_error(case):
+            return
     T, s2, _ = MR.reference(c)
     gT, gS, _ = MR.gate(c, case["family"], T)
-    dT = np.abs(np.asarray(o["Y"]) - T.astype(np.float64))
+    dT = np.abs(Tk - T.astype(np.float64))
     qt = float((dT / gT).max()); qs = abs(o["sigma2"] - float(s2)) / gS
-    k = f"{name} {'f64' if case['prec'] else 'f32'}"
     a, b = WORST.get(k, (0.0, 0.0)); WORST[k] = (max(a, qt), max(b, qs))
     print(f"{cid(case)} -> {name}: |dT| / gate {qt:.3g} (max |dT| {dT.max():.3g} m), |d sigma2| / gate {qs:.3g}")
     assert qt <= 1.0, (cid(case), qt)
@@ -405,6 +451,42 @@ def test_stopping_decision_and_refusals(ctx, case):
     d = T - c.y.astype(LD)
     Rm = c.sums[M:4 * M].reshape(3, M).T; P1 = c.sums[:M]
     q0 = LD(2) * (d * Rm).sum() - (P1[:, None] * d * d).sum()                          # Q at which sigma2 = 0
+    bad = c.sums.copy(); bad[4 * M] = q0 - LD(0.5) * abs(c.sums[4 * M] - q0)
+    rc, _, _, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), bad, priors, c.H)
+    assert rc == B.TDLO_E_NUMERIC, (cid(case), "sigma2 < 0", rc)
+    empty = c.sums.copy(); empty[:4 * M] = 0
+    rc, _, _, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), empty, priors, c.H)
+    assert rc == B.TDLO_E_NUMERIC, (cid(case), "N_p = 0", rc)
+
+
+@pytest.mark.parametrize("M", [257, 512])
+def test_band_stopping_decision_at_its_own_T(ctx, M):
+    """The band above 129 nodes has no forward gate on crit: one M-step with tol = 0 gives the kernel's T, crit follows from it in longdouble
+    (mstep_ref.held_at_T; its own-rounding gate is far below 1e-6 crit), and tol at that crit (1 +- 1e-6) must give done / converged exactly as
+    mstep_ref.decision.  257 nodes: an exact sigma2 < 0 and N_p = 0 end in TDLO_E_NUMERIC."""
+    from trackdlo_amd import binding as B
+    case = _c("band", "band", M, "typical")
+    c, X, Y0, priors = build_case(case, with_scene=True)
+    set_route("band")
+    rc, done, o, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=10, tol=0.0), c.sums, priors, c.H)
+    assert rc == 0 and not done and ctx.profile_iteration(1)[3] == "k_mstep_band"
+    Tk = np.asarray(o["Y"])
+    _, _, crit, gC = MR.held_at_T(c, Tk)
+    print(f"{cid(case)}: crit {float(crit):.6g}, its gate / crit {gC / float(crit):.3g}")
+    assert gC < 1e-7 * float(crit)
+    for f, want in ((1 + 1e-6, True), (1 - 1e-6, False)):
+        tol = float(crit) * f
+        rc, done, o2, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=10, tol=tol), c.sums, priors, c.H)
+        assert MR.decision(float(crit), 1, tol, 10) == (want, True)
+        assert done == want, (cid(case), f, done)
+        assert np.array_equal(np.asarray(o2["Y"]), Tk)                  # (the same M-step: crit is this T's)
+        if want:
+            assert rc == 0 and o2["iters"] == 1 and o2["converged"] is True
+    if M != 257:
+        return
+    d = Tk.astype(LD) - c.y.astype(LD)
+    Rm = c.sums[M:4 * M].reshape(3, M).T; P1 = c.sums[:M]
+    q0 = LD(2) * (d * Rm).sum() - (P1[:, None] * d * d).sum()                          # Q at which sigma2 = 0 at this T
     bad = c.sums.copy(); bad[4 * M] = q0 - LD(0.5) * abs(c.sums[4 * M] - q0)
     rc, _, _, _ = run_mstep(ctx, X, Y0, c.s2, make_params(case, max_iter=1), bad, priors, c.H)
     assert rc == B.TDLO_E_NUMERIC, (cid(case), "sigma2 < 0", rc)

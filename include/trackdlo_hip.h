@@ -742,6 +742,64 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
                               int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                               int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each);
 
+/* ---- cloud views for many slots in one call ----------------------------------------------------------- */
+/* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
+ * views become the resident clouds of F slots in one call -- down-sampled (tdlo_cloud_view_voxel_grid_batch) or as they are (tdlo_set_cloud_view_batch).
+ * A FRAME names a slot, a view, its N and optional selection bytes (NULL: every element).  Frames may differ in N, dtype, strides, location and
+ * ready_stream; any number of frames may name the SAME view with different selection bytes (one organized cloud, several ropes).
+ *   tdlo_cloud_view_voxel_grid_batch: per frame the result is exactly tdlo_cloud_view_voxel_grid(ctx, slot, view, N, select, leaf_size, NULL, 0, ...) on that
+ * frame alone -- V above, rules 1 - 12, the sign of a zero included -- whatever else shares the call and in whatever order; a frame that keeps no point leaves
+ * an empty cloud (n = 0).  ONE launch of k_cloud_view_batch (csrc/tdlo_cloud.hip; grid: tiles of the largest frame x frames; the frame's load form -- float64,
+ * 12-byte points, column-major pairs, element by element -- behind a workgroup-uniform switch in front of phase A; every frame with its own state words,
+ * tile regions, compacted points, tile counts and pinned result words; no workgroup waits for another: a workgroup beyond its frame's tiles leaves at once,
+ * the last ticket of a frame finishes it) and ONE host wait.  Device views are read in place (one event per distinct ready_stream); host views are packed
+ * column-major in their own precision into one pinned block, a view named by several frames once, and read there by the kernel, as the single call does;
+ * host selection bytes are copied into the same block and read in place as well (the kernel reads each byte once: a copy to the device would move the same
+ * bytes over the same link behind one more command on the stream).  The arena's layout is csrc/tdlo_view_batch_plan.h (tdlo_debug_view_batch_plan).
+ *   A frame goes into the launch when TDLO_CLOUD_FUSED is on and its N <= 1 048 576 (256 tiles); the kernel passes on what the one-launch form passes on --
+ * more than 32 704 kept points, cell-index bits + rank bits beyond 32, pass-through, the cases 8 / 9.  Every other frame, and every frame passed on, goes
+ * through the single call for its slot alone, which decides those cases as before; its code goes to rc_each, and the call returns the first non-zero code.
+ * tdlo_debug_route_count 38 counts the frames the batch launch served, 39 the frames passed on; 21 / 27 / 28 keep counting what the single route does.
+ *   Refused as a whole with TDLO_E_INVALID before anything is touched (resident clouds intact): F < 1 or F greater than the context's slot count, a slot out of
+ * range or named twice, a view tdlo_cloud_view_check refuses, TDLO_VIEW_ASYNC on any view, N > 2^26, a leaf that is not a positive finite float, a pointer
+ * on another GPU, a device view (or device select) that overlaps the resident cloud of ANY slot the call names.  Past that point the named slots' former
+ * clouds are gone, as for tdlo_depth_to_cloud_batch.
+ *   tdlo_set_cloud_view_batch: per slot what tdlo_set_cloud_view leaves, bit for bit, by ONE launch of k_cloud_import_batch (csrc/tdlo_import.hip: grid
+ * (blocks of the largest frame, F), the single kernel's loaders behind a switch on the frame's form; no load touches a byte outside a view's extent) and one
+ * wait.  Host views are packed into the pinned block and read in place (TDLO_VIEW_INPLACE=0: copied to the device first).  Refusals as above (no leaf, no
+ * select); TDLO_VIEW_ASYNC is refused here too.  tdlo_debug_route_count 40 counts the frames the batch launch imported, 41 the frames of calls below
+ * the crossover, which take the single route.
+ *   CROSSOVERS (csrc/tdlo_api.cpp; below them the calls loop over the single calls: the same bits).  MEASURED (profiles/view_batch_ab.txt, _run2.txt, rope
+ * clouds of 5 000 points and organized 640 x 480 clouds, F = 1 .. 32, batch and single calls alternating): one frame costs more as a batch (voxel grid 0.058
+ * against 0.041 ms, import 0.021 against 0.014 ms); from 2 frames on every value of every voxel and import line wins -- 4 device views 0.058 against 0.163 ms,
+ * 32 device views 0.063 against 1.29 ms, 32 host views at PointXYZRGB's stride 0.19 against 1.45 ms, 32 organized clouds under selections 0.17 against 1.19 ms
+ * (one cloud shared by 32 frames: 0.16 against 1.19), the import 0.024 against 0.43 ms (device) and 0.15 against 0.56 ms (host);
+ * tdlo_tracker_frames_from_cloud_view_batch 1.92 against 5.27 ms for 32 trackers, but with the registrations' own spread it won on every value from 4 trackers
+ * on in one run and from 8 in others.  The rule set beforehand -- the smallest F from which every batch value lies below every single-calls value -- over the
+ * lines a call stands for gives TWO constants: kViewBatchMin = 2 for tdlo_cloud_view_voxel_grid_batch and tdlo_set_cloud_view_batch called by themselves,
+ * kViewBatchTrackerMin = 8 for the two tracker calls below (tdlo_tracker_tracking_step_view_batch has no line of its own and takes the same).
+ * TDLO_VIEW_BATCH_MIN=n (read when the context is made) overrides both. */
+typedef struct { int slot; const tdlo_cloud_view *view; int N; const unsigned char *select; /* NULL: every element */ } tdlo_view_frame;
+int tdlo_cloud_view_voxel_grid_batch(tdlo_ctx *ctx, const tdlo_view_frame *frames, int F, double leaf_size,
+                                     int *n_out /* F */, int *n_raw_out /* F */, int *rc_each /* F or NULL */);
+int tdlo_set_cloud_view_batch(tdlo_ctx *ctx, const int *slots, const tdlo_cloud_view *const *views, const int *N, int F, int *rc_each /* F or NULL */);
+/* tdlo_set_cloud_view_batch into the trackers' slots, enqueued without a host wait (device sources must stay valid until the call returns), then
+ * tdlo_tracker_tracking_step_batch: the bits and the refusals of the two, except that no cloud need be resident. */
+int tdlo_tracker_tracking_step_view_batch(tdlo_tracker *const *trackers, int F, const tdlo_cloud_view *const *views, const int *N,
+                                          const int *const *visible_nodes, const int *n_vis, const int *const *visible_nodes_extended, const int *n_vis_ext,
+                                          const double *const *H_pre, tdlo_stats *stats, int *rc_each);
+/* tdlo_cloud_view_voxel_grid_batch into the trackers' slots (frame i: tracker i's slot -- the slot of the record is ignored), then tdlo_tracker_frame_batch on
+ * the trackers whose cloud is not empty.  A tracker whose view keeps no point gets TDLO_E_EMPTY in rc_each and is left untouched; the others go on.  Outputs
+ * as for tdlo_tracker_frames_batch; the bits and the refusals are those of the parts, except that no cloud need be resident. */
+int tdlo_tracker_frames_from_cloud_view_batch(tdlo_tracker *const *trackers, int F, const tdlo_view_frame *frames /* slot ignored: the tracker's */,
+                                              double leaf_size, double d_vis,
+                                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                              int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each);
+/* Test aid: where tdlo_cloud_view_voxel_grid_batch keeps the blocks of F frames of N[f] elements in its arena (csrc/tdlo_view_batch_plan.h; offsets in bytes;
+ * any output may be NULL; Fcap: the context's slot count).  TDLO_E_INVALID for F < 1, F > Fcap or an N[f] outside 1 .. 1 048 576. */
+int tdlo_debug_view_batch_plan(const int *N, int F, int Fcap, long long *state_off, long long *tiles_off, long long *pts_off, long long *cnt_off,
+                               long long *table_off, long long *total);
+
 /* ---- frames as they arrive: image views in device or host memory ------------------------------------ */
 /* A view of one rows x cols image where its producer holds it; nothing is copied to build one.  The packed calls above take one shape only (packed
  * rows, 3-channel colour, uint16 millimetres, a host pointer); a renderer, simulator or decoder on the same GPU, or a torch tensor, delivers RGBA8 /
@@ -1049,6 +1107,10 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 36 / 37: frames of tdlo_reg_batch, tdlo_sort_pts_batch and tdlo_tracker_initialize_from_cloud_batch served by the batch launches (k_reg_estep_batch /
  * k_reg_mstep_batch, k_sort_pts_batch; a frame that ends on TDLO_E_NUMERIC included) / handed to the single call because the batch was smaller than
  * TDLO_INIT_BATCH_MIN; 25 / 26 keep counting the single calls only, those of the second route among them.
+ * 38 / 39: frames of tdlo_cloud_view_voxel_grid_batch (tdlo_tracker_frames_from_cloud_view_batch's among them) served by the batch launch k_cloud_view_batch /
+ * passed on to the single call for their slot -- by the kernel, or by the host (more than 1 048 576 elements, TDLO_CLOUD_FUSED=0); frames of a batch below
+ * the crossover count in 21 / 27 / 28 alone.  40 / 41: frames of tdlo_set_cloud_view_batch (tdlo_tracker_tracking_step_view_batch's among them)
+ * imported by the batch launch k_cloud_import_batch / by the single route because the batch was smaller than the crossover.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

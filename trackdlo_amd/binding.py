@@ -95,6 +95,10 @@ class BatchFrame(C.Structure):                     # tdlo_batch_frame: a slot, t
     _fields_ = [("slot", C.c_int), ("image", C.c_int), ("colour_params", C.c_void_p)]
 
 
+class ViewFrame(C.Structure):                      # tdlo_view_frame: a slot, the cloud view it takes, its N and selection bytes (NULL: every element)
+    _fields_ = [("slot", C.c_int), ("view", C.c_void_p), ("N", C.c_int), ("select", C.c_void_p)]
+
+
 class FrameView(C.Structure):
     """tdlo_frame_view: the images of one frame; an image whose data is NULL is absent."""
     _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
@@ -126,6 +130,8 @@ SYMBOLS = [
     "tdlo_depth_to_cloud_batch", "tdlo_tracker_frames_batch",
     "tdlo_render_batch_table", "tdlo_render_result_batch", "tdlo_tracker_render_result_batch",
     "tdlo_reg_batch", "tdlo_sort_pts_batch", "tdlo_tracker_initialize_from_cloud_batch", "tdlo_debug_reg_batch_plan",
+    "tdlo_cloud_view_voxel_grid_batch", "tdlo_set_cloud_view_batch", "tdlo_tracker_tracking_step_view_batch", "tdlo_tracker_frames_from_cloud_view_batch",
+    "tdlo_debug_view_batch_plan",
 ]
 
 _lib = None
@@ -334,6 +340,12 @@ def load_library(path: str | None = None):
         lib.tdlo_sort_pts_batch.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
         lib.tdlo_tracker_initialize_from_cloud_batch.argtypes = [vp, ci, cd, ci, vp, vp]
         lib.tdlo_debug_reg_batch_plan.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
+    if hasattr(lib, "tdlo_cloud_view_voxel_grid_batch"):
+        lib.tdlo_cloud_view_voxel_grid_batch.argtypes = [vp, vp, ci, cd, vp, vp, vp]
+        lib.tdlo_set_cloud_view_batch.argtypes = [vp, vp, vp, vp, ci, vp]
+        lib.tdlo_tracker_tracking_step_view_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.tdlo_tracker_frames_from_cloud_view_batch.argtypes = [vp, ci, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.tdlo_debug_view_batch_plan.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     if path is None:
         _lib = lib
     return lib
@@ -603,6 +615,32 @@ def _colour_images(depth, colour, occluder):
     return depth, colour, occluder, (occluder.ctypes.data_as(C.c_void_p) if occluder is not None else None)
 
 
+def _view_frames(frames, ready_stream=None):
+    """The tdlo_view_frame table of (slot, view, select) triples -- view: a CloudView or anything cloud_view() takes; select: None or N selection bytes (a
+    numpy array, or anything with a device pointer).  Returns (table, F, what must stay alive for the call)."""
+    F = len(frames)
+    tab = (ViewFrame * max(F, 1))()
+    keep = []
+    for i, (slot, view, select) in enumerate(frames):
+        v = view if isinstance(view, CloudView) else cloud_view(view, ready_stream)
+        sp, owner = _select_ptr(select, int(v.N))
+        tab[i].slot, tab[i].view, tab[i].N, tab[i].select = int(slot), C.addressof(v), int(v.N), sp
+        keep.append((v, owner))
+    return tab, F, keep
+
+
+def view_batch_plan(N, Fcap):
+    """tdlo_debug_view_batch_plan: where the voxel-grid view batch keeps the blocks of frames of N[f] elements (bytes from the arena's start).
+    Returns dict(state, tiles, pts, cnt: F offsets each; table, total) or None where the library refuses the sizes."""
+    Na = np.ascontiguousarray(N, dtype=np.int32)
+    F = len(Na)
+    o = [np.zeros(max(F, 1), dtype=np.int64) for _ in range(4)]
+    tab = C.c_longlong(0); tot = C.c_longlong(0)
+    if load_library().tdlo_debug_view_batch_plan(_ptr(Na), F, int(Fcap), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), C.byref(tab), C.byref(tot)):
+        return None
+    return dict(state=o[0][:F].tolist(), tiles=o[1][:F].tolist(), pts=o[2][:F].tolist(), cnt=o[3][:F].tolist(), table=tab.value, total=tot.value)
+
+
 def _batch_plane(p, dtype, shape, what):
     """(address, owner) of one plane of a batch image: anything numpy takes (host memory), or an object with data_ptr() -- a torch tensor, in host or device
     memory -- which must already be packed, of the right element size and shape."""
@@ -782,6 +820,41 @@ class Context:
                                                                  C.byref(n), C.byref(nraw)))
         self._async_src = None
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
+    def set_cloud_view_batch(self, slots, objs, ready_stream=None, check=True):
+        """tdlo_set_cloud_view_batch: the clouds of F slots from F views where they lie, imported as they are in one launch (objs: CloudViews or anything
+        cloud_view() takes).  Returns the F per-frame codes; raises on the first non-zero one unless check=False."""
+        F = len(slots)
+        assert len(objs) == F
+        vs = [o if isinstance(o, CloudView) else cloud_view(o, ready_stream) for o in objs]
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        N = np.array([int(v.N) for v in vs], dtype=np.int32)
+        pv = (C.c_void_p * max(F, 1))(*[C.addressof(v) for v in vs])
+        rcs = np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.tdlo_set_cloud_view_batch(self.h, _ptr(sl), C.cast(pv, C.c_void_p), _ptr(N), F, _ptr(rcs))
+        self._async_src = None
+        del vs
+        if rc and check:
+            self._chk(rc)
+        return [int(r) for r in rcs[:F]]
+
+    def voxel_grid_view_batch(self, frames, leaf_size, ready_stream=None, check=True):
+        """tdlo_cloud_view_voxel_grid_batch: pcl::VoxelGrid on F clouds where they lie into F slots in one call.  frames: (slot, view, select or None) -- view
+        a CloudView or anything cloud_view() takes; several frames may name one view with different selections.  The clouds stay resident in the slots
+        (get_cloud).  Returns (n [F], n_raw [F], codes [F]); raises on the first non-zero code unless check=False."""
+        tab, F, keep = _view_frames(frames, ready_stream)
+        n = np.zeros(max(F, 1), dtype=np.int32); nraw = np.zeros(max(F, 1), dtype=np.int32); rcs = np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.tdlo_cloud_view_voxel_grid_batch(self.h, C.cast(tab, C.c_void_p), F, float(leaf_size), _ptr(n), _ptr(nraw), _ptr(rcs))
+        self._async_src = None
+        del keep
+        if rc and check:
+            self._chk(rc)
+        return [int(v) for v in n[:F]], [int(v) for v in nraw[:F]], [int(v) for v in rcs[:F]]
+
+    def view_batch_route_counts(self):
+        """[frames the voxel-grid view batch launch served, frames passed on to the single call, frames the import batch launch imported, frames of import
+        batches below TDLO_VIEW_BATCH_MIN] (tdlo_debug_route_count 38 .. 41)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (38, 39, 40, 41)]
 
     def view_route_counts(self):
         """[voxel-grid view calls served by the one-launch kernel, calls it passed on to the multi-launch form, view frames whose visibility pre-pass rode
@@ -1615,6 +1688,44 @@ def frames_batch(trackers, images, image_of, colour_params, leaf_size, d_vis, ch
     rc = trackers[0].ctx.lib.tdlo_tracker_frames_batch(C.cast(tab, C.c_void_p), F, C.cast(itab, C.c_void_p), K, rows, cols, _ptr(io),
                                                        C.cast(cp, C.c_void_p) if cp is not None else None, float(leaf_size), float(d_vis),
                                                        _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
+    del keep
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def tracking_step_view_batch(trackers, objs, vis, vext, H_pre=None, ready_stream=None, check=True):
+    """tdlo_tracker_tracking_step_view_batch: the trackers' clouds from F views where they lie (Context.set_cloud_view_batch into the trackers' slots, without
+    a host wait), then tracking_step_batch.  Returns the F per-tracker codes; raises on the first non-zero one unless check=False."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    assert len(objs) == F and len(vis) == F and len(vext) == F and (H_pre is None or len(H_pre) == F)
+    vs = [o if isinstance(o, CloudView) else cloud_view(o, ready_stream) for o in objs]
+    N = np.array([int(v.N) for v in vs], dtype=np.int32)
+    pc = (C.c_void_p * F)(*[C.addressof(v) for v in vs])
+    v = [np.ascontiguousarray(x, dtype=np.int32) for x in vis]
+    ve = [np.ascontiguousarray(x, dtype=np.int32) for x in vext]
+    Hm = None if H_pre is None else [None if h is None else _f64(h) for h in H_pre]
+    pv = (C.c_void_p * F)(*[x.ctypes.data for x in v]); pe = (C.c_void_p * F)(*[x.ctypes.data for x in ve])
+    nv = np.array([len(x) for x in v], dtype=np.int32); ne = np.array([len(x) for x in ve], dtype=np.int32)
+    ph = None if Hm is None else (C.c_void_p * F)(*[None if h is None else h.ctypes.data for h in Hm])
+    rc = trackers[0].ctx.lib.tdlo_tracker_tracking_step_view_batch(C.cast(tab, C.c_void_p), F, C.cast(pc, C.c_void_p), _ptr(N), C.cast(pv, C.c_void_p), _ptr(nv),
+                                                                   C.cast(pe, C.c_void_p), _ptr(ne), C.cast(ph, C.c_void_p) if ph is not None else None,
+                                                                   C.cast(st, C.c_void_p), _ptr(rcs))
+    del vs
+    return _batch_done(trackers, st, rcs, rc, check)
+
+
+def frames_from_cloud_view_batch(trackers, views, leaf_size, d_vis, selects=None, ready_stream=None, check=True):
+    """tdlo_tracker_frames_from_cloud_view_batch: the trackers' frames from clouds where they lie -- Context.voxel_grid_view_batch into the trackers' slots
+    (tracker i: views[i] under selects[i], every element where that is None or selects is None), then frame_batch on the trackers that got a cloud.
+    Returns (codes, [visible_nodes], [visible_nodes_extended], n [F], n_raw [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    assert len(views) == F and (selects is None or len(selects) == F)
+    ftab, _, keep = _view_frames([(0, views[i], None if selects is None else selects[i]) for i in range(F)], ready_stream)
+    M = trackers[0].M
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_cloud_view_batch(C.cast(tab, C.c_void_p), F, C.cast(ftab, C.c_void_p), float(leaf_size), float(d_vis),
+                                                                       _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]

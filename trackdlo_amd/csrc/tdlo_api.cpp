@@ -7,6 +7,7 @@
 #include "tdlo_image.h"
 #include "tdlo_rccl.h"
 #include "tdlo_reg_plan.h"
+#include "tdlo_view_batch_plan.h"
 
 #include <algorithm>
 #include <limits>
@@ -216,6 +217,20 @@ struct tdlo_ctx {
     int cbat_armed_F = 0, cbat_armed_P = 0;
     int cloud_batch_min = (getenv("TDLO_CLOUD_BATCH_MIN") && atoi(getenv("TDLO_CLOUD_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_CLOUD_BATCH_MIN")) : 0;      // 0: kCloudBatchMin
     long long cbat_route[2] = {0, 0};    // tdlo_debug_route_count 32 / 33: frames served by the batch launch / passed on by it to the single call
+    // cloud views for F slots in one call (tdlo_cloud_view_voxel_grid_batch: k_cloud_view_batch; tdlo_set_cloud_view_batch: k_cloud_import_batch).  wbat_dev: the
+    // arena of tdlo_view_batch_plan.h -- [one state block per slot of the context | descriptor table | the frames' blocks] -- grown on demand; the state blocks
+    // are armed when wbat_armed says so (the kernel keeps them so; a call that did not complete or a reallocation has them initialised again).  wbat_pin:
+    // [2 F result words | the table as it is uploaded | the host views packed column-major in their own precision, every distinct view once | the host
+    // selection bytes], read in place by the kernels.  wbat_ev: one event per distinct ready_stream of a call.  TDLO_VIEW_BATCH_MIN=n: below n frames the
+    // calls loop over the single calls (0: kViewBatchMin / kViewBatchTrackerMin).  wbat_route: tdlo_debug_route_count 38 .. 41
+    void *wbat_dev = nullptr;
+    size_t wbat_dev_cap = 0;
+    char *wbat_pin = nullptr;
+    size_t wbat_pin_cap = 0;
+    bool wbat_armed = false;
+    std::vector<hipEvent_t> wbat_ev;
+    int view_batch_min = (getenv("TDLO_VIEW_BATCH_MIN") && atoi(getenv("TDLO_VIEW_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_VIEW_BATCH_MIN")) : 0;
+    long long wbat_route[4] = {0, 0, 0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1765,6 +1780,9 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->cbat_dev) hipFree(c->cbat_dev);
     if (c->cbat_img) hipFree(c->cbat_img);
     if (c->cbat_pin) hipHostFree(c->cbat_pin);
+    if (c->wbat_dev) hipFree(c->wbat_dev);
+    if (c->wbat_pin) hipHostFree(c->wbat_pin);
+    for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
     if (c->vis_nodes_pin) hipHostFree(c->vis_nodes_pin);
@@ -3741,6 +3759,322 @@ int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, 
     return cloud_view_voxel_impl(c, slot, v, N, select, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
 }
 
+// ---- cloud views for F slots in one call (include/trackdlo_hip.h: tdlo_cloud_view_voxel_grid_batch, tdlo_set_cloud_view_batch) --------------------------
+// From this many frames on the calls are one batch launch each; below it they loop over the single calls (the same bits).  Set from
+// profiles/view_batch_ab.txt and view_batch_ab_run2.txt by the rule "the smallest F from which on every batch value lies below every single-calls value", taken
+// over the lines a call stands for -- TWO constants, because the data ask for it:
+//   kViewBatchMin         tdlo_cloud_view_voxel_grid_batch / tdlo_set_cloud_view_batch called by themselves: the voxel lines (device and host views of 5 000
+//                         points, organized 640 x 480 clouds under selections, one cloud shared by all frames) and the import lines (device, host).  ONE frame
+//                         costs more as a batch on every line (0.058 against 0.041 ms for the voxel grid, 0.021 against 0.014 ms for the import: a table
+//                         upload and a one-workgroup finish where the single call has a team of eight); from 2 frames on every value of every such line
+//                         wins (4 device views 0.058 against 0.163 ms; 32: 0.063 against 1.29 ms, the import 0.024 against 0.43 ms)
+//   kViewBatchTrackerMin  the two tracker calls: the tracker line, whose registrations bring a spread of their own, won on every value from 4 frames on in
+//                         one run and from 8 in others; the largest is the constant.  (tdlo_tracker_tracking_step_view_batch has no line of its own -- not
+//                         measured -- and takes the same constant.)
+// TDLO_VIEW_BATCH_MIN=n, read when the context is made, overrides both.
+constexpr int kViewBatchMin = 2;
+constexpr int kViewBatchTrackerMin = 8;
+static int view_batch_min(const tdlo_ctx *c, bool tracker) { return c->view_batch_min ? c->view_batch_min : (tracker ? kViewBatchTrackerMin : kViewBatchMin); }
+
+int tdlo_debug_view_batch_plan(const int *N, int F, int Fcap, long long *state_off, long long *tiles_off, long long *pts_off, long long *cnt_off,
+                               long long *table_off, long long *total) {
+    return view_batch_plan(N, F, Fcap, (long long)view_batch_desc_bytes(), state_off, tiles_off, pts_off, cnt_off, table_off, total) ? TDLO_E_INVALID : TDLO_OK;
+}
+
+// where the views (and selection bytes) of a view batch lie
+struct ViewBatchWhere { bool dev = false, sel_dev = false; };
+
+// Everything that refuses a view batch as a whole; nothing of the context or the slots is touched.  select / leaf: the voxel grid's (select == nullptr and
+// leaf_size < 0: the plain import, which has neither)
+static int view_batch_refusal(tdlo_ctx *c, const char *what, const int *slots, const tdlo_cloud_view *const *views, const int *N, const unsigned char *const *select,
+                              int F, bool voxel, double leaf_size, std::vector<ViewBatchWhere> &where) {
+    const std::string w(what);
+    if (!slots || !views || !N || F < 1) return fail(c, TDLO_E_INVALID, w + ": no frames");
+    if (F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, w + ": more frames than the context has slots");
+    if (voxel) {
+        const float leaf = (float)leaf_size;
+        if (!(leaf > 0.0f) || !std::isfinite(leaf)) return fail(c, TDLO_E_INVALID, "voxel grid: the leaf size is not a positive finite float");
+    }
+    for (int f = 0; f < F; ++f) {
+        if (const char *why = view_fault(views[f], N[f])) return fail(c, TDLO_E_INVALID, w + ": frame " + std::to_string(f) + ": " + why);
+        if (slots[f] < 0 || slots[f] >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+        for (int g = 0; g < f; ++g) if (slots[g] == slots[f]) return fail(c, TDLO_E_INVALID, w + ": a slot is named twice");
+        if (views[f]->flags & TDLO_VIEW_ASYNC) return fail(c, TDLO_E_INVALID, w + ": TDLO_VIEW_ASYNC is not available (the call ends with one wait for all frames)");
+        if (voxel && N[f] > (1 << 26)) return fail(c, TDLO_E_INVALID, "voxel grid on a view: more than 2^26 points");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    where.assign(F, ViewBatchWhere{});
+    for (int f = 0; f < F; ++f) {
+        if (int rc = view_location(c, views[f], &where[f].dev)) return rc;
+        if (select && select[f]) { if (int rc = pointer_location(c, select[f], TDLO_MEM_AUTO, "select", &where[f].sel_dev)) return rc; }
+    }
+    // a device source that overlaps the resident cloud of ANY slot the call names: that cloud is written while the source is still being read
+    for (int f = 0; f < F; ++f) {
+        const char *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;
+        if (where[f].dev) {
+            long long lo = 0, hi = 0;
+            (void)tdlo_cloud_view_extent(views[f], N[f], &lo, &hi);
+            a0 = (const char *)views[f]->data + lo; a1 = (const char *)views[f]->data + hi;
+        }
+        if (where[f].sel_dev) { b0 = (const char *)select[f]; b1 = b0 + N[f]; }
+        if (!a0 && !b0) continue;
+        for (int g = 0; g < F; ++g) {
+            const Slot &s = c->slots[slots[g]];
+            if (!s.Xraw) continue;
+            const char *x0 = (const char *)s.Xraw, *x1 = x0 + 3 * (size_t)s.cap_points * sizeof(double);
+            if ((a0 && a0 < x1 && x0 < a1) || (b0 && b0 < x1 && x0 < b1)) return fail(c, TDLO_E_INVALID, w + ": a view aliases the resident cloud of a slot the call names");
+        }
+    }
+    return TDLO_OK;
+}
+
+// the arena (device) and the pinned block of a view batch, grown on demand; the state blocks armed
+static int view_batch_room(tdlo_ctx *c, size_t dev_bytes, size_t pin_bytes) {
+    hipStream_t st = c->stream;
+    if (dev_bytes > c->wbat_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->wbat_dev) hipFree(c->wbat_dev);
+        c->wbat_dev = nullptr; c->wbat_dev_cap = 0; c->wbat_armed = false;
+        HIPCHK(c, hipMalloc(&c->wbat_dev, dev_bytes));
+        c->wbat_dev_cap = dev_bytes;
+    }
+    if (pin_bytes > c->wbat_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->wbat_pin) hipHostFree(c->wbat_pin);
+        c->wbat_pin = nullptr; c->wbat_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->wbat_pin, pin_bytes, hipHostMallocDefault));
+        std::memset(c->wbat_pin, 0, pin_bytes);
+        c->wbat_pin_cap = pin_bytes;
+    }
+    if (!c->wbat_armed) {
+        HIPCHK(c, view_batch_arm(c->wbat_dev, (int)c->slots.size(), st));
+        c->wbat_armed = true;
+    }
+    return TDLO_OK;
+}
+
+// the context's stream waits for what the views' ready_streams hold so far: one event per distinct stream
+static int view_batch_ready(tdlo_ctx *c, const tdlo_cloud_view *const *views, const std::vector<ViewBatchWhere> &where, const std::vector<int> &which) {
+    std::vector<void *> seen;
+    for (int f : which) {
+        void *rs = views[f]->ready_stream;
+        if (!where[f].dev || !rs || std::find(seen.begin(), seen.end(), rs) != seen.end()) continue;
+        if (seen.size() >= c->wbat_ev.size()) {
+            hipEvent_t e = nullptr;
+            HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            c->wbat_ev.push_back(e);
+        }
+        hipEvent_t e = c->wbat_ev[seen.size()];
+        HIPCHK(c, hipEventRecord(e, (hipStream_t)rs));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
+        seen.push_back(rs);
+    }
+    return TDLO_OK;
+}
+
+// The host views among `which` packed column-major in their own precision behind `at` of the pinned block, every distinct view once: off[f] = where frame
+// f's lies (a device view: not touched).  size_only: nothing is written, *at advances all the same.
+static void view_batch_pack(const tdlo_cloud_view *const *views, const int *N, const std::vector<ViewBatchWhere> &where, const std::vector<int> &which, char *pin,
+                            size_t *at, std::vector<size_t> &off, bool size_only) {
+    for (size_t k = 0; k < which.size(); ++k) {
+        const int f = which[k];
+        if (where[f].dev) continue;
+        const tdlo_cloud_view *v = views[f];
+        bool had = false;
+        for (size_t j = 0; j < k && !had; ++j) {
+            const int g = which[j];
+            const tdlo_cloud_view *u = views[g];
+            if (!where[g].dev && u->data == v->data && u->dtype == v->dtype && u->stride_point == v->stride_point && u->stride_comp == v->stride_comp && N[g] == N[f]) {
+                off[f] = off[g]; had = true;
+            }
+        }
+        if (had) continue;
+        const bool f64 = v->dtype == TDLO_F64;
+        off[f] = *at;
+        if (!size_only) {
+            if (f64) view_gather((double *)(pin + *at), (const double *)v->data, v->stride_point, v->stride_comp, N[f]);
+            else view_gather((float *)(pin + *at), (const float *)v->data, v->stride_point, v->stride_comp, N[f]);
+        }
+        *at += (3 * (size_t)N[f] * (f64 ? 8 : 4) + 255) & ~(size_t)255;
+    }
+}
+
+static int view_voxel_batch_impl(tdlo_ctx *c, const int *slots, const tdlo_cloud_view *const *views, const int *N, const unsigned char *const *select, int F,
+                                 double leaf_size, int *n_out, int *n_raw_out, int *rc_each, bool tracker) {
+    std::vector<ViewBatchWhere> where;
+    int rc = view_batch_refusal(c, "view voxel batch", slots, views, N, select, F, true, leaf_size, where);
+    if (rc) return rc;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    auto finish = [&]() {
+        if (n_out) std::copy(n.begin(), n.end(), n_out);
+        if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int f = 0; f < F; ++f) if (rcs[f]) return rcs[f];
+        return (int)TDLO_OK;
+    };
+    auto single = [&](int f) { rcs[f] = cloud_view_voxel_impl(c, slots[f], views[f], N[f], select[f], leaf_size, nullptr, 0, &n[f], &nraw[f], nullptr, 0, nullptr); };
+    if (F < view_batch_min(c, tracker)) {
+        for (int f = 0; f < F; ++f) single(f);
+        return finish();
+    }
+    // ---- who goes into the launch: the others are passed on to the single call, after it
+    std::vector<int> in, passed;
+    for (int f = 0; f < F; ++f) {
+        if (c->cloud_fused_on && N[f] <= view_batch_max_elements()) in.push_back(f);
+        else { passed.push_back(f); ++c->wbat_route[1]; }
+    }
+    const int Fi = (int)in.size();
+    if (Fi > 0) {
+        hipStream_t st = c->stream;
+        if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+        // ---- the arena by the plan; the pinned block: result words, table, packed host views, host selection bytes
+        std::vector<int> Ni(Fi);
+        for (int j = 0; j < Fi; ++j) Ni[j] = N[in[j]];
+        std::vector<long long> o_state(Fi), o_tiles(Fi), o_pts(Fi), o_cnt(Fi);
+        long long o_table = 0, total = 0;
+        const size_t desc = view_batch_desc_bytes();
+        if (view_batch_plan(Ni.data(), Fi, (int)c->slots.size(), (long long)desc, o_state.data(), o_tiles.data(), o_pts.data(), o_cnt.data(), &o_table, &total))
+            return fail(c, TDLO_E_INVALID, "view voxel batch: no plan for these frames");
+        auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t p_tab = r256(2 * sizeof(unsigned long long) * (size_t)Fi);
+        size_t at = p_tab + r256(desc * (size_t)Fi);
+        std::vector<size_t> voff(F, 0), soff(F, 0);
+        const size_t p_views = at;
+        view_batch_pack(views, N, where, in, nullptr, &at, voff, true);
+        // (host selection bytes are READ IN PLACE from the pinned block, like the packed views: the kernel reads every byte exactly once in phase A, so a copy
+        //  to the device in front of the launch would move the same bytes over the same link and add a copy command to the stream)
+        for (int f : in) if (select[f] && !where[f].sel_dev) { soff[f] = at; at += r256((size_t)N[f]); }
+        if ((rc = view_batch_room(c, (size_t)total, at))) return rc;
+        char *dev = (char *)c->wbat_dev, *pin = c->wbat_pin;
+        unsigned long long *res = (unsigned long long *)pin;
+        std::memset(res, 0, 2 * sizeof(unsigned long long) * (size_t)Fi);      // (no word may look like this call's epoch)
+        {
+            size_t at2 = p_views;
+            view_batch_pack(views, N, where, in, pin, &at2, voff, false);
+        }
+        for (int f : in) if (select[f] && !where[f].sel_dev) std::memcpy(pin + soff[f], select[f], (size_t)N[f]);
+        // ---- the slots: room for every point the kernel can leave; whatever was resident is gone from here on
+        for (int f : in) {
+            Slot &s = c->slots[slots[f]];
+            if ((rc = ensure_points(c, s, std::min(N[f], cloud_fused_max_points())))) return rc;
+            s.N0 = 0; s.sorted_valid = false;
+        }
+        if ((rc = view_batch_ready(c, views, where, in))) return rc;
+        std::vector<ViewBatchFrameHost> bf(Fi);
+        for (int j = 0; j < Fi; ++j) {
+            const int f = in[j];
+            const tdlo_cloud_view *v = views[f];
+            ViewBatchFrameHost &b = bf[j];
+            b = ViewBatchFrameHost{};
+            b.src = CloudViewSrc{v->data, v->dtype == TDLO_F64, v->stride_point, v->stride_comp, select[f]};
+            if (!where[f].dev) { b.src.data = pin + voff[f]; b.src.stride_point = 1; b.src.stride_comp = N[f]; }
+            if (select[f] && !where[f].sel_dev) b.src.select = (const unsigned char *)(pin + soff[f]);
+            b.N = N[f];
+            b.state = dev + o_state[j]; b.tiles = dev + o_tiles[j]; b.pts = dev + o_pts[j]; b.tcnt = dev + o_cnt[j];
+            Slot &s = c->slots[slots[f]];
+            b.X = s.Xraw; b.cap = s.cap_points; b.res = res + 2 * (size_t)j;
+        }
+        if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+        const unsigned epoch = c->cloud_epoch;
+        const float inv = 1.0f / (float)leaf_size;
+        {
+            const hipError_t e = launch_cloud_view_batch(bf.data(), Fi, inv, epoch, pin + p_tab, dev + o_table, st);
+            if (e != hipSuccess) { c->wbat_armed = false; HIPCHK(c, e); }
+        }
+        {
+            const hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { c->wbat_armed = false; HIPCHK(c, e); }
+        }
+        for (int j = 0; j < Fi; ++j) {
+            const int f = in[j];
+            const unsigned long long w0 = __atomic_load_n(res + 2 * (size_t)j, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(res + 2 * (size_t)j + 1, __ATOMIC_RELAXED);
+            const unsigned status = (unsigned)w0;
+            if ((unsigned)(w0 >> 32) != epoch) { c->wbat_armed = false; rcs[f] = fail(c, TDLO_E_HIP, "the stream drained, but a frame of the view voxel batch did not report"); continue; }
+            nraw[f] = (int)(unsigned)(w1 >> 32);
+            const int nf = (int)(unsigned)w1;
+            if (status == 1u) {
+                if (nf < 0 || nf > c->slots[slots[f]].cap_points || nf > nraw[f]) { rcs[f] = fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count"); continue; }
+                n[f] = nf; c->slots[slots[f]].N0 = nf; ++c->wbat_route[0];
+            } else { passed.push_back(f); ++c->wbat_route[1]; }      // not taken (2); the slot would have to grow (3: the single call does that)
+        }
+    }
+    std::sort(passed.begin(), passed.end());
+    for (int f : passed) single(f);
+    return finish();
+}
+
+// tracker: the call stands behind a tracker entrance (view_batch_min)
+static int view_voxel_batch_frames(tdlo_ctx *c, const tdlo_view_frame *frames, int F, double leaf_size, int *n_out, int *n_raw_out, int *rc_each, bool tracker) {
+    if (!frames || F < 1) return fail(c, TDLO_E_INVALID, "view voxel batch: no frames");
+    std::vector<int> slots(F), N(F);
+    std::vector<const tdlo_cloud_view *> views(F);
+    std::vector<const unsigned char *> sel(F);
+    for (int f = 0; f < F; ++f) { slots[f] = frames[f].slot; views[f] = frames[f].view; N[f] = frames[f].N; sel[f] = frames[f].select; }
+    return view_voxel_batch_impl(c, slots.data(), views.data(), N.data(), sel.data(), F, leaf_size, n_out, n_raw_out, rc_each, tracker);
+}
+
+int tdlo_cloud_view_voxel_grid_batch(tdlo_ctx *c, const tdlo_view_frame *frames, int F, double leaf_size, int *n_out, int *n_raw_out, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    return view_voxel_batch_frames(c, frames, F, leaf_size, n_out, n_raw_out, rc_each, false);
+}
+
+// tdlo_set_cloud_view_batch on checked arguments.  wait: the call returns when the imports have finished (false: the tracker call, whose registrations wait
+// for the stream before it returns -- the pinned block is free again by then)
+static int view_import_batch_impl(tdlo_ctx *c, const int *slots, const tdlo_cloud_view *const *views, const int *N, int F, int *rc_each, bool wait, bool tracker) {
+    std::vector<ViewBatchWhere> where;
+    int rc = view_batch_refusal(c, "view import batch", slots, views, N, nullptr, F, false, -1.0, where);
+    if (rc) return rc;
+    std::vector<int> rcs(F, 0);
+    auto finish = [&]() {
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int f = 0; f < F; ++f) if (rcs[f]) return rcs[f];
+        return (int)TDLO_OK;
+    };
+    if (F < view_batch_min(c, tracker)) {
+        for (int f = 0; f < F; ++f) { rcs[f] = import_view(c, slots[f], views[f], N[f], where[f].dev, wait || !where[f].dev); if (!rcs[f]) ++c->wbat_route[3]; }
+        return finish();
+    }
+    hipStream_t st = c->stream;
+    if ((rc = flush_pending_cloud(c))) return rc;
+    std::vector<int> all(F);
+    for (int f = 0; f < F; ++f) all[f] = f;
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t tab = r256(sizeof(ImportBatchFrame) * (size_t)F);
+    std::vector<size_t> voff(F, 0);
+    size_t at = tab;
+    view_batch_pack(views, N, where, all, nullptr, &at, voff, true);
+    const size_t packed = at - tab;
+    // the arena: [state blocks (the voxel grid's: not touched) | table | TDLO_VIEW_INPLACE=0: the packed views' copy]
+    const size_t d_tab = (size_t)kViewBatchState * c->slots.size();
+    if ((rc = view_batch_room(c, d_tab + tab + (c->view_inplace ? 0 : packed), at))) return rc;
+    char *dev = (char *)c->wbat_dev, *pin = c->wbat_pin;
+    {
+        size_t at2 = tab;
+        view_batch_pack(views, N, where, all, pin, &at2, voff, false);
+    }
+    for (int f = 0; f < F; ++f) if ((rc = ensure_points(c, c->slots[slots[f]], N[f]))) return rc;
+    if ((rc = view_batch_ready(c, views, where, all))) return rc;
+    if (!c->view_inplace && packed > 0) HIPCHK(c, hipMemcpyAsync(dev + d_tab + tab, pin + tab, packed, hipMemcpyHostToDevice, st));
+    std::vector<ImportBatchFrame> bf(F);
+    std::vector<char> f64(F);
+    for (int f = 0; f < F; ++f) {
+        const tdlo_cloud_view *v = views[f];
+        f64[f] = v->dtype == TDLO_F64;
+        if (where[f].dev) bf[f] = ImportBatchFrame{v->data, v->stride_point, v->stride_comp, c->slots[slots[f]].Xraw, N[f], 0};
+        else bf[f] = ImportBatchFrame{(c->view_inplace ? pin : dev + d_tab) + voff[f], 1, (long long)N[f], c->slots[slots[f]].Xraw, N[f], 0};
+    }
+    HIPCHK(c, launch_cloud_import_batch(bf.data(), (const bool *)f64.data(), F, pin, dev + d_tab, st));
+    for (int f = 0; f < F; ++f) { Slot &s = c->slots[slots[f]]; s.N0 = N[f]; s.sorted_valid = false; }
+    c->wbat_route[2] += F;
+    if (wait) HIPCHK(c, wait_stream(st));
+    return finish();
+}
+
+int tdlo_set_cloud_view_batch(tdlo_ctx *c, const int *slots, const tdlo_cloud_view *const *views, const int *N, int F, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    return view_import_batch_impl(c, slots, views, N, F, rc_each, true, false);
+}
+
 // ---- caller-side visibility pre-pass ------------------------------------------------------------
 static void vis_threshold_and_fill(const double *min_d2, int M, double visibility_threshold, double d_vis, const double *geodesic_coord, double *node_dist,
                                    int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext);
@@ -4337,7 +4671,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 37) return -1;
+    if (!c || which < 0 || which > 41) return -1;
+    if (which >= 38) return c->wbat_route[which - 38];
     if (which >= 36) return c->ibat_route[which - 36];
     if (which >= 34) return c->rbat_route[which - 34];
     if (which >= 32) return c->cbat_route[which - 32];
@@ -5082,22 +5417,29 @@ static const char *tracker_batch_refusal(tdlo_tracker *const *tr, int F, bool ne
     return nullptr;
 }
 
+// what is wrong with the visible sets of a batch of M-node trackers, or nullptr
+static const char *step_batch_sets_fault(int F, int M, const int *const *visible_nodes, const int *n_vis, const int *const *visible_nodes_extended, const int *n_vis_ext) {
+    if (!visible_nodes_extended || !n_vis_ext) return "null visible_nodes_extended / n_vis_ext";
+    auto nv = [&](int i) { return (visible_nodes && n_vis && visible_nodes[i]) ? n_vis[i] : 0; };
+    for (int i = 0; i < F; ++i) {
+        const int ne = n_vis_ext[i];
+        if (!visible_nodes_extended[i] || ne <= 0 || ne > M) return "visible_nodes_extended must hold 1..M indices (empty is undefined in the reference, trackdlo_node.cpp:351)";
+        for (int k = 0; k < ne; ++k) if (visible_nodes_extended[i][k] < 0 || visible_nodes_extended[i][k] >= M) return "visible_nodes_extended index out of range";
+        if (nv(i) < 0) return "n_vis < 0";
+        for (int k = 0; k < nv(i); ++k) if (visible_nodes[i][k] < 0 || visible_nodes[i][k] >= M) return "visible_nodes index out of range";
+    }
+    return nullptr;
+}
+
 int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F, const int *const *visible_nodes, const int *n_vis,
                                      const int *const *visible_nodes_extended, const int *n_vis_ext, const double *const *H_pre,
                                      tdlo_stats *stats, int *rc_each) {
     if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
     tdlo_ctx *c = trackers[0]->ctx;
     if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
-    if (!visible_nodes_extended || !n_vis_ext) return fail(c, TDLO_E_INVALID, "null visible_nodes_extended / n_vis_ext");
     const int M = trackers[0]->M;
+    if (const char *why = step_batch_sets_fault(F, M, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext)) return fail(c, TDLO_E_INVALID, why);
     auto nv = [&](int i) { return (visible_nodes && n_vis && visible_nodes[i]) ? n_vis[i] : 0; };
-    for (int i = 0; i < F; ++i) {
-        const int ne = n_vis_ext[i];
-        if (!visible_nodes_extended[i] || ne <= 0 || ne > M) return fail(c, TDLO_E_INVALID, "visible_nodes_extended must hold 1..M indices (empty is undefined in the reference, trackdlo_node.cpp:351)");
-        for (int k = 0; k < ne; ++k) if (visible_nodes_extended[i][k] < 0 || visible_nodes_extended[i][k] >= M) return fail(c, TDLO_E_INVALID, "visible_nodes_extended index out of range");
-        if (nv(i) < 0) return fail(c, TDLO_E_INVALID, "n_vis < 0");
-        for (int k = 0; k < nv(i); ++k) if (visible_nodes[i][k] < 0 || visible_nodes[i][k] >= M) return fail(c, TDLO_E_INVALID, "visible_nodes index out of range");
-    }
     std::vector<int> rcs(F, 0);
     std::vector<tdlo_stats> st(2 * (size_t)F);
     std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
@@ -5325,6 +5667,84 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
     if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "the mask selects no pixel: no cloud for this frame") : rcs[i];
+    return TDLO_OK;
+}
+
+// tracking_step of F trackers on clouds where they lie: tdlo_set_cloud_view_batch into the trackers' slots, enqueued (the registrations wait for the stream
+// before the call returns), then tdlo_tracker_tracking_step_batch
+int tdlo_tracker_tracking_step_view_batch(tdlo_tracker *const *trackers, int F, const tdlo_cloud_view *const *views, const int *N,
+                                          const int *const *visible_nodes, const int *n_vis, const int *const *visible_nodes_extended, const int *n_vis_ext,
+                                          const double *const *H_pre, tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (const char *why = step_batch_sets_fault(F, trackers[0]->M, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext)) return fail(c, TDLO_E_INVALID, why);
+    std::vector<int> slots(F), rcs(F, 0);
+    for (int i = 0; i < F; ++i) slots[i] = trackers[i]->slot;
+    int rc = view_import_batch_impl(c, slots.data(), views, N, F, rcs.data(), false, true);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);          // (whatever was enqueued has left the pinned block before the caller hears of the failure)
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        return rc;
+    }
+    rc = tdlo_tracker_tracking_step_batch(trackers, F, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, H_pre, stats, rc_each);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// The frames of F trackers from clouds where they lie: tdlo_cloud_view_voxel_grid_batch into the trackers' slots, then tdlo_tracker_frame_batch on the trackers
+// that got a cloud (tdlo_tracker_frames_batch with views where it has images)
+int tdlo_tracker_frames_from_cloud_view_batch(tdlo_tracker *const *trackers, int F, const tdlo_view_frame *frames, double leaf_size, double d_vis,
+                                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out,
+                                              tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (!frames) return fail(c, TDLO_E_INVALID, "null frames");
+    const int M = trackers[0]->M;
+    std::vector<tdlo_view_frame> fr(frames, frames + F);
+    for (int i = 0; i < F; ++i) fr[i].slot = trackers[i]->slot;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    int rc = view_voxel_batch_frames(c, fr.data(), F, leaf_size, n.data(), nraw.data(), rcs.data(), true);
+    if (n_out) std::copy(n.begin(), n.end(), n_out);
+    if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+    bool any = false;
+    for (int r : rcs) any = any || r != 0;
+    if (rc && !any) return rc;                     // (refused as a whole: nothing was touched)
+    std::vector<tdlo_tracker *> sub;
+    std::vector<int> who;
+    for (int i = 0; i < F; ++i) {
+        if (!rcs[i] && n[i] == 0) rcs[i] = TDLO_E_EMPTY;      // the view keeps no point: no cloud, the tracker is left as it is
+        if (!rcs[i]) { sub.push_back(trackers[i]); who.push_back(i); }
+    }
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
+    if (!sub.empty()) {
+        const int Fs = (int)sub.size();
+        std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
+        std::vector<tdlo_stats> sst(2 * (size_t)Fs);
+        std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+        const int brc = tdlo_tracker_frame_batch(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data());
+        bool sany = false;
+        for (int r : src) sany = sany || r != 0;
+        for (int k = 0; k < Fs; ++k) {
+            const int i = who[k];
+            rcs[i] = (brc && !sany) ? brc : src[k];
+            nv[i] = snv[k]; ne[i] = sne[k];
+            std::copy(&svis[(size_t)M * k], &svis[(size_t)M * k] + M, &vis[(size_t)M * i]);
+            std::copy(&sext[(size_t)M * k], &sext[(size_t)M * k] + M, &ext[(size_t)M * i]);
+            st[2 * (size_t)i] = sst[2 * (size_t)k]; st[2 * (size_t)i + 1] = sst[2 * (size_t)k + 1];
+        }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "the view keeps no point: no cloud for this frame") : rcs[i];
     return TDLO_OK;
 }
 

@@ -24,8 +24,10 @@
 #include "tdlo_devcommon.h"
 #include "tdlo_view_load.h"
 #include "tdlo_view_lane.h"
+#include "tdlo_view_batch_plan.h"
 #include <cstdint>
 #include <cstdlib>
+#include <vector>
 
 namespace tdlo {
 
@@ -661,8 +663,13 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
 
 // the whole of k_cloud_fused for the frame `a` describes, called by every thread of a workgroup whose blockIdx.x is one of the frame's tiles: the single-frame
 // kernel and the batch kernel (one frame per blockIdx.y) are this body behind two ways of finding the descriptor
-template <bool kColour>
-__device__ __forceinline__ void cloud_fused_body(const FusedCloud &a) {
+// kSrc: the point source of phase A, as k_cloud_team has it (kSrcMask / kSrcColour: the two image kernels; kSrcView with VT / VFORM: one load form of a cloud
+// view; kSrcViewAny: a cloud view whose load form `form` -- kViewForm* -- is the frame's own, decided by a workgroup-uniform switch in front of phase A:
+// k_cloud_view_batch).  Everything behind phase A is the same code.
+enum { kSrcViewAny = 3 };
+enum { kViewFormF64 = 0, kViewFormXyz12 = 1, kViewFormCols2 = 2, kViewFormF32 = 3 };
+template <int kSrc, typename VT = float, int VFORM = kGeneric>
+__device__ __forceinline__ void cloud_fused_body(const FusedCloud &a, [[maybe_unused]] int form = 0) {
     extern __shared__ __attribute__((aligned(16))) char fsm[];
     unsigned *E = (unsigned *)fsm;                                           // kFNmax sort words (through sw(): bank swizzle)
     unsigned *cnt32 = (unsigned *)(fsm + kFLdsE);                            // 32 KB: per (digit, thread) counts as bytes, then start offsets as 16-bit words
@@ -679,7 +686,16 @@ __device__ __forceinline__ void cloud_fused_body(const FusedCloud &a) {
 #endif
 
     // ================= phase A: this tile
-    if (cloud_phase_a<kColour ? kSrcColour : kSrcMask>(a, wtot, &sticket, (unsigned *)fsm) != (unsigned)(a.T - 1)) return;
+    unsigned ticket;
+    if constexpr (kSrc == kSrcViewAny) {
+        switch (form) {                                                      // (the same for every thread of the workgroup: the barriers of phase A are met by all)
+        case kViewFormF64: ticket = cloud_phase_a<kSrcView, double, kGeneric>(a, wtot, &sticket, (unsigned *)fsm); break;
+        case kViewFormXyz12: ticket = cloud_phase_a<kSrcView, float, kXyz12>(a, wtot, &sticket, (unsigned *)fsm); break;
+        case kViewFormCols2: ticket = cloud_phase_a<kSrcView, float, kCols2>(a, wtot, &sticket, (unsigned *)fsm); break;
+        default: ticket = cloud_phase_a<kSrcView, float, kGeneric>(a, wtot, &sticket, (unsigned *)fsm); break;
+        }
+    } else ticket = cloud_phase_a<kSrc, VT, VFORM>(a, wtot, &sticket, (unsigned *)fsm);
+    if (ticket != (unsigned)(a.T - 1)) return;
 
     // ================= phase B: the workgroup with the last ticket
     FSTAMP(0);
@@ -947,7 +963,7 @@ __device__ __forceinline__ void cloud_fused_body(const FusedCloud &a) {
 }
 
 template <bool kColour>
-__global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) { cloud_fused_body<kColour>(a); }
+__global__ __launch_bounds__(kFT) void k_cloud_fused(const FusedCloud a) { cloud_fused_body<kColour ? kSrcColour : kSrcMask>(a); }
 
 // F frames in one launch (tdlo_depth_to_cloud_batch): grid (T, F), blockIdx.y picks the frame's descriptor out of a table in device memory.  Every frame has
 // its own state words, tile regions, compacted points, tile counts, destination and pinned result words, so the frames share nothing: each one's last ticket
@@ -957,7 +973,21 @@ template <bool kColour>
 __global__ __launch_bounds__(kFT) void k_cloud_fused_batch(const FusedCloud *__restrict__ table) {
     const FusedCloud a = table[blockIdx.y];
     if ((int)blockIdx.x >= a.T) return;
-    cloud_fused_body<kColour>(a);
+    cloud_fused_body<kColour ? kSrcColour : kSrcMask>(a);
+}
+
+// F cloud views in one launch (tdlo_cloud_view_voxel_grid_batch): grid (Tmax, F) -- Tmax the tiles of the largest frame --, blockIdx.y picks the frame's record out
+// of a table in device memory: a FusedCloud (its view in vdata / vsp / vsc / vsel; P = the frame's OWN element count, T its own tiles) and the frame's load
+// form.  A workgroup beyond its frame's tiles leaves at once; every frame has its own state words, tile regions, compacted points, tile counts, destination and
+// pinned result words.  As in k_cloud_fused_batch the last-ticket rule of the body is the ONLY hand-over between workgroups: no spin, no barrier across
+// workgroups, no team (k_cloud_team's waits are the thing a batch must not multiply) -- a frame's phase B is one workgroup where the single view call has eight.
+struct ViewBatchFrame { FusedCloud a; int form, pad; };
+__global__ __launch_bounds__(kFT) void k_cloud_view_batch(const ViewBatchFrame *__restrict__ table) {
+    const ViewBatchFrame *f = table + blockIdx.y;
+    const int T = f->a.T;
+    if ((int)blockIdx.x >= T) return;
+    const FusedCloud a = f->a;
+    cloud_fused_body<kSrcViewAny>(a, f->form);
 }
 
 }  // namespace
@@ -1486,6 +1516,47 @@ hipError_t launch_cloud_fused_batch(const CloudBatchFrame *fr, int Fm, int Fc, i
         if (const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_fused_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;
         hipLaunchKernelGGL(k_cloud_fused_batch<true>, dim3(T, Fc), dim3(kFT), kFLds, s, (const FusedCloud *)table_dev + Fm);
     }
+    return hipGetLastError();
+}
+
+// ---- k_cloud_view_batch: where a frame's blocks lie is the host's business (tdlo_view_batch_plan.h); the table is written to pinned memory, copied, read
+size_t view_batch_desc_bytes() { return sizeof(ViewBatchFrame); }
+int view_batch_max_elements() { return kViewBatchMaxN; }
+static_assert(kViewBatchTile == kFPix && kViewBatchPts == kFNmax && kViewBatchMaxN / kFPix <= kFTmax, "tdlo_view_batch_plan.h sizes a frame's blocks by these");
+
+hipError_t view_batch_arm(void *states, int F, hipStream_t s) {
+    std::vector<unsigned> init(64 * (size_t)F, 0u);
+    for (int f = 0; f < F; ++f) init[64 * (size_t)f] = init[64 * (size_t)f + 1] = init[64 * (size_t)f + 2] = ~0u;      // box minima; maxima, tickets: 0
+    if (const hipError_t e = hipMemcpyAsync(states, init.data(), init.size() * sizeof(unsigned), hipMemcpyHostToDevice, s)) return e;
+    return hipStreamSynchronize(s);                           // (init is this function's: the copy has left it)
+}
+
+hipError_t launch_cloud_view_batch(const ViewBatchFrameHost *fr, int F, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev, hipStream_t s) {
+    if (F < 1) return hipErrorInvalidValue;
+    ViewBatchFrame *tab = (ViewBatchFrame *)table_pinned;
+    int Tmax = 0;
+    for (int f = 0; f < F; ++f) {
+        const CloudViewSrc &v = fr[f].src;
+        const int N = fr[f].N;
+        if (N <= 0 || N > kViewBatchMaxN) return hipErrorInvalidValue;
+        ViewBatchFrame b{};
+        FusedCloud &a = b.a;
+        a.vdata = v.data; a.vsp = v.stride_point; a.vsc = v.stride_comp; a.vsel = v.select;
+        a.P = N; a.T = (N + kFPix - 1) / kFPix;
+        a.inv_leaf = inv_leaf;
+        a.ex = (float *)fr[f].tiles; a.ey = a.ex + N; a.ez = a.ey + N;
+        a.state = (unsigned *)fr[f].state;
+        a.cx = (float *)fr[f].pts; a.cy = a.cx + kFNmax; a.cz = a.cy + kFNmax;
+        a.tcnt = (int *)fr[f].tcnt;
+        a.X = fr[f].X; a.cap = fr[f].cap; a.res = fr[f].res; a.epoch = epoch;
+        const int form = cloud_import_form(v.data, v.f64, v.stride_point, v.stride_comp);
+        b.form = v.f64 ? kViewFormF64 : (form == kXyz12 ? kViewFormXyz12 : (form == kCols2 ? kViewFormCols2 : kViewFormF32));
+        tab[f] = b;
+        Tmax = a.T > Tmax ? a.T : Tmax;
+    }
+    if (const hipError_t e = hipMemcpyAsync(table_dev, tab, sizeof(ViewBatchFrame) * (size_t)F, hipMemcpyHostToDevice, s)) return e;
+    if (const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_view_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;      // (per device: see launch_cloud_fused)
+    hipLaunchKernelGGL(k_cloud_view_batch, dim3(Tmax, F), dim3(kFT), kFLds, s, (const ViewBatchFrame *)table_dev);
     return hipGetLastError();
 }
 

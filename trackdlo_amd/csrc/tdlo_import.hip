@@ -25,9 +25,9 @@ namespace tdlo {
 
 namespace {
 
+// what lane i of a frame does: the frame's point i (kCols2: its points 2 i and 2 i + 1); a lane beyond the frame's points does nothing
 template <typename T, int FORM>
-__global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ src, long long sp, long long sc, int N, double *__restrict__ X) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void cloud_import_lane(const T *__restrict__ src, long long sp, long long sc, int N, double *__restrict__ X, long long i) {
     const size_t ld = (size_t)N;
     if constexpr (FORM == kCols2) {
         const long long n = 2 * i;
@@ -51,6 +51,28 @@ __global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ s
     }
 }
 
+template <typename T, int FORM>
+__global__ __launch_bounds__(kBlock) void k_cloud_import(const T *__restrict__ src, long long sp, long long sc, int N, double *__restrict__ X) {
+    cloud_import_lane<T, FORM>(src, sp, sc, N, X, (long long)blockIdx.x * kBlock + threadIdx.x);
+}
+
+// F views in one launch (tdlo_set_cloud_view_batch): grid (blocks of the frame with the most lanes, F), blockIdx.y picks the frame's record out of a table in
+// device memory.  The same lane behind a switch on the frame's form (the same for every thread of the block); a block beyond its frame's lanes leaves.
+// THE RULE holds unchanged: the loaders are the single kernel's, and a lane loads nothing but elements of its own frame's view.
+__global__ __launch_bounds__(kBlock) void k_cloud_import_batch(const ImportBatchFrame *__restrict__ table) {
+    const ImportBatchFrame f = table[blockIdx.y];
+    const long long lanes = f.form == 2 ? ((long long)f.N + 1) / 2 : (long long)f.N;
+    const long long i0 = (long long)blockIdx.x * kBlock;
+    if (i0 >= lanes) return;
+    const long long i = i0 + threadIdx.x;
+    switch (f.form) {
+    case 0: cloud_import_lane<double, kGeneric>((const double *)f.src, f.sp, f.sc, f.N, f.X, i); break;
+    case 1: cloud_import_lane<float, kXyz12>((const float *)f.src, f.sp, f.sc, f.N, f.X, i); break;
+    case 2: cloud_import_lane<float, kCols2>((const float *)f.src, f.sp, f.sc, f.N, f.X, i); break;
+    default: cloud_import_lane<float, kGeneric>((const float *)f.src, f.sp, f.sc, f.N, f.X, i); break;
+    }
+}
+
 }  // namespace
 
 int cloud_import_form(const void *src, bool f64, long long sp, long long sc) {
@@ -71,6 +93,23 @@ hipError_t launch_cloud_import(const void *src, bool f64, long long sp, long lon
     else if (form == kXyz12) hipLaunchKernelGGL((k_cloud_import<float, kXyz12>), grid, block, 0, s, f, sp, sc, N, Xraw);
     else if (form == kCols2) hipLaunchKernelGGL((k_cloud_import<float, kCols2>), grid, block, 0, s, f, sp, sc, N, Xraw);
     else hipLaunchKernelGGL((k_cloud_import<float, kGeneric>), grid, block, 0, s, f, sp, sc, N, Xraw);
+    return hipGetLastError();
+}
+
+hipError_t launch_cloud_import_batch(const ImportBatchFrame *frames, const bool *f64, int F, void *table_pinned, void *table_dev, hipStream_t s) {
+    if (F < 1) return hipErrorInvalidValue;
+    ImportBatchFrame *tab = (ImportBatchFrame *)table_pinned;
+    long long most = 0;
+    for (int f = 0; f < F; ++f) {
+        if (frames[f].N <= 0) return hipErrorInvalidValue;
+        tab[f] = frames[f];
+        const int form = cloud_import_form(frames[f].src, f64[f], frames[f].sp, frames[f].sc);
+        tab[f].form = f64[f] ? 0 : (form == kXyz12 ? 1 : (form == kCols2 ? 2 : 3));
+        const long long lanes = tab[f].form == 2 ? ((long long)frames[f].N + 1) / 2 : (long long)frames[f].N;
+        most = lanes > most ? lanes : most;
+    }
+    if (const hipError_t e = hipMemcpyAsync(table_dev, tab, sizeof(ImportBatchFrame) * (size_t)F, hipMemcpyHostToDevice, s)) return e;
+    hipLaunchKernelGGL(k_cloud_import_batch, dim3((unsigned)((most + kBlock - 1) / kBlock), (unsigned)F), dim3(kBlock), 0, s, (const ImportBatchFrame *)table_dev);
     return hipGetLastError();
 }
 

@@ -336,6 +336,16 @@ hipError_t launch_cloud_fused_batch(const CloudBatchFrame *frames, int Fm, int F
 hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,
                             unsigned epoch, hipStream_t s, const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr,
                             unsigned long long *vis_out_pinned = nullptr);
+// k_cloud_fused over F cloud views in ONE launch (k_cloud_view_batch: grid (tiles of the largest frame, frames); tdlo_cloud_view_voxel_grid_batch).  Per frame:
+// the view as the kernels read it (CloudViewSrc: device memory or pinned host memory), its own N <= view_batch_max_elements(), and blocks of device memory that
+// belong to the frame alone (tdlo_view_batch_plan.h lays them out): 256 bytes of state words (view_batch_arm initialises them; the kernel re-arms them), the
+// tile regions (3 N floats), the compacted points (3 x 32 704 floats), the tile counts; the slot's raw cloud and two pinned words as for
+// launch_cloud_fused_batch.  table_pinned / table_dev: F x view_batch_desc_bytes() bytes each.  Reports 1 done, 2 not taken, 3 capacity.
+struct ViewBatchFrameHost { CloudViewSrc src; int N; void *state, *tiles, *pts, *tcnt; double *X; int cap; unsigned long long *res; };
+size_t view_batch_desc_bytes();
+int view_batch_max_elements();
+hipError_t view_batch_arm(void *states, int F, hipStream_t s);
+hipError_t launch_cloud_view_batch(const ViewBatchFrameHost *frames, int F, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev, hipStream_t s);
 // colour != nullptr above: `mask` is not read, the kernel forms its mask words from the colour image (tdlo_colour_*).  The segmentation on its own
 // (k_colour_mask): mask (rows x cols bytes, 0 / 255) and, when hsv != nullptr, the HSV image (3 bytes a pixel), both device memory padded to 16 bytes beyond the image
 hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s);
@@ -353,6 +363,11 @@ hipError_t launch_render_batch(const RenderBatchImage *images, int K, const int 
 // 1 one 12-byte load per point, 2 column-major pairs -- follows from the strides and the alignment of src only
 int cloud_import_form(const void *src, bool f64, long long stride_point, long long stride_comp);
 hipError_t launch_cloud_import(const void *src, bool f64, long long stride_point, long long stride_comp, int N, double *Xraw, hipStream_t s);
+// ... F views into F clouds in one launch (k_cloud_import_batch: grid (blocks of the frame with the most lanes, F); tdlo_set_cloud_view_batch).  A record of the
+// table: the view as the kernel reads it, its destination, and its load form (written by the launcher: 0 float64, 1 .. 3 float32 by 12-byte points / by
+// column-major pairs / element by element).  table_pinned / table_dev: F x sizeof(ImportBatchFrame) bytes each
+struct ImportBatchFrame { const void *src; long long sp, sc; double *X; int N; int form; };
+hipError_t launch_cloud_import_batch(const ImportBatchFrame *frames, const bool *f64, int F, void *table_pinned, void *table_dev, hipStream_t s);
 // tdlo_image.hip: a frame's device-resident image views -> the packed canonical images, all of them in one launch (k_image_import; tdlo_image.h)
 struct ImageJob;
 hipError_t launch_image_import(const ImageJob &job, hipStream_t s);

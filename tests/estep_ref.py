@@ -15,8 +15,10 @@ reference would take the other branch.
 
 Besides the sums it returns what the gates need: each element's absolute mass (sum of |terms|, distances measured from
 an origin up to `rho` away -- the kernels sum relative to a wave-local origin), the mass weighted by the exponent
-argument of every term, the bound on what a node window of E bits may drop, the mass of points whose discrete decisions
-are within rounding of a tie (fp32 mode), and per-point contributions.
+argument of every term (`wmass`; `cmass`: the same with the cancellation of the normalisation, to first order), the bound on what a node
+window of E bits may drop, the mass of points whose discrete decisions
+are within rounding of a tie (fp32 mode), per-point contributions, and per kept point its nearest node, its pair (lo, hi) and whether
+its whole column underflowed (`near`, `lo`, `hi`, `under`).
 """
 import numpy as np
 
@@ -153,6 +155,8 @@ def estep(X, Y0, Y, sigma2, *, mu, k_vis=0.0, visibility_threshold=0.008, visibl
     coordL = coord.astype(LD)
     acc_sum = _Acc(4 * M + 1); acc_mass = _Acc(4 * M + 1); acc_wmass = _Acc(4 * M + 1); acc_win = _Acc(4 * M + 1); acc_amb = _Acc(4 * M + 1)
     pmax = np.zeros(N); parg = np.zeros(N, dtype=np.int64); rmax = np.zeros(N); qn = np.zeros(N)
+    acc_cmass = _Acc(4 * M + 1)
+    near = np.zeros(N, dtype=np.int64); p_lo = np.zeros(N, dtype=np.int64); p_hi = np.zeros(N, dtype=np.int64); under = np.zeros(N, dtype=bool)
     gap = 0; n_under = 0; n_amb = 0
     B = max(1, chunk_elems // M)
     m_idx = np.arange(M)
@@ -217,6 +221,12 @@ def estep(X, Y0, Y, sigma2, *, mu, k_vis=0.0, visibility_threshold=0.008, visibl
         acc_mass.add(np.concatenate([mP, mR, mR, mR, [mQ]]))
         wP = (P * relw).T.sum(axis=1); wR = (Pd * relw).T.sum(axis=1); wQ = (P * (dist + LD(rho)) ** 2 * relw).sum()
         acc_wmass.add(np.concatenate([wP, wR, wR, wR, [wQ]]))
+        # the same to first order WITH the normalisation's cancellation: relative errors delta_k of a point's unnormalised memberships move
+        # P_m by P_m (delta_m - sum_k P_k delta_k), at most P_m (|delta_m| (1 - P_m) + sum_{k != m} P_k |delta_k|); here |delta_k| = rel_k
+        cw = P * (rel * (LD(1) - LD(2) * P) + (P * rel).sum(axis=1)[:, None])
+        cR = (cw * (dist + LD(rho))).T.sum(axis=1)
+        acc_cmass.add(np.concatenate([cw.T.sum(axis=1), cR, cR, cR, [(cw * (dist + LD(rho)) ** 2).sum()]]))
+        near[s:s + nb] = a; p_lo[s:s + nb] = lo; p_hi[s:s + nb] = hi; under[s:s + nb] = allz
         if win_e is not None:
             pm = P.max(axis=1)
             small = P < pm[:, None] * LD(2.0) ** LD(-win_e)
@@ -236,6 +246,7 @@ def estep(X, Y0, Y, sigma2, *, mu, k_vis=0.0, visibility_threshold=0.008, visibl
     v = acc_sum.value()
     out = dict(P1=v[:M], R=v[M:4 * M].reshape(3, M).T, Q=v[4 * M], N=N, sigma2=s2, coord=coord, vis_branch=vis_branch,
                mass=acc_mass.value(), wmass=acc_wmass.value(), win=acc_win.value(), amb=acc_amb.value(),
+               cmass=acc_cmass.value(), near=near, lo=p_lo, hi=p_hi, under=under,
                pmax=pmax, parg=parg, rmax=rmax, qn=qn, gap_quirk=gap, n_underflow=n_under, n_amb=n_amb, keep=keep)
     out["sums"] = sums_vector(out)
     return out

@@ -10,7 +10,10 @@
 //   * the next batch's coordinates are requested while the current one is worked on.
 // What it computes is the same mathematics as k_estep (same exact candidate pruning of the nearest-node search, same window rule, same
 // 64-bit fixed-point sums, range-checked); the GRAIN of the fp32 tile sums is one wave x one 128-point batch, so its sums are not the bits of
-// k_estep's -- both are held to the oracle at the fp32 mode's gate (1e-5 m, 1e-3 on sigma2), and each is repeatable bit for bit run to run.
+// k_estep's -- each is held, element by element, to the extended-precision sums of tests/estep_ref.py within a gate counted from its own arithmetic
+// (this kernel: gate2 of tests/test_estep_sums_gpu.py, on every branch below -- both searches, the four forms of geo_t, the chunked window, Q's parts,
+// the visibility prologue, the node-0 rule, the last batch), end to end to the oracle at the fp32 mode's gate (1e-5 m, 1e-3 on sigma2:
+// tests/test_estep2_gpu.py), and each is repeatable bit for bit run to run.
 // fp32 mode, chains of 8 .. 64 nodes; everything else stays with k_estep (launch_estep_T, FrameDev::estep2).
 #include "tdlo_devcommon.h"
 #include "tdlo_mstep_generic.h"

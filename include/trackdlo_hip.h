@@ -719,7 +719,7 @@ int tdlo_tracker_frame_from_colour(tdlo_tracker *t, const unsigned short *depth,
  * no ranges on an image without mask, bad tdlo_colour_params, and what the single call refuses of size, leaf and intrinsics.
  *   rc_each (NULL or F codes): a frame that fails on its own (passed on, then refused by the single route) gets its code; the call returns the first one.
  *   Fewer than kCloudBatchMin frames (csrc/tdlo_api.cpp) loop over the single calls: the same bits.  MEASURED (profiles/cloud_batch_ab.txt, rope frames,
- * F = 1 .. 32): from pageable images the batch call wins from 2 frames at 640 x 480 (0.155 against 0.175 ms; 1.40 against 2.82 ms at 32) and from 3 at
+ * F = 1 .. 32): from pageable images the batch call wins from 2 frames at 640 x 480 (0.155 against 0.175 ms; 1.42 against 2.82 ms at 32) and from 3 at
  * 1280 x 720 (3.31 against 4.81 ms at 32); frames that share one image cost 0.19 ms at 32 frames of 640 x 480; but F single calls on the context's pinned
  * image buffers, read in place, beat a batch that copies caller-pinned images up at every F at 1280 x 720 (2.13 against 2.63 ms at 32) and up to 8 frames at
  * 640 x 480.  The rule "every batch value below every single-calls value at both sizes" is met by no F up to 32, so kCloudBatchMin is 33: BY DEFAULT THE
@@ -867,6 +867,59 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
                             double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
                             int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                             int *n_out, int *n_raw_out, tdlo_stats *stats);
+/* ---- image views for many slots in one call ----------------------------------------------------------- */
+/* tdlo_depth_to_cloud_batch for callers who come with image VIEWS: a simulator, renderer or decoder on the same GPU that makes K camera images as one device
+ * tensor ([K, H, W, 4] uint8 and [K, H, W] float32) and steps as many trackers.  An IMAGE is a tdlo_frame_view -- depth, and a mask, or a colour view (with
+ * an optional occluder), or both -- and its intrinsics; FRAMES and their sharing are those of the packed batch: colour_params == NULL takes the image's mask,
+ * otherwise the segmentation is formed from its colour view under these ranges; any number of frames may name one image, each with its own ranges.
+ *   BITS: every slot's cloud, n_out[f] and n_raw_out[f] are those of tdlo_frame_to_cloud_view on that frame alone (i.e. what the packed call computes from
+ * the canonical images of tests/image_view_ref.py), the sign of a zero included, whatever else shares the call and in whatever order.
+ *   PLANES: only views a frame reads are imported, every distinct (data, format, row_stride, role) once, into the arena of the packed batch.  Device views
+ * are written there by ONE launch of k_image_import_batch (csrc/tdlo_image.hip: grid (blocks of an image's lanes, images); a job of its table is one image,
+ * the load form per view as tdlo_image_view_form gives it; no load touches a byte outside a view's extent; no workgroup waits for another), behind one event
+ * per distinct ready_stream.  Host views are packed by the host into one pinned block laid out as their arena region and go up, together with the two tables,
+ * in ONE copy.  Per call, then: at most one copy, one import launch, at most two k_cloud_fused_batch launches and one host wait.
+ *   ROUTES: below the crossover (next paragraph), with TDLO_CLOUD_FUSED off or for an image size the one-launch cloud kernel does not take, the call loops
+ * over tdlo_frame_to_cloud_view.  A frame the cloud kernel passes on (more than 32 704 masked pixels, word-layout limits, pass-through) goes through the
+ * single view call for its slot alone; its code goes to rc_each, and the call returns the first non-zero code.  tdlo_debug_route_count 42 counts the frames
+ * the batch launches served, 43 the frames passed on or looped, 44 the planes k_image_import_batch wrote; 6 / 7 / 15 .. 18 keep counting what the single
+ * route does, and 32 / 33 (the packed batch's) do not move.
+ *   CROSSOVER: kFrameViewBatchMin for this call, kFrameViewBatchTrackerMin for the tracker call (csrc/tdlo_api.cpp), by the rule set beforehand -- the
+ * smallest F from which every batch value lies below every single-calls value on the lines a call stands for, at 640 x 480 and 1280 x 720
+ * (scripts/gpu_frame_view_batch.py -> profiles/frame_view_batch_ab.txt).  MEASURED against F single view calls through the parent commit's library (rope
+ * frames, F = 1 .. 32, five alternating rounds of 20 calls): one frame costs more as a batch (0.075 against 0.044 ms at 640 x 480, 0.142 against 0.057 ms at
+ * 1280 x 720); DEVICE views win on every value from 2 frames at 640 x 480 and from 4 at 1280 x 720 -- 32 RGBA8 + 32FC1 images 0.20 against 1.42 ms and 0.58
+ * against 1.84 ms, bgr8 + 16UC1 the same -- but HOST views, packed and copied up, stay behind single calls that read the context's pinned buffers in place at
+ * every F at 1280 x 720 (32 images 9.6 against 7.3 ms; at 640 x 480 they win at some F and lose at others).  So the rule gives kFrameViewBatchMin = 33:
+ * BY DEFAULT tdlo_frame_views_to_cloud_batch LOOPS OVER THE SINGLE VIEW CALLS, and TDLO_FRAME_VIEW_BATCH_MIN=n (read when the context is made) turns the batch
+ * launches on from n frames -- worth it for callers whose views lie in device memory.  The tracker call (measured on device views) wins on every value from 4
+ * trackers on at both sizes -- 32 trackers 2.13 against 5.69 ms at 640 x 480, 2.29 against 5.74 ms at 1280 x 720 -- so kFrameViewBatchTrackerMin = 4.
+ *   Refused as a whole with TDLO_E_INVALID before anything is touched (resident clouds intact, no counter moved): what tdlo_depth_to_cloud_batch refuses;
+ * per view what tdlo_image_view_check refuses; an occluder without a colour view; a pointer on another GPU; a host view inside the context's pinned image
+ * buffers; a device view that overlaps the batch arena or the resident cloud of any slot the call names.
+ *   NOT DONE HERE (follow-ups): k_cloud_fused_batch reading the views in place, which would save the import's round trip through the arena (the bytes per
+ * call in the profile file are what that decision rests on); the packed batch's device planes through k_image_import_batch; any change to kCloudBatchMin. */
+typedef struct { tdlo_frame_view fv; double fx, fy, cx, cy; } tdlo_view_image;
+int tdlo_frame_views_to_cloud_batch(tdlo_ctx *ctx, const tdlo_view_image *images, int K, int rows, int cols,
+                                    const tdlo_batch_frame *frames, int F, double leaf_size,
+                                    int *n_out /* F */, int *n_raw_out /* F */, int *rc_each /* F or NULL */);
+/* The call above into the trackers' slots (under kFrameViewBatchTrackerMin), then tdlo_tracker_frame_batch on the trackers whose cloud is not empty: the
+ * bits of the two, under tdlo_tracker_frame_batch's stated conditions.  Arguments, outputs, TDLO_E_EMPTY and refusals as for tdlo_tracker_frames_batch. */
+int tdlo_tracker_frame_views_batch(tdlo_tracker *const *trackers, int F, const tdlo_view_image *images, int K, int rows, int cols,
+                                   const int *image_of /* F */, const tdlo_colour_params *const *colour_params /* NULL or F entries, each NULL = mask */,
+                                   double leaf_size, double d_vis,
+                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                   int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each);
+/* The device addresses of image k's canonical planes (tightly packed rows x cols x {2, 3, 1, 1} bytes, 256-byte aligned) in the arena, as the most recent
+ * view batch on the context left them; a plane that call did not import -- no frame read it, or the call looped over the single calls -- is NULL.  Any output
+ * may be NULL.  The pointers are valid until the next batch call (packed or views) on the context.  The colour plane is what a caller who came with RGBA views
+ * hands to tdlo_tracker_render_result_batch, which reads 4-byte aligned device memory in place.  TDLO_E_INVALID: no such call yet, or k out of range. */
+int tdlo_view_batch_images(tdlo_ctx *ctx, int k, const unsigned short **depth, const unsigned char **colour,
+                           const unsigned char **occluder, const unsigned char **mask);
+/* Test aid: where the slot's resident cloud lies in device memory (NULL: none yet) and how many points the block holds (3 x capacity doubles) -- the memory
+ * a device view must not overlap.  Either output may be NULL. */
+int tdlo_debug_slot_cloud(tdlo_ctx *ctx, int slot, const double **X, int *capacity);
+
 /* Test aid: copies out the canonical images the context's last view call left (device buffers or the pinned ones), each to a host buffer that may be
  * NULL.  TDLO_E_INVALID when there was no such call, its shape differs, or an image is asked for that the frame did not have. */
 int tdlo_debug_read_images(tdlo_ctx *ctx, int rows, int cols, unsigned short *depth_out, unsigned char *colour_out, unsigned char *occluder_out,
@@ -1111,6 +1164,9 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * passed on to the single call for their slot -- by the kernel, or by the host (more than 1 048 576 elements, TDLO_CLOUD_FUSED=0); frames of a batch below
  * the crossover count in 21 / 27 / 28 alone.  40 / 41: frames of tdlo_set_cloud_view_batch (tdlo_tracker_tracking_step_view_batch's among them)
  * imported by the batch launch k_cloud_import_batch / by the single route because the batch was smaller than the crossover.
+ * 42 / 43 / 44: frames of tdlo_frame_views_to_cloud_batch (tdlo_tracker_frame_views_batch's among them) served by the batch launches / passed on by the cloud
+ * kernel or looped over the single view calls (a batch below the crossover, TDLO_CLOUD_FUSED=0, an image size the one-launch form does not take) / planes
+ * written by k_image_import_batch (distinct device views a frame reads; host views are not counted).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

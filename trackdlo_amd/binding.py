@@ -104,6 +104,10 @@ class FrameView(C.Structure):
     _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
 
 
+class ViewImage(C.Structure):                      # tdlo_view_image: one image of a view batch -- its views and its camera
+    _fields_ = [("fv", FrameView), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
 # every symbol include/trackdlo_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "tdlo_abi_version", "tdlo_device_count", "tdlo_default_config", "tdlo_create", "tdlo_destroy", "tdlo_last_error",
@@ -132,6 +136,7 @@ SYMBOLS = [
     "tdlo_reg_batch", "tdlo_sort_pts_batch", "tdlo_tracker_initialize_from_cloud_batch", "tdlo_debug_reg_batch_plan",
     "tdlo_cloud_view_voxel_grid_batch", "tdlo_set_cloud_view_batch", "tdlo_tracker_tracking_step_view_batch", "tdlo_tracker_frames_from_cloud_view_batch",
     "tdlo_debug_view_batch_plan",
+    "tdlo_frame_views_to_cloud_batch", "tdlo_tracker_frame_views_batch", "tdlo_view_batch_images", "tdlo_debug_slot_cloud",
 ]
 
 _lib = None
@@ -346,6 +351,11 @@ def load_library(path: str | None = None):
         lib.tdlo_tracker_tracking_step_view_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.tdlo_tracker_frames_from_cloud_view_batch.argtypes = [vp, ci, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.tdlo_debug_view_batch_plan.argtypes = [vp, ci, ci, vp, vp, vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    if hasattr(lib, "tdlo_frame_views_to_cloud_batch"):
+        lib.tdlo_frame_views_to_cloud_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, cd, vp, vp, vp]
+        lib.tdlo_tracker_frame_views_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.tdlo_view_batch_images.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        lib.tdlo_debug_slot_cloud.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(ci)]
     if path is None:
         _lib = lib
     return lib
@@ -641,6 +651,23 @@ def view_batch_plan(N, Fcap):
     return dict(state=o[0][:F].tolist(), tiles=o[1][:F].tolist(), pts=o[2][:F].tolist(), cnt=o[3][:F].tolist(), table=tab.value, total=tot.value)
 
 
+class DevicePlane:
+    """A packed plane at a raw address (one of Context.view_batch_images(k), say) in the shape _batch_plane takes a tensor: what render_result_batch is
+    handed as `colour` by a caller whose colour image exists only as a canonical plane of the batch arena."""
+
+    def __init__(self, address, shape, itemsize=1):
+        self.address, self.shape, self.itemsize = int(address), tuple(int(d) for d in shape), int(itemsize)
+
+    def data_ptr(self):
+        return self.address
+
+    def element_size(self):
+        return self.itemsize
+
+    def is_contiguous(self):
+        return True
+
+
 def _batch_plane(p, dtype, shape, what):
     """(address, owner) of one plane of a batch image: anything numpy takes (host memory), or an object with data_ptr() -- a torch tensor, in host or device
     memory -- which must already be packed, of the right element size and shape."""
@@ -669,6 +696,22 @@ def _batch_images(images):
             setattr(tab[k], name, adr); keep.append(owner)
         tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = (float(v) for v in im["cam"])
     return tab, K, rows, cols, keep
+
+
+def _view_images(images):
+    """tdlo_view_image table of a list of dicts {depth, mask and / or colour (+ occluder), cam: (fx, fy, cx, cy)}, each image an ImageView or anything
+    image_view() takes (or {fv: a FrameView, cam}).  Returns (table, K, rows, cols, owners)."""
+    K = len(images)
+    assert K >= 1
+    tab = (ViewImage * K)(); keep = []
+    for k, im in enumerate(images):
+        fv = im["fv"] if "fv" in im else frame_view(im["depth"], im.get("colour"), im.get("occluder"), im.get("mask"))
+        if keep and (fv.rows, fv.cols) != (keep[0].rows, keep[0].cols):
+            raise ValueError(f"image {k}: the images of a batch have one shape")
+        tab[k].fv = fv
+        tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = (float(v) for v in im["cam"])
+        keep.append(fv)
+    return tab, K, int(keep[0].rows), int(keep[0].cols), keep
 
 
 def _params_address(p):
@@ -1295,6 +1338,41 @@ class Context:
             self._chk(rc)
         return [int(v) for v in n[:F]], [int(v) for v in nraw[:F]], [int(v) for v in rcs[:F]]
 
+    def frame_view_batch_route_counts(self):
+        """[frames served by the view batch's launches, frames passed on or looped, planes k_image_import_batch wrote] (tdlo_debug_route_count 42 / 43 / 44)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (42, 43, 44)]
+
+    def frame_views_to_cloud_batch(self, images, frames, leaf_size, check=True):
+        """tdlo_frame_views_to_cloud_batch: depth_to_cloud_batch from image views where they lie.  images: dicts {depth, mask and / or colour (+ occluder),
+        cam: (fx, fy, cx, cy)}, each image an ImageView or anything image_view() takes (numpy arrays: host memory; objects with
+        __cuda_array_interface__: device memory); frames: (slot, image index, ColourParams or None = the image's mask).  The clouds stay resident in the
+        slots (get_cloud).  Returns (n [F], n_raw [F], codes [F]); raises on the first non-zero code unless check=False."""
+        tab, K, rows, cols, keep = _view_images(images)
+        F = len(frames)
+        fr = (BatchFrame * max(F, 1))()
+        for i, (slot, image, params) in enumerate(frames):
+            fr[i].slot, fr[i].image, fr[i].colour_params = int(slot), int(image), _params_address(params)
+        n = np.zeros(max(F, 1), dtype=np.int32); nraw = np.zeros(max(F, 1), dtype=np.int32); rcs = np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.tdlo_frame_views_to_cloud_batch(self.h, C.cast(tab, C.c_void_p), K, rows, cols, C.cast(fr, C.c_void_p), F, float(leaf_size), _ptr(n), _ptr(nraw),
+                                                      _ptr(rcs))
+        del keep
+        if rc and check:
+            self._chk(rc)
+        return [int(v) for v in n[:F]], [int(v) for v in nraw[:F]], [int(v) for v in rcs[:F]]
+
+    def view_batch_images(self, k):
+        """tdlo_view_batch_images: the device addresses (integers; None: not imported) of image k's canonical planes as the most recent view batch left them
+        in the arena -- a dict {depth, colour, occluder, mask}.  Valid until the next batch call on the context."""
+        p = [C.c_void_p(None) for _ in range(4)]
+        self._chk(self.lib.tdlo_view_batch_images(self.h, int(k), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(p[3])))
+        return dict(zip(("depth", "colour", "occluder", "mask"), (v.value for v in p)))
+
+    def debug_slot_cloud(self, slot):
+        """tdlo_debug_slot_cloud: (device address of the slot's resident cloud or None, the points its block holds)."""
+        p = C.c_void_p(None); cap = C.c_int(0)
+        self._chk(self.lib.tdlo_debug_slot_cloud(self.h, int(slot), C.byref(p), C.byref(cap)))
+        return p.value, cap.value
+
     def depth_to_cloud_visibility(self, slot, depth, mask, fx, fy, cx, cy, leaf_size, Y, visibility_threshold, d_vis, geodesic_coord):
         """One frame of the ROS node up to tracking_step (trackdlo_node.cpp:195-277, :345-360): depth_to_cloud (the cloud stays resident in the slot) and
         the visibility pre-pass of the nodes Y against it, in one launch where the library can (tdlo_depth_to_cloud_visibility).
@@ -1688,6 +1766,25 @@ def frames_batch(trackers, images, image_of, colour_params, leaf_size, d_vis, ch
     rc = trackers[0].ctx.lib.tdlo_tracker_frames_batch(C.cast(tab, C.c_void_p), F, C.cast(itab, C.c_void_p), K, rows, cols, _ptr(io),
                                                        C.cast(cp, C.c_void_p) if cp is not None else None, float(leaf_size), float(d_vis),
                                                        _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
+    del keep
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def frame_views_batch(trackers, images, image_of, colour_params, leaf_size, d_vis, check=True):
+    """tdlo_tracker_frame_views_batch: frames_batch from image views where they lie (images as Context.frame_views_to_cloud_batch takes them).
+    Returns (codes, [visible_nodes], [visible_nodes_extended], n [F], n_raw [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    itab, K, rows, cols, keep = _view_images(images)
+    M = trackers[0].M
+    io = np.ascontiguousarray(image_of, dtype=np.int32)
+    assert len(io) == F and (colour_params is None or len(colour_params) == F)
+    cp = None if colour_params is None else (C.c_void_p * F)(*[_params_address(p) for p in colour_params])
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frame_views_batch(C.cast(tab, C.c_void_p), F, C.cast(itab, C.c_void_p), K, rows, cols, _ptr(io),
+                                                            C.cast(cp, C.c_void_p) if cp is not None else None, float(leaf_size), float(d_vis),
+                                                            _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]

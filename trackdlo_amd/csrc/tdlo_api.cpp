@@ -217,6 +217,16 @@ struct tdlo_ctx {
     int cbat_armed_F = 0, cbat_armed_P = 0;
     int cloud_batch_min = (getenv("TDLO_CLOUD_BATCH_MIN") && atoi(getenv("TDLO_CLOUD_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_CLOUD_BATCH_MIN")) : 0;      // 0: kCloudBatchMin
     long long cbat_route[2] = {0, 0};    // tdlo_debug_route_count 32 / 33: frames served by the batch launch / passed on by it to the single call
+    // image views for F slots in one call (tdlo_frame_views_to_cloud_batch: k_image_import_batch into the same arena, then k_cloud_fused_batch).  Behind the
+    // descriptor table the arena holds the import's job table, in pinned memory behind both the host views' canonical planes as their arena region has them
+    // (one copy brings tables and planes up).  fvbat_planes: per image of the most recent view batch the arena addresses of its canonical planes by role
+    // (depth, colour, occluder, mask; nullptr: not imported) -- tdlo_view_batch_images; emptied by whatever writes the arena next.
+    // TDLO_FRAME_VIEW_BATCH_MIN=n: below n frames the calls loop over the single view calls (0: kFrameViewBatchMin / kFrameViewBatchTrackerMin).
+    // fvbat_route: tdlo_debug_route_count 42 / 43 / 44 -- frames served by the batch launches / passed on or looped / planes k_image_import_batch wrote
+    struct ViewBatchPlanes { const void *p[4]; };
+    std::vector<ViewBatchPlanes> fvbat_planes;
+    int frame_view_batch_min = (getenv("TDLO_FRAME_VIEW_BATCH_MIN") && atoi(getenv("TDLO_FRAME_VIEW_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_FRAME_VIEW_BATCH_MIN")) : 0;
+    long long fvbat_route[3] = {0, 0, 0};
     // cloud views for F slots in one call (tdlo_cloud_view_voxel_grid_batch: k_cloud_view_batch; tdlo_set_cloud_view_batch: k_cloud_import_batch).  wbat_dev: the
     // arena of tdlo_view_batch_plan.h -- [one state block per slot of the context | descriptor table | the frames' blocks] -- grown on demand; the state blocks
     // are armed when wbat_armed says so (the kernel keeps them so; a call that did not complete or a reallocation has them initialised again).  wbat_pin:
@@ -3426,21 +3436,18 @@ constexpr int kCloudBatchMin = 33;
 struct BatchPlanes { bool dev[4] = {false, false, false, false}; };      // depth, mask, colour, occluder
 
 // Everything that refuses the call as a whole; nothing of the context or the slots is touched.  where: per image, where its planes lie.
-static int cloud_batch_refusal(tdlo_ctx *c, const tdlo_batch_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
-                               std::vector<BatchPlanes> &where) {
-    if (!images || !frames || K < 1 || F < 1) return fail(c, TDLO_E_INVALID, "cloud batch: no images / no frames");
+// The part of it that does not depend on how an image is handed over (packed planes, image views).  image(k): what image k has -- depth, mask, colour,
+// fx, fy -- and, behind that, whatever the entrance itself refuses of the image (its planes' locations among it); called for k = 0 .. K - 1 in order.
+struct BatchImageHas { bool depth, mask, colour; double fx, fy; };
+static int cloud_batch_refusal_common(tdlo_ctx *c, bool have_images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                                      const std::function<int(int, BatchImageHas &)> &image) {
+    if (!have_images || !frames || K < 1 || F < 1) return fail(c, TDLO_E_INVALID, "cloud batch: no images / no frames");
     if (F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "cloud batch: more frames than the context has slots");
     if (rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 26)) return fail(c, TDLO_E_INVALID, "bad image");
     if (!(leaf_size > 0)) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
-    where.assign(K, BatchPlanes{});
-    for (int k = 0; k < K; ++k) {
-        const tdlo_batch_image &im = images[k];
-        if (!im.depth || (!im.mask && !im.colour)) return fail(c, TDLO_E_INVALID, "cloud batch: an image needs depth and a mask or a colour image");
-        if (im.fx == 0 || im.fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
-        const void *pl[4] = {im.depth, im.mask, im.colour, im.colour ? im.occluder : nullptr};
-        for (int q = 0; q < 4; ++q)
-            if (pl[q]) { if (int rc = pointer_location(c, pl[q], TDLO_MEM_AUTO, "cloud batch image", &where[k].dev[q])) return rc; }
-    }
+    std::vector<BatchImageHas> has(K);
+    for (int k = 0; k < K; ++k)
+        if (int rc = image(k, has[k])) return rc;
     for (int f = 0; f < F; ++f) {
         const tdlo_batch_frame &fr = frames[f];
         if (fr.slot < 0 || fr.slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
@@ -3449,10 +3456,25 @@ static int cloud_batch_refusal(tdlo_ctx *c, const tdlo_batch_image *images, int 
         if (fr.colour_params) {
             CloudColour cc;
             if (!colour_pack(fr.colour_params, cc)) return fail(c, TDLO_E_INVALID, "tdlo_colour_params: 1 .. 4 ranges");
-            if (!images[fr.image].colour) return fail(c, TDLO_E_INVALID, "cloud batch: colour ranges for an image without a colour image");
-        } else if (!images[fr.image].mask) return fail(c, TDLO_E_INVALID, "cloud batch: no colour ranges for an image without a mask");
+            if (!has[fr.image].colour) return fail(c, TDLO_E_INVALID, "cloud batch: colour ranges for an image without a colour image");
+        } else if (!has[fr.image].mask) return fail(c, TDLO_E_INVALID, "cloud batch: no colour ranges for an image without a mask");
     }
     return TDLO_OK;
+}
+
+static int cloud_batch_refusal(tdlo_ctx *c, const tdlo_batch_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                               std::vector<BatchPlanes> &where) {
+    where.assign(images && K >= 1 ? K : 0, BatchPlanes{});
+    return cloud_batch_refusal_common(c, images != nullptr, K, rows, cols, frames, F, leaf_size, [&](int k, BatchImageHas &h) -> int {
+        const tdlo_batch_image &im = images[k];
+        h = BatchImageHas{im.depth != nullptr, im.mask != nullptr, im.colour != nullptr, im.fx, im.fy};
+        if (!im.depth || (!im.mask && !im.colour)) return fail(c, TDLO_E_INVALID, "cloud batch: an image needs depth and a mask or a colour image");
+        if (im.fx == 0 || im.fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
+        const void *pl[4] = {im.depth, im.mask, im.colour, im.colour ? im.occluder : nullptr};
+        for (int q = 0; q < 4; ++q)
+            if (pl[q]) { if (int rc = pointer_location(c, pl[q], TDLO_MEM_AUTO, "cloud batch image", &where[k].dev[q])) return rc; }
+        return TDLO_OK;
+    });
 }
 
 // one frame of a batch through the single call (a batch below the crossover, a frame the batch launch passed on): device planes are brought to the host
@@ -3483,6 +3505,119 @@ static int cloud_batch_single(tdlo_ctx *c, const tdlo_batch_image &im, const Bat
                                nullptr, &ci);
 }
 
+// What the batch entrances share (tdlo_depth_to_cloud_batch: packed images; tdlo_frame_views_to_cloud_batch: image views): the arena, the arming of the
+// state words, the descriptor table, the launches' place on the stream, the one host wait and the result words.  A frame as this part sees it: its slot,
+// where its canonical planes lie in the arena's plane region (byte offsets; kNoPlane: none), its colour ranges (nullptr: the mask) and its camera.
+constexpr size_t kNoPlane = ~(size_t)0;
+struct CloudBatchIn { int slot; size_t depth, mask, colour, occluder; const tdlo_colour_params *cp; double cam[4]; };
+// the arena of one call: [descriptor table | the entrance's second table (tab2 bytes, may be none) | plane region] in device memory; the same two tables and
+// `tail` bytes of the entrance's own behind them in pinned memory
+struct CloudBatchArena { char *d_tab, *d_tab2, *d_img, *h_tab, *h_tab2, *h_tail; };
+// What an entrance does between the armed arena and the host wait, all on the context's stream: bring the planes into the plane region, upload the table(s),
+// launch.  bf: the frames in launch order (Fm that bring a mask, then Fc that form it from colour), ready for launch_cloud_fused_batch / cloud_fused_batch_table
+using CloudBatchEnqueue = std::function<int(const CloudBatchArena &, const CloudBatchFrame *bf, int Fm, int Fc, float inv_leaf, unsigned epoch)>;
+
+// route: the entrance's two counters (frames served / passed on).  passed: the frames the kernel did not take, for the entrance's single route.
+static int cloud_batch_run(tdlo_ctx *c, const std::vector<CloudBatchIn> &in, int P, double leaf_size, size_t tab2, size_t img_bytes, size_t tail,
+                           const CloudBatchEnqueue &enqueue, long long *route, std::vector<int> &n, std::vector<int> &nraw, std::vector<int> &rcs, std::vector<int> &passed) {
+    const int F = (int)in.size();
+    int rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+    c->fvbat_planes.clear();                                  // (tdlo_view_batch_images: the arena is about to be written)
+    // ---- the arena: F frame blocks; the table(s) and the planes of the images in use
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t fb = cloud_batch_frame_bytes(P), tab = r256(cloud_batch_desc_bytes() * (size_t)F);
+    // (two device blocks: a frame block's place must not depend on what else a call brings -- its state words stay armed from call to call -- so the table
+    // and the planes, whose sizes change with every call, live apart from the frame blocks)
+    if (fb * (size_t)F > c->cbat_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_dev) hipFree(c->cbat_dev);
+        c->cbat_dev = nullptr; c->cbat_dev_cap = 0; c->cbat_armed_F = 0;
+        HIPCHK(c, hipMalloc(&c->cbat_dev, fb * (size_t)F));
+        c->cbat_dev_cap = fb * (size_t)F;
+    }
+    if (tab + tab2 + img_bytes > c->cbat_img_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_img) hipFree(c->cbat_img);
+        c->cbat_img = nullptr; c->cbat_img_cap = 0;
+        HIPCHK(c, hipMalloc(&c->cbat_img, tab + tab2 + img_bytes));
+        c->cbat_img_cap = tab + tab2 + img_bytes;
+    }
+    const size_t pin_need = 2 * sizeof(unsigned long long) * (size_t)F + tab + tab2 + tail;
+    if (pin_need > c->cbat_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_pin) hipHostFree(c->cbat_pin);
+        c->cbat_pin = nullptr; c->cbat_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->cbat_pin, pin_need, hipHostMallocDefault));
+        std::memset(c->cbat_pin, 0, pin_need);
+        c->cbat_pin_cap = pin_need;
+    }
+    char *base = (char *)c->cbat_dev;
+    unsigned long long *res = (unsigned long long *)c->cbat_pin;
+    CloudBatchArena ar;
+    ar.d_tab = (char *)c->cbat_img; ar.d_tab2 = ar.d_tab + tab; ar.d_img = ar.d_tab2 + tab2;
+    ar.h_tab = c->cbat_pin + 2 * sizeof(unsigned long long) * (size_t)F; ar.h_tab2 = ar.h_tab + tab; ar.h_tail = ar.h_tab2 + tab2;
+    std::memset(res, 0, 2 * sizeof(unsigned long long) * (size_t)F);      // (where another F had its table: no word may look like this call's epoch)
+    // ---- the slots: room for a point per masked pixel the kernel takes; whatever was resident is gone from here on
+    for (int f = 0; f < F; ++f) {
+        Slot &s = c->slots[in[f].slot];
+        if ((rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;
+        s.N0 = 0; s.sorted_valid = false;
+    }
+    // ---- state words
+    if (c->cbat_armed_P != P || F > c->cbat_armed_F) {
+        std::vector<void *> blocks(F);
+        for (int f = 0; f < F; ++f) blocks[f] = base + fb * (size_t)f;
+        c->cbat_armed_F = 0;
+        HIPCHK(c, cloud_batch_arm(blocks.data(), F, P, st));
+        c->cbat_armed_F = F; c->cbat_armed_P = P;
+    }
+    // ---- the table: the frames that bring a mask, then the frames that form it from the colour image
+    std::vector<int> order;
+    for (int f = 0; f < F; ++f) if (!in[f].cp) order.push_back(f);
+    const int Fm = (int)order.size();
+    for (int f = 0; f < F; ++f) if (in[f].cp) order.push_back(f);
+    std::vector<CloudBatchFrame> bf(F);
+    for (int j = 0; j < F; ++j) {
+        const CloudBatchIn &fr = in[order[j]];
+        CloudBatchFrame &b = bf[j];
+        b = CloudBatchFrame{};
+        b.depth = (const unsigned short *)(ar.d_img + fr.depth);
+        if (fr.cp) {
+            colour_pack(fr.cp, b.colour);
+            b.colour.colour = (const unsigned char *)(ar.d_img + fr.colour);
+            b.colour.occluder = fr.occluder != kNoPlane ? (const unsigned char *)(ar.d_img + fr.occluder) : nullptr;
+        } else b.mask = (const unsigned char *)(ar.d_img + fr.mask);
+        for (int q = 0; q < 4; ++q) b.cam[q] = fr.cam[q];
+        b.ws = base + fb * (size_t)j;
+        Slot &s = c->slots[fr.slot];
+        b.X = s.Xraw; b.cap = s.cap_points; b.res = res + 2 * (size_t)j;
+    }
+    if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+    const unsigned epoch = c->cloud_epoch;
+    const float leaf = (float)leaf_size, inv = 1.0f / leaf;
+    // ---- the planes, the table(s), the launches: the entrance's
+    if ((rc = enqueue(ar, bf.data(), Fm, F - Fm, inv, epoch))) { c->cbat_armed_F = 0; return rc; }
+    {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { c->cbat_armed_F = 0; HIPCHK(c, e); }
+    }
+    // ---- the frames' words; a frame the kernel did not take goes through the single call for its slot alone
+    for (int j = 0; j < F; ++j) {
+        const int f = order[j];
+        const unsigned long long w0 = __atomic_load_n(res + 2 * (size_t)j, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(res + 2 * (size_t)j + 1, __ATOMIC_RELAXED);
+        const unsigned status = (unsigned)w0;
+        if ((unsigned)(w0 >> 32) != epoch) { c->cbat_armed_F = 0; rcs[f] = fail(c, TDLO_E_HIP, "the stream drained, but a frame of the depth -> cloud batch did not report"); continue; }
+        nraw[f] = (int)(unsigned)(w1 >> 32);
+        if (status == 1u) { n[f] = (int)(unsigned)w1; c->slots[in[f].slot].N0 = n[f]; ++route[0]; }
+        else if (status == 2u) { passed.push_back(f); ++route[1]; }
+        else rcs[f] = fail(c, TDLO_E_HIP, "voxel grid produced more points than the slot holds");
+    }
+    return TDLO_OK;
+}
+
 int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
                               int *n_out, int *n_raw_out, int *rc_each) {
     if (!c) return TDLO_E_INVALID;
@@ -3503,12 +3638,7 @@ int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K
             rcs[f] = cloud_batch_single(c, images[frames[f].image], where[frames[f].image], frames[f], rows, cols, leaf_size, &n[f], &nraw[f]);
         return finish();
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
-    // ---- the arena: F frame blocks; the descriptor table and the planes of the images in use
-    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t fb = cloud_batch_frame_bytes(P), tab = r256(cloud_batch_desc_bytes() * (size_t)F);
+    // ---- the planes of the images in use
     const size_t plane_bytes[4] = {img_depth_bytes(P), img_mask_bytes(P), img_colour_bytes(P), img_occ_bytes(P)}, plane_copy[4] = {2 * (size_t)P, (size_t)P, 3 * (size_t)P, (size_t)P};
     std::vector<char> use(4 * (size_t)K, 0);                  // plane q of image k is read by a frame
     for (int f = 0; f < F; ++f) {
@@ -3531,98 +3661,22 @@ int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K
             at[4 * k + q] = planes[j].off;
         }
     }
-    // (two device blocks: a frame block's place must not depend on what else a call brings -- its state words stay armed from call to call -- so the table
-    // and the planes, whose sizes change with every call, live apart from the frame blocks)
-    if (fb * (size_t)F > c->cbat_dev_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cbat_dev) hipFree(c->cbat_dev);
-        c->cbat_dev = nullptr; c->cbat_dev_cap = 0; c->cbat_armed_F = 0;
-        HIPCHK(c, hipMalloc(&c->cbat_dev, fb * (size_t)F));
-        c->cbat_dev_cap = fb * (size_t)F;
-    }
-    if (tab + img_bytes > c->cbat_img_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cbat_img) hipFree(c->cbat_img);
-        c->cbat_img = nullptr; c->cbat_img_cap = 0;
-        HIPCHK(c, hipMalloc(&c->cbat_img, tab + img_bytes));
-        c->cbat_img_cap = tab + img_bytes;
-    }
-    const size_t pin_need = 2 * sizeof(unsigned long long) * (size_t)F + tab;
-    if (pin_need > c->cbat_pin_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cbat_pin) hipHostFree(c->cbat_pin);
-        c->cbat_pin = nullptr; c->cbat_pin_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->cbat_pin, pin_need, hipHostMallocDefault));
-        std::memset(c->cbat_pin, 0, pin_need);
-        c->cbat_pin_cap = pin_need;
-    }
-    char *base = (char *)c->cbat_dev, *d_tab = (char *)c->cbat_img, *d_img = d_tab + tab;
-    unsigned long long *res = (unsigned long long *)c->cbat_pin;
-    char *h_tab = c->cbat_pin + 2 * sizeof(unsigned long long) * (size_t)F;
-    std::memset(res, 0, 2 * sizeof(unsigned long long) * (size_t)F);      // (where another F had its table: no word may look like this call's epoch)
-    // ---- the slots: room for a point per masked pixel the kernel takes; whatever was resident is gone from here on
+    std::vector<CloudBatchIn> in(F);
     for (int f = 0; f < F; ++f) {
-        Slot &s = c->slots[frames[f].slot];
-        if ((rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;
-        s.N0 = 0; s.sorted_valid = false;
+        const int k = frames[f].image;
+        const tdlo_batch_image &im = images[k];
+        in[f] = CloudBatchIn{frames[f].slot, at[4 * k], at[4 * k + 1], at[4 * k + 2], im.occluder ? at[4 * k + 3] : kNoPlane, frames[f].colour_params, {im.fx, im.fy, im.cx, im.cy}};
     }
-    // ---- state words
-    if (c->cbat_armed_P != P || F > c->cbat_armed_F) {
-        std::vector<void *> blocks(F);
-        for (int f = 0; f < F; ++f) blocks[f] = base + fb * (size_t)f;
-        c->cbat_armed_F = 0;
-        HIPCHK(c, cloud_batch_arm(blocks.data(), F, P, st));
-        c->cbat_armed_F = F; c->cbat_armed_P = P;
-    }
-    // ---- every distinct plane once (device planes device to device: the kernel's loads want the padding behind the image)
-    for (const Plane &pl : planes)
-        HIPCHK(c, hipMemcpyAsync(d_img + pl.off, pl.src, plane_copy[pl.kind], pl.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    // ---- the table: the frames that bring a mask, then the frames that form it from the colour image
-    std::vector<int> order;
-    for (int f = 0; f < F; ++f) if (!frames[f].colour_params) order.push_back(f);
-    const int Fm = (int)order.size();
-    for (int f = 0; f < F; ++f) if (frames[f].colour_params) order.push_back(f);
-    std::vector<CloudBatchFrame> bf(F);
-    for (int j = 0; j < F; ++j) {
-        const tdlo_batch_frame &fr = frames[order[j]];
-        const tdlo_batch_image &im = images[fr.image];
-        const int k = fr.image;
-        CloudBatchFrame &b = bf[j];
-        b = CloudBatchFrame{};
-        b.depth = (const unsigned short *)(d_img + at[4 * k]);
-        if (fr.colour_params) {
-            colour_pack(fr.colour_params, b.colour);
-            b.colour.colour = (const unsigned char *)(d_img + at[4 * k + 2]);
-            b.colour.occluder = im.occluder ? (const unsigned char *)(d_img + at[4 * k + 3]) : nullptr;
-        } else b.mask = (const unsigned char *)(d_img + at[4 * k + 1]);
-        b.cam[0] = im.fx; b.cam[1] = im.fy; b.cam[2] = im.cx; b.cam[3] = im.cy;
-        b.ws = base + fb * (size_t)j;
-        Slot &s = c->slots[fr.slot];
-        b.X = s.Xraw; b.cap = s.cap_points; b.res = res + 2 * (size_t)j;
-    }
-    if (++c->cloud_epoch == 0) ++c->cloud_epoch;
-    const unsigned epoch = c->cloud_epoch;
-    const float leaf = (float)leaf_size, inv = 1.0f / leaf;
-    {
-        const hipError_t e = launch_cloud_fused_batch(bf.data(), Fm, F - Fm, P, cols, inv, epoch, h_tab, d_tab, st);
-        if (e != hipSuccess) { c->cbat_armed_F = 0; HIPCHK(c, e); }
-    }
-    {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { c->cbat_armed_F = 0; HIPCHK(c, e); }
-    }
-    // ---- the frames' words; a frame the kernel did not take goes through the single call for its slot alone
+    hipStream_t st = c->stream;
+    const CloudBatchEnqueue enqueue = [&](const CloudBatchArena &ar, const CloudBatchFrame *bf, int Fm, int Fc, float inv, unsigned epoch) -> int {
+        // every distinct plane once (device planes device to device: the kernel's loads want the padding behind the image)
+        for (const Plane &pl : planes)
+            HIPCHK(c, hipMemcpyAsync(ar.d_img + pl.off, pl.src, plane_copy[pl.kind], pl.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        HIPCHK(c, launch_cloud_fused_batch(bf, Fm, Fc, P, cols, inv, epoch, ar.h_tab, ar.d_tab, st));
+        return TDLO_OK;
+    };
     std::vector<int> passed;
-    for (int j = 0; j < F; ++j) {
-        const int f = order[j];
-        const unsigned long long w0 = __atomic_load_n(res + 2 * (size_t)j, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(res + 2 * (size_t)j + 1, __ATOMIC_RELAXED);
-        const unsigned status = (unsigned)w0;
-        if ((unsigned)(w0 >> 32) != epoch) { c->cbat_armed_F = 0; rcs[f] = fail(c, TDLO_E_HIP, "the stream drained, but a frame of the depth -> cloud batch did not report"); continue; }
-        nraw[f] = (int)(unsigned)(w1 >> 32);
-        if (status == 1u) { n[f] = (int)(unsigned)w1; c->slots[frames[f].slot].N0 = n[f]; ++c->cbat_route[0]; }
-        else if (status == 2u) { passed.push_back(f); ++c->cbat_route[1]; }
-        else rcs[f] = fail(c, TDLO_E_HIP, "voxel grid produced more points than the slot holds");
-    }
+    if ((rc = cloud_batch_run(c, in, P, leaf_size, 0, img_bytes, 0, enqueue, c->cbat_route, n, nraw, rcs, passed))) return rc;
     for (int f : passed)
         rcs[f] = cloud_batch_single(c, images[frames[f].image], where[frames[f].image], frames[f], rows, cols, leaf_size, &n[f], &nraw[f]);
     return finish();
@@ -4459,6 +4513,219 @@ int tdlo_frame_to_cloud_visibility_view(tdlo_ctx *c, int slot, const tdlo_frame_
                                           d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
 }
 
+// ---- image views for F slots in one call (include/trackdlo_hip.h: tdlo_frame_views_to_cloud_batch) ------------------------------------------------
+// From this many frames on the calls are the batch launches; below it they loop over the single view calls (the same bits).  The rule, set beforehand, is the
+// packed batch's: the smallest F from which every batch value lies below every single-calls value on the lines a call stands for, at both image sizes
+// (scripts/gpu_frame_view_batch.py -> profiles/frame_view_batch_ab.txt); the cloud call and the tracker call take separate constants.  33 = off by default.
+// Measured against the parent commit's library: device views win on every value from 2 frames at 640 x 480 and from 4 at 1280 x 720 (32 RGBA8 + 32FC1
+// images 0.20 against 1.42 ms and 0.58 against 1.83 ms), but F host views, packed into the pinned block and copied up, stay behind F single calls that read
+// the context's pinned image buffers in place at 1280 x 720 at every F (9.6 against 7.3 ms at 32) -- what happened to the packed batch -- so the cloud call
+// is OFF by default.  The tracker call (device views) wins on every value from 4 trackers on at both sizes (32 trackers 2.13 against 5.69 ms and 2.29
+// against 5.74 ms).  TDLO_FRAME_VIEW_BATCH_MIN=n, read when the context is made, overrides both.
+constexpr int kFrameViewBatchMin = 33;
+constexpr int kFrameViewBatchTrackerMin = 4;
+static int frame_view_batch_min(const tdlo_ctx *c, bool tracker) {
+    return c->frame_view_batch_min ? c->frame_view_batch_min : (tracker ? kFrameViewBatchTrackerMin : kFrameViewBatchMin);
+}
+
+// [a0, a1) of a checked view
+static void image_view_bytes(const tdlo_image_view *v, int rows, int cols, const char **a0, const char **a1) {
+    long long lo, hi;
+    image_view_span(v, rows, cols, &lo, &hi);
+    *a0 = (const char *)v->data + lo; *a1 = (const char *)v->data + hi;
+}
+
+struct ViewImageWhere { bool dev[4] = {false, false, false, false}; };      // by role: depth, colour, occluder, mask
+
+// Everything that refuses the call as a whole; nothing of the context or the slots is touched.  where: per image, which of its views lie in device memory.
+static int frame_views_batch_refusal(tdlo_ctx *c, const tdlo_view_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                                     std::vector<ViewImageWhere> &where) {
+    where.assign(images && K >= 1 ? K : 0, ViewImageWhere{});
+    int rc = cloud_batch_refusal_common(c, images != nullptr, K, rows, cols, frames, F, leaf_size, [&](int k, BatchImageHas &h) -> int {
+        const tdlo_view_image &im = images[k];
+        const tdlo_image_view *iv[4] = {&im.fv.depth, &im.fv.colour, &im.fv.occluder, &im.fv.mask};
+        h = BatchImageHas{im.fv.depth.data != nullptr, im.fv.mask.data != nullptr, im.fv.colour.data != nullptr, im.fx, im.fy};
+        if (!h.depth || (!h.mask && !h.colour)) return fail(c, TDLO_E_INVALID, "cloud batch: an image needs depth and a mask or a colour image");
+        if (im.fv.occluder.data && !h.colour) return fail(c, TDLO_E_INVALID, "frame view: an occluder goes with a colour image, not with a mask");
+        if (im.fx == 0 || im.fy == 0) return fail(c, TDLO_E_INVALID, "bad leaf size / intrinsics");
+        for (int r = 0; r < 4; ++r) {
+            if (!iv[r]->data) continue;
+            if (const char *why = image_view_fault(iv[r], rows, cols, r)) return fail(c, TDLO_E_INVALID, why);
+            if (int e = pointer_location(c, iv[r]->data, iv[r]->location, "image view", &where[k].dev[r])) return e;
+            const char *a0, *a1;
+            image_view_bytes(iv[r], rows, cols, &a0, &a1);
+            auto hits = [&](const void *p, size_t bytes) { return p && a0 < (const char *)p + bytes && (const char *)p < a1; };
+            if (!where[k].dev[r]) {
+                if (hits(c->img_pin, c->img_pin_cap) || hits(c->col_pin, c->col_pin_cap))
+                    return fail(c, TDLO_E_INVALID, "image view: a host view inside the context's pinned image buffers (hand those to the packed calls)");
+            } else if (hits(c->cbat_dev, c->cbat_dev_cap) || hits(c->cbat_img, c->cbat_img_cap))
+                return fail(c, TDLO_E_INVALID, "frame view batch: a device view overlaps the batch arena");
+        }
+        return TDLO_OK;
+    });
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) {
+        const tdlo_image_view *iv[4] = {&images[k].fv.depth, &images[k].fv.colour, &images[k].fv.occluder, &images[k].fv.mask};
+        for (int r = 0; r < 4; ++r) {
+            if (!iv[r]->data || !where[k].dev[r]) continue;
+            const char *a0, *a1;
+            image_view_bytes(iv[r], rows, cols, &a0, &a1);
+            for (int f = 0; f < F; ++f) {
+                const Slot &s = c->slots[frames[f].slot];
+                const char *x0 = (const char *)s.Xraw, *x1 = x0 + 3 * (size_t)s.cap_points * sizeof(double);
+                if (s.Xraw && a0 < x1 && x0 < a1) return fail(c, TDLO_E_INVALID, "frame view batch: a device view overlaps the resident cloud of a slot the call names");
+            }
+        }
+    }
+    return TDLO_OK;
+}
+
+// tracker: the call stands behind the tracker entrance (frame_view_batch_min)
+static int frame_views_batch_impl(tdlo_ctx *c, const tdlo_view_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                                  int *n_out, int *n_raw_out, int *rc_each, bool tracker) {
+    if (!c) return TDLO_E_INVALID;
+    std::vector<ViewImageWhere> where;
+    int rc = frame_views_batch_refusal(c, images, K, rows, cols, frames, F, leaf_size, where);
+    if (rc) return rc;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    auto finish = [&]() {
+        if (n_out) std::copy(n.begin(), n.end(), n_out);
+        if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int f = 0; f < F; ++f) if (rcs[f]) return rcs[f];
+        return (int)TDLO_OK;
+    };
+    // one frame through the single view call: the views it reads, and no others
+    auto single = [&](int f) {
+        const tdlo_view_image &im = images[frames[f].image];
+        tdlo_frame_view one{};
+        one.depth = im.fv.depth;
+        if (frames[f].colour_params) { one.colour = im.fv.colour; one.occluder = im.fv.occluder; }
+        else one.mask = im.fv.mask;
+        return tdlo_frame_to_cloud_view(c, frames[f].slot, &one, frames[f].colour_params, rows, cols, im.fx, im.fy, im.cx, im.cy, leaf_size, nullptr, 0, &n[f], &nraw[f]);
+    };
+    const int P = rows * cols;
+    if (F < frame_view_batch_min(c, tracker) || !c->cloud_fused_on || !cloud_fused_ok(P)) {
+        c->fvbat_planes.assign(K, tdlo_ctx::ViewBatchPlanes{{nullptr, nullptr, nullptr, nullptr}});      // (a view batch that imported nothing into the arena)
+        for (int f = 0; f < F; ++f) { ++c->fvbat_route[1]; rcs[f] = single(f); }
+        return finish();
+    }
+    // ---- the views the frames read, every distinct (data, format, row_stride, role) once: the host views first (their part of the plane region goes up in
+    // one copy from a pinned block laid out the same), then the device views (written by the import launch)
+    const size_t plane_bytes[4] = {img_depth_bytes(P), img_colour_bytes(P), img_occ_bytes(P), img_mask_bytes(P)};
+    std::vector<char> use(4 * (size_t)K, 0);
+    for (int f = 0; f < F; ++f) {
+        const int k = frames[f].image;
+        use[4 * k + kRoleDepth] = 1;
+        if (frames[f].colour_params) { use[4 * k + kRoleColour] = 1; if (images[k].fv.occluder.data) use[4 * k + kRoleOccluder] = 1; }
+        else use[4 * k + kRoleMask] = 1;
+    }
+    struct Plane { const tdlo_image_view *v; int role; bool dev; size_t off; int image; };
+    std::vector<Plane> planes;
+    std::vector<size_t> at(4 * (size_t)K, kNoPlane);
+    size_t img_bytes = 0, host_bytes = 0;
+    int dev_planes = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int k = 0; k < K; ++k) {
+            const tdlo_image_view *iv[4] = {&images[k].fv.depth, &images[k].fv.colour, &images[k].fv.occluder, &images[k].fv.mask};
+            for (int r = 0; r < 4; ++r) {
+                if (!use[4 * k + r] || where[k].dev[r] != (pass == 1)) continue;
+                size_t j = 0;
+                while (j < planes.size() && !(planes[j].role == r && planes[j].v->data == iv[r]->data && planes[j].v->format == iv[r]->format && planes[j].v->row_stride == iv[r]->row_stride)) ++j;
+                if (j == planes.size()) { planes.push_back(Plane{iv[r], r, pass == 1, img_bytes, k}); img_bytes += plane_bytes[r]; dev_planes += pass; }
+                at[4 * k + r] = planes[j].off;
+            }
+        }
+        if (pass == 0) host_bytes = img_bytes;
+    }
+    // a job of the import launch is one image: the device views it is the first to name
+    std::vector<int> job_of(K, -1);
+    int J = 0;
+    for (const Plane &pl : planes) if (pl.dev && job_of[pl.image] < 0) job_of[pl.image] = J++;
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t tab2 = r256(sizeof(ImageJob) * (size_t)J);
+    std::vector<CloudBatchIn> in(F);
+    for (int f = 0; f < F; ++f) {
+        const int k = frames[f].image;
+        const tdlo_view_image &im = images[k];
+        in[f] = CloudBatchIn{frames[f].slot, at[4 * k + kRoleDepth], at[4 * k + kRoleMask], at[4 * k + kRoleColour],
+                             frames[f].colour_params ? at[4 * k + kRoleOccluder] : kNoPlane, frames[f].colour_params, {im.fx, im.fy, im.cx, im.cy}};
+    }
+    hipStream_t st = c->stream;
+    char *d_img = nullptr;
+    const CloudBatchEnqueue enqueue = [&](const CloudBatchArena &ar, const CloudBatchFrame *bf, int Fm, int Fc, float inv, unsigned epoch) -> int {
+        d_img = ar.d_img;
+        ImageJob *jobs = (ImageJob *)ar.h_tab2;
+        for (int j = 0; j < J; ++j) { jobs[j] = ImageJob{}; jobs[j].P = P; jobs[j].cols = cols; }
+        for (const Plane &pl : planes) {
+            if (!pl.dev) { image_pack_host(pl.v, rows, cols, ar.h_tail + pl.off); continue; }
+            ImageJob &job = jobs[job_of[pl.image]];
+            job.src[pl.role] = ImageSrc{(const unsigned char *)pl.v->data, pl.v->row_stride, pl.v->format, image_import_form(pl.v->data, pl.v->row_stride, cols, pl.v->format)};
+            job.dst[pl.role] = (unsigned char *)ar.d_img + pl.off;
+        }
+        HIPCHK(c, cloud_fused_batch_table(bf, Fm, Fc, P, cols, inv, epoch, ar.h_tab));
+        // the context's stream waits for what the device views' ready_streams hold so far: one event per distinct stream
+        std::vector<void *> seen;
+        for (int k = 0; k < K; ++k) {
+            const tdlo_image_view *iv[4] = {&images[k].fv.depth, &images[k].fv.colour, &images[k].fv.occluder, &images[k].fv.mask};
+            for (int r = 0; r < 4; ++r) {
+                void *rs = iv[r]->ready_stream;
+                if (!use[4 * k + r] || !where[k].dev[r] || !rs || std::find(seen.begin(), seen.end(), rs) != seen.end()) continue;
+                if (seen.size() >= c->wbat_ev.size()) {
+                    hipEvent_t e = nullptr;
+                    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                    c->wbat_ev.push_back(e);
+                }
+                hipEvent_t e = c->wbat_ev[seen.size()];
+                HIPCHK(c, hipEventRecord(e, (hipStream_t)rs));
+                HIPCHK(c, hipStreamWaitEvent(st, e, 0));
+                seen.push_back(rs);
+            }
+        }
+        // ONE copy: the descriptor table, the job table and the host views' planes, which lie behind one another on both sides
+        HIPCHK(c, hipMemcpyAsync(ar.d_tab, ar.h_tab, (size_t)(ar.h_tail - ar.h_tab) + host_bytes, hipMemcpyHostToDevice, st));
+        if (J > 0) {
+            HIPCHK(c, launch_image_import_batch(jobs, J, ar.d_tab2, st));
+            c->fvbat_route[2] += dev_planes;
+        }
+        HIPCHK(c, launch_cloud_fused_batch_tabled(Fm, Fc, P, ar.d_tab, st));
+        return TDLO_OK;
+    };
+    std::vector<int> passed;
+    if ((rc = cloud_batch_run(c, in, P, leaf_size, tab2, img_bytes, host_bytes, enqueue, c->fvbat_route, n, nraw, rcs, passed))) return rc;
+    c->fvbat_planes.assign(K, tdlo_ctx::ViewBatchPlanes{{nullptr, nullptr, nullptr, nullptr}});
+    for (int k = 0; k < K; ++k)
+        for (int r = 0; r < 4; ++r)
+            if (at[4 * k + r] != kNoPlane) c->fvbat_planes[k].p[r] = d_img + at[4 * k + r];
+    for (int f : passed) rcs[f] = single(f);                  // (cloud_batch_run has counted them)
+    return finish();
+}
+
+int tdlo_frame_views_to_cloud_batch(tdlo_ctx *c, const tdlo_view_image *images, int K, int rows, int cols, const tdlo_batch_frame *frames, int F, double leaf_size,
+                                    int *n_out, int *n_raw_out, int *rc_each) {
+    return frame_views_batch_impl(c, images, K, rows, cols, frames, F, leaf_size, n_out, n_raw_out, rc_each, false);
+}
+
+int tdlo_view_batch_images(tdlo_ctx *c, int k, const unsigned short **depth, const unsigned char **colour, const unsigned char **occluder, const unsigned char **mask) {
+    if (!c) return TDLO_E_INVALID;
+    if (c->fvbat_planes.empty()) return fail(c, TDLO_E_INVALID, "tdlo_view_batch_images: no view batch since the arena was last written");
+    if (k < 0 || k >= (int)c->fvbat_planes.size()) return fail(c, TDLO_E_INVALID, "tdlo_view_batch_images: image index out of range");
+    const tdlo_ctx::ViewBatchPlanes &pl = c->fvbat_planes[k];
+    if (depth) *depth = (const unsigned short *)pl.p[kRoleDepth];
+    if (colour) *colour = (const unsigned char *)pl.p[kRoleColour];
+    if (occluder) *occluder = (const unsigned char *)pl.p[kRoleOccluder];
+    if (mask) *mask = (const unsigned char *)pl.p[kRoleMask];
+    return TDLO_OK;
+}
+
+int tdlo_debug_slot_cloud(tdlo_ctx *c, int slot, const double **X, int *capacity) {
+    if (!c) return TDLO_E_INVALID;
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    if (X) *X = c->slots[slot].Xraw;
+    if (capacity) *capacity = c->slots[slot].Xraw ? c->slots[slot].cap_points : 0;
+    return TDLO_OK;
+}
+
 int tdlo_debug_read_images(tdlo_ctx *c, int rows, int cols, unsigned short *depth_out, unsigned char *colour_out, unsigned char *occluder_out,
                            unsigned char *mask_out) {
     if (!c) return TDLO_E_INVALID;
@@ -4671,7 +4938,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 41) return -1;
+    if (!c || which < 0 || which > 44) return -1;
+    if (which >= 42) return c->fvbat_route[which - 42];
     if (which >= 38) return c->wbat_route[which - 38];
     if (which >= 36) return c->ibat_route[which - 36];
     if (which >= 34) return c->rbat_route[which - 34];
@@ -5611,9 +5879,11 @@ int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
 }
 
 // The frames of F trackers from their images: tdlo_depth_to_cloud_batch into the trackers' slots, then tdlo_tracker_frame_batch on the trackers that got a cloud
-int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_batch_image *images, int K, int rows, int cols, const int *image_of,
-                              const tdlo_colour_params *const *colour_params, double leaf_size, double d_vis,
-                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each) {
+// clouds: the entrance's cloud batch call over the frames (frames, n, n_raw, rc_each); cam: the camera of image k, read once the cloud call has accepted the images
+static int tracker_frames_batch_common(tdlo_tracker *const *trackers, int F, const int *image_of, const tdlo_colour_params *const *colour_params,
+                                       const std::function<int(tdlo_ctx *, const tdlo_batch_frame *, int *, int *, int *)> &clouds,
+                                       const std::function<void(int, double *)> &cam, double d_vis,
+                                       int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each) {
     if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
     tdlo_ctx *c = trackers[0]->ctx;
     if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
@@ -5622,7 +5892,7 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
     std::vector<tdlo_batch_frame> fr(F);
     for (int i = 0; i < F; ++i) fr[i] = tdlo_batch_frame{trackers[i]->slot, image_of[i], colour_params ? colour_params[i] : nullptr};
     std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
-    int rc = tdlo_depth_to_cloud_batch(c, images, K, rows, cols, fr.data(), F, leaf_size, n.data(), nraw.data(), rcs.data());
+    int rc = clouds(c, fr.data(), n.data(), nraw.data(), rcs.data());
     if (n_out) std::copy(n.begin(), n.end(), n_out);
     if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
     bool any = false;
@@ -5634,8 +5904,8 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
         if (!rcs[i] && n[i] == 0) rcs[i] = TDLO_E_EMPTY;      // the frame selects no pixel: no cloud, the tracker is left as it is
         if (!rcs[i]) {
             tdlo_tracker *t = trackers[i];
-            const tdlo_batch_image &im = images[image_of[i]];
-            t->frame_cam[0] = im.fx; t->frame_cam[1] = im.fy; t->frame_cam[2] = im.cx; t->frame_cam[3] = im.cy; t->frame_seen = true;
+            cam(image_of[i], t->frame_cam);
+            t->frame_seen = true;
             sub.push_back(t); who.push_back(i);
         }
     }
@@ -5668,6 +5938,27 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "the mask selects no pixel: no cloud for this frame") : rcs[i];
     return TDLO_OK;
+}
+
+int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_batch_image *images, int K, int rows, int cols, const int *image_of,
+                              const tdlo_colour_params *const *colour_params, double leaf_size, double d_vis,
+                              int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each) {
+    return tracker_frames_batch_common(
+        trackers, F, image_of, colour_params,
+        [&](tdlo_ctx *c, const tdlo_batch_frame *fr, int *n, int *nraw, int *rcs) { return tdlo_depth_to_cloud_batch(c, images, K, rows, cols, fr, F, leaf_size, n, nraw, rcs); },
+        [&](int k, double *cam) { cam[0] = images[k].fx; cam[1] = images[k].fy; cam[2] = images[k].cx; cam[3] = images[k].cy; }, d_vis, visible_nodes, n_vis,
+        visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats, rc_each);
+}
+
+// The same from image views: tdlo_frame_views_to_cloud_batch (under the tracker entrance's crossover) into the trackers' slots, then tdlo_tracker_frame_batch
+int tdlo_tracker_frame_views_batch(tdlo_tracker *const *trackers, int F, const tdlo_view_image *images, int K, int rows, int cols, const int *image_of,
+                                   const tdlo_colour_params *const *colour_params, double leaf_size, double d_vis,
+                                   int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each) {
+    return tracker_frames_batch_common(
+        trackers, F, image_of, colour_params,
+        [&](tdlo_ctx *c, const tdlo_batch_frame *fr, int *n, int *nraw, int *rcs) { return frame_views_batch_impl(c, images, K, rows, cols, fr, F, leaf_size, n, nraw, rcs, true); },
+        [&](int k, double *cam) { cam[0] = images[k].fx; cam[1] = images[k].fy; cam[2] = images[k].cx; cam[3] = images[k].cy; }, d_vis, visible_nodes, n_vis,
+        visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats, rc_each);
 }
 
 // tracking_step of F trackers on clouds where they lie: tdlo_set_cloud_view_batch into the trackers' slots, enqueued (the registrations wait for the stream

@@ -1484,8 +1484,7 @@ hipError_t cloud_batch_arm(void *const *frame_ws, int F, int P, hipStream_t s) {
     return hipSuccess;
 }
 
-hipError_t launch_cloud_fused_batch(const CloudBatchFrame *fr, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev,
-                                    hipStream_t s) {
+hipError_t cloud_fused_batch_table(const CloudBatchFrame *fr, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned) {
     const int F = Fm + Fc;
     if (F < 1 || P <= 0 || !cloud_fused_ok(P)) return hipErrorInvalidValue;
     FusedCloud *tab = (FusedCloud *)table_pinned;
@@ -1505,7 +1504,18 @@ hipError_t launch_cloud_fused_batch(const CloudBatchFrame *fr, int Fm, int Fc, i
         a.X = fr[f].X; a.cap = fr[f].cap; a.res = fr[f].res; a.epoch = epoch;
         tab[f] = a;
     }
-    if (const hipError_t e = hipMemcpyAsync(table_dev, tab, sizeof(FusedCloud) * (size_t)F, hipMemcpyHostToDevice, s)) return e;
+    return hipSuccess;
+}
+
+hipError_t launch_cloud_fused_batch(const CloudBatchFrame *fr, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev,
+                                    hipStream_t s) {
+    if (const hipError_t e = cloud_fused_batch_table(fr, Fm, Fc, P, cols, inv_leaf, epoch, table_pinned)) return e;
+    if (const hipError_t e = hipMemcpyAsync(table_dev, table_pinned, sizeof(FusedCloud) * (size_t)(Fm + Fc), hipMemcpyHostToDevice, s)) return e;
+    return launch_cloud_fused_batch_tabled(Fm, Fc, P, table_dev, s);
+}
+
+hipError_t launch_cloud_fused_batch_tabled(int Fm, int Fc, int P, const void *table_dev, hipStream_t s) {
+    if (Fm + Fc < 1 || P <= 0 || !cloud_fused_ok(P)) return hipErrorInvalidValue;
     const int T = (P + kFPix - 1) / kFPix;
     if (Fm > 0) {
         if (const hipError_t e = hipFuncSetAttribute((const void *)k_cloud_fused_batch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;      // (per device: see launch_cloud_fused)

@@ -26,12 +26,36 @@ namespace {
 
 __global__ __launch_bounds__(kBlock) void k_image_import(const ImageJob job) { image_import_lane(job, blockIdx.x * kBlock + threadIdx.x); }
 
+// K images in one launch (tdlo_frame_views_to_cloud_batch): grid (blocks of an image's lanes, jobs), blockIdx.y picks the image's job out of a table in
+// device memory.  A job is one image -- its up to four device sources, each in the form image_import_form chose for it (uniform over the workgroup, so
+// still a scalar branch; it may differ from job to job), and the arena addresses of its canonical planes.  All jobs share P and cols.  The lane is the
+// single kernel's, the rule of this file holds unchanged, and no workgroup waits for another.
+__global__ __launch_bounds__(kBlock) void k_image_import_batch(const ImageJob *__restrict__ table) {
+    image_import_lane(table[blockIdx.y], blockIdx.x * kBlock + threadIdx.x);
+}
+
+bool image_job_ok(const ImageJob &job) {
+    if (job.P <= 0 || job.cols <= 0 || job.P % job.cols) return false;
+    for (int r = 0; r < 4; ++r)
+        if (job.src[r].data && (!job.dst[r] || ((uintptr_t)job.dst[r] & 7u))) return false;
+    return true;
+}
+
 }  // namespace
 
+// jobs: the table as the host wrote it (checked here), table_dev: the same bytes in device memory, uploaded by the caller on stream s before this call
+hipError_t launch_image_import_batch(const ImageJob *jobs, int J, const void *table_dev, hipStream_t s) {
+    if (!jobs || !table_dev || J < 1 || J > 65535) return hipErrorInvalidValue;
+    for (int j = 0; j < J; ++j)
+        if (!image_job_ok(jobs[j]) || jobs[j].P != jobs[0].P || jobs[j].cols != jobs[0].cols) return hipErrorInvalidValue;
+    const long long lanes = ((long long)jobs[0].P + 3) / 4;
+    const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)J), block(kBlock);
+    hipLaunchKernelGGL(k_image_import_batch, grid, block, 0, s, (const ImageJob *)table_dev);
+    return hipGetLastError();
+}
+
 hipError_t launch_image_import(const ImageJob &job, hipStream_t s) {
-    if (job.P <= 0 || job.cols <= 0 || job.P % job.cols) return hipErrorInvalidValue;
-    for (int r = 0; r < 4; ++r)
-        if (job.src[r].data && (!job.dst[r] || ((uintptr_t)job.dst[r] & 7u))) return hipErrorInvalidValue;
+    if (!image_job_ok(job)) return hipErrorInvalidValue;
     const long long lanes = ((long long)job.P + 3) / 4;
     const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock)), block(kBlock);
     hipLaunchKernelGGL(k_image_import, grid, block, 0, s, job);

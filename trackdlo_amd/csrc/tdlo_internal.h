@@ -331,6 +331,10 @@ size_t cloud_batch_desc_bytes();
 hipError_t cloud_batch_arm(void *const *frame_ws, int F, int P, hipStream_t s);
 hipError_t launch_cloud_fused_batch(const CloudBatchFrame *frames, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev,
                                     hipStream_t s);
+// the two halves of the call above for a caller that uploads the table itself, together with other tables and ahead of other work on the stream
+// (tdlo_frame_views_to_cloud_batch): the table written to table_pinned; the launches over the table where the caller's copy put it
+hipError_t cloud_fused_batch_table(const CloudBatchFrame *frames, int Fm, int Fc, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned);
+hipError_t launch_cloud_fused_batch_tabled(int Fm, int Fc, int P, const void *table_dev, hipStream_t s);
 // the team kernel with a cloud view as its point source (k_cloud_team's view instantiations; CloudViewSrc as for the multi-launch form): reports like
 // launch_cloud_fused's team launch -- 1 done, 2 not taken, 3 the slot's capacity `cap` does not hold the result (nothing of Xraw is written), 4 given up
 hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,
@@ -371,5 +375,9 @@ hipError_t launch_cloud_import_batch(const ImportBatchFrame *frames, const bool 
 // tdlo_image.hip: a frame's device-resident image views -> the packed canonical images, all of them in one launch (k_image_import; tdlo_image.h)
 struct ImageJob;
 hipError_t launch_image_import(const ImageJob &job, hipStream_t s);
+// ... the device views of J images of one size in one launch (k_image_import_batch: grid (blocks of an image's lanes, J); tdlo_frame_views_to_cloud_batch).
+// jobs: the table on the host, checked per job as launch_image_import checks its argument; table_dev: the same J x sizeof(ImageJob) bytes in device memory,
+// which the caller has enqueued on s ahead of this call (it travels with the call's descriptor table)
+hipError_t launch_image_import_batch(const ImageJob *jobs, int J, const void *table_dev, hipStream_t s);
 
 }  // namespace tdlo

@@ -742,6 +742,75 @@ int tdlo_tracker_frames_batch(tdlo_tracker *const *trackers, int F, const tdlo_b
                               int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                               int *n_out, int *n_raw_out, tdlo_stats *stats, int *rc_each);
 
+/* ---- one cloud from several cameras: a rig's frames fused in one launch ------------------------------------ */
+/* A work cell with two or three RGB-D cameras wants ONE cloud in ONE common frame for its rope -- a node is then visible as soon as any camera sees it --
+ * where the reference takes one image pair per callback (trackdlo_node.cpp:158).  A RIG is K cameras of one image size; a camera brings its depth image, a
+ * mask or a colour image (with optional occluder and its own ranges), its intrinsics and, optionally, the 3 x 4 matrix that takes its frame to the common one.
+ * The planes are packed and row-major as in the single calls, in host memory or in device memory of the context's GPU (the runtime is asked, as for
+ * tdlo_depth_to_cloud_batch); every distinct plane is copied once per call into the context's batch arena, so that the kernels' loads stay inside memory the
+ * library owns.  Depth is 16UC1 millimetres.
+ *
+ * THE RIG'S POINT LIST R:
+ *   - for k = 0 .. K - 1 in the caller's order, the kept pixels of camera k in row-major order;
+ *   - kept: mask byte != 0; in a colour rig, the segmentation of tdlo_colour_mask under that camera's ranges with its occluder byte;
+ *   - the camera-frame point in double: zd = depth / 1000.0, xd = ((double)j - cx) * zd / fx, yd = ((double)i - cy) * zd / fy (pixel row i, column j) -- the
+ *     arithmetic of trackdlo_node.cpp:219-224 before it is stored as float;
+ *   - cam_to_rig == NULL: the point is ((float)xd, (float)yd, (float)zd), the single call's bits, the sign of a zero included;
+ *   - otherwise, with cam_to_rig = [A | b]: component r is (float)(((A[r][0] * xd + A[r][1] * yd) + A[r][2] * zd) + b[r]), every product and every sum
+ *     rounded to double on its own -- no fused multiply-add -- in this order;
+ *   - a point whose three floats are not all finite is dropped (rule 2 of the view contract);
+ *   - n_raw is the length of R.
+ * The slot's cloud is V(R, leaf) of the view contract above, steps 3 - 12: pass-through, both refusals (8, 9: the slot's cloud untouched), the empty case and
+ * the sign of a zero included.  Two consequences (the heart of tests/test_rig_gpu.py; tests/rig_ref.py is the numpy statement):
+ *   (a) K = 1 with cam_to_rig == NULL is tdlo_depth_to_cloud (or tdlo_colour_depth_to_cloud) bit for bit;
+ *   (b) for any rig, tdlo_cloud_view_voxel_grid on R held as a float32 host array leaves the same cloud bit for bit.
+ * CAMERA ORDER IS PART OF THE CONTRACT: two cameras' points that share a cell are summed in float in list order.  (K calls of tdlo_depth_to_cloud and a
+ * merge are something else: a voxel grid of voxel grids.)
+ * A rig is segmented one way: a camera that brings a mask is segmented by it (its colour fields are not read), a camera without a mask by its colour image
+ * under colour_params; all cameras of a rig the same way.  cam_to_rig need not be a rigid motion.
+ * Refused as a whole with TDLO_E_INVALID before anything is touched (the resident cloud intact): K < 1 or K > 64; K rows cols > 2^26; a camera without depth;
+ * a camera with neither mask nor colour; cameras that mix the two kinds; colour without ranges, or bad ranges; fx or fy equal to 0; an entry of cam_to_rig
+ * that is not finite; a plane in device memory of another GPU; what the single call and V refuse of size and leaf.
+ * Routes (the same bits on each): a rig of up to 4095 tiles -- K x ceil(rows cols / 4096) -- is first handed to the ONE-LAUNCH kernel, k_cloud_team with the
+ * rig as its point source (csrc/tdlo_cloud.hip: tile b is camera b / Tc and fetches that camera's record of a table in device memory; csrc/tdlo_rig_point.h has
+ * the lane's loads and arithmetic, shared with the host): one launch, the counts through pinned memory.  It serves up to 32 704 kept points whose cell-index bits
+ * and rank bits fit 32 (tdlo_debug_route_count 45) and passes everything else on (46) -- more kept points, pass-through, the refusals of 8 and 9, a result the
+ * slot's present capacity does not hold, a team that gave its launch up -- to the multi-launch form over the same element order (element p: camera p / P,
+ * pixel p % P; a colour rig's masks by k_colour_mask per camera into the arena first).  TDLO_CLOUD_FUSED=0, TDLO_CLOUD_TEAM=0 or more than 4095 tiles: the
+ * multi-launch form at once (counted by 46 as well: 45 + 46 are the rigs that reached the kernels).
+ * MEASURED (profiles/rig_ab.txt, scripts/gpu_rig.py; rope frames, K = 1 .. 4, the clouds bit-equal on both sides): three 640 x 480 cameras cost 0.083 ms from
+ * device planes and 0.182 ms from pageable host planes, against 0.83 / 0.64 ms for the composition a caller had before -- R by tdlo_rig_points_host, then
+ * tdlo_cloud_view_voxel_grid -- and 1.88 / 1.68 ms with R formed by numpy; rigs the one launch passes on (more than 32 704 kept pixels: K = 4 at 640 x 480,
+ * K >= 2 at 1280 x 720) take 0.6 - 1.4 ms on the multi-launch form, against 1.22 - 4.0 ms for the composition. */
+typedef struct { const unsigned short *depth; const unsigned char *mask;      /* mask, or: */
+                 const unsigned char *colour; const unsigned char *occluder;  /* colour (+ optional occluder) */
+                 const tdlo_colour_params *colour_params;                     /* with colour: this camera's ranges */
+                 double fx, fy, cx, cy;
+                 const double *cam_to_rig;  /* NULL, or 12 doubles: 3 x 4 row-major [A | b], camera frame -> common frame */
+               } tdlo_rig_camera;
+int tdlo_rig_to_cloud(tdlo_ctx *ctx, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size,
+                      double *X_out, int x_capacity, int *n_out, int *n_raw_out);
+/* tdlo_depth_to_cloud_visibility for a rig: tdlo_rig_to_cloud into `slot` (no X_out) followed by tdlo_visibility_prepass of the nodes Y against the cloud it
+ * left, the outputs of the two calls bit for bit.  With M <= 64, the one-launch kernel serving the rig and TDLO_DIRECT_UPLOAD on, the pre-pass rides in that
+ * launch (tdlo_debug_route_count 47); otherwise the two steps run one behind the other.  A rig that keeps no pixel: TDLO_OK, *n_out = *n_vis = *n_vis_ext = 0. */
+int tdlo_rig_to_cloud_visibility(tdlo_ctx *ctx, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size,
+                                 const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                 double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                 int *n_out, int *n_raw_out);
+/* A whole frame from a rig: tdlo_rig_to_cloud_visibility with the tracker's own nodes, threshold and geodesic coordinates, then tdlo_tracker_tracking_step on
+ * the cloud left in the tracker's slot, as tdlo_tracker_frame_from_depth composes its two -- the bits of the calls made by hand.  An empty cloud or no visible
+ * node is TDLO_E_EMPTY with the tracker untouched.  A tracker whose self-occlusion switch is on (tdlo_tracker_set_self_occlusion) is refused with
+ * TDLO_E_INVALID: that test is one camera's, and for a rig it is undefined.  A refused rig leaves tracker and slot as they were. */
+int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size, double d_vis,
+                                int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                int *n_out, int *n_raw_out, tdlo_stats *stats);
+/* The host half (csrc/tdlo_rig_host.cpp; no context, no GPU).  tdlo_rig_check: TDLO_E_INVALID for what refuses a rig call as a whole (the list above, the
+ * planes' locations apart).  tdlo_rig_points_host: R of a rig whose planes lie in HOST memory, as float32 x y z per point, through the very header the kernel
+ * compiles (csrc/tdlo_rig_point.h) -- to pre-compute or inspect R, and the composition (b).  Up to `capacity` points are written (R_out may be NULL:
+ * count only); *n_raw_out is the length of R; TDLO_E_INVALID when R_out is too short, or the rig is refused. */
+int tdlo_rig_check(const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size);
+int tdlo_rig_points_host(const tdlo_rig_camera *cams, int K, int rows, int cols, float *R_out, int capacity, int *n_raw_out);
+
 /* ---- cloud views for many slots in one call ----------------------------------------------------------- */
 /* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
  * views become the resident clouds of F slots in one call -- down-sampled (tdlo_cloud_view_voxel_grid_batch) or as they are (tdlo_set_cloud_view_batch).
@@ -1167,6 +1236,9 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 42 / 43 / 44: frames of tdlo_frame_views_to_cloud_batch (tdlo_tracker_frame_views_batch's among them) served by the batch launches / passed on by the cloud
  * kernel or looped over the single view calls (a batch below the crossover, TDLO_CLOUD_FUSED=0, an image size the one-launch form does not take) / planes
  * written by k_image_import_batch (distinct device views a frame reads; host views are not counted).
+ * 45 / 46 / 47: rigs (tdlo_rig_to_cloud, tdlo_rig_to_cloud_visibility, tdlo_tracker_frame_from_rig) served by the one-launch kernel / passed on by it to the
+ * multi-launch form (a team that gave up, and the rigs the host never hands to the kernel -- more than 4095 tiles, TDLO_CLOUD_FUSED=0, TDLO_CLOUD_TEAM=0 --
+ * included) / whose visibility pre-pass rode in that launch.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -95,6 +95,11 @@ class BatchFrame(C.Structure):                     # tdlo_batch_frame: a slot, t
     _fields_ = [("slot", C.c_int), ("image", C.c_int), ("colour_params", C.c_void_p)]
 
 
+class RigCameraC(C.Structure):                     # tdlo_rig_camera: one camera of a rig -- its planes (host or device pointers), ranges, intrinsics, transform
+    _fields_ = [("depth", C.c_void_p), ("mask", C.c_void_p), ("colour", C.c_void_p), ("occluder", C.c_void_p), ("colour_params", C.c_void_p),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("cam_to_rig", C.c_void_p)]
+
+
 class ViewFrame(C.Structure):                      # tdlo_view_frame: a slot, the cloud view it takes, its N and selection bytes (NULL: every element)
     _fields_ = [("slot", C.c_int), ("view", C.c_void_p), ("N", C.c_int), ("select", C.c_void_p)]
 
@@ -137,6 +142,7 @@ SYMBOLS = [
     "tdlo_cloud_view_voxel_grid_batch", "tdlo_set_cloud_view_batch", "tdlo_tracker_tracking_step_view_batch", "tdlo_tracker_frames_from_cloud_view_batch",
     "tdlo_debug_view_batch_plan",
     "tdlo_frame_views_to_cloud_batch", "tdlo_tracker_frame_views_batch", "tdlo_view_batch_images", "tdlo_debug_slot_cloud",
+    "tdlo_rig_to_cloud", "tdlo_rig_to_cloud_visibility", "tdlo_tracker_frame_from_rig", "tdlo_rig_check", "tdlo_rig_points_host",
 ]
 
 _lib = None
@@ -336,6 +342,12 @@ def load_library(path: str | None = None):
     if hasattr(lib, "tdlo_depth_to_cloud_batch"):
         lib.tdlo_depth_to_cloud_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, cd, vp, vp, vp]
         lib.tdlo_tracker_frames_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "tdlo_rig_to_cloud"):
+        lib.tdlo_rig_to_cloud.argtypes = [vp, ci, vp, ci, ci, ci, cd, vp, ci, C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_rig_to_cloud_visibility.argtypes = [vp, ci, vp, ci, ci, ci, cd, vp, ci, cd, cd, vp, vp, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_tracker_frame_from_rig.argtypes = [vp, vp, ci, ci, ci, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
+        lib.tdlo_rig_check.argtypes = [vp, ci, ci, ci, cd]
+        lib.tdlo_rig_points_host.argtypes = [vp, ci, ci, ci, vp, ci, C.POINTER(ci)]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -698,6 +710,67 @@ def _batch_images(images):
     return tab, K, rows, cols, keep
 
 
+class RigCamera:
+    """One camera of a rig (tdlo_rig_camera): depth [rows x cols] uint16 millimetres; mask [rows x cols] uint8, or colour [rows x cols x 3] uint8 with
+    params (a ColourParams: this camera's ranges) and an optional occluder [rows x cols] uint8; cam = (fx, fy, cx, cy); cam_to_rig None or a 3 x 4 matrix (or its 12 entries row by row)
+    [A | b] that takes the camera's frame to the common one.  Planes: numpy arrays (host memory), or anything with data_ptr() -- a packed torch tensor in
+    host or device memory."""
+
+    def __init__(self, depth, mask=None, colour=None, params: "ColourParams" = None, occluder=None, cam=(1.0, 1.0, 0.0, 0.0), cam_to_rig=None):
+        self.depth, self.mask, self.colour, self.params, self.occluder = depth, mask, colour, params, occluder
+        self.cam = tuple(float(v) for v in cam)
+        self.cam_to_rig = None
+        if cam_to_rig is not None:
+            T = np.asarray(cam_to_rig, dtype=np.float64)
+            if T.shape not in ((3, 4), (12, )):                      # (nothing is cut out of a larger matrix)
+                raise ValueError("cam_to_rig: a 3 x 4 matrix [A | b], or its 12 entries row by row")
+            self.cam_to_rig = np.ascontiguousarray(T).reshape(12).copy()
+
+
+def _rig_cameras(cams):
+    """tdlo_rig_camera table of a list of RigCamera.  Returns (table, K, rows, cols, owners)."""
+    cams = list(cams)
+    K = len(cams)
+    if K < 1:
+        raise ValueError("a rig has at least one camera")
+    rows, cols = (int(v) for v in cams[0].depth.shape)
+    tab = (RigCameraC * K)(); keep = []
+    for k, cm in enumerate(cams):
+        for name, dt, shape in (("depth", np.uint16, (rows, cols)), ("mask", np.uint8, (rows, cols)), ("colour", np.uint8, (rows, cols, 3)),
+                                ("occluder", np.uint8, (rows, cols))):
+            adr, owner = _batch_plane(getattr(cm, name), dt, shape, f"camera {k}: {name}")
+            setattr(tab[k], name, adr); keep.append(owner)
+        tab[k].colour_params = _params_address(cm.params)
+        tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = cm.cam
+        tab[k].cam_to_rig = None if cm.cam_to_rig is None else cm.cam_to_rig.ctypes.data
+        keep.append(cm)
+    return tab, K, rows, cols, keep
+
+
+def rig_check(cams, leaf_size=0.008) -> int:
+    """tdlo_rig_check: TDLO_OK, or TDLO_E_INVALID for a rig that every rig call refuses as a whole (no context, no GPU)."""
+    tab, K, rows, cols, keep = _rig_cameras(cams)
+    return int(load_library().tdlo_rig_check(C.cast(tab, C.c_void_p), K, rows, cols, float(leaf_size)))
+
+
+def rig_points_host(cams):
+    """tdlo_rig_points_host: the rig's point list R [n_raw x 3] float32 -- camera after camera, kept pixels in row-major order, back-projected in double,
+    taken to the common frame product by product, rounded to float, non-finite points dropped -- formed on the host through the header the kernel compiles.
+    The planes must be host memory."""
+    tab, K, rows, cols, keep = _rig_cameras(cams)
+    lib = load_library()
+    n = C.c_int(0)
+    rc = lib.tdlo_rig_points_host(C.cast(tab, C.c_void_p), K, rows, cols, None, 0, C.byref(n))
+    if rc:
+        raise TdloError(rc, "tdlo_rig_points_host: the rig is refused")
+    R = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+    rc = lib.tdlo_rig_points_host(C.cast(tab, C.c_void_p), K, rows, cols, R.ctypes.data, n.value, C.byref(n))
+    if rc:
+        raise TdloError(rc, "tdlo_rig_points_host")
+    del keep
+    return R[:n.value]
+
+
 def _view_images(images):
     """tdlo_view_image table of a list of dicts {depth, mask and / or colour (+ occluder), cam: (fx, fy, cx, cy)}, each image an ImageView or anything
     image_view() takes (or {fv: a FrameView, cam}).  Returns (table, K, rows, cols, owners)."""
@@ -863,6 +936,38 @@ class Context:
                                                                  C.byref(n), C.byref(nraw)))
         self._async_src = None
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
+    def rig_to_cloud(self, slot, cams, leaf_size, *, fetch=True):
+        """One cloud from the images of a rig's K cameras (tdlo_rig_to_cloud; cams: RigCamera objects of one image size, in the order their points are
+        summed): the voxel grid over the rig's point list into the slot's resident cloud.  Returns (X [n x 3] or None, n, n_raw)."""
+        tab, K, rows, cols, keep = _rig_cameras(cams)
+        n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_rig_to_cloud(self.h, slot, C.cast(tab, C.c_void_p), K, rows, cols, float(leaf_size), None, 0, C.byref(n), C.byref(nraw)))
+        del keep
+        return (self.get_cloud(slot) if fetch else None), n.value, nraw.value
+
+    def rig_to_cloud_visibility(self, slot, cams, leaf_size, Y, visibility_threshold, d_vis, geodesic_coord):
+        """rig_to_cloud into the slot and the visibility pre-pass of the nodes Y against the cloud it left, in one launch where the library can
+        (tdlo_rig_to_cloud_visibility).  Returns (node_dist, visible_nodes, visible_nodes_extended, n, n_raw)."""
+        tab, K, rows, cols, keep = _rig_cameras(cams)
+        Y = _f64(Y); M = Y.shape[0]
+        coord = np.ascontiguousarray(geodesic_coord, dtype=np.float64)
+        dist = np.zeros(M); vis = np.zeros(M, dtype=np.int32); ext = np.zeros(M, dtype=np.int32)
+        nv = C.c_int(0); ne = C.c_int(0); n = C.c_int(0); nraw = C.c_int(0)
+        self._chk(self.lib.tdlo_rig_to_cloud_visibility(self.h, slot, C.cast(tab, C.c_void_p), K, rows, cols, float(leaf_size), _ptr(Y), M, float(visibility_threshold),
+                                                        float(d_vis), _ptr(coord), _ptr(dist), _ptr(vis), C.byref(nv), _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
+        del keep
+        return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
+
+    def rig_route_counts(self):
+        """[rigs served by the one-launch kernel, rigs it passed on to the multi-launch form, rigs whose visibility pre-pass rode in the launch]
+        (tdlo_debug_route_count 45 / 46 / 47)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (45, 46, 47)]
+
+    @staticmethod
+    def rig_points_host(cams):
+        """The rig's point list R on the host (module function rig_points_host)."""
+        return rig_points_host(cams)
 
     def set_cloud_view_batch(self, slots, objs, ready_stream=None, check=True):
         """tdlo_set_cloud_view_batch: the clouds of F slots from F views where they lie, imported as they are in one launch (objs: CloudViews or anything
@@ -1634,6 +1739,22 @@ class trackdlo:
         rc = self.ctx.lib.tdlo_tracker_frame_from_cloud_view(self.h, C.byref(cv), N, sp, leaf_size, d_vis,
                                                              v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
         self._stats_raw = self._st
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def frame_from_rig(self, cams, leaf_size=0.008, d_vis=0.06):
+        """A frame from the images of a rig's cameras (tdlo_tracker_frame_from_rig): Context.rig_to_cloud_visibility with the tracker's nodes into its slot,
+        tracking_step on the resident cloud.  Refused with the self-occlusion switch on.
+        Returns (visible_nodes, visible_nodes_extended, n, n_raw); the nodes: get_tracking_result()."""
+        tab, K, rows, cols, keep = _rig_cameras(cams)
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        rc = self.ctx.lib.tdlo_tracker_frame_from_rig(self.h, C.cast(tab, C.c_void_p), K, rows, cols, leaf_size, d_vis,
+                                                      v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr)
+        self._stats_raw = self._st
+        del keep
         if rc:
             self.ctx._chk(rc)
         return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value

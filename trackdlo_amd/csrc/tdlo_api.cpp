@@ -7,6 +7,7 @@
 #include "tdlo_image.h"
 #include "tdlo_rccl.h"
 #include "tdlo_reg_plan.h"
+#include "tdlo_rig_host.h"
 #include "tdlo_view_batch_plan.h"
 
 #include <algorithm>
@@ -241,6 +242,7 @@ struct tdlo_ctx {
     std::vector<hipEvent_t> wbat_ev;
     int view_batch_min = (getenv("TDLO_VIEW_BATCH_MIN") && atoi(getenv("TDLO_VIEW_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_VIEW_BATCH_MIN")) : 0;
     long long wbat_route[4] = {0, 0, 0, 0};
+    long long rig_route[3] = {0, 0, 0};         // tdlo_debug_route_count 45 / 46 / 47: rigs (tdlo_rig_to_cloud) served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -2822,21 +2824,10 @@ struct ColourIn { const unsigned char *colour; const tdlo_colour_params *params;
 
 // tdlo_colour_params as the kernels take it: bounds clamped to 0 .. 255 and packed H | S << 8 | V << 16, upper - lower per channel beside them; a range
 // whose lower bound lies above its upper bound on a channel passes nothing and is left out
+// (the rule itself is colour_ranges_pack, tdlo_rig_host.cpp: HIP-free, so that the host half of a rig packs by the same statement)
 static bool colour_pack(const tdlo_colour_params *p, CloudColour &cc) {
-    if (!p || p->n_ranges < 1 || p->n_ranges > 4) return false;
     cc = CloudColour{};
-    cc.rgb = p->rgb_order ? 1 : 0;
-    for (int k = 0; k < p->n_ranges; ++k) {
-        unsigned lo = 0, sp = 0;
-        bool empty = false;
-        for (int ch = 0; ch < 3; ++ch) {
-            const int l = std::min(std::max(p->lower[k][ch], 0), 255), u = std::min(std::max(p->upper[k][ch], 0), 255);
-            if (l > u) empty = true;
-            lo |= (unsigned)l << (8 * ch); sp |= (unsigned)(u - l) << (8 * ch);
-        }
-        if (!empty) { cc.lo[cc.n] = lo; cc.span[cc.n] = sp; ++cc.n; }
-    }
-    return true;
+    return colour_ranges_pack(p, cc.lo, cc.span, &cc.n, &cc.rgb);
 }
 
 int tdlo_colour_buffers(tdlo_ctx *c, int rows, int cols, unsigned char **colour, unsigned char **occluder) {
@@ -3517,6 +3508,51 @@ struct CloudBatchArena { char *d_tab, *d_tab2, *d_img, *h_tab, *h_tab2, *h_tail;
 // launch.  bf: the frames in launch order (Fm that bring a mask, then Fc that form it from colour), ready for launch_cloud_fused_batch / cloud_fused_batch_table
 using CloudBatchEnqueue = std::function<int(const CloudBatchArena &, const CloudBatchFrame *bf, int Fm, int Fc, float inv_leaf, unsigned epoch)>;
 
+// the arena's table-and-plane block in device memory and its pinned block, grown on demand (the cloud batch's entrances and the rig calls: whoever comes
+// next writes both from their start)
+static int ensure_batch_arena(tdlo_ctx *c, size_t dev_bytes, size_t pin_bytes) {
+    hipStream_t st = c->stream;
+    if (dev_bytes > c->cbat_img_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_img) hipFree(c->cbat_img);
+        c->cbat_img = nullptr; c->cbat_img_cap = 0;
+        HIPCHK(c, hipMalloc(&c->cbat_img, dev_bytes));
+        c->cbat_img_cap = dev_bytes;
+    }
+    if (pin_bytes > c->cbat_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cbat_pin) hipHostFree(c->cbat_pin);
+        c->cbat_pin = nullptr; c->cbat_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->cbat_pin, pin_bytes, hipHostMallocDefault));
+        std::memset(c->cbat_pin, 0, pin_bytes);
+        c->cbat_pin_cap = pin_bytes;
+    }
+    return TDLO_OK;
+}
+
+// the packed planes a call brings into the arena's plane region: every distinct (pointer, kind) once -- kind: 0 depth, 1 mask, 2 colour, 3 occluder -- each in
+// a padded place of its own (the kernels' loads run up to 16 bytes beyond an image); device planes are copied device to device
+struct BatchPlaneSet {
+    struct Plane { const void *src; int kind; size_t off; bool dev; };
+    std::vector<Plane> planes;
+    size_t bytes = 0;
+    size_t add(const void *src, int kind, bool dev, size_t P) {      // the plane's byte offset in the plane region
+        size_t j = 0;
+        while (j < planes.size() && !(planes[j].src == src && planes[j].kind == kind)) ++j;
+        if (j == planes.size()) {
+            planes.push_back(Plane{src, kind, bytes, dev});
+            bytes += kind == 0 ? img_depth_bytes(P) : kind == 1 ? img_mask_bytes(P) : kind == 2 ? img_colour_bytes(P) : img_occ_bytes(P);
+        }
+        return planes[j].off;
+    }
+};
+static int batch_planes_copy(tdlo_ctx *c, const BatchPlaneSet &set, char *d_img, size_t P) {
+    const size_t plane_copy[4] = {2 * P, P, 3 * P, P};
+    for (const BatchPlaneSet::Plane &pl : set.planes)
+        HIPCHK(c, hipMemcpyAsync(d_img + pl.off, pl.src, plane_copy[pl.kind], pl.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    return TDLO_OK;
+}
+
 // route: the entrance's two counters (frames served / passed on).  passed: the frames the kernel did not take, for the entrance's single route.
 static int cloud_batch_run(tdlo_ctx *c, const std::vector<CloudBatchIn> &in, int P, double leaf_size, size_t tab2, size_t img_bytes, size_t tail,
                            const CloudBatchEnqueue &enqueue, long long *route, std::vector<int> &n, std::vector<int> &nraw, std::vector<int> &rcs, std::vector<int> &passed) {
@@ -3538,22 +3574,7 @@ static int cloud_batch_run(tdlo_ctx *c, const std::vector<CloudBatchIn> &in, int
         HIPCHK(c, hipMalloc(&c->cbat_dev, fb * (size_t)F));
         c->cbat_dev_cap = fb * (size_t)F;
     }
-    if (tab + tab2 + img_bytes > c->cbat_img_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cbat_img) hipFree(c->cbat_img);
-        c->cbat_img = nullptr; c->cbat_img_cap = 0;
-        HIPCHK(c, hipMalloc(&c->cbat_img, tab + tab2 + img_bytes));
-        c->cbat_img_cap = tab + tab2 + img_bytes;
-    }
-    const size_t pin_need = 2 * sizeof(unsigned long long) * (size_t)F + tab + tab2 + tail;
-    if (pin_need > c->cbat_pin_cap) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->cbat_pin) hipHostFree(c->cbat_pin);
-        c->cbat_pin = nullptr; c->cbat_pin_cap = 0;
-        HIPCHK(c, hipHostMalloc((void **)&c->cbat_pin, pin_need, hipHostMallocDefault));
-        std::memset(c->cbat_pin, 0, pin_need);
-        c->cbat_pin_cap = pin_need;
-    }
+    if ((rc = ensure_batch_arena(c, tab + tab2 + img_bytes, 2 * sizeof(unsigned long long) * (size_t)F + tab + tab2 + tail))) return rc;
     char *base = (char *)c->cbat_dev;
     unsigned long long *res = (unsigned long long *)c->cbat_pin;
     CloudBatchArena ar;
@@ -3639,7 +3660,6 @@ int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K
         return finish();
     }
     // ---- the planes of the images in use
-    const size_t plane_bytes[4] = {img_depth_bytes(P), img_mask_bytes(P), img_colour_bytes(P), img_occ_bytes(P)}, plane_copy[4] = {2 * (size_t)P, (size_t)P, 3 * (size_t)P, (size_t)P};
     std::vector<char> use(4 * (size_t)K, 0);                  // plane q of image k is read by a frame
     for (int f = 0; f < F; ++f) {
         const int k = frames[f].image;
@@ -3647,20 +3667,14 @@ int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K
         if (frames[f].colour_params) { use[4 * k + 2] = 1; if (images[k].occluder) use[4 * k + 3] = 1; }
         else use[4 * k + 1] = 1;
     }
-    struct Plane { const void *src; int kind; size_t off; bool dev; };
-    std::vector<Plane> planes;                                // every distinct (pointer, kind) once
+    BatchPlaneSet planes;                                     // every distinct (pointer, kind) once
     std::vector<size_t> at(4 * (size_t)K, 0);
-    size_t img_bytes = 0;
     for (int k = 0; k < K; ++k) {
         const void *pl[4] = {images[k].depth, images[k].mask, images[k].colour, images[k].occluder};
-        for (int q = 0; q < 4; ++q) {
-            if (!use[4 * k + q]) continue;
-            size_t j = 0;
-            while (j < planes.size() && !(planes[j].src == pl[q] && planes[j].kind == q)) ++j;
-            if (j == planes.size()) { planes.push_back(Plane{pl[q], q, img_bytes, where[k].dev[q]}); img_bytes += plane_bytes[q]; }
-            at[4 * k + q] = planes[j].off;
-        }
+        for (int q = 0; q < 4; ++q)
+            if (use[4 * k + q]) at[4 * k + q] = planes.add(pl[q], q, where[k].dev[q], (size_t)P);
     }
+    const size_t img_bytes = planes.bytes;
     std::vector<CloudBatchIn> in(F);
     for (int f = 0; f < F; ++f) {
         const int k = frames[f].image;
@@ -3670,8 +3684,7 @@ int tdlo_depth_to_cloud_batch(tdlo_ctx *c, const tdlo_batch_image *images, int K
     hipStream_t st = c->stream;
     const CloudBatchEnqueue enqueue = [&](const CloudBatchArena &ar, const CloudBatchFrame *bf, int Fm, int Fc, float inv, unsigned epoch) -> int {
         // every distinct plane once (device planes device to device: the kernel's loads want the padding behind the image)
-        for (const Plane &pl : planes)
-            HIPCHK(c, hipMemcpyAsync(ar.d_img + pl.off, pl.src, plane_copy[pl.kind], pl.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        if (int rcp = batch_planes_copy(c, planes, ar.d_img, (size_t)P)) return rcp;
         HIPCHK(c, launch_cloud_fused_batch(bf, Fm, Fc, P, cols, inv, epoch, ar.h_tab, ar.d_tab, st));
         return TDLO_OK;
     };
@@ -3811,6 +3824,150 @@ static int cloud_view_voxel_impl(tdlo_ctx *c, int slot, const tdlo_cloud_view *v
 int tdlo_cloud_view_voxel_grid(tdlo_ctx *c, int slot, const tdlo_cloud_view *v, int N, const unsigned char *select, double leaf_size,
                                double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
     return cloud_view_voxel_impl(c, slot, v, N, select, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
+}
+
+// ---- one cloud from several cameras (include/trackdlo_hip.h: the rig's point list R, then V(R, leaf)) ------------------------------------------------------
+// Everything that refuses the call as a whole; nothing of the context or the slot is touched.  dev: per camera, which of its planes (depth, mask, colour,
+// occluder) lie in device memory
+static int rig_refusal(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size, std::vector<BatchPlanes> &dev) {
+    if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+    if (const char *why = rig_fault(cams, K, rows, cols, leaf_size)) return fail(c, TDLO_E_INVALID, why);
+    dev.assign(K, BatchPlanes{});
+    for (int k = 0; k < K; ++k) {
+        const bool colour = rig_camera_colour(cams[k]);
+        const void *pl[4] = {cams[k].depth, colour ? nullptr : cams[k].mask, colour ? cams[k].colour : nullptr, colour ? cams[k].occluder : nullptr};
+        for (int q = 0; q < 4; ++q)
+            if (pl[q]) { if (int rc = pointer_location(c, pl[q], TDLO_MEM_AUTO, "rig camera", &dev[k].dev[q])) return rc; }
+    }
+    return TDLO_OK;
+}
+
+// vis_Y != nullptr: the caller wants the frame's visibility pre-pass as well; *vis_done = true when the team kernel has left the M squared minima in
+// c->vis_res[1 ..], as for cloud_view_voxel_impl -- whose result words, epoch, riding pre-pass and hand-over these are
+static int rig_to_cloud_impl(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size,
+                             double *X_out, int x_capacity, int *n_out, int *n_raw_out, const double *vis_Y, int vis_M, bool *vis_done) {
+    if (!c) return TDLO_E_INVALID;
+    std::vector<BatchPlanes> where;
+    int rc = rig_refusal(c, slot, cams, K, rows, cols, leaf_size, where);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    Slot &s = c->slots[slot];
+    hipStream_t st = c->stream;
+    const int P = rows * cols, Tc = rig_tiles_per_camera(P);
+    const bool colour = rig_camera_colour(cams[0]);
+    const int E = K * Tc * kRigTile;                             // elements of the one-launch form's tile regions (K P <= 2^26: below 2^27)
+    // ---- the arena (the cloud batch's device block and pinned block, by its helpers): [camera table | every distinct plane once | a colour rig's K mask planes]
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    BatchPlaneSet planes;
+    std::vector<size_t> at(4 * (size_t)K, kNoPlane);
+    const size_t tab = r256(rig_table_bytes(K));
+    for (int k = 0; k < K; ++k) {
+        const void *pl[4] = {cams[k].depth, colour ? nullptr : cams[k].mask, colour ? cams[k].colour : nullptr, colour ? cams[k].occluder : nullptr};
+        for (int q = 0; q < 4; ++q)
+            if (pl[q]) at[4 * k + q] = planes.add(pl[q], q, where[k].dev[q], (size_t)P);
+    }
+    const size_t masks_at = planes.bytes, mask_bytes = img_mask_bytes(P);
+    const size_t img_bytes = planes.bytes + (colour ? mask_bytes * (size_t)K : 0);
+    for (const BatchPlaneSet::Plane &pl : planes.planes) {        // (a device plane is copied device to device: it must not lie in the arena itself)
+        const size_t len = (pl.kind == 0 ? 2 : pl.kind == 2 ? 3 : 1) * (size_t)P;
+        if (pl.dev && c->cbat_img && (const char *)pl.src < (const char *)c->cbat_img + c->cbat_img_cap && (const char *)c->cbat_img < (const char *)pl.src + len)
+            return fail(c, TDLO_E_INVALID, "rig: a device plane overlaps the batch arena");
+    }
+    if ((rc = ensure_cloud_ws(c, E)) || (rc = ensure_pin(c, 16)) || (rc = flush_pending_cloud(c))) return rc;
+    c->fvbat_planes.clear();                                      // (tdlo_view_batch_images: the arena is about to be written)
+    if ((rc = ensure_batch_arena(c, tab + img_bytes, tab))) return rc;
+    char *d_tab = (char *)c->cbat_img, *d_img = d_tab + tab;
+    if ((rc = batch_planes_copy(c, planes, d_img, (size_t)P))) return rc;
+    // ---- the camera table goes up with the launch, as the batch tables do
+    RigCam *h_tab = (RigCam *)c->cbat_pin;
+    for (int k = 0; k < K; ++k) {
+        RigCam &r = h_tab[k];
+        rig_camera_record(cams[k], r);
+        r.depth = (const unsigned short *)(d_img + at[4 * k]);
+        r.mask = (const unsigned char *)(d_img + (colour ? masks_at + mask_bytes * (size_t)k : at[4 * k + 1]));
+        r.colour = colour ? (const unsigned char *)(d_img + at[4 * k + 2]) : nullptr;
+        r.occluder = colour && at[4 * k + 3] != kNoPlane ? (const unsigned char *)(d_img + at[4 * k + 3]) : nullptr;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_tab, h_tab, rig_table_bytes(K), hipMemcpyHostToDevice, st));
+    char *ws = (char *)c->cloud_ws + img_depth_bytes(E) + img_mask_bytes(E);
+    const float inv = 1.0f / (float)leaf_size;
+    if (c->cloud_fused_on && c->cloud_team_on && (long long)K * Tc <= 4095) {
+        // ---- one launch (k_cloud_team over the rig).  As for a view: launched with the slot's capacity AS IT IS where a cloud is resident -- growing the slot
+        // frees that cloud, which a refusal must leave intact -- and the kernel writes nothing to the slot unless the result fits; an empty slot is sized first
+        if ((rc = ensure_cloud_fws(c, E))) return rc;
+        if (s.N0 == 0 && (rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;
+        if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+        const bool vis_ride = vis_Y != nullptr && vis_M >= 1 && vis_M <= 64 && c->direct_in;
+        if (vis_ride && (rc = stage_vis_ride(c, vis_Y, vis_M))) return rc;
+        HIPCHK(c, launch_rig_team(d_tab, K, P, cols, colour, inv, ws, c->cloud_fws, c->cloud_fused_first, s.Xraw, s.cap_points, c->cloud_res, c->cloud_epoch, st,
+                                  vis_ride ? c->vis_nodes_pin : nullptr, vis_ride ? vis_M : 0, c->vis_state, c->vis_res));
+        c->cloud_fused_first = false;
+        const int status = cloud_wait(c, st, c->cloud_epoch);
+        if (status != 1 && vis_ride) c->vis_armed = false;      // (whatever the team left in the minima: armed again before their next use)
+        if (status < 0) { c->cloud_fused_first = true; return status; }
+        if (status == 0) { c->cloud_fused_first = true; return fail(c, TDLO_E_HIP, "the stream drained, but the rig kernel did not report"); }
+        if (status == 1) {
+            const unsigned long long w1 = __atomic_load_n(c->cloud_res + 1, __ATOMIC_RELAXED);
+            const int n = (int)(unsigned)w1, nraw = (int)(unsigned)(w1 >> 32);
+            ++c->rig_route[0];
+            if (n < 0 || n > s.cap_points || n > nraw) return fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count");
+            s.N0 = n; s.sorted_valid = false;
+            if (n_out) *n_out = n;
+            if (n_raw_out) *n_raw_out = nraw;
+            if (n > 0 && vis_ride && vis_done) { *vis_done = true; ++c->rig_route[2]; }
+            if (X_out && n > 0) {
+                if (n > x_capacity) return fail(c, TDLO_E_INVALID, "X_out too small for the down-sampled cloud");
+                HIPCHK(c, hipMemcpyAsync(X_out, s.Xraw, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+            return TDLO_OK;
+        }
+        if (status == 4) c->cloud_fused_first = true;           // the team gave the launch up (a wait of 2 s): state words initialised again
+    }
+    ++c->rig_route[1];               // passed on -- by the kernel: not taken (2), the slot has to grow first (3), given up (4); by the host: tiles, switches
+    // ---- the multi-launch form over K P elements (element p: camera p / P, pixel p % P): a colour rig's masks first, per camera, into the arena
+    if (colour)
+        for (int k = 0; k < K; ++k) {
+            CloudColour cc{};
+            (void)colour_pack(cams[k].colour_params, cc);
+            cc.colour = h_tab[k].colour; cc.occluder = h_tab[k].occluder;
+            HIPCHK(c, launch_colour_mask(cc, P, (unsigned char *)h_tab[k].mask, nullptr, st));
+        }
+    const int N = K * P;
+    unsigned *d_bbox = (unsigned *)(ws + cloud_ws_bytes(N) - 256);
+    int *d_total = (int *)(d_bbox + 8);
+    unsigned *hb = (unsigned *)c->pin;
+    hb[0] = hb[1] = hb[2] = ~0u; hb[3] = hb[4] = hb[5] = 0u; hb[6] = 0u; hb[7] = 0u; hb[8] = 0u;
+    HIPCHK(c, hipMemcpyAsync(d_bbox, hb, 9 * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_rig_bbox(d_tab, K, P, cols, d_bbox, ws, st));
+    HIPCHK(c, hipMemcpyAsync(hb, d_bbox, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int nraw = (int)hb[6];
+    if (n_out) *n_out = 0;
+    if (n_raw_out) *n_raw_out = nraw;
+    if (nraw == 0) { s.N0 = 0; s.sorted_valid = false; return TDLO_OK; }      // the slot as tdlo_depth_to_cloud leaves it for an all-zero mask
+    int min_b[3], div_b[3], nodown = 0, passes = 1;
+    if ((rc = voxel_grid_from_box(c, hb, leaf_size, min_b, div_b, &nodown, &passes))) return rc;      // (the slot's cloud is untouched)
+    if ((rc = ensure_points(c, s, nraw))) return rc;
+    s.N0 = 0; s.sorted_valid = false;
+    HIPCHK(c, launch_rig_voxels(d_tab, K, P, cols, min_b, div_b[0], voxel_mul2(div_b), inv, nodown, passes, nraw, ws, d_total, s.cap_points, s.Xraw, st));
+    HIPCHK(c, hipMemcpyAsync(hb, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const int n = (int)hb[0];
+    if (n < 0 || n > s.cap_points) return fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count");
+    s.N0 = n;
+    if (n_out) *n_out = n;
+    if (X_out && n > 0) {
+        if (n > x_capacity) return fail(c, TDLO_E_INVALID, "X_out too small for the down-sampled cloud");
+        HIPCHK(c, hipMemcpyAsync(X_out, s.Xraw, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    return TDLO_OK;
+}
+
+int tdlo_rig_to_cloud(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size,
+                      double *X_out, int x_capacity, int *n_out, int *n_raw_out) {
+    return rig_to_cloud_impl(c, slot, cams, K, rows, cols, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
 }
 
 // ---- cloud views for F slots in one call (include/trackdlo_hip.h: tdlo_cloud_view_voxel_grid_batch, tdlo_set_cloud_view_batch) --------------------------
@@ -4356,6 +4513,28 @@ int tdlo_cloud_view_voxel_grid_visibility(tdlo_ctx *c, int slot, const tdlo_clou
     bool vis_done = false;
     int n = 0;
     int rc = cloud_view_voxel_impl(c, slot, v, N, select, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done);
+    if (n_out) *n_out = n;
+    if (rc) return rc;
+    if (n_vis) *n_vis = 0;
+    if (n_vis_ext) *n_vis_ext = 0;
+    if (n == 0) return TDLO_OK;                  // no cloud, nothing visible (tdlo_visibility_prepass would refuse the empty slot)
+    if (!vis_done) return tdlo_visibility_prepass(c, slot, Y, M, visibility_threshold, d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext);
+    if ((rc = ensure_pin(c, (size_t)M + 8))) return rc;
+    std::memcpy(c->pin, c->vis_res + 1, sizeof(double) * M);
+    vis_threshold_and_fill(c->pin, M, visibility_threshold, d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext);
+    return TDLO_OK;
+}
+
+// The rig counterpart: V(R, leaf) into the slot and the pre-pass against it; with up to 64 nodes it rides in the team kernel's launch
+int tdlo_rig_to_cloud_visibility(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size,
+                                 const double *Y, int M, double visibility_threshold, double d_vis, const double *geodesic_coord,
+                                 double *node_dist, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                 int *n_out, int *n_raw_out) {
+    if (!c) return TDLO_E_INVALID;
+    if (!Y || M < 1 || !geodesic_coord) return fail(c, TDLO_E_INVALID, "null Y / geodesic_coord");
+    bool vis_done = false;
+    int n = 0;
+    int rc = rig_to_cloud_impl(c, slot, cams, K, rows, cols, leaf_size, nullptr, 0, &n, n_raw_out, Y, M, &vis_done);
     if (n_out) *n_out = n;
     if (rc) return rc;
     if (n_vis) *n_vis = 0;
@@ -4938,7 +5117,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 44) return -1;
+    if (!c || which < 0 || which > 47) return -1;
+    if (which >= 45) return c->rig_route[which - 45];
     if (which >= 42) return c->fvbat_route[which - 42];
     if (which >= 38) return c->wbat_route[which - 38];
     if (which >= 36) return c->ibat_route[which - 36];
@@ -5649,6 +5829,38 @@ int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v
     if (visible_nodes_extended) std::copy(ve.begin(), ve.begin() + ne, visible_nodes_extended);
     if (rc) return rc;
     if (n == 0) return fail(c, TDLO_E_EMPTY, "no point of the view is kept: no cloud for this frame");
+    if (ne == 0) return fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)");
+    return tdlo_tracker_tracking_step(t, nullptr, 0, vv.data(), nv, ve.data(), ne, nullptr, stats);
+}
+
+// The same from a rig's images: tdlo_rig_to_cloud_visibility with the tracker's nodes into its slot, tdlo_tracker_tracking_step.  The self-occlusion test is
+// one camera's (it projects the nodes with ONE matrix): a tracker with the switch on is refused.  After a rig frame the tracker holds no camera of its own:
+// tdlo_tracker_render_result wants the matrix P_k rig_to_cam_k of the camera whose image it draws over.
+int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size, double d_vis,
+                                int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                int *n_out, int *n_raw_out, tdlo_stats *stats) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    const int M = t->M;
+    if (t->geodesic_coord.size() != (size_t)M) return fail(c, TDLO_E_INVALID, "the tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)");
+    if (t->painter_on) return fail(c, TDLO_E_INVALID, "a rig frame with the self-occlusion switch on: that test is one camera's");
+    std::vector<BatchPlanes> where;
+    int rc = rig_refusal(c, t->slot, cams, K, rows, cols, leaf_size, where);
+    if (rc) return rc;
+    std::vector<int> &ve = t->frame_vis_ext, &vv = t->frame_vis;
+    vv.resize(M); ve.resize(M);
+    int nv = 0, ne = 0, n = 0;
+    t->frame_dist.resize(M);
+    t->frame_Y0.clear(); t->frame_seen = false;
+    rc = tdlo_rig_to_cloud_visibility(c, t->slot, cams, K, rows, cols, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis, t->geodesic_coord.data(),
+                                      t->frame_dist.data(), vv.data(), &nv, ve.data(), &ne, &n, n_raw_out);
+    if (n_out) *n_out = n;
+    if (n_vis) *n_vis = nv;
+    if (n_vis_ext) *n_vis_ext = ne;
+    if (visible_nodes) std::copy(vv.begin(), vv.begin() + nv, visible_nodes);
+    if (visible_nodes_extended) std::copy(ve.begin(), ve.begin() + ne, visible_nodes_extended);
+    if (rc) return rc;
+    if (n == 0) return fail(c, TDLO_E_EMPTY, "no pixel of the rig is kept: no cloud for this frame");
     if (ne == 0) return fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)");
     return tdlo_tracker_tracking_step(t, nullptr, 0, vv.data(), nv, ve.data(), ne, nullptr, stats);
 }

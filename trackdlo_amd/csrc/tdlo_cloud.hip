@@ -25,6 +25,7 @@
 #include "tdlo_view_load.h"
 #include "tdlo_view_lane.h"
 #include "tdlo_view_batch_plan.h"
+#include "tdlo_rig_point.h"
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
@@ -477,6 +478,9 @@ struct FusedCloud {
     // optional selection bytes, any alignment, no padding; depth, mask, col, cols and cam are not read.  At the END of the descriptor: the image
     // instantiations find every field where it was
     const void *vdata; long long vsp, vsc; const unsigned char *vsel;
+    // the rig instantiations of k_cloud_team (tdlo_rig_to_cloud): T = K x rigTc tiles, tile b is camera b / rigTc, its pixels from (b % rigTc) x 4096 on; P and
+    // cols are ONE camera's; the camera's planes, intrinsics, transform and colour ranges come from record b / rigTc of the table.  depth, mask, col, cam are not read
+    const RigCam *rig; int rigTc;
 };
 
 __device__ __forceinline__ float ordered_decode(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
@@ -549,10 +553,14 @@ __device__ __forceinline__ void cloud_grid(const unsigned *sbox, int n, float in
 // The ONLY part of the kernels that knows where the points come from: kSrcMask the depth image under a mask, kSrcColour under the segmentation it forms
 // itself, kSrcView the elements of a cloud view in the load form VFORM (tdlo_view_lane.h has the lane's loads and the rule they keep): a thread's four
 // consecutive elements, the kept ones -- selected, three finite floats -- to the tile's region in element order, as masked pixels go in pixel order.
-enum { kSrcMask = 0, kSrcColour = 1, kSrcView = 2 };
+// kSrcRigMask / kSrcRigColour: the images of a rig's cameras (tdlo_rig_point.h has the lane's loads and arithmetic): tile b is camera b / rigTc, whose record
+// of the camera table every thread of the workgroup fetches (one address: scalar loads); a masked pixel whose point is not finite is not kept, as in a view.
+enum { kSrcMask = 0, kSrcColour = 1, kSrcView = 2, kSrcRigMask = 4, kSrcRigColour = 5 };
 template <int kSrc, typename VT = float, int VFORM = kGeneric>
 __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot, unsigned *sticket, unsigned *sbx /* kFW x 6 words of LDS nobody uses yet */) {
     const int t = threadIdx.x, lane = t & 63, b = blockIdx.x;
+    constexpr bool kRig = kSrc == kSrcRigMask || kSrc == kSrcRigColour;
+    constexpr bool kImg = kSrc == kSrcMask || kSrc == kSrcColour;           // the single image: depth words and the camera of the descriptor
 #ifdef TDLO_CLOUD_STAMPS      // wall-clock (100 MHz) split of phase A in the middle tile: words 12 .. 18 behind the state words (scripts/archive/gpu_cloud_stamps.py)
 #define ASTAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (t == 0 && b == a.T / 2) ((unsigned long long *)(a.state + 16))[12 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -560,10 +568,32 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
 #endif
     ASTAMP(0);
     {
-        const int p0 = b * kFPix + 4 * t;
+        [[maybe_unused]] const RigCam *rc = nullptr;
+        int bt = b;                                                           // the tile's number inside its image
+        if constexpr (kRig) { const int k = b / a.rigTc; bt = b - k * a.rigTc; rc = a.rig + k; }
+        const int p0 = bt * kFPix + 4 * t;
         unsigned m4 = 0;
         [[maybe_unused]] float vx[4], vy[4], vz[4];
-        if constexpr (kSrc == kSrcView) {
+        if constexpr (kSrc == kSrcRigMask) {
+            m4 = rig_mask4(rc->mask, p0, a.P);
+        } else if constexpr (kSrc == kSrcRigColour) {
+            // as kSrcColour below, the images and the packed ranges from the camera's record
+            CloudColour cc;
+            cc.colour = rc->colour; cc.occluder = rc->occluder; cc.n = rc->n_ranges; cc.rgb = rc->rgb;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { cc.lo[q] = rc->lo[q]; cc.span[q] = rc->span[q]; }
+            unsigned c0 = 0u, c1 = 0u, c2 = 0u, o4 = 0x01010101u;
+            if (p0 < a.P) {
+                const unsigned *cp = (const unsigned *)(cc.colour + 3 * (size_t)p0);
+                c0 = cp[0]; c1 = cp[1]; c2 = cp[2];
+                if (cc.occluder) o4 = *(const unsigned *)(cc.occluder + p0);
+            }
+            int *tab = (int *)(sbx + 128);                                    // 2 KB
+            if (t < 512) colour_fill_tables(tab, t);
+            __syncthreads();
+            unsigned w[4];
+            if (p0 < a.P) m4 = colour_quad(c0, c1, c2, o4, cc, tab, w);
+        } else if constexpr (kSrc == kSrcView) {
             const unsigned keep = view_lane4<VT, VFORM>((const VT *)a.vdata, a.vsp, a.vsc, a.vsel, p0, a.P, vx, vy, vz);
             m4 = (keep & 1u) | ((keep & 2u) << 7) | ((keep & 4u) << 14) | ((keep & 8u) << 21);      // (a byte per element, as a mask word has)
         } else if constexpr (kSrc == kSrcColour) {
@@ -588,10 +618,14 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
             const int keep = a.P - p0;
             m4 = keep <= 0 ? 0u : (m4 & (0xffffffffu >> (8 * (4 - keep))));
         }
+        if constexpr (kRig) {                                                 // depth, back-projection, transform: kept = masked and finite
+            const unsigned keep = rig_lane4(*rc, m4, p0, a.P, a.cols, vx, vy, vz);
+            m4 = (keep & 1u) | ((keep & 2u) << 7) | ((keep & 4u) << 14) | ((keep & 8u) << 21);
+        }
         const int k0 = (m4 & 0xffu) != 0u, k1 = (m4 & 0xff00u) != 0u, k2 = (m4 & 0xff0000u) != 0u, k3 = (m4 & 0xff000000u) != 0u;
         const int c = k0 + k1 + k2 + k3;
         uint2 d4 = make_uint2(0u, 0u);
-        if constexpr (kSrc != kSrcView) { if (c) d4 = *(const uint2 *)(a.depth + p0); }
+        if constexpr (kImg) { if (c) d4 = *(const uint2 *)(a.depth + p0); }
         ASTAMP(2);
         int total;
         int rnk = block_excl_scan_i(c, wtot, t, &total);
@@ -599,14 +633,14 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
         unsigned mn[3] = {~0u, ~0u, ~0u}, mx[3] = {0u, 0u, 0u};
         if (c) {
             int i = 0, j = 0;
-            if constexpr (kSrc != kSrcView) { i = p0 / a.cols; j = p0 - i * a.cols; }
+            if constexpr (kImg) { i = p0 / a.cols; j = p0 - i * a.cols; }
             const size_t dst = (size_t)b * kFPix;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const bool on = (k == 0 ? k0 : (k == 1 ? k1 : (k == 2 ? k2 : k3))) != 0;
                 if (on) {
                     float x, y, z;
-                    if constexpr (kSrc == kSrcView) { x = vx[k]; y = vy[k]; z = vz[k]; }
+                    if constexpr (!kImg) { x = vx[k]; y = vy[k]; z = vz[k]; }
                     else {
                         const unsigned dv = ((k < 2 ? d4.x : d4.y) >> (16 * (k & 1))) & 0xffffu;
                         const double pc_z = (double)dv / 1000.0;                          // trackdlo_node.cpp:220
@@ -623,7 +657,7 @@ __device__ __forceinline__ unsigned cloud_phase_a(const FusedCloud &a, int *wtot
                     mn[1] = o1 < mn[1] ? o1 : mn[1]; mx[1] = o1 > mx[1] ? o1 : mx[1];
                     mn[2] = o2 < mn[2] ? o2 : mn[2]; mx[2] = o2 > mx[2] ? o2 : mx[2];
                 }
-                if constexpr (kSrc != kSrcView) { if (++j == a.cols) { j = 0; ++i; } }
+                if constexpr (kImg) { if (++j == a.cols) { j = 0; ++i; } }
             }
         }
         ASTAMP(4);
@@ -1669,6 +1703,60 @@ hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *
     if (form == kXyz12) return view_team_launch<float, kXyz12>(a, s);
     if (form == kCols2) return view_team_launch<float, kCols2>(a, s);
     return view_team_launch<float, kGeneric>(a, s);
+}
+
+// ---- a rig: the images of K cameras of one size as ONE point list (tdlo_rig_to_cloud; include/trackdlo_hip.h has the contract, tdlo_rig_point.h the arithmetic)
+// the multi-launch form's source: element p is pixel p % P of camera p / P -- the order of the rig's point list, hence the one-launch kernel's bits.  The
+// cameras' mask planes hold the segmentation (a colour rig's were written by k_colour_mask first)
+namespace {
+struct RigSrc {
+    const RigCam *__restrict__ cams; int P, cols;
+    __device__ __forceinline__ bool fetch(int p, int Ptot, float v[3]) const {
+        if (p >= Ptot) return false;
+        const int k = p / P, q = p - k * P;
+        const RigCam &c = cams[k];
+        if (c.mask[q] == 0) return false;
+        const int i = q / cols, j = q - i * cols;
+        return rig_point(c, i, j, c.depth[q], v[0], v[1], v[2]);
+    }
+    __device__ __forceinline__ void point(int p, float &x, float &y, float &z) const {
+        const int k = p / P, q = p - k * P;
+        const RigCam &c = cams[k];
+        const int i = q / cols, j = q - i * cols;
+        (void)rig_point(c, i, j, c.depth[q], x, y, z);
+    }
+};
+}  // namespace
+
+size_t rig_table_bytes(int K) { return sizeof(RigCam) * (size_t)K; }
+int rig_tiles_per_camera(int P) { return (P + kFPix - 1) / kFPix; }
+
+hipError_t launch_rig_bbox(const void *table_dev, int K, int P, int cols, unsigned *bbox, void *ws, hipStream_t s) {
+    return cloud_bbox_from(RigSrc{(const RigCam *)table_dev, P, cols}, K * P, bbox, ws, s);
+}
+
+hipError_t launch_rig_voxels(const void *table_dev, int K, int P, int cols, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                             void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s) {
+    return cloud_voxels_from(RigSrc{(const RigCam *)table_dev, P, cols}, K * P, min_b, mul1, mul2, inv_leaf, nodown, passes, n, ws, total_dev, cap, Xraw, s);
+}
+
+// the team kernel over a rig: K x Tc tiles (at most 4095); ws holds three regions of K x Tc x 4096 floats, fws is cloud_fused_ws_bytes(K x Tc x 4096) bytes;
+// the rest as for launch_view_team.  The test hook of the image launches does not count these.
+hipError_t launch_rig_team(const void *table_dev, int K, int P, int cols, bool colour, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap,
+                           unsigned long long *res_pinned, unsigned epoch, hipStream_t s, const double *vis_nodes_pinned, int vis_M, unsigned long long *vis_state,
+                           unsigned long long *vis_out_pinned) {
+    const int Tc = rig_tiles_per_camera(P);
+    if (K < 1 || K > kRigMaxCams || P <= 0 || (long long)K * Tc > kFTmax) return hipErrorInvalidValue;
+    FusedCloud a{};
+    fused_describe(a, K * Tc * kFPix, inv_leaf, ws, fws, true, Xraw, cap, res_pinned, epoch, vis_nodes_pinned, vis_M, vis_state, vis_out_pinned);
+    a.P = P; a.cols = cols;                                      // (one camera's; a.T stays K x Tc, the regions K x Tc x 4096 floats each)
+    a.rig = (const RigCam *)table_dev; a.rigTc = Tc;
+    if (const hipError_t e = fused_arm(a, first, s)) return e;
+    const void *fn = colour ? (const void *)k_cloud_team<kSrcRigColour> : (const void *)k_cloud_team<kSrcRigMask>;
+    if (const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTLds)) return e;      // (per device: see launch_cloud_fused)
+    if (colour) hipLaunchKernelGGL(k_cloud_team<kSrcRigColour>, dim3(a.T), dim3(kFT), kTLds, s, a);
+    else hipLaunchKernelGGL(k_cloud_team<kSrcRigMask>, dim3(a.T), dim3(kFT), kTLds, s, a);
+    return hipGetLastError();
 }
 
 }  // namespace tdlo

@@ -340,6 +340,18 @@ hipError_t launch_cloud_fused_batch_tabled(int Fm, int Fc, int P, const void *ta
 hipError_t launch_view_team(const CloudViewSrc &v, int N, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap, unsigned long long *res_pinned,
                             unsigned epoch, hipStream_t s, const double *vis_nodes_pinned = nullptr, int vis_M = 0, unsigned long long *vis_state = nullptr,
                             unsigned long long *vis_out_pinned = nullptr);
+// a rig (tdlo_rig_to_cloud): the images of K cameras of P pixels each as one point list, camera after camera.  table_dev: K records of tdlo_rig_point.h's RigCam
+// in device memory (rig_table_bytes(K) bytes).  launch_rig_team: k_cloud_team's rig instantiations, K x rig_tiles_per_camera(P) tiles (refused beyond 4095);
+// ws: three regions of K x tiles x 4096 floats, fws: cloud_fused_ws_bytes(K x tiles x 4096); reports like launch_view_team.  launch_rig_bbox / launch_rig_voxels:
+// the multi-launch form over K x P elements, the cameras' mask planes holding the segmentation
+size_t rig_table_bytes(int K);
+int rig_tiles_per_camera(int P);
+hipError_t launch_rig_team(const void *table_dev, int K, int P, int cols, bool colour, float inv_leaf, void *ws, void *fws, bool first, double *Xraw, int cap,
+                           unsigned long long *res_pinned, unsigned epoch, hipStream_t s, const double *vis_nodes_pinned = nullptr, int vis_M = 0,
+                           unsigned long long *vis_state = nullptr, unsigned long long *vis_out_pinned = nullptr);
+hipError_t launch_rig_bbox(const void *table_dev, int K, int P, int cols, unsigned *bbox, void *ws, hipStream_t s);
+hipError_t launch_rig_voxels(const void *table_dev, int K, int P, int cols, const int min_b[3], int mul1, int mul2, float inv_leaf, int nodown, int passes, int n,
+                             void *ws, int *total_dev, int cap, double *Xraw, hipStream_t s);
 // k_cloud_fused over F cloud views in ONE launch (k_cloud_view_batch: grid (tiles of the largest frame, frames); tdlo_cloud_view_voxel_grid_batch).  Per frame:
 // the view as the kernels read it (CloudViewSrc: device memory or pinned host memory), its own N <= view_batch_max_elements(), and blocks of device memory that
 // belong to the frame alone (tdlo_view_batch_plan.h lays them out): 256 bytes of state words (view_batch_arm initialises them; the kernel re-arms them), the

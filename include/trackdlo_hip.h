@@ -1239,6 +1239,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 45 / 46 / 47: rigs (tdlo_rig_to_cloud, tdlo_rig_to_cloud_visibility, tdlo_tracker_frame_from_rig) served by the one-launch kernel / passed on by it to the
  * multi-launch form (a team that gave up, and the rigs the host never hands to the kernel -- more than 4095 tiles, TDLO_CLOUD_FUSED=0, TDLO_CLOUD_TEAM=0 --
  * included) / whose visibility pre-pass rode in that launch.
+ * 48: calls whose prologue was the two launches k_prune_nodes / k_scatter_scan (frames that all prune and sort afresh with one tile per workgroup, at most 256 prune
+ * workgroups -- 65 536 points -- and 64 nodes, beyond the fused prologue or with TDLO_DIRECT_UPLOAD=0; TDLO_PROLOGUE_SCAN=0: none, the three-kernel form, the same bits).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -29,6 +29,7 @@ cd $S
 /opt/rocm/bin/hipcc $F -x hip -c tdlo_rccl.cpp -o $B/tdlo_rccl.o &
 g++ -O3 -std=c++17 -fPIC -ffp-contract=off $* -c tdlo_host.cpp -o $B/tdlo_host.o &
 g++ -O3 -std=c++17 -fPIC -ffp-contract=off $* -c tdlo_image_host.cpp -o $B/tdlo_image_host.o &
+g++ -O3 -std=c++17 -fPIC -ffp-contract=off $* -c tdlo_rig_host.cpp -o $B/tdlo_rig_host.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/scripts/tmp/libtrackdlo_$name.so $B/*.o -ldl
 ls -la $R/scripts/tmp/libtrackdlo_$name.so

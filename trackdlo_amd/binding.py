@@ -1177,6 +1177,10 @@ class Context:
         prologue's grid barrier was abandoned] (tdlo_debug_route_count)."""
         return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in range(6)]
 
+    def prologue_scan_calls(self):
+        """Calls whose prologue was the two launches k_prune_nodes / k_scatter_scan (tdlo_debug_route_count 48; TDLO_PROLOGUE_SCAN=0: none)."""
+        return int(self.lib.tdlo_debug_route_count(self.h, 48))
+
     def cloud_stamps(self, n=8):
         out = (C.c_ulonglong * n)()
         self._chk(self.lib.tdlo_debug_cloud_stamps(self.h, out, n))

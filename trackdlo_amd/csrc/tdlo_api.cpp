@@ -300,6 +300,10 @@ struct tdlo_ctx {
     double *mbox = nullptr;
     size_t mbox_doubles = 0;
     unsigned mbox_epoch = 0;
+    // TDLO_PROLOGUE_SCAN=0: clouds beyond the fused prologue keep k_prune_pass1 / k_setup / k_prune_scatter (the comparator of the two-launch
+    // prologue k_prune_nodes / k_scatter_scan, launch_prologue_scan; the same bits)
+    bool prologue_scan_on = !(getenv("TDLO_PROLOGUE_SCAN") && atoi(getenv("TDLO_PROLOGUE_SCAN")) == 0);
+    long long prologue_scan_calls = 0;    // calls whose prologue was those two launches, as launch_prologue_scan reports them (tdlo_debug_route_count 48)
     bool direct_in = !(getenv("TDLO_DIRECT_UPLOAD") && atoi(getenv("TDLO_DIRECT_UPLOAD")) == 0);   // one frame per call: the set-up kernels read the host-supplied block from pinned host
                                                                                                 // memory themselves (small clouds: the fused prologue); 0: copy + three launches (comparator)
     double *late_buf = nullptr;           // pinned: [alpha J | alpha (Y_ext - Y0)] of priors that arrive after the set-up kernel was launched (FrameDev::late_aJ)
@@ -1311,7 +1315,10 @@ int FramesCall::upload_and_prologue() {
         if (f2) pn.state = 2;
     } else {
         if (!merged) HIPCHK(c, hipMemcpyAsync(slot0().nodeblk, c->pin, up * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHK(c, launch_prune_and_setup(fdp, c->fh.data(), F, s));
+        bool scan = false;
+        if (c->prologue_scan_on) HIPCHK(c, launch_prologue_scan(fdp, c->fh.data(), F, s, &scan));
+        if (scan) ++c->prologue_scan_calls;
+        else HIPCHK(c, launch_prune_and_setup(fdp, c->fh.data(), F, s));
     }
     g_prof.mark(g_prof.base + 3);
     for (int i = 0; i < F; ++i) {           // the slots' sorted clouds now belong to these nodes (recorded as soon as the prologue is enqueued: whatever fails later, the device's sort is this one)
@@ -5117,7 +5124,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 47) return -1;
+    if (!c || which < 0 || which > 48) return -1;
+    if (which == 48) return c->prologue_scan_calls;
     if (which >= 45) return c->rig_route[which - 45];
     if (which >= 42) return c->fvbat_route[which - 42];
     if (which >= 38) return c->wbat_route[which - 38];

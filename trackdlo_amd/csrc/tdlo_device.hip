@@ -5,7 +5,7 @@
 // iteration on one CPU thread; here no M x N matrix ever exists.
 //
 // Kernels (one EM iteration = [k_dmin] -> k_estep -> M-step, all on one stream, no host sync):
-//   k_prune_pass1 / k_setup / k_prune_scatter   once per call   (:177-273)
+//   k_prune_pass1 / k_setup / k_prune_scatter   once per call   (:177-273); k_prune_nodes / k_scatter_scan: the same in two launches
 //   k_dmin    per-node minimum distance to the cloud (visibility weighting only, :278-296, :358-372)
 //   k_estep   fused distances + nearest-node + geodesic membership + normalisation + column sums
 //             (:278-389): thread = point, nodes via scalar loads, 64x64 lane-transposed LDS tile so
@@ -733,6 +733,138 @@ __global__ __launch_bounds__(kBlock) void k_prune_scatter(const FrameDev *__rest
             __syncthreads();
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The prologue in TWO launches (clouds of up to kScanMaxBlocks x 256 points on chains of up to 64 nodes, one tile per workgroup, sort not reused):
+// k_setup stood between k_prune_pass1 and k_prune_scatter as ONE workgroup that walked the nb x M counts twice before doing node work that never
+// needed them.  Here the node work rides beside the prune (k_prune_nodes: one more workgroup per frame, setup_body<FUSED> as in k_prologue) and
+// every scatter workgroup forms its own start offsets from the counts (k_scatter_scan).  The counts were written by the PREVIOUS launch: plain
+// loads, no agent-scope traffic, no flag, no grid barrier -- the kernel boundary is the hand-over.  The numbers are k_setup's (integers; the
+// sigma2 initialisation sum in its order), so the bits are those of the three-kernel form.
+// ------------------------------------------------------------------------------------------------
+constexpr int kScanMaxBlocks = 256;      // prune workgroups per frame: a thread's quarter of the counts is at most 64 loads, all in flight at once
+constexpr int kScanMaxNodes = 64;        // lane = node in the offset computation
+
+// launch A, grid (gx + 1, F): workgroups 0 .. nb - 1 are k_prune_pass1; workgroup gx of every frame (gridDim.x - 1: frames of a batch have their
+// own nb) is the node work.  Nothing the node workgroup writes is read by the point workgroups.
+__device__ __forceinline__ void prune_block(const FrameDev &f) {
+    __shared__ double scratch[4];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int *lh = (int *)smem;                            // M: kept points of this block per nearest node
+    const int N0 = f.N0, M = f.M;
+    double *Yl = (double *)(lh + ((M + 3) & ~3));     // 3M: the nodes, staged once per block
+    for (int m = threadIdx.x; m < M; m += kBlock) lh[m] = 0;
+    for (int i = threadIdx.x; i < 3 * M; i += kBlock) Yl[i] = f.Yin[i];
+    __syncthreads();
+    const int n = blockIdx.x * kBlock + threadIdx.x;      // (prune_tiles == 1 on this route)
+    const bool valid = n < N0;
+    double x = 0, y = 0, z = 0;
+    if (valid) { x = f.Xraw[n]; y = f.Xraw[(size_t)N0 + n]; z = f.Xraw[2 * (size_t)N0 + n]; }
+    double best, sum;
+    int a0;
+    nearest_node(Yl, M, x, y, z, best, a0, sum);
+    const bool keep = valid && (::sqrt(best) < 0.1);
+    if (valid) f.bucket[n] = keep ? (unsigned short)a0 : (unsigned short)0xffff;
+    if (keep) atomicAdd(&lh[a0], 1);
+    double ssum = 0;
+    ssum += block_sum(keep ? sum : 0.0, scratch);
+    __syncthreads();
+    for (int m = threadIdx.x; m < M; m += kBlock) f.hist[(size_t)blockIdx.x * M + m] = lh[m];
+    if (threadIdx.x == 0) f.blksum[blockIdx.x] = ssum;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_prune_nodes(const FrameDev *__restrict__ frames) {
+    const FrameDev &f = frames[blockIdx.y];
+    if (blockIdx.x == gridDim.x - 1) { setup_body<T, true, kFuseMaxNodes>(f, 0, nullptr, nullptr, 0, 0, 0u); return; }
+    if ((int)blockIdx.x >= f.nprune_blocks) return;
+    prune_block(f);
+}
+
+// launch B, grid (gx, F): k_prune_scatter with base[] formed here.  Thread = (node = lane, quarter of the blocks = wave), k_setup's split of the
+// blocks; all of a thread's counts are requested before any is added, the index clamped instead of tested.  Per node the total over all blocks
+// and the part in front of this workgroup's block go through LDS, every wave scans the 64 totals (wave 0 writes base[]).  Workgroup 0 also forms
+// the sigma2 initialisation sum in k_setup's order (thread i takes block i's share -- per == 1 for nb <= 256 --, wave_sum's butterfly, the four
+// waves left to right) and, behind its scatter, the iteration-0 state (fused_iter0).  hist_off is not written.
+// K: loads per thread, at least a quarter of the launch's largest nb (rounded up) -- an instantiation per tier, so that a batch of small frames is
+// not held to the registers of 64 loads in flight.
+template <typename T, int K>
+__global__ __launch_bounds__(kBlock) void k_scatter_scan(const FrameDev *__restrict__ frames) {
+    const FrameDev &f = frames[blockIdx.y];
+    const int nb = f.nprune_blocks;
+    if ((int)blockIdx.x >= nb) return;
+    __shared__ int ctot[4][kScanMaxNodes], cpre[4][kScanMaxNodes], base[kScanMaxNodes], wcnt[4 * kScanMaxNodes];
+    __shared__ double wsd[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, blk = blockIdx.x, M = f.M;
+#ifdef TDLO_CHAIN_STAMPS      // phase stamps of workgroup 0 of frame 0 (instrumented build only): f.dbg[24 ..], as k_prologue's
+#define PSTAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (t == 0 && blk == 0) f.dbg[24 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define PSTAMP(i) do { } while (0)
+#endif
+    PSTAMP(0);
+    const int n = blk * kBlock + t;                   // (prune_tiles == 1 on this route)
+    const int b = (n < f.N0) ? (int)f.bucket[n] : 0xffff;
+    const bool keep = b != 0xffff;
+    for (int i = t; i < 4 * M; i += kBlock) wcnt[i] = 0;
+    double sh0 = 0.0;
+    if (blk == 0 && t < nb) sh0 = f.blksum[t];
+    {
+        const int cb0 = (int)((long long)nb * w / 4), cb1 = (int)((long long)nb * (w + 1) / 4);      // this wave's quarter of the blocks: at most 64
+        const int mc = lane < M ? lane : M - 1, last = cb1 > 0 ? cb1 - 1 : 0;                       // (clamped loads: an empty quarter reads block 0 and counts nothing)
+        const int cnt = cb1 - cb0, cpr = (blk < cb1 ? blk : cb1) - cb0;                             // the quarter's blocks, and those of them in front of this workgroup's block
+        const auto hb = TDLO_AS_GLOBAL(char, f.hist);
+        int tot = 0, pre = 0;
+        {
+            int v[K];
+#pragma unroll
+            for (int u = 0; u < K; ++u) v[u] = *(const __attribute__((address_space(1))) int *)(hb + (unsigned)(4 * (min(cb0 + u, last) * M + mc)));      // (32-bit offsets from one base: nb M <= 16 384)
+            __builtin_amdgcn_sched_barrier(0);       // (every load is on its way before the first count is used: one round trip)
+#pragma unroll
+            for (int u = 0; u < K; ++u) { tot += u < cnt ? v[u] : 0; pre += u < cpr ? v[u] : 0; }
+        }
+        ctot[w][lane] = lane < M ? tot : 0;
+        cpre[w][lane] = lane < M ? pre : 0;
+    }
+    if (blk == 0) {
+        const double ssum = wave_sum(sh0);
+        if (lane == 0) wsd[w] = ssum;
+    }
+    __syncthreads();
+    PSTAMP(1);
+    // first index of every node's run (exclusive scan of the totals: integers, any order) + the counts of the blocks in front of this one
+    const int ntot = (ctot[0][lane] + ctot[1][lane]) + (ctot[2][lane] + ctot[3][lane]);
+    int incl = ntot;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+    if (w == 0) base[lane] = incl - ntot + ((cpre[0][lane] + cpre[1][lane]) + (cpre[2][lane] + cpre[3][lane]));
+    const int Nk = __builtin_amdgcn_readlane(incl, 63);
+    // rank of this point among the earlier points of the wave with the same nearest node (stable order), as k_prune_scatter
+    int rank = 0;
+    unsigned long long remaining = __ballot(keep);
+    while (remaining) {
+        const int leader = (int)__builtin_ctzll(remaining);
+        const int b0 = __builtin_amdgcn_readlane(b, leader);
+        const unsigned long long mask = __ballot(keep && b == b0);
+        if (keep && b == b0) rank = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == leader) wcnt[w * M + b0] = __popcll(mask);
+        remaining &= ~mask;
+    }
+    __syncthreads();
+    PSTAMP(2);
+    if (keep) {
+        int dst = base[b] + rank;
+        for (int i = 0; i < w; ++i) dst += wcnt[i * M + b];
+        T *xs = (T *)f.Xs;
+        const size_t N0 = f.N0, ld = f.ldx;
+        xs[dst] = (T)(f.Xraw[n] - f.ctr[0]);
+        xs[ld + dst] = (T)(f.Xraw[N0 + n] - f.ctr[1]);
+        xs[2 * ld + dst] = (T)(f.Xraw[2 * N0 + n] - f.ctr[2]);
+    }
+    PSTAMP(3);
+    if (blk == 0 && t == 0) fused_iter0(f, Nk, ((wsd[0] + wsd[1]) + wsd[2]) + wsd[3]);
+    PSTAMP(4);
+#undef PSTAMP
 }
 
 // split mode: global N and sum_d2 arrive from the all-reduce
@@ -1659,6 +1791,35 @@ hipError_t launch_prune_and_setup(const FrameDev *fd, const FrameDev *fh, int F,
         if (f64) hipLaunchKernelGGL((k_prune_scatter<double>), dim3(gx, F), dim3(kBlock), sizeof(int) * 5 * fh[0].M, s, fd);
         else hipLaunchKernelGGL((k_prune_scatter<float>), dim3(gx, F), dim3(kBlock), sizeof(int) * 5 * fh[0].M, s, fd);
     }
+    return hipGetLastError();
+}
+
+// The two-launch prologue (k_prune_nodes, k_scatter_scan) serves a call whose frames all prune and sort afresh with one tile per workgroup, at most
+// kScanMaxBlocks workgroups and kScanMaxNodes nodes; *taken says whether it was launched (tdlo_debug_route_count 48 counts from here) -- if not,
+// nothing was, and the caller takes launch_prune_and_setup.
+bool prologue_scan_ok(const FrameDev *fh, int F) {
+    for (int i = 0; i < F; ++i)
+        if (fh[i].reuse_sorted || fh[i].prune_tiles != 1 || fh[i].M > kScanMaxNodes || fh[i].nprune_blocks > kScanMaxBlocks || fh[i].nprune_blocks < 1) return false;
+    return F >= 1;
+}
+hipError_t launch_prologue_scan(const FrameDev *fd, const FrameDev *fh, int F, hipStream_t s, bool *taken) {
+    *taken = prologue_scan_ok(fh, F);
+    if (!*taken) return hipSuccess;
+    int gx = 0;
+    for (int i = 0; i < F; ++i) gx = fh[i].nprune_blocks > gx ? fh[i].nprune_blocks : gx;
+    const bool f64 = fh[0].precision == TDLO_PREC_F64;
+    const size_t lds = sizeof(int) * ((fh[0].M + 3) & ~3) + sizeof(double) * (3 * fh[0].M + kPrunePad);
+    if (f64) hipLaunchKernelGGL((k_prune_nodes<double>), dim3(gx + 1, F), dim3(kBlock), lds, s, fd);
+    else hipLaunchKernelGGL((k_prune_nodes<float>), dim3(gx + 1, F), dim3(kBlock), lds, s, fd);
+    auto scatter = [&](auto KC) {
+        constexpr int K = decltype(KC)::value;
+        if (f64) hipLaunchKernelGGL((k_scatter_scan<double, K>), dim3(gx, F), dim3(kBlock), 0, s, fd);
+        else hipLaunchKernelGGL((k_scatter_scan<float, K>), dim3(gx, F), dim3(kBlock), 0, s, fd);
+    };
+    if (gx <= 16) scatter(std::integral_constant<int, 4>());
+    else if (gx <= 64) scatter(std::integral_constant<int, 16>());
+    else if (gx <= 128) scatter(std::integral_constant<int, 32>());
+    else scatter(std::integral_constant<int, kScanMaxBlocks / 4>());
     return hipGetLastError();
 }
 

@@ -229,6 +229,8 @@ __host__ __device__ inline int band_rec_pos(int q) { return (q & 3) * 4 + (q >> 
 
 // launchers implemented in tdlo_device.hip
 hipError_t launch_prune_and_setup(const FrameDev *frames_dev, const FrameDev *frames_host, int F, hipStream_t s);
+bool prologue_scan_ok(const FrameDev *frames_host, int F);      // the two-launch prologue serves these frames (no reused sort, one tile, <= 64 nodes, <= 256 prune workgroups)
+hipError_t launch_prologue_scan(const FrameDev *frames_dev, const FrameDev *frames_host, int F, hipStream_t s, bool *taken);      // *taken false: nothing was launched
 bool prologue_direct_ok(const FrameDev &f);
 bool prologue_pair_ok(const FrameDev &f);      // the fused form itself (not the reused-sort set-up): a second registration's set-up can ride along
 hipError_t launch_prologue_direct(const FrameDev *fh, const double *host_up, double *dev_up, int up_doubles, int yin_off, unsigned epoch, hipStream_t s,

@@ -811,6 +811,60 @@ int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, in
 int tdlo_rig_check(const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size);
 int tdlo_rig_points_host(const tdlo_rig_camera *cams, int K, int rows, int cols, float *R_out, int capacity, int *n_raw_out);
 
+/* ---- many ropes under one rig in one call: batched rig frames ------------------------------------------------ */
+/* The cell that has two or three cameras is the cell that tracks several ropes at once: one camera set, one colour range or mask per rope.  A FRAME is a slot
+ * and a rig of its own -- K_f cameras of the call's image size, each with its intrinsics, cam_to_rig and mask or colour ranges.  Frames may differ in K_f
+ * (1 .. 64) and in kind (a mask rig and a colour rig may share a call; inside one frame all cameras are one kind, as in the single call).  Any number of
+ * frames may name the SAME plane pointers -- F ropes under one rig, each frame with its own colour_params or mask planes --: every distinct plane (pointer and
+ * kind) is copied ONCE per call into the context's rig-batch arena, a device plane device to device.
+ *   BITS: for every frame the slot's cloud, n_out[f] and n_raw_out[f] are those of tdlo_rig_to_cloud on that frame alone -- R in camera order, then V(R, leaf):
+ * the rig contract above stays the one statement of the result, this call adds no arithmetic of its own -- bit for bit, the sign of a zero included, whatever
+ * else shares the call and in whatever order the frames stand.  A frame that keeps no pixel leaves an empty cloud (n = 0), as the single call does.  A frame
+ * whose single call would end in refusal 8 or 9 of V gets that code in rc_each, its slot's cloud untouched, and the other frames complete.
+ *   Refused as a whole with TDLO_E_INVALID before anything is touched (resident clouds intact): F < 1 or F greater than the context's slot count; a slot out of
+ * range or named twice; any frame's rig failing tdlo_rig_check; a plane in another GPU's memory; a device plane that overlaps a batch arena.
+ *   rc_each (NULL or F codes): a frame that fails on its own gets its code; the call returns the first one.
+ *   Routes: the mask frames and the colour frames are one launch each of k_cloud_rig_batch (csrc/tdlo_cloud.hip: grid (most tiles of a frame, frames); block row
+ * f takes frame f's descriptor out of a table in device memory -- its own K_f camera records, state words, tile regions, compacted points, tile counts and
+ * pinned result words; a workgroup beyond its frame's K_f x Tc tiles leaves at once; a frame's last ticket finishes it in one workgroup; no workgroup waits
+ * for another), on one stream behind the copies, followed by ONE host wait.  csrc/tdlo_rig_batch_plan.h lays the arena out and states its bytes: K times the
+ * cloud batch's, about 33 MB a frame for three 1280 x 720 cameras, so one launch covers only as many frames as keep the arena within 1 GiB (kRigBatchBudget)
+ * and further frames go in further launches back to back under the same wait.  A frame the kernel does not take -- more than 32 704 kept points, cell-index
+ * bits + rank bits beyond 32, PCL's pass-through, a result the slot's present capacity does not hold (the slot is not grown in front of the launch: that would
+ * free a cloud a refusal must leave intact) -- and a frame of more than 4095 tiles then goes through tdlo_rig_to_cloud for its slot alone; with
+ * TDLO_CLOUD_FUSED=0 every frame does.  tdlo_debug_route_count 49 counts the frames the batch launch served, 50 the frames passed on; 45 - 47 keep counting what
+ * the single route does.
+ *   Fewer than kRigBatchMin frames (csrc/tdlo_api.cpp) loop over the single calls: the same bits.  MEASURED (profiles/rig_batch_ab.txt, scripts/gpu_rig_batch.py;
+ * rope frames of 45 nodes under K = 3 cameras, F = 1 .. 32, the clouds bit-equal on both sides): at 640 x 480 the batch call loses at 1 and 2 frames and wins
+ * from 4 on -- 32 ropes under one rig cost 0.70 ms against 2.18 ms from device planes and 2.05 against 6.16 ms from pageable host planes, 32 rigs with planes
+ * of their own 1.04 against 2.25 ms --; at 1280 x 720 three cameras keep 96 805 pixels, the kernel passes every frame on and the call loses by 3 - 9 %.  The
+ * rule "every batch value below every single-calls value at both sizes" is met by no F up to 32, so kRigBatchMin is 33: BY DEFAULT tdlo_rig_to_cloud_batch
+ * LOOPS OVER THE SINGLE CALLS.  The tracker call wins on every value from 4 trackers on at both sizes (32 trackers: 2.26 against 5.69 ms at 640 x 480, 32.6
+ * against 35.6 ms at 1280 x 720): kRigBatchTrackerMin is 4.  TDLO_RIG_BATCH_MIN=n (read when the context is made) sets both -- worth it for a cell whose ropes
+ * keep fewer than 32 704 pixels over all cameras. */
+typedef struct { int slot; const tdlo_rig_camera *cams; int K; } tdlo_rig_frame;
+int tdlo_rig_to_cloud_batch(tdlo_ctx *ctx, const tdlo_rig_frame *frames, int F, int rows, int cols, double leaf_size,
+                            int *n_out /* F */, int *n_raw_out /* F */, int *rc_each /* F or NULL */);
+/* The call above into the trackers' slots (frames[i] is tracker i's rig; its .slot is not read), then tdlo_tracker_frame_batch on the trackers whose cloud is
+ * not empty: the bits of the two calls made by hand.  A tracker whose frame keeps nothing gets TDLO_E_EMPTY in rc_each and is left untouched; the others go on.
+ * A tracker with the self-occlusion switch on refuses the WHOLE call before anything is touched (the single call refuses that tracker too).  Otherwise refused
+ * as tdlo_tracker_frame_batch and the call above refuse, except that no cloud need be resident.  visible_nodes / visible_nodes_extended: F rows of
+ * num_of_nodes entries; stats: 2 F entries; any output may be NULL. */
+int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, const tdlo_rig_frame *frames /* .slot not read */,
+                                       int rows, int cols, double leaf_size, double d_vis,
+                                       int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                       int *n_out, int *n_raw_out, tdlo_stats *stats /* 2 F */, int *rc_each);
+/* The arena layout of csrc/tdlo_rig_batch_plan.h (no context, no GPU), shaped like tdlo_debug_view_batch_plan: frames of K[f] cameras of rows x cols pixels into
+ * the slots slot[f] of a context of Fcap slots; plane: 4 keys per camera -- depth, mask, colour, occluder; 0: none --, camera after camera, frame after frame
+ * (two entries with the same key and kind are one plane); budget: the bytes one launch may address (<= 0: the library's 1 GiB).  Outputs in bytes from the
+ * arena's start, any may be NULL: state_off / cams_off / tiles_off / pts_off / cnt_off / launch_of: F entries; plane_off: one entry per key (-1: none).
+ * Blocks of DIFFERENT launches share their place.  TDLO_E_INVALID: what the header refuses (a slot named twice, K outside 1 .. 64, more than 4095 tiles, ...).
+ * tdlo_debug_rig_batch_arena: where the context's rig-batch arena lies at present (a test aid for the overlap refusal; NULL / 0 before the first batch). */
+int tdlo_debug_rig_batch_plan(const int *slot, const int *K, int F, int Fcap, int rows, int cols, const unsigned long long *plane, long long budget,
+                              long long *state_off, long long *cams_off, long long *plane_off, long long *tiles_off, long long *pts_off, long long *cnt_off,
+                              int *launch_of, long long *table_off, long long *total, int *n_planes, int *n_launches);
+int tdlo_debug_rig_batch_arena(tdlo_ctx *ctx, const void **base, long long *bytes);
+
 /* ---- cloud views for many slots in one call ----------------------------------------------------------- */
 /* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
  * views become the resident clouds of F slots in one call -- down-sampled (tdlo_cloud_view_voxel_grid_batch) or as they are (tdlo_set_cloud_view_batch).
@@ -1241,6 +1295,10 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * included) / whose visibility pre-pass rode in that launch.
  * 48: calls whose prologue was the two launches k_prune_nodes / k_scatter_scan (frames that all prune and sort afresh with one tile per workgroup, at most 256 prune
  * workgroups -- 65 536 points -- and 64 nodes, beyond the fused prologue or with TDLO_DIRECT_UPLOAD=0; TDLO_PROLOGUE_SCAN=0: none, the three-kernel form, the same bits).
+ * 49 / 50: frames of tdlo_rig_to_cloud_batch (tdlo_tracker_frames_from_rig_batch's among them) served by the batch launch k_cloud_rig_batch / passed on to
+ * tdlo_rig_to_cloud for their slot -- by the kernel (more than 32 704 kept points, too many cell bits, pass-through, the refusals 8 and 9, a result the slot's
+ * capacity does not hold), or by the host (more than 4095 tiles, TDLO_CLOUD_FUSED=0); frames of a batch below the crossover count in 45 - 47 alone, and a
+ * frame passed on counts there as well.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -100,6 +100,10 @@ class RigCameraC(C.Structure):                     # tdlo_rig_camera: one camera
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("cam_to_rig", C.c_void_p)]
 
 
+class RigFrameC(C.Structure):                      # tdlo_rig_frame: a slot and a rig of its own (K tdlo_rig_camera records)
+    _fields_ = [("slot", C.c_int), ("cams", C.c_void_p), ("K", C.c_int)]
+
+
 class ViewFrame(C.Structure):                      # tdlo_view_frame: a slot, the cloud view it takes, its N and selection bytes (NULL: every element)
     _fields_ = [("slot", C.c_int), ("view", C.c_void_p), ("N", C.c_int), ("select", C.c_void_p)]
 
@@ -143,6 +147,7 @@ SYMBOLS = [
     "tdlo_debug_view_batch_plan",
     "tdlo_frame_views_to_cloud_batch", "tdlo_tracker_frame_views_batch", "tdlo_view_batch_images", "tdlo_debug_slot_cloud",
     "tdlo_rig_to_cloud", "tdlo_rig_to_cloud_visibility", "tdlo_tracker_frame_from_rig", "tdlo_rig_check", "tdlo_rig_points_host",
+    "tdlo_rig_to_cloud_batch", "tdlo_tracker_frames_from_rig_batch", "tdlo_debug_rig_batch_plan", "tdlo_debug_rig_batch_arena",
 ]
 
 _lib = None
@@ -348,6 +353,12 @@ def load_library(path: str | None = None):
         lib.tdlo_tracker_frame_from_rig.argtypes = [vp, vp, ci, ci, ci, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp]
         lib.tdlo_rig_check.argtypes = [vp, ci, ci, ci, cd]
         lib.tdlo_rig_points_host.argtypes = [vp, ci, ci, ci, vp, ci, C.POINTER(ci)]
+    if hasattr(lib, "tdlo_rig_to_cloud_batch"):
+        ll = C.c_longlong
+        lib.tdlo_rig_to_cloud_batch.argtypes = [vp, vp, ci, ci, ci, cd, vp, vp, vp]
+        lib.tdlo_tracker_frames_from_rig_batch.argtypes = [vp, ci, vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.tdlo_debug_rig_batch_plan.argtypes = [vp, vp, ci, ci, ci, ci, vp, ll, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ci), C.POINTER(ci)]
+        lib.tdlo_debug_rig_batch_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(ll)]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -771,6 +782,57 @@ def rig_points_host(cams):
     return R[:n.value]
 
 
+def _rig_frames(frames):
+    """tdlo_rig_frame table of (slot, cams) pairs -- cams: the RigCamera objects of the frame's own rig; all rigs of one image size.  Planes handed over as the
+    same object (or the same tensor) by several cameras or frames are one address: the library copies each distinct plane once.
+    Returns (table, F, rows, cols, owners)."""
+    frames = list(frames)
+    F = len(frames)
+    tab = (RigFrameC * max(F, 1))(); keep = []
+    rows = cols = 0
+    for f, (slot, cams) in enumerate(frames):
+        ctab, K, r, c, owners = _rig_cameras(cams)
+        if f and (r, c) != (rows, cols):
+            raise ValueError(f"frame {f}: the rigs of a batch share one image size")
+        rows, cols = r, c
+        tab[f].slot, tab[f].cams, tab[f].K = int(slot), C.addressof(ctab), K
+        keep.append((ctab, owners))
+    return tab, F, rows, cols, keep
+
+
+def rig_batch_plan(slots, Ks, rows, cols, planes, Fcap, budget=0):
+    """tdlo_debug_rig_batch_plan: where the rig batch keeps the blocks of frames of Ks[f] cameras of rows x cols pixels into the slots slots[f] (bytes from the
+    arena's start).  planes: 4 keys per camera (depth, mask, colour, occluder; 0: none), camera after camera, frame after frame; budget: the bytes one launch
+    may address (0: the library's constant).  Returns dict(state, cams, tiles, pts, cnt, launch: F entries each; plane: one offset per key, -1 where there is
+    none; table, total, n_planes, n_launches) or None where the library refuses."""
+    sl = np.ascontiguousarray(slots, dtype=np.int32); Ka = np.ascontiguousarray(Ks, dtype=np.int32)
+    F = len(sl)
+    keys = np.ascontiguousarray(planes, dtype=np.uint64)
+    if len(Ka) != F or (F and len(keys) != 4 * int(Ka.clip(0, 64).sum())):
+        return None
+    o = [np.zeros(max(F, 1), dtype=np.int64) for _ in range(5)]
+    po = np.zeros(max(len(keys), 1), dtype=np.int64); lo = np.zeros(max(F, 1), dtype=np.int32)
+    tab = C.c_longlong(0); tot = C.c_longlong(0); npl = C.c_int(0); nl = C.c_int(0)
+    if load_library().tdlo_debug_rig_batch_plan(_ptr(sl), _ptr(Ka), F, int(Fcap), int(rows), int(cols), _ptr(keys), int(budget), _ptr(o[0]), _ptr(o[1]), _ptr(po),
+                                                _ptr(o[2]), _ptr(o[3]), _ptr(o[4]), _ptr(lo), C.byref(tab), C.byref(tot), C.byref(npl), C.byref(nl)):
+        return None
+    return dict(state=o[0][:F].tolist(), cams=o[1][:F].tolist(), tiles=o[2][:F].tolist(), pts=o[3][:F].tolist(), cnt=o[4][:F].tolist(), launch=lo[:F].tolist(),
+                plane=po[:len(keys)].tolist(), table=tab.value, total=tot.value, n_planes=npl.value, n_launches=nl.value)
+
+
+def rig_plane_keys(frames):
+    """The plane keys of (slot, cams) frames as rig_batch_plan takes them: the addresses the library is handed (a colour camera's mask and a mask camera's
+    colour planes are not read: 0).  Returns (keys, owners)."""
+    tab, F, rows, cols, keep = _rig_frames(frames)
+    keys = []
+    for f in range(F):
+        cams = (RigCameraC * tab[f].K).from_address(tab[f].cams)
+        colour = not cams[0].mask
+        for cm in cams:
+            keys += [cm.depth or 0, 0 if colour else (cm.mask or 0), (cm.colour or 0) if colour else 0, (cm.occluder or 0) if colour else 0]
+    return keys, keep
+
+
 def _view_images(images):
     """tdlo_view_image table of a list of dicts {depth, mask and / or colour (+ occluder), cam: (fx, fy, cx, cy)}, each image an ImageView or anything
     image_view() takes (or {fv: a FrameView, cam}).  Returns (table, K, rows, cols, owners)."""
@@ -968,6 +1030,30 @@ class Context:
     def rig_points_host(cams):
         """The rig's point list R on the host (module function rig_points_host)."""
         return rig_points_host(cams)
+
+    def rig_to_cloud_batch(self, frames, leaf_size, check=True):
+        """tdlo_rig_to_cloud_batch: the clouds of F slots from F rigs of one image size in one call.  frames: (slot, cams) pairs, cams the RigCamera objects of
+        the frame's own rig; frames may share planes (F ropes under one rig: the same depth and colour arrays, each frame's cameras with their own params or
+        masks).  The clouds stay resident in the slots (get_cloud).  Returns (n [F], n_raw [F], codes [F]); raises on the first non-zero code unless
+        check=False."""
+        tab, F, rows, cols, keep = _rig_frames(frames)
+        n = np.zeros(max(F, 1), dtype=np.int32); nraw = np.zeros(max(F, 1), dtype=np.int32); rcs = np.zeros(max(F, 1), dtype=np.int32)
+        rc = self.lib.tdlo_rig_to_cloud_batch(self.h, C.cast(tab, C.c_void_p), F, rows, cols, float(leaf_size), _ptr(n), _ptr(nraw), _ptr(rcs))
+        self._async_src = None
+        del keep
+        if rc and check:
+            self._chk(rc)
+        return [int(v) for v in n[:F]], [int(v) for v in nraw[:F]], [int(v) for v in rcs[:F]]
+
+    def rig_batch_route_counts(self):
+        """[frames the rig batch launch served, frames passed on to the single call] (tdlo_debug_route_count 49 / 50)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (49, 50)]
+
+    def rig_batch_arena(self):
+        """(address, bytes) of the rig-batch arena as it stands (tdlo_debug_rig_batch_arena; (0, 0) before the first batch launch)."""
+        base = C.c_void_p(0); size = C.c_longlong(0)
+        self._chk(self.lib.tdlo_debug_rig_batch_arena(self.h, C.byref(base), C.byref(size)))
+        return int(base.value or 0), int(size.value)
 
     def set_cloud_view_batch(self, slots, objs, ready_stream=None, check=True):
         """tdlo_set_cloud_view_batch: the clouds of F slots from F views where they lie, imported as they are in one launch (objs: CloudViews or anything
@@ -1948,6 +2034,22 @@ def frames_from_cloud_view_batch(trackers, views, leaf_size, d_vis, selects=None
     nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
     rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_cloud_view_batch(C.cast(tab, C.c_void_p), F, C.cast(ftab, C.c_void_p), float(leaf_size), float(d_vis),
                                                                        _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
+    del keep
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def frames_from_rig_batch(trackers, rigs, leaf_size, d_vis, check=True):
+    """tdlo_tracker_frames_from_rig_batch: the trackers' frames from rigs -- Context.rig_to_cloud_batch into the trackers' slots (tracker i: the cameras
+    rigs[i]), then frame_batch on the trackers that got a cloud.  Returns (codes, [visible_nodes], [visible_nodes_extended], n [F], n_raw [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    assert len(rigs) == F
+    ftab, _, rows, cols, keep = _rig_frames([(0, cams) for cams in rigs])
+    M = trackers[0].M
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_rig_batch(C.cast(tab, C.c_void_p), F, C.cast(ftab, C.c_void_p), rows, cols, float(leaf_size), float(d_vis),
+                                                                _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs))
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]

@@ -9,6 +9,7 @@
 #include "tdlo_reg_plan.h"
 #include "tdlo_rig_host.h"
 #include "tdlo_view_batch_plan.h"
+#include "tdlo_rig_batch_plan.h"
 
 #include <algorithm>
 #include <limits>
@@ -243,6 +244,18 @@ struct tdlo_ctx {
     int view_batch_min = (getenv("TDLO_VIEW_BATCH_MIN") && atoi(getenv("TDLO_VIEW_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_VIEW_BATCH_MIN")) : 0;
     long long wbat_route[4] = {0, 0, 0, 0};
     long long rig_route[3] = {0, 0, 0};         // tdlo_debug_route_count 45 / 46 / 47: rigs (tdlo_rig_to_cloud) served by the one-launch kernel / passed on by it / whose pre-pass rode in it
+    // rigs for F slots in one call (tdlo_rig_to_cloud_batch: k_cloud_rig_batch).  rbatch_dev: the arena of tdlo_rig_batch_plan.h -- [one state block per slot of
+    // the context | frame table | camera table | every distinct plane once | the frame blocks of one launch] -- grown on demand; the state blocks are armed when
+    // rbatch_armed says so (the kernel keeps them so; a call that did not complete or a reallocation has them initialised again).  rbatch_pin: [result words |
+    // frame table | camera table].  TDLO_RIG_BATCH_MIN=n: below n frames the calls loop over the single calls (0: kRigBatchMin / kRigBatchTrackerMin).
+    // rbatch_route: tdlo_debug_route_count 49 / 50: frames the batch launch served / frames passed on to the single call
+    void *rbatch_dev = nullptr;
+    size_t rbatch_dev_cap = 0;
+    char *rbatch_pin = nullptr;
+    size_t rbatch_pin_cap = 0;
+    bool rbatch_armed = false;
+    int rig_batch_min = (getenv("TDLO_RIG_BATCH_MIN") && atoi(getenv("TDLO_RIG_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_RIG_BATCH_MIN")) : 0;
+    long long rbatch_route[2] = {0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1801,6 +1814,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->cbat_pin) hipHostFree(c->cbat_pin);
     if (c->wbat_dev) hipFree(c->wbat_dev);
     if (c->wbat_pin) hipHostFree(c->wbat_pin);
+    if (c->rbatch_dev) hipFree(c->rbatch_dev);
+    if (c->rbatch_pin) hipHostFree(c->rbatch_pin);
     for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
@@ -3977,6 +3992,241 @@ int tdlo_rig_to_cloud(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, int K,
     return rig_to_cloud_impl(c, slot, cams, K, rows, cols, leaf_size, X_out, x_capacity, n_out, n_raw_out, nullptr, 0, nullptr);
 }
 
+// ---- rigs for F slots in one call (include/trackdlo_hip.h: tdlo_rig_to_cloud_batch, tdlo_tracker_frames_from_rig_batch) ---------------------------------
+// From this many frames on the calls are batch launches; below it they loop over the single calls (the same bits).  The rule is the one of every batch route
+// here (scripts/gpu_rig_batch.py -> profiles/rig_batch_ab.txt): the smallest F from which on every batch value lies below every single-calls value on the
+// lines a call stands for, 33 where no F up to 32 qualifies.  Measured, rope frames of 45 nodes under K = 3 cameras, F = 1 .. 32:
+//   kRigBatchMin         lines (a) - (c): ropes that share the rig's planes from device and from pageable host planes, rigs with planes of their own.  At
+//                        640 x 480 (25 429 kept pixels) the batch loses at 1 and 2 frames (a table upload and a one-workgroup finish where the single call
+//                        has a team of eight: 0.137 against 0.068 ms) and wins every value from 4 on (32 ropes under one rig: 0.70 against 2.18 ms from
+//                        device planes, 2.05 against 6.16 ms from host planes).  At 1280 x 720 the three cameras keep 96 805 pixels: the kernel passes every
+//                        frame on, the call is its launch plus the F single calls and loses by 3 - 9 % at every F.  No F qualifies at both sizes: 33, BY
+//                        DEFAULT tdlo_rig_to_cloud_batch LOOPS OVER THE SINGLE CALLS; a cell whose ropes keep fewer than 32 704 pixels sets the variable
+//   kRigBatchTrackerMin  line (d), against F x tdlo_tracker_frame_from_rig: every value wins from 4 trackers on at both sizes (32 trackers: 2.26 against
+//                        5.69 ms; at 1280 x 720, where the clouds take the single route, the batched pre-pass and step still win: 32.6 against 35.6 ms)
+// TDLO_RIG_BATCH_MIN=n, read when the context is made, overrides both.
+constexpr int kRigBatchMin = 33;
+constexpr int kRigBatchTrackerMin = 4;
+static int rig_batch_min(const tdlo_ctx *c, bool tracker) { return c->rig_batch_min ? c->rig_batch_min : (tracker ? kRigBatchTrackerMin : kRigBatchMin); }
+
+int tdlo_debug_rig_batch_plan(const int *slot, const int *K, int F, int Fcap, int rows, int cols, const unsigned long long *plane, long long budget,
+                              long long *state_off, long long *cams_off, long long *plane_off, long long *tiles_off, long long *pts_off, long long *cnt_off,
+                              int *launch_of, long long *table_off, long long *total, int *n_planes, int *n_launches) {
+    if (rows < 1 || cols < 1 || (long long)rows * cols > (1ll << 26)) return TDLO_E_INVALID;
+    return rig_batch_plan(slot, K, F, Fcap, rows * cols, plane, (long long)rig_batch_desc_bytes(), (long long)sizeof(RigCam), budget > 0 ? budget : kRigBatchBudget,
+                          state_off, cams_off, plane_off, tiles_off, pts_off, cnt_off, launch_of, table_off, total, n_planes, n_launches) ? TDLO_E_INVALID : TDLO_OK;
+}
+
+int tdlo_debug_rig_batch_arena(tdlo_ctx *c, const void **base, long long *bytes) {
+    if (!c || !base || !bytes) return TDLO_E_INVALID;
+    *base = c->rbatch_dev; *bytes = (long long)c->rbatch_dev_cap;
+    return TDLO_OK;
+}
+
+static const void *rig_camera_plane(const tdlo_rig_camera &cam, bool colour, int q) {
+    return q == 0 ? (const void *)cam.depth : q == 1 ? (colour ? nullptr : (const void *)cam.mask) : q == 2 ? (colour ? (const void *)cam.colour : nullptr)
+                                                     : (colour ? (const void *)cam.occluder : nullptr);
+}
+
+// Everything that refuses a rig batch as a whole; nothing of the context or the slots is touched.  where[f][k]: which planes of frame f's camera k lie in device memory
+static int rig_batch_refusal(tdlo_ctx *c, const tdlo_rig_frame *frames, int F, int rows, int cols, double leaf_size, std::vector<std::vector<BatchPlanes>> &where) {
+    if (!frames || F < 1) return fail(c, TDLO_E_INVALID, "rig batch: no frames");
+    if (F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "rig batch: more frames than the context has slots");
+    for (int f = 0; f < F; ++f) {
+        if (frames[f].slot < 0 || frames[f].slot >= (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "bad slot");
+        for (int g = 0; g < f; ++g) if (frames[g].slot == frames[f].slot) return fail(c, TDLO_E_INVALID, "rig batch: a slot is named twice");
+        if (const char *why = rig_fault(frames[f].cams, frames[f].K, rows, cols, leaf_size)) return fail(c, TDLO_E_INVALID, "rig batch: frame " + std::to_string(f) + ": " + why);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    where.assign(F, std::vector<BatchPlanes>());
+    const size_t P = (size_t)rows * cols;
+    for (int f = 0; f < F; ++f) {
+        if (int rc = rig_refusal(c, frames[f].slot, frames[f].cams, frames[f].K, rows, cols, leaf_size, where[f])) return rc;
+        const bool colour = rig_camera_colour(frames[f].cams[0]);
+        for (int k = 0; k < frames[f].K; ++k)
+            for (int q = 0; q < 4; ++q) {      // (a device plane is copied device to device: it must lie in neither arena a frame of this call may be served from)
+                const char *p = (const char *)rig_camera_plane(frames[f].cams[k], colour, q);
+                if (!p || !where[f][k].dev[q]) continue;
+                const size_t len = (q == 0 ? 2 : q == 2 ? 3 : 1) * P;
+                const char *a0 = (const char *)c->rbatch_dev, *b0 = (const char *)c->cbat_img;
+                if ((a0 && p < a0 + c->rbatch_dev_cap && a0 < p + len) || (b0 && p < b0 + c->cbat_img_cap && b0 < p + len))
+                    return fail(c, TDLO_E_INVALID, "rig batch: a device plane overlaps the batch arena");
+            }
+    }
+    return TDLO_OK;
+}
+
+// the arena (device) and the pinned block of a rig batch, grown on demand; the state blocks armed
+static int rig_batch_room(tdlo_ctx *c, size_t dev_bytes, size_t pin_bytes) {
+    hipStream_t st = c->stream;
+    if (dev_bytes > c->rbatch_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->rbatch_dev) hipFree(c->rbatch_dev);
+        c->rbatch_dev = nullptr; c->rbatch_dev_cap = 0; c->rbatch_armed = false;
+        HIPCHK(c, hipMalloc(&c->rbatch_dev, dev_bytes));
+        c->rbatch_dev_cap = dev_bytes;
+    }
+    if (pin_bytes > c->rbatch_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->rbatch_pin) hipHostFree(c->rbatch_pin);
+        c->rbatch_pin = nullptr; c->rbatch_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->rbatch_pin, pin_bytes, hipHostMallocDefault));
+        std::memset(c->rbatch_pin, 0, pin_bytes);
+        c->rbatch_pin_cap = pin_bytes;
+    }
+    if (!c->rbatch_armed) {
+        HIPCHK(c, view_batch_arm(c->rbatch_dev, (int)c->slots.size(), st));      // (the same state block: box minima ~0, everything else 0)
+        c->rbatch_armed = true;
+    }
+    return TDLO_OK;
+}
+
+// tracker: the call stands behind the tracker entrance (rig_batch_min)
+static int rig_batch_impl(tdlo_ctx *c, const tdlo_rig_frame *frames, int F, int rows, int cols, double leaf_size, int *n_out, int *n_raw_out, int *rc_each, bool tracker) {
+    std::vector<std::vector<BatchPlanes>> where;
+    int rc = rig_batch_refusal(c, frames, F, rows, cols, leaf_size, where);
+    if (rc) return rc;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    auto finish = [&]() {
+        if (n_out) std::copy(n.begin(), n.end(), n_out);
+        if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+        if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+        for (int f = 0; f < F; ++f) if (rcs[f]) return rcs[f];
+        return (int)TDLO_OK;
+    };
+    auto single = [&](int f) {
+        rcs[f] = rig_to_cloud_impl(c, frames[f].slot, frames[f].cams, frames[f].K, rows, cols, leaf_size, nullptr, 0, &n[f], &nraw[f], nullptr, 0, nullptr);
+    };
+    if (F < rig_batch_min(c, tracker)) {
+        for (int f = 0; f < F; ++f) single(f);
+        return finish();
+    }
+    // ---- who goes into the launches, the frames that bring masks in front of the frames that bring colour: the others are passed on to the single call, after them
+    const int P = rows * cols, Tc = rig_tiles_per_camera(P);
+    std::vector<int> in, passed;
+    for (int kind = 0; kind < 2; ++kind)
+        for (int f = 0; f < F; ++f) {
+            if ((rig_camera_colour(frames[f].cams[0]) ? 1 : 0) != kind) continue;
+            if (c->cloud_fused_on && (long long)frames[f].K * Tc <= kRigBatchMaxTiles) in.push_back(f);
+            else { passed.push_back(f); ++c->rbatch_route[1]; }
+        }
+    const int Fi = (int)in.size();
+    if (Fi > 0) {
+        hipStream_t st = c->stream;
+        if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+        // ---- the arena by the plan; the pinned block: result words, frame table, camera table (the two tables one behind the other, as in the arena)
+        std::vector<int> slots(Fi), Ks(Fi), kinds(Fi), launch_of(Fi);
+        std::vector<unsigned long long> keys;
+        for (int j = 0; j < Fi; ++j) {
+            const tdlo_rig_frame &fr = frames[in[j]];
+            slots[j] = fr.slot; Ks[j] = fr.K; kinds[j] = rig_camera_colour(fr.cams[0]) ? 1 : 0;
+            for (int k = 0; k < fr.K; ++k)
+                for (int q = 0; q < 4; ++q) keys.push_back((unsigned long long)(uintptr_t)rig_camera_plane(fr.cams[k], kinds[j] != 0, q));
+        }
+        const size_t cams_total = keys.size() / 4;
+        std::vector<long long> o_state(Fi), o_cams(Fi), o_plane(keys.size()), o_tiles(Fi), o_pts(Fi), o_cnt(Fi);
+        long long o_table = 0, total = 0;
+        const size_t desc = rig_batch_desc_bytes();
+        if (rig_batch_plan(slots.data(), Ks.data(), Fi, (int)c->slots.size(), P, keys.data(), (long long)desc, (long long)sizeof(RigCam), kRigBatchBudget, o_state.data(),
+                           o_cams.data(), o_plane.data(), o_tiles.data(), o_pts.data(), o_cnt.data(), launch_of.data(), &o_table, &total, nullptr, nullptr))
+            return fail(c, TDLO_E_INVALID, "rig batch: no plan for these frames");
+        auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t p_tab = r256(2 * sizeof(unsigned long long) * (size_t)Fi), tab_bytes = r256(desc * (size_t)Fi), cam_bytes = sizeof(RigCam) * cams_total;
+        if ((rc = rig_batch_room(c, (size_t)total, p_tab + tab_bytes + r256(cam_bytes)))) return rc;
+        char *dev = (char *)c->rbatch_dev, *pin = c->rbatch_pin;
+        unsigned long long *res = (unsigned long long *)pin;
+        std::memset(res, 0, 2 * sizeof(unsigned long long) * (size_t)Fi);      // (no word may look like this call's epoch)
+        // ---- the slots: an EMPTY slot is sized for every result the kernel can leave, as the single call sizes it; a slot with a resident cloud is launched
+        // with its capacity as it is -- growing it frees the cloud, which a refused frame must find intact -- and the capacity report sends the frame on
+        for (int f : in) {
+            Slot &s = c->slots[frames[f].slot];
+            if (s.N0 == 0 && (rc = ensure_points(c, s, cloud_fused_max_points()))) return rc;
+        }
+        // ---- every distinct plane once, the camera records, the descriptors
+        {
+            long long copied = -1;                               // (distinct planes take ascending offsets in the order of their first entries)
+            size_t e = 0;
+            for (int j = 0; j < Fi; ++j) {
+                const tdlo_rig_frame &fr = frames[in[j]];
+                for (int k = 0; k < fr.K; ++k)
+                    for (int q = 0; q < 4; ++q, ++e) {
+                        if (o_plane[e] < 0 || o_plane[e] <= copied) continue;
+                        copied = o_plane[e];
+                        const size_t len = (q == 0 ? 2 : q == 2 ? 3 : 1) * (size_t)P;
+                        const hipError_t er = hipMemcpyAsync(dev + o_plane[e], (const void *)(uintptr_t)keys[e], len,
+                                                             where[in[j]][k].dev[q] ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+                        if (er != hipSuccess) { (void)hipStreamSynchronize(st); HIPCHK(c, er); }
+                    }
+            }
+        }
+        RigCam *h_cam = (RigCam *)(pin + p_tab + tab_bytes);
+        std::vector<RigBatchFrameHost> bf(Fi);
+        {
+            size_t e = 0, k0 = 0;
+            for (int j = 0; j < Fi; ++j) {
+                const tdlo_rig_frame &fr = frames[in[j]];
+                for (int k = 0; k < fr.K; ++k, e += 4) {
+                    RigCam &r = h_cam[k0 + k];
+                    rig_camera_record(fr.cams[k], r);
+                    r.depth = (const unsigned short *)(dev + o_plane[e]);
+                    r.mask = o_plane[e + 1] >= 0 ? (const unsigned char *)(dev + o_plane[e + 1]) : nullptr;
+                    r.colour = o_plane[e + 2] >= 0 ? (const unsigned char *)(dev + o_plane[e + 2]) : nullptr;
+                    r.occluder = o_plane[e + 3] >= 0 ? (const unsigned char *)(dev + o_plane[e + 3]) : nullptr;
+                }
+                k0 += fr.K;
+                Slot &s = c->slots[fr.slot];
+                RigBatchFrameHost &b = bf[j];
+                b = RigBatchFrameHost{};
+                b.cams_dev = dev + o_cams[j]; b.K = fr.K;
+                b.state = dev + o_state[j]; b.tiles = dev + o_tiles[j]; b.pts = dev + o_pts[j]; b.tcnt = dev + o_cnt[j];
+                b.X = s.Xraw; b.cap = s.cap_points; b.res = res + 2 * (size_t)j;
+            }
+        }
+        if (++c->cloud_epoch == 0) ++c->cloud_epoch;
+        const unsigned epoch = c->cloud_epoch;
+        const float inv = 1.0f / (float)leaf_size;
+        auto enqueue = [&]() -> hipError_t {
+            if (const hipError_t e = rig_batch_table(bf.data(), Fi, P, cols, inv, epoch, pin + p_tab)) return e;
+            if (const hipError_t e = hipMemcpyAsync(dev + o_table, pin + p_tab, tab_bytes + cam_bytes, hipMemcpyHostToDevice, st)) return e;
+            // a launch per kind and budget group, back to back: the frames [a, b) of one group and one kind stand together in the table
+            for (int a = 0; a < Fi;) {
+                int b = a, Tmax = 0;
+                while (b < Fi && launch_of[b] == launch_of[a] && kinds[b] == kinds[a]) { Tmax = std::max(Tmax, Ks[b] * Tc); ++b; }
+                if (const hipError_t e = launch_cloud_rig_batch(dev + o_table, a, b - a, Tmax, kinds[a] != 0, st)) return e;
+                a = b;
+            }
+            return hipSuccess;
+        };
+        {
+            hipError_t e = enqueue();
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            else (void)hipStreamSynchronize(st);                  // (whatever was enqueued has left the caller's planes and the pinned block)
+            if (e != hipSuccess) { c->rbatch_armed = false; HIPCHK(c, e); }
+        }
+        for (int j = 0; j < Fi; ++j) {
+            const int f = in[j];
+            Slot &s = c->slots[frames[f].slot];
+            const unsigned long long w0 = __atomic_load_n(res + 2 * (size_t)j, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(res + 2 * (size_t)j + 1, __ATOMIC_RELAXED);
+            const unsigned status = (unsigned)w0;
+            if ((unsigned)(w0 >> 32) != epoch) { c->rbatch_armed = false; rcs[f] = fail(c, TDLO_E_HIP, "the stream drained, but a frame of the rig batch did not report"); continue; }
+            nraw[f] = (int)(unsigned)(w1 >> 32);
+            const int nf = (int)(unsigned)w1;
+            if (status == 1u) {
+                if (nf < 0 || nf > s.cap_points || nf > nraw[f]) { rcs[f] = fail(c, TDLO_E_HIP, "voxel grid produced an impossible point count"); continue; }
+                n[f] = nf; s.N0 = nf; s.sorted_valid = false; ++c->rbatch_route[0];
+            } else { nraw[f] = 0; passed.push_back(f); ++c->rbatch_route[1]; }      // not taken (2); the slot would have to grow (3: the single call does that)
+        }
+    }
+    std::sort(passed.begin(), passed.end());
+    for (int f : passed) single(f);
+    return finish();
+}
+
+int tdlo_rig_to_cloud_batch(tdlo_ctx *c, const tdlo_rig_frame *frames, int F, int rows, int cols, double leaf_size, int *n_out, int *n_raw_out, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    return rig_batch_impl(c, frames, F, rows, cols, leaf_size, n_out, n_raw_out, rc_each, false);
+}
+
 // ---- cloud views for F slots in one call (include/trackdlo_hip.h: tdlo_cloud_view_voxel_grid_batch, tdlo_set_cloud_view_batch) --------------------------
 // From this many frames on the calls are one batch launch each; below it they loop over the single calls (the same bits).  Set from
 // profiles/view_batch_ab.txt and view_batch_ab_run2.txt by the rule "the smallest F from which on every batch value lies below every single-calls value", taken
@@ -5124,7 +5374,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 48) return -1;
+    if (!c || which < 0 || which > 50) return -1;
+    if (which >= 49) return c->rbatch_route[which - 49];
     if (which == 48) return c->prologue_scan_calls;
     if (which >= 45) return c->rig_route[which - 45];
     if (which >= 42) return c->fvbat_route[which - 42];
@@ -6256,6 +6507,64 @@ int tdlo_tracker_frames_from_cloud_view_batch(tdlo_tracker *const *trackers, int
     if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "the view keeps no point: no cloud for this frame") : rcs[i];
+    return TDLO_OK;
+}
+
+// The frames of F trackers from F rigs: tdlo_rig_to_cloud_batch into the trackers' slots (frames[i].slot is not read), then tdlo_tracker_frame_batch on the
+// trackers that got a cloud.  The self-occlusion test is one camera's: a tracker with the switch on refuses the call, as tdlo_tracker_frame_from_rig refuses it
+int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, const tdlo_rig_frame *frames, int rows, int cols, double leaf_size, double d_vis,
+                                       int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out,
+                                       tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (!frames) return fail(c, TDLO_E_INVALID, "null frames");
+    for (int i = 0; i < F; ++i)
+        if (trackers[i]->painter_on) return fail(c, TDLO_E_INVALID, "a rig frame with the self-occlusion switch on: that test is one camera's");
+    const int M = trackers[0]->M;
+    std::vector<tdlo_rig_frame> fr(frames, frames + F);
+    for (int i = 0; i < F; ++i) fr[i].slot = trackers[i]->slot;
+    std::vector<int> n(F, 0), nraw(F, 0), rcs(F, 0);
+    int rc = rig_batch_impl(c, fr.data(), F, rows, cols, leaf_size, n.data(), nraw.data(), rcs.data(), true);
+    if (n_out) std::copy(n.begin(), n.end(), n_out);
+    if (n_raw_out) std::copy(nraw.begin(), nraw.end(), n_raw_out);
+    bool any = false;
+    for (int r : rcs) any = any || r != 0;
+    if (rc && !any) return rc;                     // (refused as a whole: nothing was touched)
+    std::vector<tdlo_tracker *> sub;
+    std::vector<int> who;
+    for (int i = 0; i < F; ++i) {
+        if (!rcs[i] && n[i] == 0) rcs[i] = TDLO_E_EMPTY;      // the rig keeps no pixel: no cloud, the tracker is left as it is
+        if (!rcs[i]) { trackers[i]->frame_seen = false; sub.push_back(trackers[i]); who.push_back(i); }      // (after a rig frame the tracker holds no camera of its own)
+    }
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
+    if (!sub.empty()) {
+        const int Fs = (int)sub.size();
+        std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
+        std::vector<tdlo_stats> sst(2 * (size_t)Fs);
+        std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+        const int brc = tdlo_tracker_frame_batch(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data());
+        bool sany = false;
+        for (int r : src) sany = sany || r != 0;
+        for (int k = 0; k < Fs; ++k) {
+            const int i = who[k];
+            rcs[i] = (brc && !sany) ? brc : src[k];
+            nv[i] = snv[k]; ne[i] = sne[k];
+            std::copy(&svis[(size_t)M * k], &svis[(size_t)M * k] + M, &vis[(size_t)M * i]);
+            std::copy(&sext[(size_t)M * k], &sext[(size_t)M * k] + M, &ext[(size_t)M * i]);
+            st[2 * (size_t)i] = sst[2 * (size_t)k]; st[2 * (size_t)i + 1] = sst[2 * (size_t)k + 1];
+        }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "no pixel of the rig is kept: no cloud for this frame") : rcs[i];
     return TDLO_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "tdlo_view_load.h"
 #include "tdlo_view_lane.h"
 #include "tdlo_view_batch_plan.h"
+#include "tdlo_rig_batch_plan.h"
 #include "tdlo_rig_point.h"
 #include <cstdint>
 #include <cstdlib>
@@ -1024,6 +1025,20 @@ __global__ __launch_bounds__(kFT) void k_cloud_view_batch(const ViewBatchFrame *
     cloud_fused_body<kSrcViewAny>(a, f->form);
 }
 
+// F rigs in one launch (tdlo_rig_to_cloud_batch): grid (Tmax, F) -- Tmax the largest K_f x Tc of the launch's frames --, blockIdx.y picks the frame's descriptor
+// out of a table in device memory: rig points at the frame's own K_f camera records, rigTc and T = K_f x Tc are its own, P and cols one camera's (the call's
+// image size), and the state words, tile regions (3 x T x 4096 floats), compacted points, tile counts, destination and pinned result words belong to the frame
+// alone.  A workgroup beyond its frame's tiles leaves before any barrier; the frame's last ticket finishes it in ONE workgroup (cloud_fused_body, not the team):
+// no spin, no barrier across workgroups.  Phase A is the rig source of k_cloud_team (cloud_phase_a, tdlo_rig_point.h), so a frame's R, and behind it the same
+// words, the same stable order and the same float sums, are the single call's.
+template <bool kColour>
+__global__ __launch_bounds__(kFT) void k_cloud_rig_batch(const FusedCloud *__restrict__ table) {
+    const FusedCloud *f = table + blockIdx.y;
+    if ((int)blockIdx.x >= f->T) return;
+    const FusedCloud a = *f;
+    cloud_fused_body<kColour ? kSrcRigColour : kSrcRigMask>(a);
+}
+
 }  // namespace
 
 
@@ -1756,6 +1771,42 @@ hipError_t launch_rig_team(const void *table_dev, int K, int P, int cols, bool c
     if (const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTLds)) return e;      // (per device: see launch_cloud_fused)
     if (colour) hipLaunchKernelGGL(k_cloud_team<kSrcRigColour>, dim3(a.T), dim3(kFT), kTLds, s, a);
     else hipLaunchKernelGGL(k_cloud_team<kSrcRigMask>, dim3(a.T), dim3(kFT), kTLds, s, a);
+    return hipGetLastError();
+}
+
+// ---- k_cloud_rig_batch: where a frame's blocks lie is the host's business (tdlo_rig_batch_plan.h); the table is written to pinned memory, copied by the caller
+size_t rig_batch_desc_bytes() { return sizeof(FusedCloud); }
+static_assert(kRigBatchTile == kFPix && kRigBatchPts == kFNmax && kRigBatchMaxTiles == kFTmax, "tdlo_rig_batch_plan.h sizes a frame's blocks by these");
+
+hipError_t rig_batch_table(const RigBatchFrameHost *fr, int F, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned) {
+    if (F < 1 || P <= 0) return hipErrorInvalidValue;
+    const int Tc = rig_tiles_per_camera(P);
+    FusedCloud *tab = (FusedCloud *)table_pinned;
+    for (int f = 0; f < F; ++f) {
+        const int K = fr[f].K;
+        if (K < 1 || K > kRigMaxCams || (long long)K * Tc > kFTmax) return hipErrorInvalidValue;
+        FusedCloud a{};
+        a.P = P; a.cols = cols; a.T = K * Tc;                    // (P and cols are ONE camera's)
+        a.rig = (const RigCam *)fr[f].cams_dev; a.rigTc = Tc;
+        a.inv_leaf = inv_leaf;
+        const size_t E = (size_t)a.T * kFPix;
+        a.ex = (float *)fr[f].tiles; a.ey = a.ex + E; a.ez = a.ey + E;
+        a.state = (unsigned *)fr[f].state;
+        a.cx = (float *)fr[f].pts; a.cy = a.cx + kFNmax; a.cz = a.cy + kFNmax;
+        a.tcnt = (int *)fr[f].tcnt;
+        a.X = fr[f].X; a.cap = fr[f].cap; a.res = fr[f].res; a.epoch = epoch;
+        tab[f] = a;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_cloud_rig_batch(const void *table_dev, int first, int F, int Tmax, bool colour, hipStream_t s) {
+    if (F < 1 || first < 0 || Tmax < 1 || Tmax > kFTmax) return hipErrorInvalidValue;
+    const void *fn = colour ? (const void *)k_cloud_rig_batch<true> : (const void *)k_cloud_rig_batch<false>;
+    if (const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFLds)) return e;      // (per device: see launch_cloud_fused)
+    const FusedCloud *tab = (const FusedCloud *)table_dev + first;
+    if (colour) hipLaunchKernelGGL(k_cloud_rig_batch<true>, dim3(Tmax, F), dim3(kFT), kFLds, s, tab);
+    else hipLaunchKernelGGL(k_cloud_rig_batch<false>, dim3(Tmax, F), dim3(kFT), kFLds, s, tab);
     return hipGetLastError();
 }
 

@@ -364,6 +364,15 @@ size_t view_batch_desc_bytes();
 int view_batch_max_elements();
 hipError_t view_batch_arm(void *states, int F, hipStream_t s);
 hipError_t launch_cloud_view_batch(const ViewBatchFrameHost *frames, int F, float inv_leaf, unsigned epoch, void *table_pinned, void *table_dev, hipStream_t s);
+// k_cloud_fused over F rigs in ONE launch (k_cloud_rig_batch: grid (K_f x tiles of the frame with the most, frames); tdlo_rig_to_cloud_batch).  Per frame: its
+// K camera records in device memory (cams_dev), and the blocks tdlo_rig_batch_plan.h lays out -- state words (view_batch_arm's layout: the kernel re-arms them),
+// tile regions (3 x K x tiles x 4096 floats), compacted points, tile counts; the slot's raw cloud and two pinned words as above.  rig_batch_table writes the F
+// descriptors (rig_batch_desc_bytes() each) to pinned memory; launch_cloud_rig_batch launches the frames [first, first + F) of the table's copy in device
+// memory, all of one kind (mask or colour), Tmax the most tiles any of them has.  Reports 1 done, 2 not taken, 3 capacity.
+struct RigBatchFrameHost { const void *cams_dev; int K; void *state, *tiles, *pts, *tcnt; double *X; int cap; unsigned long long *res; };
+size_t rig_batch_desc_bytes();
+hipError_t rig_batch_table(const RigBatchFrameHost *frames, int F, int P, int cols, float inv_leaf, unsigned epoch, void *table_pinned);
+hipError_t launch_cloud_rig_batch(const void *table_dev, int first, int F, int Tmax, bool colour, hipStream_t s);
 // colour != nullptr above: `mask` is not read, the kernel forms its mask words from the colour image (tdlo_colour_*).  The segmentation on its own
 // (k_colour_mask): mask (rows x cols bytes, 0 / 255) and, when hsv != nullptr, the HSV image (3 bytes a pixel), both device memory padded to 16 bytes beyond the image
 hipError_t launch_colour_mask(const CloudColour &colour, int P, unsigned char *mask, unsigned char *hsv, hipStream_t s);

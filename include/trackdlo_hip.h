@@ -800,7 +800,7 @@ int tdlo_rig_to_cloud_visibility(tdlo_ctx *ctx, int slot, const tdlo_rig_camera 
 /* A whole frame from a rig: tdlo_rig_to_cloud_visibility with the tracker's own nodes, threshold and geodesic coordinates, then tdlo_tracker_tracking_step on
  * the cloud left in the tracker's slot, as tdlo_tracker_frame_from_depth composes its two -- the bits of the calls made by hand.  An empty cloud or no visible
  * node is TDLO_E_EMPTY with the tracker untouched.  A tracker whose self-occlusion switch is on (tdlo_tracker_set_self_occlusion) is refused with
- * TDLO_E_INVALID: that test is one camera's, and for a rig it is undefined.  A refused rig leaves tracker and slot as they were. */
+ * TDLO_E_INVALID: that test is one camera's; the test for a rig is tdlo_tracker_set_rig_self_occlusion, below.  A refused rig leaves tracker and slot as they were. */
 int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size, double d_vis,
                                 int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                 int *n_out, int *n_raw_out, tdlo_stats *stats);
@@ -864,6 +864,60 @@ int tdlo_debug_rig_batch_plan(const int *slot, const int *K, int F, int Fcap, in
                               long long *state_off, long long *cams_off, long long *plane_off, long long *tiles_off, long long *pts_off, long long *cnt_off,
                               int *launch_of, long long *table_off, long long *total, int *n_planes, int *n_launches);
 int tdlo_debug_rig_batch_arena(tdlo_ctx *ctx, const void **base, long long *bytes);
+
+/* ---- self-occlusion under a rig: a node is hidden only if every camera that sees it hides it ------------------ */
+/* Where a rope crosses itself, the strand one camera sees painted over usually lies in plain view of another.  tdlo_self_occlusion_visible is one camera's test
+ * (one projection matrix); THIS is the test for a rig.  Inputs: the nodes Y (M x 3 doubles, column-major as everywhere, in the rig's common frame); per camera k
+ * the intrinsics fx, fy, cx, cy of cams[k] (nothing else of a tdlo_rig_camera is read) and an optional 3 x 4 row-major matrix rig_to_cam_k = [A | b] -- the
+ * argument rig_to_cam is NULL (every camera frame is the rig frame) or K x 12 doubles, where a camera whose 12 entries are ALL NaN has no matrix --; the image
+ * size rows x cols; dlo_pixel_width w; node_dist[M]; visibility_threshold.
+ * PER CAMERA k:
+ *   1. camera-frame node: x_c = ((A00 x + A01 y) + A02 z) + b0, likewise y_c, z_c -- double, every product and sum rounded on its own, left to right, never fused
+ *      (the discipline of the rig's point list above); without a matrix the node as it is.
+ *   2. pixel: u = fx x_c + cx z_c, v = fy y_c + cy z_c, qc = u / z_c, qr = v / z_c: tdlo_self_occlusion_visible's projection with the matrix
+ *      {fx,0,cx,0, 0,fy,cy,0, 0,0,1,0}, in the same order of operations.  The node is DRAWABLE in k when z_c > 0 and both quotients lie in (-8193, 8192) (the
+ *      rule of the result image; NaN and infinities fail it); its pixel is then ((int)qc, (int)qr).  It is SEEN by k when it is drawable and 0 <= c < cols,
+ *      0 <= r < rows.  (The single test casts before it checks; this one checks first.)
+ *   3. painted edges: edge i joins nodes i and i + 1 and is PAINTED in k when both ends are drawable; its key is sqrt(mx^2 + my^2 + mz^2) of the camera-frame
+ *      mid-point ((a + b) / 2 per coordinate).  Painted edges are ranked by (key, index) ascending: nearest first, equal keys by ascending index.
+ *   4. first_k(m): the smaller rank of node m's painted incident edges; the number of painted edges if it has none.
+ *   5. node m is HIDDEN in k when it is drawable and some painted edge of rank < first_k(m) covers its pixel -- within w / 2 of the segment between the edge's
+ *      end pixels, in exact integer arithmetic, as in the single test.
+ * THE RIG'S VERDICT: node m is visible when node_dist[m] <= visibility_threshold (a NaN distance fails) AND at least one camera sees it and does not hide it.
+ * A camera that does not see a node has no say: without that rule a camera looking elsewhere would vouch for every node.  The set is ascending; the extended set
+ * is tdlo_extend_visible_nodes over it, as everywhere.  Camera order does not matter to the set; it does to the per-camera words.
+ * CONSEQUENCE (tests/test_rig_painter_ref.py): K = 1 without a matrix and every node's pixel inside the image gives tdlo_self_occlusion_visible's set on the
+ * same Y with the matrix above, the same width, distances and threshold.  Parity against OpenCV's rasteriser stays UNPINNED, as for the single test.
+ * seen_words / hidden_words (optional): K x ceil(M / 32) words each, bit m % 32 of word m / 32 of camera k; in the batch call frame after frame, packed.
+ *
+ * tdlo_rig_self_occlusion_visible: the host statement (csrc/tdlo_painter_host.cpp through csrc/tdlo_painter_lane.h, the header the kernel compiles; no
+ * context, no GPU).  tdlo_rig_self_occlusion_batch: F frames -- each its own nodes, rig, width, distances and threshold -- in ONE upload of tables and nodes,
+ * ONE launch of k_rig_painter_batch (csrc/tdlo_painter.hip: grid (largest K_f, F), a workgroup is one (camera, frame) job and fetches its frame's record from a
+ * table in device memory; a workgroup beyond its frame's K_f leaves at once; no workgroup waits for another), one wait; the words arrive in pinned memory and
+ * the host forms union, threshold and order.  visible_nodes: F rows of Mmax entries, Mmax the largest M of the call.  Always the kernel: the same sets and
+ * words as the host statement, bit for bit.
+ * Both are refused as a whole with TDLO_E_INVALID before anything is touched: F < 1; M outside 1 .. 1024; K outside 1 .. 64; dlo_pixel_width outside 1 .. 255;
+ * rows or cols outside 1 .. 8192; an intrinsic or a matrix entry that is not finite (a camera's 12 NaN apart); fx or fy equal to 0; a null Y, cams or node_dist.
+ * tdlo_debug_route_count 51 counts the (camera, frame) jobs the kernel served, 52 the jobs the host statement did inside a tracker call.
+ *
+ * tdlo_tracker_set_rig_self_occlusion (K = 0: off, the default; the matrices are copied): with it on, tdlo_tracker_frame_from_rig and
+ * tdlo_tracker_frames_from_rig_batch replace the pre-pass's visible set by the rig's verdict -- on the tracker's nodes as they stand before the step, with the
+ * pre-pass's node_dist, the call's cameras, rows and cols --, then fill the gaps, then step.  A rig frame whose K differs from the switch's, or that the test
+ * refuses, is TDLO_E_INVALID with tracker, slot and counters as they were.  The single switch (tdlo_tracker_set_self_occlusion) keeps refusing rig calls, with
+ * or without this one.  Every call that is not a rig frame call ignores the switch; tdlo_tracker_render_result* draw every node after a rig frame.
+ * In the batch call the kernel is enqueued in front of the batched pre-pass and its words are read after that call's wait: no wait is added.
+ * Route: a tracker call with at least kRigPainterMin (camera, frame) jobs takes the kernel, below it the host statement; the same sets.  NOT MEASURED YET
+ * (scripts/gpu_rig_painter.py writes profiles/rig_painter_ab.txt; the rule set beforehand: the smallest F K from which the kernel wins on every measured value
+ * at M = 45 and M = 300, else a value above any batch): kRigPainterMin is above any batch, BY DEFAULT THE TRACKER CALLS RUN THE HOST STATEMENT.
+ * TDLO_RIG_PAINTER_MIN=n (read when the context is made) overrides. */
+typedef struct { const double *Y; int M; const tdlo_rig_camera *cams; const double *rig_to_cam; /* NULL or K x 12 */ int K; int dlo_pixel_width;
+                 const double *node_dist; double visibility_threshold; } tdlo_rig_painter_frame;
+int tdlo_rig_self_occlusion_visible(const double *Y, int M, const tdlo_rig_camera *cams, const double *rig_to_cam, int K, int rows, int cols,
+                                    int dlo_pixel_width, const double *node_dist, double visibility_threshold,
+                                    int *visible_nodes, int *n_vis, unsigned *seen_words /* NULL or K x ceil(M / 32) */, unsigned *hidden_words);
+int tdlo_rig_self_occlusion_batch(tdlo_ctx *ctx, int F, const tdlo_rig_painter_frame *frames, int rows, int cols,
+                                  int *visible_nodes /* F x Mmax */, int *n_vis /* F */, unsigned *seen_words, unsigned *hidden_words);
+int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_cam /* NULL or K x 12 */, int K, int dlo_pixel_width);
 
 /* ---- cloud views for many slots in one call ----------------------------------------------------------- */
 /* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
@@ -1299,6 +1353,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * tdlo_rig_to_cloud for their slot -- by the kernel (more than 32 704 kept points, too many cell bits, pass-through, the refusals 8 and 9, a result the slot's
  * capacity does not hold), or by the host (more than 4095 tiles, TDLO_CLOUD_FUSED=0); frames of a batch below the crossover count in 45 - 47 alone, and a
  * frame passed on counts there as well.
+ * 51 / 52: (camera, frame) jobs of the self-occlusion test under a rig served by k_rig_painter_batch (tdlo_rig_self_occlusion_batch, and the rig tracker calls
+ * from kRigPainterMin jobs on) / done by the host statement inside a rig tracker call.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -104,6 +104,11 @@ class RigFrameC(C.Structure):                      # tdlo_rig_frame: a slot and 
     _fields_ = [("slot", C.c_int), ("cams", C.c_void_p), ("K", C.c_int)]
 
 
+class RigPainterFrameC(C.Structure):               # tdlo_rig_painter_frame: one rope's nodes under one rig for the self-occlusion test under a rig
+    _fields_ = [("Y", C.c_void_p), ("M", C.c_int), ("cams", C.c_void_p), ("rig_to_cam", C.c_void_p), ("K", C.c_int), ("dlo_pixel_width", C.c_int),
+                ("node_dist", C.c_void_p), ("visibility_threshold", C.c_double)]
+
+
 class ViewFrame(C.Structure):                      # tdlo_view_frame: a slot, the cloud view it takes, its N and selection bytes (NULL: every element)
     _fields_ = [("slot", C.c_int), ("view", C.c_void_p), ("N", C.c_int), ("select", C.c_void_p)]
 
@@ -148,6 +153,7 @@ SYMBOLS = [
     "tdlo_frame_views_to_cloud_batch", "tdlo_tracker_frame_views_batch", "tdlo_view_batch_images", "tdlo_debug_slot_cloud",
     "tdlo_rig_to_cloud", "tdlo_rig_to_cloud_visibility", "tdlo_tracker_frame_from_rig", "tdlo_rig_check", "tdlo_rig_points_host",
     "tdlo_rig_to_cloud_batch", "tdlo_tracker_frames_from_rig_batch", "tdlo_debug_rig_batch_plan", "tdlo_debug_rig_batch_arena",
+    "tdlo_rig_self_occlusion_visible", "tdlo_rig_self_occlusion_batch", "tdlo_tracker_set_rig_self_occlusion",
 ]
 
 _lib = None
@@ -359,6 +365,10 @@ def load_library(path: str | None = None):
         lib.tdlo_tracker_frames_from_rig_batch.argtypes = [vp, ci, vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.tdlo_debug_rig_batch_plan.argtypes = [vp, vp, ci, ci, ci, ci, vp, ll, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ll), C.POINTER(ll), C.POINTER(ci), C.POINTER(ci)]
         lib.tdlo_debug_rig_batch_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(ll)]
+    if hasattr(lib, "tdlo_rig_self_occlusion_visible"):
+        lib.tdlo_rig_self_occlusion_visible.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, vp, cd, vp, C.POINTER(ci), vp, vp]
+        lib.tdlo_rig_self_occlusion_batch.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
+        lib.tdlo_tracker_set_rig_self_occlusion.argtypes = [vp, vp, ci, ci]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -1048,6 +1058,41 @@ class Context:
     def rig_batch_route_counts(self):
         """[frames the rig batch launch served, frames passed on to the single call] (tdlo_debug_route_count 49 / 50)."""
         return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (49, 50)]
+
+    def rig_self_occlusion_batch(self, frames, rows, cols, words=False):
+        """tdlo_rig_self_occlusion_batch: the self-occlusion test under a rig for F frames in one launch of k_rig_painter_batch.  frames: tuples
+        (Y [M x 3], cams, rig_to_cam, dlo_pixel_width, node_dist, visibility_threshold) with cams and rig_to_cam as rig_self_occlusion_visible takes them;
+        frames may differ in M and in the number of cameras.  Returns the visible indices per frame; with words=True also the lists of the frames' seen and
+        hidden words, [K_f x ceil(M_f / 32)] uint32 each."""
+        frames = list(frames)
+        F = len(frames)
+        tab = (RigPainterFrameC * max(F, 1))(); keep = []
+        Ms, Ks = [], []
+        for f, (Y, cams, rig_to_cam, width, node_dist, thr) in enumerate(frames):
+            Y = _f64(Y); ct, K = _painter_cams(cams); T = _painter_matrices(rig_to_cam, K); nd = np.ascontiguousarray(node_dist, dtype=np.float64)
+            keep += [Y, ct, T, nd]
+            tab[f].Y = Y.ctypes.data; tab[f].M = Y.shape[0]; tab[f].cams = C.cast(ct, C.c_void_p).value; tab[f].rig_to_cam = None if T is None else T.ctypes.data
+            tab[f].K = K; tab[f].dlo_pixel_width = int(width); tab[f].node_dist = nd.ctypes.data; tab[f].visibility_threshold = float(thr)
+            Ms.append(Y.shape[0]); Ks.append(K)
+        Mmax = max(Ms + [1])
+        nw = [K * ((M + 31) // 32) for K, M in zip(Ks, Ms)]
+        vis = np.zeros((max(F, 1), Mmax), dtype=np.int32); nv = np.zeros(max(F, 1), dtype=np.int32)
+        seen = np.zeros(max(sum(nw), 1), dtype=np.uint32); hidden = np.zeros_like(seen)
+        rc = self.lib.tdlo_rig_self_occlusion_batch(self.h, F, C.cast(tab, C.c_void_p), int(rows), int(cols), _ptr(vis), _ptr(nv),
+                                                    _ptr(seen) if words else None, _ptr(hidden) if words else None)
+        del keep
+        self._chk(rc)
+        out = [vis[f, :nv[f]].copy() for f in range(F)]
+        if not words:
+            return out
+        off = np.concatenate(([0], np.cumsum(nw))).astype(int)
+        cut = lambda a: [a[off[f]:off[f + 1]].reshape(Ks[f], -1).copy() for f in range(F)]
+        return out, cut(seen), cut(hidden)
+
+    def rig_painter_route_counts(self):
+        """[(camera, frame) jobs of the self-occlusion test under a rig served by the kernel, jobs done by the host statement inside a rig tracker call]
+        (tdlo_debug_route_count 51 / 52)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (51, 52)]
 
     def rig_batch_arena(self):
         """(address, bytes) of the rig-batch arena as it stands (tdlo_debug_rig_batch_arena; (0, 0) before the first batch launch)."""
@@ -1777,6 +1822,12 @@ class trackdlo:
         pj = None if proj is None else np.ascontiguousarray(proj, dtype=np.float64).reshape(12)
         self.ctx._chk(self.ctx.lib.tdlo_tracker_set_self_occlusion(self.h, _ptr(pj), int(dlo_pixel_width)))
 
+    def set_rig_self_occlusion(self, rig_to_cam, K, dlo_pixel_width=0):
+        """frame_from_rig / frames_from_rig_batch replace the pre-pass's visible set by the self-occlusion test under a rig of K cameras
+        (tdlo_tracker_set_rig_self_occlusion; rig_to_cam: None, or per camera a 3 x 4 matrix or None; the matrices are copied).  K = 0: off (default)."""
+        T = _painter_matrices(rig_to_cam, int(K)) if K else None
+        self.ctx._chk(self.ctx.lib.tdlo_tracker_set_rig_self_occlusion(self.h, _ptr(T), int(K), int(dlo_pixel_width)))
+
     def frame_from_depth(self, depth, mask, fx, fy, cx, cy, leaf_size=0.008, d_vis=0.06):
         """The ROS node's callback from the images to the nodes (trackdlo_node.cpp:195-369) in one call: cloud + voxel grid + visibility pre-pass (one
         launch), tracking_step on the resident cloud.  depth / mask: rows x cols uint16 / uint8 arrays (the context's image buffers are read in place).
@@ -2152,6 +2203,52 @@ def self_occlusion_visible(Y, proj, dlo_pixel_width, node_dist, visibility_thres
     if rc:
         raise TdloError(rc, "tdlo_self_occlusion_visible")
     return v[:nv.value].copy()
+
+
+def _painter_cams(cams):
+    """tdlo_rig_camera table for the self-occlusion test under a rig, which reads the intrinsics alone: cams are (fx, fy, cx, cy) tuples or RigCamera objects."""
+    cams = list(cams)
+    tab = (RigCameraC * max(len(cams), 1))()
+    for k, cm in enumerate(cams):
+        tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = (float(v) for v in (cm.cam if hasattr(cm, "cam") else cm))
+    return tab, len(cams)
+
+
+def _painter_matrices(rig_to_cam, K):
+    """rig_to_cam as the library takes it: None, or K x 12 float64 -- from a (K, 3, 4) / (K, 12) array, or a list whose members are a 3 x 4 matrix or None
+    (that camera's frame is the rig frame: 12 NaN)."""
+    if rig_to_cam is None:
+        return None
+    T = np.full((K, 12), np.nan)
+    if len(rig_to_cam) != K:
+        raise ValueError("rig_to_cam: one entry per camera")
+    for k, t in enumerate(rig_to_cam):
+        if t is not None:
+            t = np.asarray(t, dtype=np.float64)
+            if t.shape not in ((3, 4), (12, )):
+                raise ValueError("rig_to_cam: 3 x 4 matrices [A | b], or their 12 entries row by row")
+            T[k] = t.reshape(12)
+    return T
+
+
+def rig_self_occlusion_visible(Y, cams, rig_to_cam, rows, cols, dlo_pixel_width, node_dist, visibility_threshold, words=False):
+    """tdlo_rig_self_occlusion_visible, the host statement of the self-occlusion test under a rig (no context, no GPU; parity against OpenCV's rasteriser
+    unpinned): a node is visible when it is near enough to the cloud and at least one camera sees it and does not hide it.  Y [M x 3]; cams: (fx, fy, cx, cy)
+    tuples or RigCamera objects; rig_to_cam: None, or per camera a 3 x 4 matrix or None.  Returns the visible indices; with words=True also the cameras' seen
+    and hidden bit words, [K x ceil(M / 32)] uint32 each."""
+    lib = load_library()
+    Y = _f64(Y); M = Y.shape[0]
+    tab, K = _painter_cams(cams)
+    T = _painter_matrices(rig_to_cam, K)
+    nd = np.ascontiguousarray(node_dist, dtype=np.float64)
+    W = (M + 31) // 32
+    v = np.zeros(max(M, 1), dtype=np.int32); nv = C.c_int(0)
+    seen = np.zeros((max(K, 1), max(W, 1)), dtype=np.uint32); hidden = np.zeros_like(seen)
+    rc = lib.tdlo_rig_self_occlusion_visible(_ptr(Y), M, C.cast(tab, C.c_void_p), _ptr(T), K, int(rows), int(cols), int(dlo_pixel_width), _ptr(nd),
+                                             float(visibility_threshold), _ptr(v), C.byref(nv), _ptr(seen) if words else None, _ptr(hidden) if words else None)
+    if rc:
+        raise TdloError(rc, "tdlo_rig_self_occlusion_visible")
+    return (v[:nv.value].copy(), seen[:K, :W], hidden[:K, :W]) if words else v[:nv.value].copy()
 
 
 def extend_visible_nodes(visible_nodes, geodesic_coord, d_vis, M):

@@ -8,6 +8,7 @@
 #include "tdlo_rccl.h"
 #include "tdlo_reg_plan.h"
 #include "tdlo_rig_host.h"
+#include "tdlo_painter_host.h"
 #include "tdlo_view_batch_plan.h"
 #include "tdlo_rig_batch_plan.h"
 
@@ -256,6 +257,16 @@ struct tdlo_ctx {
     bool rbatch_armed = false;
     int rig_batch_min = (getenv("TDLO_RIG_BATCH_MIN") && atoi(getenv("TDLO_RIG_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_RIG_BATCH_MIN")) : 0;
     long long rbatch_route[2] = {0, 0};
+    // the self-occlusion test under a rig (tdlo_rig_self_occlusion_batch: k_rig_painter_batch).  pnt_pin: [frame table | camera records | nodes | result words]
+    // in pinned host memory -- the first three go up in ONE copy into pnt_dev, the kernel stores the words where they lie --, both grown on demand.
+    // TDLO_RIG_PAINTER_MIN=n: tracker calls with fewer than n (camera, frame) jobs run the host statement (0: kRigPainterMin).
+    // pnt_route: tdlo_debug_route_count 51 / 52: jobs served by the kernel / done by the host statement
+    void *pnt_dev = nullptr;
+    size_t pnt_dev_cap = 0;
+    char *pnt_pin = nullptr;
+    size_t pnt_pin_cap = 0;
+    int rig_painter_min = (getenv("TDLO_RIG_PAINTER_MIN") && atoi(getenv("TDLO_RIG_PAINTER_MIN")) >= 1) ? atoi(getenv("TDLO_RIG_PAINTER_MIN")) : 0;
+    long long pnt_route[2] = {0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1816,6 +1827,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->wbat_pin) hipHostFree(c->wbat_pin);
     if (c->rbatch_dev) hipFree(c->rbatch_dev);
     if (c->rbatch_pin) hipHostFree(c->rbatch_pin);
+    if (c->pnt_dev) hipFree(c->pnt_dev);
+    if (c->pnt_pin) hipHostFree(c->pnt_pin);
     for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
@@ -5374,7 +5387,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 50) return -1;
+    if (!c || which < 0 || which > 52) return -1;
+    if (which >= 51) return c->pnt_route[which - 51];
     if (which >= 49) return c->rbatch_route[which - 49];
     if (which == 48) return c->prologue_scan_calls;
     if (which >= 45) return c->rig_route[which - 45];
@@ -5552,6 +5566,9 @@ struct tdlo_tracker {
     bool painter_on = false;                       // tdlo_tracker_set_self_occlusion: frame_from_depth applies trackdlo_node.cpp:279-343 (off by default)
     double painter_proj[12] = {0};
     int painter_width = 0;
+    int rig_painter_K = 0;                         // tdlo_tracker_set_rig_self_occlusion: the rig frame calls apply the test under a rig (0: off, the default)
+    std::vector<double> rig_painter_T;             // ... its K x 12 rig_to_cam entries, copied (empty: every camera frame is the rig frame)
+    int rig_painter_width = 0;
     // tdlo_tracker_render_result: the nodes the last frame_from_* call STARTED from (kept only while the self-occlusion test is on: the picture's
     // not-self-occluded set is formed from them, trackdlo_node.cpp:279-343 / :401) and that call's intrinsics
     std::vector<double> frame_Y0;
@@ -6092,8 +6109,140 @@ int tdlo_tracker_frame_from_cloud_view(tdlo_tracker *t, const tdlo_cloud_view *v
     return tdlo_tracker_tracking_step(t, nullptr, 0, vv.data(), nv, ve.data(), ne, nullptr, stats);
 }
 
-// The same from a rig's images: tdlo_rig_to_cloud_visibility with the tracker's nodes into its slot, tdlo_tracker_tracking_step.  The self-occlusion test is
-// one camera's (it projects the nodes with ONE matrix): a tracker with the switch on is refused.  After a rig frame the tracker holds no camera of its own:
+// ---- self-occlusion under a rig (include/trackdlo_hip.h has the statement; tdlo_painter_lane.h the lane, tdlo_painter_host.cpp the host statement) ----
+// From this many (camera, frame) jobs on, the rig tracker calls hand the test to k_rig_painter_batch; below it they run the host statement: the same sets.
+// NOT MEASURED YET (scripts/gpu_rig_painter.py writes profiles/rig_painter_ab.txt; the rule: the smallest F K from which the kernel wins on every measured value
+// at M = 45 and M = 300, else a value above any batch): until it is, the default is the host statement.  TDLO_RIG_PAINTER_MIN=n, read when the context is
+// made, overrides.
+constexpr int kRigPainterMin = 1 << 30;
+static int rig_painter_min(const tdlo_ctx *c) { return c->rig_painter_min ? c->rig_painter_min : kRigPainterMin; }
+
+// where the kernel's words of the frames of one call lie in pnt_pin (valid until the next enqueue)
+struct PainterWords { std::vector<const unsigned *> seen, hidden; };
+
+// One upload of [frame table | camera records | nodes], one launch; the words are in place once the stream has passed the launch.  The frames are checked
+// (rig_painter_fault); nothing waits here
+static int rig_painter_enqueue(tdlo_ctx *c, int F, const tdlo_rig_painter_frame *fr, int rows, int cols, PainterWords &pw) {
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t sumK = 0, sumY = 0, sumW = 0;
+    int Kmax = 0;
+    for (int f = 0; f < F; ++f) {
+        sumK += (size_t)fr[f].K; sumY += 3 * (size_t)fr[f].M; sumW += (size_t)fr[f].K * ((fr[f].M + 31) / 32);
+        Kmax = std::max(Kmax, fr[f].K);
+    }
+    const size_t cams_off = sizeof(PainterFrame) * (size_t)F, y_off = cams_off + sizeof(PainterCam) * sumK, up = y_off + sizeof(double) * sumY;
+    const size_t pin_bytes = up + sizeof(unsigned) * 2 * sumW;
+    hipStream_t st = c->stream;
+    if (up > c->pnt_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->pnt_dev) hipFree(c->pnt_dev);
+        c->pnt_dev = nullptr; c->pnt_dev_cap = 0;
+        const size_t cap = (up + (up >> 1) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipMalloc(&c->pnt_dev, cap));
+        c->pnt_dev_cap = cap;
+    }
+    if (pin_bytes > c->pnt_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->pnt_pin) hipHostFree(c->pnt_pin);
+        c->pnt_pin = nullptr; c->pnt_pin_cap = 0;
+        const size_t cap = (pin_bytes + (pin_bytes >> 1) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipHostMalloc((void **)&c->pnt_pin, cap, hipHostMallocDefault));
+        std::memset(c->pnt_pin, 0, cap);
+        c->pnt_pin_cap = cap;
+    }
+    char *pin = c->pnt_pin, *dev = (char *)c->pnt_dev;
+    PainterFrame *tab = (PainterFrame *)pin;
+    PainterCam *cams = (PainterCam *)(pin + cams_off);
+    double *Yp = (double *)(pin + y_off);
+    unsigned *words = (unsigned *)(pin + up);
+    pw.seen.assign(F, nullptr); pw.hidden.assign(F, nullptr);
+    size_t ik = 0, iy = 0, iw = 0;
+    for (int f = 0; f < F; ++f) {
+        const int M = fr[f].M, K = fr[f].K, W = (M + 31) / 32;
+        for (int k = 0; k < K; ++k) rig_painter_camera(fr[f].cams[k], fr[f].rig_to_cam ? fr[f].rig_to_cam + 12 * (size_t)k : nullptr, cams[ik + k]);
+        std::memcpy(Yp + iy, fr[f].Y, sizeof(double) * 3 * M);
+        tab[f] = PainterFrame{(const double *)(dev + y_off) + iy, (const PainterCam *)(dev + cams_off) + ik, words + iw, words + iw + (size_t)K * W, M, K, fr[f].dlo_pixel_width, 0};
+        pw.seen[f] = words + iw; pw.hidden[f] = words + iw + (size_t)K * W;
+        ik += (size_t)K; iy += 3 * (size_t)M; iw += 2 * (size_t)K * W;
+    }
+    HIPCHK(c, hipMemcpyAsync(dev, pin, up, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_rig_painter_batch((const PainterFrame *)dev, F, Kmax, rows, cols, st));
+    c->pnt_route[0] += (long long)sumK;
+    return TDLO_OK;
+}
+
+int tdlo_rig_self_occlusion_batch(tdlo_ctx *c, int F, const tdlo_rig_painter_frame *frames, int rows, int cols, int *visible_nodes, int *n_vis,
+                                  unsigned *seen_words, unsigned *hidden_words) {
+    if (!c) return TDLO_E_INVALID;
+    if (F < 1 || F > 65535 || !frames || !visible_nodes || !n_vis) return fail(c, TDLO_E_INVALID, "tdlo_rig_self_occlusion_batch: 1 .. 65 535 frames, visible_nodes and n_vis");
+    int Mmax = 0;
+    for (int f = 0; f < F; ++f) {
+        const tdlo_rig_painter_frame &q = frames[f];
+        if (const char *why = rig_painter_fault(q.Y, q.M, q.cams, q.rig_to_cam, q.K, rows, cols, q.dlo_pixel_width, q.node_dist)) return fail(c, TDLO_E_INVALID, why);
+        Mmax = std::max(Mmax, q.M);
+    }
+    PainterWords pw;
+    int rc = rig_painter_enqueue(c, F, frames, rows, cols, pw);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int> vis;
+    size_t iw = 0;
+    for (int f = 0; f < F; ++f) {
+        const tdlo_rig_painter_frame &q = frames[f];
+        const size_t KW = (size_t)q.K * ((q.M + 31) / 32);
+        rig_painter_verdict(pw.seen[f], pw.hidden[f], q.K, q.M, q.node_dist, q.visibility_threshold, vis);
+        n_vis[f] = (int)vis.size();
+        std::copy(vis.begin(), vis.end(), visible_nodes + (size_t)f * Mmax);
+        if (seen_words) std::copy(pw.seen[f], pw.seen[f] + KW, seen_words + iw);
+        if (hidden_words) std::copy(pw.hidden[f], pw.hidden[f] + KW, hidden_words + iw);
+        iw += KW;
+    }
+    return TDLO_OK;
+}
+
+int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_cam, int K, int dlo_pixel_width) {
+    if (!t) return TDLO_E_INVALID;
+    if (K == 0) { t->rig_painter_K = 0; t->rig_painter_T.clear(); return TDLO_OK; }
+    if (K < 1 || K > kPainterMaxCams || dlo_pixel_width < 1 || dlo_pixel_width > 255 || t->M > kPainterMaxNodes)
+        return fail(t->ctx, TDLO_E_INVALID, "tdlo_tracker_set_rig_self_occlusion: 1 .. 64 cameras, dlo_pixel_width 1 .. 255, up to 1024 nodes");
+    if (rig_to_cam)
+        for (int k = 0; k < K; ++k) {
+            bool none = true, finite = true;
+            for (int q = 0; q < 12; ++q) { none = none && std::isnan(rig_to_cam[12 * k + q]); finite = finite && std::isfinite(rig_to_cam[12 * k + q]); }
+            if (!none && !finite) return fail(t->ctx, TDLO_E_INVALID, "tdlo_tracker_set_rig_self_occlusion: rig_to_cam has an entry that is not finite");
+        }
+    t->rig_painter_K = K; t->rig_painter_width = dlo_pixel_width;
+    if (rig_to_cam) t->rig_painter_T.assign(rig_to_cam, rig_to_cam + 12 * (size_t)K); else t->rig_painter_T.clear();
+    return TDLO_OK;
+}
+
+// the frame of the test a tracker with the rig switch on brings to a rig call of K cameras (node_dist: the pre-pass's, read when the verdict is formed)
+static tdlo_rig_painter_frame tracker_painter_frame(const tdlo_tracker *t, const tdlo_rig_camera *cams) {
+    return tdlo_rig_painter_frame{t->Y.data(), t->M, cams, t->rig_painter_T.empty() ? nullptr : t->rig_painter_T.data(), t->rig_painter_K, t->rig_painter_width,
+                                  t->frame_dist.data(), t->visibility_threshold};
+}
+// what refuses a rig call for a tracker's switches: the single switch (that test is one camera's), a rig of another camera count, what the test refuses
+static const char *tracker_rig_painter_refusal(const tdlo_tracker *t, const tdlo_rig_camera *cams, int K, int rows, int cols) {
+    if (t->painter_on) return "a rig frame with the self-occlusion switch on: that test is one camera's";
+    if (!t->rig_painter_K) return nullptr;
+    if (K != t->rig_painter_K) return "a rig frame whose camera count is not the one tdlo_tracker_set_rig_self_occlusion was given";
+    static const double some_dist = 0.0;
+    return rig_painter_fault(t->Y.data(), t->M, cams, t->rig_painter_T.empty() ? nullptr : t->rig_painter_T.data(), K, rows, cols, t->rig_painter_width, &some_dist);
+}
+// the host statement for one tracker's frame (tdlo_debug_route_count 52)
+static void tracker_painter_host(tdlo_ctx *c, const tdlo_rig_painter_frame &q, int rows, int cols, std::vector<int> &vis) {
+    const int W = (q.M + 31) / 32;
+    std::vector<PainterCam> pc(q.K);
+    for (int k = 0; k < q.K; ++k) rig_painter_camera(q.cams[k], q.rig_to_cam ? q.rig_to_cam + 12 * (size_t)k : nullptr, pc[k]);
+    std::vector<unsigned> seen((size_t)q.K * W), hidden((size_t)q.K * W);
+    rig_painter_host(q.Y, q.M, pc.data(), q.K, rows, cols, q.dlo_pixel_width, seen.data(), hidden.data());
+    rig_painter_verdict(seen.data(), hidden.data(), q.K, q.M, q.node_dist, q.visibility_threshold, vis);
+    c->pnt_route[1] += q.K;
+}
+
+// The same from a rig's images: tdlo_rig_to_cloud_visibility with the tracker's nodes into its slot, tdlo_tracker_tracking_step.  The single self-occlusion
+// test is one camera's (it projects the nodes with ONE matrix): a tracker with that switch on is refused; with the rig switch on the pre-pass's visible set is
+// replaced by the rig's verdict.  After a rig frame the tracker holds no camera of its own:
 // tdlo_tracker_render_result wants the matrix P_k rig_to_cam_k of the camera whose image it draws over.
 int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, int K, int rows, int cols, double leaf_size, double d_vis,
                                 int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
@@ -6106,6 +6255,7 @@ int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, in
     std::vector<BatchPlanes> where;
     int rc = rig_refusal(c, t->slot, cams, K, rows, cols, leaf_size, where);
     if (rc) return rc;
+    if (const char *why = tracker_rig_painter_refusal(t, cams, K, rows, cols)) return fail(c, TDLO_E_INVALID, why);
     std::vector<int> &ve = t->frame_vis_ext, &vv = t->frame_vis;
     vv.resize(M); ve.resize(M);
     int nv = 0, ne = 0, n = 0;
@@ -6113,6 +6263,19 @@ int tdlo_tracker_frame_from_rig(tdlo_tracker *t, const tdlo_rig_camera *cams, in
     t->frame_Y0.clear(); t->frame_seen = false;
     rc = tdlo_rig_to_cloud_visibility(c, t->slot, cams, K, rows, cols, leaf_size, t->Y.data(), M, t->visibility_threshold, d_vis, t->geodesic_coord.data(),
                                       t->frame_dist.data(), vv.data(), &nv, ve.data(), &ne, &n, n_raw_out);
+    if (!rc && n > 0 && t->rig_painter_K) {      // the rig switch: the rig's verdict on the nodes as they stand, with the pre-pass's distances; then the gap fill
+        const tdlo_rig_painter_frame q = tracker_painter_frame(t, cams);
+        std::vector<int> qv, qe;
+        if (K >= rig_painter_min(c)) {
+            PainterWords pw;
+            if ((rc = rig_painter_enqueue(c, 1, &q, rows, cols, pw))) return rc;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            rig_painter_verdict(pw.seen[0], pw.hidden[0], K, M, q.node_dist, q.visibility_threshold, qv);
+        } else tracker_painter_host(c, q, rows, cols, qv);
+        fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
+        nv = (int)qv.size(); ne = (int)qe.size();
+        std::copy(qv.begin(), qv.end(), vv.begin()); std::copy(qe.begin(), qe.end(), ve.begin());
+    }
     if (n_out) *n_out = n;
     if (n_vis) *n_vis = nv;
     if (n_vis_ext) *n_vis_ext = ne;
@@ -6286,12 +6449,33 @@ int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F, const
     return finish();
 }
 
-int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
-                             tdlo_stats *stats, int *rc_each) {
+// rigs (NULL outside the rig calls): tracker i's cameras, for the trackers whose rig switch is on -- the test under a rig replaces the pre-pass's visible set.
+// From rig_painter_min jobs on k_rig_painter_batch is enqueued in front of the pre-pass and its words are read after that call's wait: no wait is added
+static int tracker_frame_batch_impl(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                    tdlo_stats *stats, int *rc_each, const tdlo_rig_camera *const *rigs, int rows, int cols) {
     if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
     tdlo_ctx *c = trackers[0]->ctx;
     if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
     const int M = trackers[0]->M;
+    std::vector<tdlo_rig_painter_frame> pf;      // the frames of the test, and whose they are
+    std::vector<int> pf_of(F, -1);
+    PainterWords pw;
+    bool painter_kernel = false;
+    if (rigs) {
+        int jobs = 0;
+        for (int i = 0; i < F; ++i)
+            if (trackers[i]->rig_painter_K && rigs[i]) {
+                trackers[i]->frame_dist.resize(M);
+                pf_of[i] = (int)pf.size();
+                pf.push_back(tracker_painter_frame(trackers[i], rigs[i]));
+                jobs += trackers[i]->rig_painter_K;
+            }
+        if (!pf.empty() && jobs >= rig_painter_min(c)) {
+            const int prc = rig_painter_enqueue(c, (int)pf.size(), pf.data(), rows, cols, pw);
+            if (prc) return prc;
+            painter_kernel = true;
+        }
+    }
     std::vector<int> sl(F), nv(F, 0), ne(F, 0), vis((size_t)F * M), ext((size_t)F * M);
     std::vector<double> Yall(3 * (size_t)M * F), coord((size_t)M * F), dist((size_t)M * F);
     for (int i = 0; i < F; ++i) {
@@ -6302,7 +6486,10 @@ int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
     }
     int rc = tdlo_visibility_prepass_batch(c, F, sl.data(), Yall.data(), M, trackers[0]->visibility_threshold, d_vis, coord.data(), dist.data(), vis.data(), nv.data(),
                                            ext.data(), ne.data());
-    if (rc) return rc;
+    if (rc) {
+        if (painter_kernel) (void)hipStreamSynchronize(c->stream);      // (the words are not read; nothing of this call stays in flight)
+        return rc;
+    }
     std::vector<tdlo_tracker *> sub;
     std::vector<const int *> pv, pe;
     std::vector<int> snv, sne, who;
@@ -6314,6 +6501,16 @@ int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
         if (t->painter_on) {      // the self-occlusion switch, as in tracker_frame_impl
             std::vector<int> qv, qe;
             self_occlusion_visible(t->Y.data(), M, t->painter_proj, t->painter_width, t->frame_dist.data(), t->visibility_threshold, qv);
+            fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
+            nv[i] = (int)qv.size(); ne[i] = (int)qe.size();
+            std::copy(qv.begin(), qv.end(), v); std::copy(qe.begin(), qe.end(), e);
+        }
+        if (pf_of[i] >= 0) {      // the rig switch: the rig's verdict with the pre-pass's distances, then the gap fill
+            tdlo_rig_painter_frame &q = pf[pf_of[i]];
+            q.node_dist = t->frame_dist.data();
+            std::vector<int> qv, qe;
+            if (painter_kernel) rig_painter_verdict(pw.seen[pf_of[i]], pw.hidden[pf_of[i]], q.K, M, q.node_dist, q.visibility_threshold, qv);
+            else tracker_painter_host(c, q, rows, cols, qv);
             fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
             nv[i] = (int)qv.size(); ne[i] = (int)qe.size();
             std::copy(qv.begin(), qv.end(), v); std::copy(qe.begin(), qe.end(), e);
@@ -6347,6 +6544,11 @@ int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis,
         if (rcs[i]) return rcs[i] == TDLO_E_EMPTY && ne[i] == 0
                                ? fail(c, TDLO_E_EMPTY, "no node within the visibility threshold of the cloud (the reference's callback is undefined here, trackdlo_node.cpp:351)") : rcs[i];
     return TDLO_OK;
+}
+
+int tdlo_tracker_frame_batch(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                             tdlo_stats *stats, int *rc_each) {
+    return tracker_frame_batch_impl(trackers, F, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, stats, rc_each, nullptr, 0, 0);
 }
 
 // The frames of F trackers from their images: tdlo_depth_to_cloud_batch into the trackers' slots, then tdlo_tracker_frame_batch on the trackers that got a cloud
@@ -6521,6 +6723,13 @@ int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, con
     if (!frames) return fail(c, TDLO_E_INVALID, "null frames");
     for (int i = 0; i < F; ++i)
         if (trackers[i]->painter_on) return fail(c, TDLO_E_INVALID, "a rig frame with the self-occlusion switch on: that test is one camera's");
+    bool any_painter = false;
+    for (int i = 0; i < F; ++i) {
+        if (!trackers[i]->rig_painter_K) continue;
+        any_painter = true;
+        if (!frames[i].cams) return fail(c, TDLO_E_INVALID, "rig: no cameras");
+        if (const char *why = tracker_rig_painter_refusal(trackers[i], frames[i].cams, frames[i].K, rows, cols)) return fail(c, TDLO_E_INVALID, why);
+    }
     const int M = trackers[0]->M;
     std::vector<tdlo_rig_frame> fr(frames, frames + F);
     for (int i = 0; i < F; ++i) fr[i].slot = trackers[i]->slot;
@@ -6537,6 +6746,8 @@ int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, con
         if (!rcs[i] && n[i] == 0) rcs[i] = TDLO_E_EMPTY;      // the rig keeps no pixel: no cloud, the tracker is left as it is
         if (!rcs[i]) { trackers[i]->frame_seen = false; sub.push_back(trackers[i]); who.push_back(i); }      // (after a rig frame the tracker holds no camera of its own)
     }
+    std::vector<const tdlo_rig_camera *> rigs;      // the rig switch: the cameras of the trackers that go on
+    if (any_painter) for (int i : who) rigs.push_back(frames[i].cams);
     std::vector<tdlo_stats> st(2 * (size_t)F);
     std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
     std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
@@ -6545,7 +6756,8 @@ int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, con
         std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
         std::vector<tdlo_stats> sst(2 * (size_t)Fs);
         std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
-        const int brc = tdlo_tracker_frame_batch(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data());
+        const int brc = tracker_frame_batch_impl(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data(),
+                                                 any_painter ? rigs.data() : nullptr, rows, cols);
         bool sany = false;
         for (int r : src) sany = sany || r != 0;
         for (int k = 0; k < Fs; ++k) {

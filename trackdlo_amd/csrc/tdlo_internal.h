@@ -258,6 +258,11 @@ struct VisBatchFrame { const double *X; int N0; int pad; };
 int node_min_dist_batch_wgs(int N);       // workgroups a frame of N points owns in the flat grid
 hipError_t launch_node_min_dist_batch(const VisBatchFrame *tab, const int *wg0, const double *Yhost, int F, int M, int nwg, unsigned long long *state,
                                       unsigned long long *ticket, unsigned long long *res_host, unsigned epoch, hipStream_t s);
+// tdlo_painter.hip: the self-occlusion test under a rig, one (camera, frame) job per workgroup.  PainterFrame: a frame's record of the table in device memory --
+// Y: 3 M doubles, column-major; cams: K records; seen / hidden: K x ceil(M / 32) result words each, in pinned host memory
+struct PainterCam;
+struct PainterFrame { const double *Y; const PainterCam *cams; unsigned *seen, *hidden; int M, K, width, pad; };
+hipError_t launch_rig_painter_batch(const PainterFrame *tab_dev, int F, int Kmax, int rows, int cols, hipStream_t s);
 size_t mstep_lds_bytes(int M);
 // tdlo_mstep_big.hip: M-step for 60 < M <= kMaxNodes without LLE (blocked Gauss-Jordan, tableau in global memory)
 hipError_t launch_mstep_big(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);

@@ -919,6 +919,65 @@ int tdlo_rig_self_occlusion_batch(tdlo_ctx *ctx, int F, const tdlo_rig_painter_f
                                   int *visible_nodes /* F x Mmax */, int *n_vis /* F */, unsigned *seen_words, unsigned *hidden_words);
 int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_cam /* NULL or K x 12 */, int K, int dlo_pixel_width);
 
+/* ---- ropes of one colour: one cloud dealt out among F trackers on the device ------------------------------------ */
+/* Every entrance above gives each rope a cloud of its own -- its own mask, its own colour ranges.  A harness of identical cables has ropes no segmentation
+ * can tell apart: ONE cloud and F trackers.  These calls deal one resident cloud out among F slots on the device and step the trackers on it.
+ * THE STATEMENT.  X: the n points resident in src_slot, as tdlo_get_cloud returns them.  Rope f = 0 .. F - 1: nodes Y_f (M_f x 3 column-major, all finite).
+ *   D(i, f)      = min over m of node_point_d2(Y_f[m], X_i) -- the pre-pass's own distance, same argument order, same fused form:
+ *                  fma(dz, dz, fma(dy, dy, fl(dx dx))) with dx = fl(y - x); the minimum is fmin (a NaN never wins); +inf if every term is NaN
+ *   g(i)         = min over f of D(i, f)
+ *   owner(i)     = the LOWEST f with D(i, f) = g(i) if g(i) is finite and g(i) <= fl(d_max d_max); otherwise -1 (a point with a NaN or infinite coordinate
+ *                  is never owned).  d_max = INFINITY: no gate; d_max <= 0 or NaN: TDLO_E_INVALID
+ *   owner_d2(i)  = g(i)
+ * RESULT.  Slot ropes[f].slot becomes the cloud of the points with owner(i) = f, in ascending i, every coordinate copied bit for bit (the sign of a zero
+ * counts), and is left exactly as tdlo_set_cloud of those points leaves it (the slot's sorted cloud no longer serves; an LLE regulariser left behind by a
+ * tracker stays, as it does there).  A rope that owns nothing leaves a cloud of 0 points, as tdlo_rig_to_cloud leaves a slot whose rig kept no pixel.
+ * n_each[f] and n_unowned (the points with owner -1) are returned; owner / owner_d2 (n entries each, or NULL) cost a copy and a wait of their own.
+ * Nearest NODE, not nearest segment: it is the pre-pass's own distance, the one every pre-pass kernel shares, and it has one right bit pattern; at the node
+ * spacing trackers run at (a centimetre or two) a point's distance to the chain and to its nearest node differ by less than any useful gate.
+ * tdlo_cloud_assign_host is the same statement on the host (the lane of csrc/tdlo_assign_lane.h point by point; no HIP, no context; .slot is not read).
+ * tdlo_cloud_assign_visibility: the outputs of tdlo_cloud_assign followed by tdlo_visibility_prepass on each destination slot, bit for bit (a node's minimum
+ * over the points its rope owns does not depend on how points are dealt to lanes; sqrt, the cap of 100000, the <= test and the gap fill are that call's host
+ * code).  Per-rope outputs are F pointers (rope f's: M_f entries), n_vis / n_vis_ext F counts; any output may be NULL.  A rope that owns nothing reports
+ * 100000 everywhere and n_vis = 0.
+ * tdlo_tracker_frames_from_shared_cloud_batch: the split by the trackers' CURRENT nodes into the trackers' own slots, the self-occlusion switch of a tracker
+ * applied as tdlo_tracker_frame_batch applies it, then tdlo_tracker_tracking_step_batch: the bits of tdlo_cloud_assign + tdlo_tracker_frame_batch made by hand.
+ * A tracker that owns no point, or has no visible node, gets TDLO_E_EMPTY in rc_each and is untouched; the others go on.  Refusals: tdlo_tracker_frame_batch's
+ * (except that the slots need no cloud beforehand) and those below.
+ * REFUSED as a whole with TDLO_E_INVALID, every destination cloud, tracker and route counter untouched: src_slot among the destinations; duplicate
+ * destinations; a source or destination slot the context does not have; F < 1 or F > max_frames; M_f < 1; a node that is not finite; a bad d_max.  A source of
+ * 0 points is TDLO_OK with every count 0 and every destination empty (the library does not tell a slot nobody filled from a cloud of 0 points: both are what
+ * tdlo_get_cloud reports as n = 0).
+ * KERNELS (csrc/tdlo_assign.hip): k_assign_count -- lane = point, the flat node list staged through LDS in tiles of 512 nodes, the running (g, owner) in
+ * registers, ropes in ascending order and `<` replaces; owner and g per point, an F-vector of counts per workgroup from one wave ballot per rope present --
+ * and k_assign_scatter -- every workgroup forms its F offsets from the preceding workgroups' counts (nobody waits for anybody), ranks its points by rope
+ * (ballot + popcount below the lane, the waves' counts in LDS) and writes x, y, z at column stride n_f; the workgroup that draws the last ticket hands the
+ * counts to pinned host memory and raises the word the host waits on.  Two launches and ONE host wait per call; every destination is sized for n beforehand
+ * (its capacity grows as tdlo_set_cloud grows it).  THE RIDE: in k_assign_scatter, per rope present in a wave, that rope's nodes against the wave's points
+ * (d2 = owner == f ? node_point_d2 : +inf, the wave's minimum, one atomic minimum on the ordered bits per (wave, node), as k_node_min_dist_batch does); the
+ * minima go to the host with the counts, so the pre-pass costs no launch and no wait of its own.
+ * ROUTE RULE (set before measuring): the ride stays the default of the tracker call and of tdlo_cloud_assign_visibility only if it is no slower than
+ * tdlo_cloud_assign + tdlo_visibility_prepass_batch on every measured line of profiles/cloud_assign_ab.txt (scripts/gpu_cloud_assign.py).  MEASURED (F = 2, 4, 8, 32 ropes of 45 nodes,
+ * 5 000 F points, tdlo_cloud_assign_visibility, bit-equal pairs): ride on 0.142 / 0.259 / 0.536 / 2.198 ms against ride off 0.110 / 0.190 / 0.353 / 1.398 ms --
+ * slower on every line (every wave of an interleaved cloud meets every rope, and the per-slot pre-pass reads only its own points).
+ * THE RIDE IS OFF BY DEFAULT, TDLO_ASSIGN_RIDE=1 (read when the context is made) turns it on.  Both routes give the same bits.  A rope of more than 1024
+ * nodes, or TDLO_DIRECT_UPLOAD=0 (the pre-pass's own fall-back), takes the two calls.
+ * Route counters 53 / 54: calls the split launches served (a source of 0 points launches nothing and is not counted) / calls in which the pre-pass rode.
+ * OUT OF SCOPE: starting F same-coloured ropes from one cloud (reg + sort_pts cannot separate them: the trackers come initialised); one rope hiding ANOTHER
+ * in the self-occlusion test; a joint E-step over all ropes' nodes. */
+typedef struct { int slot; const double *Y; int M; } tdlo_assign_rope;
+int tdlo_cloud_assign(tdlo_ctx *ctx, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max,
+                      int *n_each /* F or NULL */, int *n_unowned, int *owner /* n or NULL */, double *owner_d2 /* n or NULL */);
+int tdlo_cloud_assign_visibility(tdlo_ctx *ctx, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max,
+                                 double visibility_threshold, double d_vis, const double *const *geodesic_coord /* F rows of M_f */,
+                                 int *n_each, int *n_unowned, double *const *node_dist, int *const *visible_nodes, int *n_vis,
+                                 int *const *visible_nodes_extended, int *n_vis_ext);
+int tdlo_cloud_assign_host(const double *X, int n, const tdlo_assign_rope *ropes /* .slot not read */, int F, double d_max,
+                           int *owner, double *owner_d2, int *n_each, int *n_unowned);
+int tdlo_tracker_frames_from_shared_cloud_batch(tdlo_tracker *const *trackers, int F, int src_slot, double d_max, double d_vis,
+                                                int *visible_nodes /* F x M or NULL */, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                                int *n_each /* F or NULL */, tdlo_stats *stats, int *rc_each);
+
 /* ---- cloud views for many slots in one call ----------------------------------------------------------- */
 /* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
  * views become the resident clouds of F slots in one call -- down-sampled (tdlo_cloud_view_voxel_grid_batch) or as they are (tdlo_set_cloud_view_batch).
@@ -1355,6 +1414,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * frame passed on counts there as well.
  * 51 / 52: (camera, frame) jobs of the self-occlusion test under a rig served by k_rig_painter_batch (tdlo_rig_self_occlusion_batch, and the rig tracker calls
  * from kRigPainterMin jobs on) / done by the host statement inside a rig tracker call.
+ * 53 / 54: calls of tdlo_cloud_assign, tdlo_cloud_assign_visibility and tdlo_tracker_frames_from_shared_cloud_batch served by the split launches
+ * k_assign_count / k_assign_scatter / calls of the latter two in which the pre-pass rode in k_assign_scatter (TDLO_ASSIGN_RIDE=1).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -109,6 +109,10 @@ class RigPainterFrameC(C.Structure):               # tdlo_rig_painter_frame: one
                 ("node_dist", C.c_void_p), ("visibility_threshold", C.c_double)]
 
 
+class AssignRopeC(C.Structure):                    # tdlo_assign_rope: a destination slot and the rope's nodes (M x 3 column-major)
+    _fields_ = [("slot", C.c_int), ("Y", C.c_void_p), ("M", C.c_int)]
+
+
 class ViewFrame(C.Structure):                      # tdlo_view_frame: a slot, the cloud view it takes, its N and selection bytes (NULL: every element)
     _fields_ = [("slot", C.c_int), ("view", C.c_void_p), ("N", C.c_int), ("select", C.c_void_p)]
 
@@ -154,6 +158,7 @@ SYMBOLS = [
     "tdlo_rig_to_cloud", "tdlo_rig_to_cloud_visibility", "tdlo_tracker_frame_from_rig", "tdlo_rig_check", "tdlo_rig_points_host",
     "tdlo_rig_to_cloud_batch", "tdlo_tracker_frames_from_rig_batch", "tdlo_debug_rig_batch_plan", "tdlo_debug_rig_batch_arena",
     "tdlo_rig_self_occlusion_visible", "tdlo_rig_self_occlusion_batch", "tdlo_tracker_set_rig_self_occlusion",
+    "tdlo_cloud_assign", "tdlo_cloud_assign_visibility", "tdlo_cloud_assign_host", "tdlo_tracker_frames_from_shared_cloud_batch",
 ]
 
 _lib = None
@@ -369,6 +374,11 @@ def load_library(path: str | None = None):
         lib.tdlo_rig_self_occlusion_visible.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, vp, cd, vp, C.POINTER(ci), vp, vp]
         lib.tdlo_rig_self_occlusion_batch.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
         lib.tdlo_tracker_set_rig_self_occlusion.argtypes = [vp, vp, ci, ci]
+    if hasattr(lib, "tdlo_cloud_assign"):
+        lib.tdlo_cloud_assign.argtypes = [vp, ci, vp, ci, cd, vp, C.POINTER(ci), vp, vp]
+        lib.tdlo_cloud_assign_visibility.argtypes = [vp, ci, vp, ci, cd, cd, cd, vp, vp, C.POINTER(ci), vp, vp, vp, vp, vp]
+        lib.tdlo_cloud_assign_host.argtypes = [vp, ci, vp, ci, cd, vp, vp, vp, C.POINTER(ci)]
+        lib.tdlo_tracker_frames_from_shared_cloud_batch.argtypes = [vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -1365,6 +1375,43 @@ class Context:
                                                          _ptr(dist), _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne)))
         return dist, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)]
 
+    def assign_route_counts(self):
+        """[calls the split launches k_assign_count / k_assign_scatter served, calls in which the pre-pass rode] (tdlo_debug_route_count 53 / 54)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (53, 54)]
+
+    def cloud_assign(self, src_slot, ropes, d_max, owners=False, check=True):
+        """tdlo_cloud_assign: the cloud resident in src_slot dealt out among the ropes [(slot, Y [M x 3])]: a point goes to the rope with the nearest node
+        (the lowest rope on a tie) if that node is within d_max (np.inf: no gate).  Returns (n_each [F], n_unowned), with owners=True also owner [n] and
+        owner_d2 [n]; check=False: the code in front instead of raising."""
+        tab, F, keep = _assign_ropes(ropes)
+        n_each = np.zeros(F, dtype=np.int32); un = C.c_int(0)
+        own = d2 = None
+        if owners:
+            n = C.c_int(0)
+            self.lib.tdlo_get_cloud(self.h, src_slot, None, 0, C.byref(n))
+            own = np.zeros(n.value, dtype=np.int32); d2 = np.zeros(n.value)
+        rc = self.lib.tdlo_cloud_assign(self.h, int(src_slot), C.cast(tab, C.c_void_p), F, float(d_max), _ptr(n_each), C.byref(un), _ptr(own), _ptr(d2))
+        del keep
+        if check:
+            self._chk(rc)
+        out = ([int(v) for v in n_each], un.value) + ((own, d2) if owners else ())
+        return out if check else (rc,) + out
+
+    def cloud_assign_visibility(self, src_slot, ropes, d_max, visibility_threshold, d_vis, coords):
+        """tdlo_cloud_assign_visibility: cloud_assign, then the visibility pre-pass of every rope against the cloud it was dealt (coords: F arrays of M_f).
+        Returns (n_each [F], n_unowned, [node_dist], [visible_nodes], [visible_nodes_extended])."""
+        tab, F, keep = _assign_ropes(ropes)
+        Ms = [int(r.M) for r in tab]
+        co = [np.ascontiguousarray(c, dtype=np.float64) for c in coords]
+        assert len(co) == F and all(len(co[f]) == Ms[f] for f in range(F))
+        dist = [np.zeros(m) for m in Ms]; vis = [np.zeros(m, dtype=np.int32) for m in Ms]; ext = [np.zeros(m, dtype=np.int32) for m in Ms]
+        rows = lambda arrs: C.cast((C.c_void_p * F)(*[a.ctypes.data for a in arrs]), C.c_void_p)
+        n_each = np.zeros(F, dtype=np.int32); un = C.c_int(0); nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32)
+        self._chk(self.lib.tdlo_cloud_assign_visibility(self.h, int(src_slot), C.cast(tab, C.c_void_p), F, float(d_max), float(visibility_threshold), float(d_vis),
+                                                        rows(co), _ptr(n_each), C.byref(un), rows(dist), rows(vis), _ptr(nv), rows(ext), _ptr(ne)))
+        del keep
+        return [int(v) for v in n_each], un.value, dist, [vis[f][:nv[f]].copy() for f in range(F)], [ext[f][:ne[f]].copy() for f in range(F)]
+
     def reg(self, pts, M, mu=0.05, max_iter=50, slot=0):
         """reg (utils.cpp:21-82): plain GMM-EM.  pts=None: the slot's resident cloud.  Returns (Y [M x 3], sigma2)."""
         X = _f64(pts) if pts is not None else None
@@ -2104,6 +2151,46 @@ def frames_from_rig_batch(trackers, rigs, leaf_size, d_vis, check=True):
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def _assign_ropes(ropes):
+    """The tdlo_assign_rope table of [(slot, Y [M x 3])] (a bare Y: slot 0, for the host call).  Returns (table, F, what must stay alive)."""
+    F = len(ropes)
+    assert F >= 1
+    pairs = [r if isinstance(r, tuple) else (0, r) for r in ropes]
+    Ys = [_f64(Y) for _, Y in pairs]
+    assert all(Y.ndim == 2 and Y.shape[1] == 3 for Y in Ys)
+    tab = (AssignRopeC * F)(*[AssignRopeC(int(pairs[f][0]), Ys[f].ctypes.data, Ys[f].shape[0]) for f in range(F)])
+    return tab, F, Ys
+
+
+def cloud_assign_host(X, ropes, d_max, lib=None):
+    """tdlo_cloud_assign_host: the statement of Context.cloud_assign on the host (no HIP, no context).  X [n x 3], ropes: F node arrays [M_f x 3].
+    Returns (owner [n], owner_d2 [n], n_each [F], n_unowned)."""
+    lib = lib or load_library()
+    X = _f64(X)
+    assert X.ndim == 2 and X.shape[1] == 3
+    tab, F, keep = _assign_ropes(ropes)
+    n = X.shape[0]
+    own = np.zeros(n, dtype=np.int32); d2 = np.zeros(n); n_each = np.zeros(F, dtype=np.int32); un = C.c_int(0)
+    rc = lib.tdlo_cloud_assign_host(_ptr(X), n, C.cast(tab, C.c_void_p), F, float(d_max), _ptr(own), _ptr(d2), _ptr(n_each), C.byref(un))
+    del keep
+    if rc:
+        raise TdloError(rc, "tdlo_cloud_assign_host refused its arguments")
+    return own, d2, [int(v) for v in n_each], un.value
+
+
+def frames_from_shared_cloud_batch(trackers, src_slot, d_max, d_vis, check=True):
+    """tdlo_tracker_frames_from_shared_cloud_batch: the cloud resident in src_slot dealt out among the trackers' slots by the trackers' current nodes
+    (Context.cloud_assign), then frame_batch on the trackers that own a point.  Returns (codes, [visible_nodes], [visible_nodes_extended], n_each [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    M = trackers[0].M
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_shared_cloud_batch(C.cast(tab, C.c_void_p), F, int(src_slot), float(d_max), float(d_vis),
+                                                                         _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), C.cast(st, C.c_void_p), _ptr(rcs))
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n]
 
 
 def render_result_batch(trackers, images, image_of, proj=None, params=None, corners=True, check=True):

@@ -9,6 +9,7 @@
 #include "tdlo_reg_plan.h"
 #include "tdlo_rig_host.h"
 #include "tdlo_painter_host.h"
+#include "tdlo_assign_host.h"
 #include "tdlo_view_batch_plan.h"
 #include "tdlo_rig_batch_plan.h"
 
@@ -267,6 +268,18 @@ struct tdlo_ctx {
     size_t pnt_pin_cap = 0;
     int rig_painter_min = (getenv("TDLO_RIG_PAINTER_MIN") && atoi(getenv("TDLO_RIG_PAINTER_MIN")) >= 1) ? atoi(getenv("TDLO_RIG_PAINTER_MIN")) : 0;
     long long pnt_route[2] = {0, 0};
+    // one cloud dealt out among F slots (tdlo_cloud_assign and the calls built on it: k_assign_count / k_assign_scatter).  asg_dev: [table | owner | g | counts]
+    // in device memory, grown on demand; asg_state: [asg_state_cap minima | ticket], armed when allocated or after a launch that did not report, kept armed by
+    // the kernel; asg_res: [word | F counts | T minima] in pinned host memory.  TDLO_ASSIGN_RIDE=1: the pre-pass rides in k_assign_scatter (measured slower, profiles/cloud_assign_ab.txt: off by default).
+    // asg_route: tdlo_debug_route_count 53 / 54: calls the split launches served / calls in which the pre-pass rode
+    char *asg_dev = nullptr;
+    size_t asg_dev_cap = 0;
+    unsigned long long *asg_state = nullptr, *asg_res = nullptr;
+    size_t asg_state_cap = 0, asg_res_cap = 0;
+    unsigned asg_epoch = 0;
+    bool asg_armed = false;
+    bool assign_ride = getenv("TDLO_ASSIGN_RIDE") && atoi(getenv("TDLO_ASSIGN_RIDE")) != 0;
+    long long asg_route[2] = {0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1829,6 +1842,9 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->rbatch_pin) hipHostFree(c->rbatch_pin);
     if (c->pnt_dev) hipFree(c->pnt_dev);
     if (c->pnt_pin) hipHostFree(c->pnt_pin);
+    if (c->asg_dev) hipFree(c->asg_dev);
+    if (c->asg_state) hipFree(c->asg_state);
+    if (c->asg_res) hipHostFree(c->asg_res);
     for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
@@ -5387,7 +5403,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 52) return -1;
+    if (!c || which < 0 || which > 54) return -1;
+    if (which >= 53) return c->asg_route[which - 53];
     if (which >= 51) return c->pnt_route[which - 51];
     if (which >= 49) return c->rbatch_route[which - 49];
     if (which == 48) return c->prologue_scan_calls;
@@ -6452,7 +6469,7 @@ int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F, const
 // rigs (NULL outside the rig calls): tracker i's cameras, for the trackers whose rig switch is on -- the test under a rig replaces the pre-pass's visible set.
 // From rig_painter_min jobs on k_rig_painter_batch is enqueued in front of the pre-pass and its words are read after that call's wait: no wait is added
 static int tracker_frame_batch_impl(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
-                                    tdlo_stats *stats, int *rc_each, const tdlo_rig_camera *const *rigs, int rows, int cols) {
+                                    tdlo_stats *stats, int *rc_each, const tdlo_rig_camera *const *rigs, int rows, int cols, const double *pre_min_d2 = nullptr) {
     if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
     tdlo_ctx *c = trackers[0]->ctx;
     if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
@@ -6484,7 +6501,13 @@ static int tracker_frame_batch_impl(tdlo_tracker *const *trackers, int F, double
         std::memcpy(&Yall[3 * (size_t)M * i], t->Y.data(), sizeof(double) * 3 * M);
         std::memcpy(&coord[(size_t)M * i], t->geodesic_coord.data(), sizeof(double) * M);
     }
-    int rc = tdlo_visibility_prepass_batch(c, F, sl.data(), Yall.data(), M, trackers[0]->visibility_threshold, d_vis, coord.data(), dist.data(), vis.data(), nv.data(),
+    int rc = 0;
+    if (pre_min_d2)      // (the squared minima came with the clouds: the pre-pass rode in k_assign_scatter)
+        for (int i = 0; i < F; ++i)
+            vis_threshold_and_fill(pre_min_d2 + (size_t)M * i, M, trackers[0]->visibility_threshold, d_vis, &coord[(size_t)M * i], &dist[(size_t)M * i], &vis[(size_t)M * i],
+                                   &nv[i], &ext[(size_t)M * i], &ne[i]);
+    else
+        rc = tdlo_visibility_prepass_batch(c, F, sl.data(), Yall.data(), M, trackers[0]->visibility_threshold, d_vis, coord.data(), dist.data(), vis.data(), nv.data(),
                                            ext.data(), ne.data());
     if (rc) {
         if (painter_kernel) (void)hipStreamSynchronize(c->stream);      // (the words are not read; nothing of this call stays in flight)
@@ -6777,6 +6800,235 @@ int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, con
     if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "no pixel of the rig is kept: no cloud for this frame") : rcs[i];
+    return TDLO_OK;
+}
+
+// ---- ropes of one colour: one cloud dealt out among F slots (include/trackdlo_hip.h has the statement; tdlo_assign.hip the kernels) -------------------------
+// what refuses a call as a whole, nullptr when nothing does
+static const char *assign_refusal(const tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max) {
+    const int S = (int)c->slots.size();
+    if (F < 1 || F > S) return "cloud assign: F < 1 or F > max_frames";
+    if (F > kAssignMaxRopes) return "cloud assign: more than 2048 ropes";
+    if (const char *why = assign_fault(ropes, F, d_max)) return why;
+    if (src_slot < 0 || src_slot >= S) return "cloud assign: the context has no such source slot";
+    for (int f = 0; f < F; ++f) {
+        if (ropes[f].slot < 0 || ropes[f].slot >= S) return "cloud assign: the context has no such destination slot";
+        if (ropes[f].slot == src_slot) return "cloud assign: the source slot is among the destinations";
+        for (int j = 0; j < f; ++j) if (ropes[j].slot == ropes[f].slot) return "cloud assign: the destinations must be distinct";
+    }
+    return nullptr;
+}
+
+static size_t asg_pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// what a split left behind: off[F + 1] of the flat node list, the counts, and -- the pre-pass rode -- the T squared minima in pinned host memory (until the next split)
+struct AssignRun { std::vector<int> off, n_each; int n = 0, n_unowned = 0; const double *mins = nullptr; };
+
+// the split of checked arguments: two launches, one wait.  owner / owner_d2 (NULL or n entries) are copied out behind it
+static int assign_run(tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max, bool ride, int *owner, double *owner_d2, AssignRun &run) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+    const int n = c->slots[src_slot].N0;
+    run.off.assign((size_t)F + 1, 0); run.n_each.assign(F, 0); run.n = n; run.n_unowned = 0; run.mins = nullptr;
+    for (int f = 0; f < F; ++f) run.off[f + 1] = run.off[f] + ropes[f].M;
+    const int T = run.off[F];
+    if (n <= 0) {      // nothing to deal out: every destination is the cloud of 0 points
+        for (int f = 0; f < F; ++f) { Slot &d = c->slots[ropes[f].slot]; d.N0 = 0; d.sorted_valid = false; }
+        return TDLO_OK;
+    }
+    for (int f = 0; f < F; ++f) if ((rc = ensure_points(c, c->slots[ropes[f].slot], n))) return rc;      // a rope may own every point
+    int nwg, cpb;
+    assign_geometry(n, &nwg, &cpb);
+    const size_t o_dst = asg_pad16(sizeof(int) * ((size_t)F + 1)), o_Y = o_dst + asg_pad16(sizeof(double *) * (size_t)F), tab = o_Y + sizeof(double) * 3 * (size_t)T;
+    const size_t o_own = asg_pad16(tab), o_g = o_own + asg_pad16(sizeof(int) * (size_t)n), o_cnt = o_g + sizeof(double) * (size_t)n;
+    const size_t need = o_cnt + asg_pad16(sizeof(int) * (size_t)nwg * F);
+    if (need > c->asg_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_dev) hipFree(c->asg_dev);
+        c->asg_dev = nullptr; c->asg_dev_cap = 0;
+        const size_t cap = (need + (need >> 2) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipMalloc((void **)&c->asg_dev, cap));
+        c->asg_dev_cap = cap;
+    }
+    if ((size_t)T > c->asg_state_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_state) hipFree(c->asg_state);
+        c->asg_state = nullptr; c->asg_state_cap = 0;
+        const size_t cap = ((size_t)T + 1023) & ~(size_t)1023;
+        HIPCHK(c, hipMalloc((void **)&c->asg_state, sizeof(unsigned long long) * (cap + 8)));
+        c->asg_state_cap = cap; c->asg_armed = false;
+    }
+    if (!c->asg_armed) {
+        std::vector<unsigned long long> init(c->asg_state_cap + 8, 0x7ff0000000000000ull);
+        for (size_t i = c->asg_state_cap; i < c->asg_state_cap + 8; ++i) init[i] = 0ull;
+        HIPCHK(c, hipMemcpy(c->asg_state, init.data(), sizeof(unsigned long long) * init.size(), hipMemcpyHostToDevice));
+        c->asg_armed = true;
+    }
+    const size_t res_words = 1 + (size_t)F + (size_t)T;
+    if (res_words > c->asg_res_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_res) hipHostFree(c->asg_res);
+        c->asg_res = nullptr; c->asg_res_cap = 0;
+        const size_t cap = (res_words + 1023) & ~(size_t)1023;
+        HIPCHK(c, hipHostMalloc((void **)&c->asg_res, sizeof(unsigned long long) * cap, hipHostMallocDefault));
+        std::memset(c->asg_res, 0, sizeof(unsigned long long) * cap);
+        c->asg_res_cap = cap; c->asg_epoch = 0;
+    }
+    // the pinned staging block: [off | dst | Yx | Yy | Yz], copied up once
+    if ((rc = ensure_pin(c, (tab + 7) / 8 + 8))) return rc;
+    char *hp = (char *)c->pin;
+    std::memset(hp, 0, o_Y);
+    int *hoff = (int *)hp;
+    double **hdst = (double **)(hp + o_dst);
+    double *hY = (double *)(hp + o_Y);
+    assign_flatten(ropes, F, hoff, hY, hY + T, hY + 2 * (size_t)T);
+    for (int f = 0; f < F; ++f) hdst[f] = c->slots[ropes[f].slot].Xraw;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->asg_dev, hp, tab, hipMemcpyHostToDevice, st));
+    if (++c->asg_epoch == 0) ++c->asg_epoch;
+    int *d_owner = (int *)(c->asg_dev + o_own);
+    double *d_g = (double *)(c->asg_dev + o_g);
+    ++c->asg_route[0];
+    if (ride) ++c->asg_route[1];
+    HIPCHK(c, launch_assign(c->slots[src_slot].Xraw, n, (const int *)c->asg_dev, (double *const *)(c->asg_dev + o_dst), (const double *)(c->asg_dev + o_Y), F, T,
+                            d_max * d_max, d_owner, owner_d2 ? d_g : nullptr, (int *)(c->asg_dev + o_cnt), ride, c->asg_state, c->asg_state + c->asg_state_cap,
+                            c->asg_res, c->asg_epoch, st));
+    auto t_chk = std::chrono::steady_clock::now();
+    for (unsigned spins = 1;; ++spins) {
+        if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
+        if ((spins & 255u) == 0) {
+            const auto now = std::chrono::steady_clock::now();
+            if (std::chrono::duration<double, std::micro>(now - t_chk).count() > 500.0) {
+                t_chk = now;
+                const hipError_t e = hipStreamQuery(st);
+                if (e == hipSuccess) {
+                    if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
+                    c->asg_armed = false;
+                    return fail(c, TDLO_E_HIP, "the stream drained, but the cloud split did not report");
+                }
+                if (e != hipErrorNotReady) { c->asg_armed = false; return fail(c, TDLO_E_HIP, std::string("stream: ") + hipGetErrorString(e)); }
+            }
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    long long owned = 0;
+    for (int f = 0; f < F; ++f) {
+        const int nf = (int)(unsigned)c->asg_res[1 + f];
+        run.n_each[f] = nf; owned += nf;
+        Slot &d = c->slots[ropes[f].slot];
+        d.N0 = nf; d.sorted_valid = false;      // as tdlo_set_cloud leaves it (nf == 0: as a rig that kept no pixel leaves it)
+    }
+    run.n_unowned = (int)(n - owned);
+    if (ride) run.mins = (const double *)(c->asg_res + 1 + F);
+    if (owner || owner_d2) {
+        if (owner) HIPCHK(c, hipMemcpyAsync(owner, d_owner, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (owner_d2) HIPCHK(c, hipMemcpyAsync(owner_d2, d_g, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, wait_stream(st));
+    }
+    return TDLO_OK;
+}
+
+int tdlo_cloud_assign(tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max, int *n_each, int *n_unowned, int *owner, double *owner_d2) {
+    if (!c) return TDLO_E_INVALID;
+    if (const char *why = assign_refusal(c, src_slot, ropes, F, d_max)) return fail(c, TDLO_E_INVALID, why);
+    AssignRun run;
+    if (const int rc = assign_run(c, src_slot, ropes, F, d_max, false, owner, owner_d2, run)) return rc;
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    if (n_unowned) *n_unowned = run.n_unowned;
+    return TDLO_OK;
+}
+
+// whether the pre-pass of these ropes may ride in the split: the context's switch, the pre-pass's own one-launch conditions
+static bool assign_ride_ok(const tdlo_ctx *c, const tdlo_assign_rope *ropes, int F) {
+    if (!c->assign_ride || !c->direct_in) return false;
+    for (int f = 0; f < F; ++f) if (ropes[f].M > kAssignRideMaxNodes) return false;
+    return true;
+}
+
+int tdlo_cloud_assign_visibility(tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max, double visibility_threshold, double d_vis,
+                                 const double *const *geodesic_coord, int *n_each, int *n_unowned, double *const *node_dist, int *const *visible_nodes, int *n_vis,
+                                 int *const *visible_nodes_extended, int *n_vis_ext) {
+    if (!c) return TDLO_E_INVALID;
+    if (const char *why = assign_refusal(c, src_slot, ropes, F, d_max)) return fail(c, TDLO_E_INVALID, why);
+    if (!geodesic_coord) return fail(c, TDLO_E_INVALID, "cloud assign: null geodesic_coord");
+    for (int f = 0; f < F; ++f) if (!geodesic_coord[f]) return fail(c, TDLO_E_INVALID, "cloud assign: null geodesic_coord");
+    const bool ride = assign_ride_ok(c, ropes, F);
+    AssignRun run;
+    if (const int rc = assign_run(c, src_slot, ropes, F, d_max, ride, nullptr, nullptr, run)) return rc;
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    if (n_unowned) *n_unowned = run.n_unowned;
+    auto row = [&](auto *const *p, int f) { return p ? p[f] : nullptr; };
+    auto one = [&](int *p, int f) { return p ? p + f : nullptr; };
+    for (int f = 0; f < F; ++f) {
+        const int M = ropes[f].M;
+        if (ride && run.mins)
+            vis_threshold_and_fill(run.mins + run.off[f], M, visibility_threshold, d_vis, geodesic_coord[f], row(node_dist, f), row(visible_nodes, f), one(n_vis, f),
+                                   row(visible_nodes_extended, f), one(n_vis_ext, f));
+        else if (run.n_each[f] > 0) {
+            if (const int rc = tdlo_visibility_prepass(c, ropes[f].slot, ropes[f].Y, M, visibility_threshold, d_vis, geodesic_coord[f], row(node_dist, f),
+                                                       row(visible_nodes, f), one(n_vis, f), row(visible_nodes_extended, f), one(n_vis_ext, f))) return rc;
+        } else {      // a rope that owns nothing: the pre-pass of a cloud without a point
+            const std::vector<double> none((size_t)M, std::numeric_limits<double>::infinity());
+            vis_threshold_and_fill(none.data(), M, visibility_threshold, d_vis, geodesic_coord[f], row(node_dist, f), row(visible_nodes, f), one(n_vis, f),
+                                   row(visible_nodes_extended, f), one(n_vis_ext, f));
+        }
+    }
+    return TDLO_OK;
+}
+
+int tdlo_tracker_frames_from_shared_cloud_batch(tdlo_tracker *const *trackers, int F, int src_slot, double d_max, double d_vis,
+                                                int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_each, tdlo_stats *stats, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    const int M = trackers[0]->M;
+    std::vector<tdlo_assign_rope> ropes(F);
+    for (int i = 0; i < F; ++i) ropes[i] = tdlo_assign_rope{trackers[i]->slot, trackers[i]->Y.data(), M};
+    if (const char *why = assign_refusal(c, src_slot, ropes.data(), F, d_max)) return fail(c, TDLO_E_INVALID, why);
+    const bool ride = assign_ride_ok(c, ropes.data(), F);
+    AssignRun run;
+    if (const int rc = assign_run(c, src_slot, ropes.data(), F, d_max, ride, nullptr, nullptr, run)) return rc;
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    std::vector<int> rcs(F, 0), who;
+    std::vector<tdlo_tracker *> sub;
+    std::vector<double> mins;      // the riders' squared minima, the trackers that go on one behind the other
+    for (int i = 0; i < F; ++i) {
+        if (run.n_each[i] == 0) { rcs[i] = TDLO_E_EMPTY; continue; }      // the rope owns no point: no cloud, the tracker is left as it is
+        sub.push_back(trackers[i]); who.push_back(i);
+        if (ride && run.mins) mins.insert(mins.end(), run.mins + run.off[i], run.mins + run.off[i] + M);
+    }
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
+    if (!sub.empty()) {
+        const int Fs = (int)sub.size();
+        std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
+        std::vector<tdlo_stats> sst(2 * (size_t)Fs);
+        std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+        const int brc = tracker_frame_batch_impl(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data(), nullptr, 0, 0,
+                                                 (ride && run.mins) ? mins.data() : nullptr);
+        bool sany = false;
+        for (int r : src) sany = sany || r != 0;
+        for (int k = 0; k < Fs; ++k) {
+            const int i = who[k];
+            rcs[i] = (brc && !sany) ? brc : src[k];
+            nv[i] = snv[k]; ne[i] = sne[k];
+            std::copy(&svis[(size_t)M * k], &svis[(size_t)M * k] + M, &vis[(size_t)M * i]);
+            std::copy(&sext[(size_t)M * k], &sext[(size_t)M * k] + M, &ext[(size_t)M * i]);
+            st[2 * (size_t)i] = sst[2 * (size_t)k]; st[2 * (size_t)i + 1] = sst[2 * (size_t)k + 1];
+        }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && run.n_each[i] == 0) ? fail(c, TDLO_E_EMPTY, "the rope owns no point of the shared cloud: no cloud for this frame") : rcs[i];
     return TDLO_OK;
 }
 

@@ -263,6 +263,12 @@ hipError_t launch_node_min_dist_batch(const VisBatchFrame *tab, const int *wg0, 
 struct PainterCam;
 struct PainterFrame { const double *Y; const PainterCam *cams; unsigned *seen, *hidden; int M, K, width, pad; };
 hipError_t launch_rig_painter_batch(const PainterFrame *tab_dev, int F, int Kmax, int rows, int cols, hipStream_t s);
+// tdlo_assign.hip: one cloud dealt out among F slots (k_assign_count, k_assign_scatter).  off / dst / Y: the table in device memory -- off[F + 1], the F destination
+// clouds, the flat node list x | y | z of T = off[F] entries each; owner [n], g [n] (or nullptr), counts [nwg x F]: workspace; state [T] + ticket: kept armed
+constexpr int kAssignMaxRopes = 2048;     // ropes of one call (the scatter kernel's LDS tables)
+void assign_geometry(int n, int *nwg, int *cpb);      // workgroups of both kernels, chunks of kBlock points per workgroup
+hipError_t launch_assign(const double *X, int n, const int *off, double *const *dst, const double *Y, int F, int T, double dmax2, int *owner, double *g, int *counts,
+                         bool ride, unsigned long long *state, unsigned long long *ticket, unsigned long long *res_host, unsigned epoch, hipStream_t s);
 size_t mstep_lds_bytes(int M);
 // tdlo_mstep_big.hip: M-step for 60 < M <= kMaxNodes without LLE (blocked Gauss-Jordan, tableau in global memory)
 hipError_t launch_mstep_big(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);

@@ -963,8 +963,8 @@ int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_ca
  * THE RIDE IS OFF BY DEFAULT, TDLO_ASSIGN_RIDE=1 (read when the context is made) turns it on.  Both routes give the same bits.  A rope of more than 1024
  * nodes, or TDLO_DIRECT_UPLOAD=0 (the pre-pass's own fall-back), takes the two calls.
  * Route counters 53 / 54: calls the split launches served (a source of 0 points launches nothing and is not counted) / calls in which the pre-pass rode.
- * OUT OF SCOPE: starting F same-coloured ropes from one cloud (reg + sort_pts cannot separate them: the trackers come initialised); one rope hiding ANOTHER
- * in the self-occlusion test; a joint E-step over all ropes' nodes. */
+ * OUT OF SCOPE: one rope hiding ANOTHER in the self-occlusion test; a joint E-step over all ropes' nodes.  (Starting F same-coloured ropes from one cloud:
+ * the next section.) */
 typedef struct { int slot; const double *Y; int M; } tdlo_assign_rope;
 int tdlo_cloud_assign(tdlo_ctx *ctx, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max,
                       int *n_each /* F or NULL */, int *n_unowned, int *owner /* n or NULL */, double *owner_d2 /* n or NULL */);
@@ -977,6 +977,59 @@ int tdlo_cloud_assign_host(const double *X, int n, const tdlo_assign_rope *ropes
 int tdlo_tracker_frames_from_shared_cloud_batch(tdlo_tracker *const *trackers, int F, int src_slot, double d_max, double d_vis,
                                                 int *visible_nodes /* F x M or NULL */, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                                 int *n_each /* F or NULL */, tdlo_stats *stats, int *rc_each);
+
+/* ---- starting ropes of one colour: one cloud clustered into F trackers on the device ---------------------------- */
+/* The calls above need trackers that are already started.  These START them: the one cloud of F same-coloured ropes is clustered on the device (Euclidean
+ * cluster extraction, as PCL users know it), cluster c becomes the cloud of destination c, and tdlo_tracker_initialize_from_cloud_batch starts the trackers.
+ * THE STATEMENT.  X: the n points resident in src_slot, as tdlo_get_cloud returns them.
+ *   finite       point i is finite if x, y and z are all finite; a point that is not takes part in nothing
+ *   link(i, j)   i != j, both finite, and node_point_d2(X_i, X_j) <= fl(tol tol) -- the pre-pass's own distance in the fused form tdlo_cloud_assign uses:
+ *                fma(dz, dz, fma(dy, dy, fl(dx dx))) with dx = fl(a - b); symmetric in its arguments (the differences negate exactly).
+ *                tol <= 0, NaN or infinite: TDLO_E_INVALID
+ *   clusters     the connected components of the link graph over the finite points (single linkage); root(i) = the smallest index in i's component,
+ *                size(r) = its member count; a cluster is KEPT if size >= min_size.  min_size < 1: TDLO_E_INVALID
+ *   numbering    the kept clusters are numbered c = 0 .. C - 1 in ascending order of their root: the order of first appearance in the cloud.  NOT PCL's order
+ *                by size: it must not depend on scheduling, and ties in size are common
+ *   owner(i)     with F destinations: the number of i's cluster if the cluster is kept and its number is < F; otherwise -1 (a point that is not finite, a
+ *                point of a cluster that is too small, a point of a kept cluster numbered >= F)
+ * RESULT.  Destination dst_slots[f] becomes the cloud of the points with owner(i) = f, in ascending i, every coordinate copied bit for bit, and is left exactly as
+ * tdlo_set_cloud of those points leaves it: tdlo_cloud_assign's RESULT paragraph applies word for word.  A destination f >= C is left with 0 points.  Returned:
+ * n_clusters = C (it may exceed F), n_each[F], n_unowned (the points with owner -1); owner (n entries, or NULL) costs a copy and a wait of its own.
+ * tdlo_cloud_cluster_host is the same statement on the host, in the plain all-pairs form (the lane of csrc/tdlo_cluster_lane.h, every point against every
+ * point in front of it; no HIP, no context): it is the statement, not a competitor.
+ * tdlo_tracker_initialize_from_shared_cloud_batch: tdlo_cloud_cluster into the trackers' OWN slots, then -- C = F -- tdlo_tracker_initialize_from_cloud_batch on
+ * them: that composition's bits, cluster c to trackers[c].  C != F: TDLO_E_INVALID with n_clusters and n_each written and every tracker untouched (rc_each is not
+ * written); THE SLOTS HOLD THE SPLIT.  Refused as a whole, slots included: the refusals below with the trackers' slots as destinations; a null tracker; trackers of
+ * different contexts or node counts; fewer than 4 nodes or more than tdlo_reg fits; max_iter < 0; mu outside [0, 1).
+ * REFUSED as a whole with TDLO_E_INVALID, every destination cloud, tracker and route counter untouched: src_slot among the destinations; duplicate destinations;
+ * a source or destination slot the context does not have; F < 1 or F > max_frames; a bad tol or min_size; n > 262 144 -- the device route tests ALL pairs and on
+ * shared hardware a call's time must stay bounded (kClusterMaxPoints, csrc/tdlo_cluster_lane.h; the host call refuses the same n).  A source of 0 points is
+ * TDLO_OK with every count 0 and every destination empty.
+ * KERNELS (csrc/tdlo_cluster.hip).  The forest is one int per point, parent[i] <= i, and a word only ever decreases.  k_cluster_link -- lane = point i, the cloud
+ * staged through LDS in tiles of 512 points, a workgroup per (256 points, tile) and only the tiles at or below the lane's own, every point j < i within the gate
+ * joined to i's tree (the links of 64 points gathered as a word of bits, their parents loaded four at a time; a point that hangs under the lane's root already is
+ * skipped): the larger root is hooked under the smaller by an agent-scope compare-and-swap, find shortens its path by an atomic minimum.  Nobody waits for anybody (no grid barrier, no
+ * spinning on another workgroup, no residency assumption); every walk descends strictly and every retry follows a hook somebody else made, so the loops end, and
+ * the root of a component is its smallest index WHATEVER the schedule: one right bit pattern.  The retry loop is bounded all the same (1024 attempts); a lane
+ * that runs out raises a word in pinned memory and the driver serves the call by the host route -- never a wrong split.  Then k_cluster_flatten (root per point,
+ * one atomic add per finite point for the sizes), k_cluster_count / k_cluster_rank (kept roots per workgroup; every workgroup sums the counts in front of it
+ * itself), k_cluster_owner (owner per point and the per-workgroup counts in k_assign_count's layout) and tdlo_cloud_assign's own k_assign_scatter, unchanged:
+ * the stable scatter, the counts to pinned memory, the word the host waits on.  ONE host wait per call; the workspace (3 n ints) grows with the split's buffers.
+ * ROUTES.  TDLO_CLUSTER=host (read when the context is made): tdlo_get_cloud's copy, tdlo_cloud_cluster_host's owners, their per-workgroup counts formed on the
+ * host, one copy up, the same k_assign_scatter.  Both routes give the same bits.  ROUTE RULE (set before measuring): the device route is the default unless it is
+ * slower than the host route on every measured line of profiles/cloud_cluster_ab.txt (scripts/gpu_cloud_cluster.py).  MEASURED (F = 2, 4, 8, 32 ropes of 45
+ * nodes, 5 000 F points, tol = 24 mm, bit-equal pairs): tdlo_cloud_cluster 0.95 / 2.74 / 3.00 / 9.24 ms on the device route against 151 / 556 / 2 143 / 32 832 ms
+ * on the host route (the all-pairs statement: the ratio flatters the device) -- faster on every line: THE DEVICE ROUTE IS THE DEFAULT.  What clustering adds to
+ * tdlo_tracker_initialize_from_cloud_batch on clouds split beforehand: 1.0 / 2.6 / 3.0 / 9.2 ms.
+ * Route counters 55 / 56: calls served by the cluster launches / by the host route (forced, or after a give-up); a source of 0 points launches nothing and counts
+ * in neither.
+ * OUT OF SCOPE: separating ropes that TOUCH in the first frame (single linkage makes them one cluster: C < F and the tracker call refuses); choosing F from the
+ * cloud; a spatial grid in place of the all-pairs pass; max_size. */
+int tdlo_cloud_cluster(tdlo_ctx *ctx, int src_slot, const int *dst_slots /* F */, int F, double tol, int min_size,
+                       int *n_clusters, int *n_each /* F or NULL */, int *n_unowned, int *owner /* n or NULL */);
+int tdlo_cloud_cluster_host(const double *X, int n, int F, double tol, int min_size, int *owner, int *n_clusters, int *n_each, int *n_unowned);
+int tdlo_tracker_initialize_from_shared_cloud_batch(tdlo_tracker *const *trackers, int F, int src_slot, double tol, int min_size, double mu, int max_iter,
+                                                    double *sigma2_out /* F or NULL */, int *n_clusters, int *n_each /* F or NULL */, int *rc_each);
 
 /* ---- cloud views for many slots in one call ----------------------------------------------------------- */
 /* The same front end for callers who come with CLOUDS (the reference's own input, trackdlo_node.cpp:242; a PointCloud2; torch tensors on the device): F cloud
@@ -1416,6 +1469,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * from kRigPainterMin jobs on) / done by the host statement inside a rig tracker call.
  * 53 / 54: calls of tdlo_cloud_assign, tdlo_cloud_assign_visibility and tdlo_tracker_frames_from_shared_cloud_batch served by the split launches
  * k_assign_count / k_assign_scatter / calls of the latter two in which the pre-pass rode in k_assign_scatter (TDLO_ASSIGN_RIDE=1).
+ * 55 / 56: calls of tdlo_cloud_cluster and tdlo_tracker_initialize_from_shared_cloud_batch served by the cluster launches (k_cluster_link and what follows it) /
+ * served by the host route (TDLO_CLUSTER=host, or after a lane of k_cluster_link gave up).  A source of 0 points counts in neither.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -159,6 +159,7 @@ SYMBOLS = [
     "tdlo_rig_to_cloud_batch", "tdlo_tracker_frames_from_rig_batch", "tdlo_debug_rig_batch_plan", "tdlo_debug_rig_batch_arena",
     "tdlo_rig_self_occlusion_visible", "tdlo_rig_self_occlusion_batch", "tdlo_tracker_set_rig_self_occlusion",
     "tdlo_cloud_assign", "tdlo_cloud_assign_visibility", "tdlo_cloud_assign_host", "tdlo_tracker_frames_from_shared_cloud_batch",
+    "tdlo_cloud_cluster", "tdlo_cloud_cluster_host", "tdlo_tracker_initialize_from_shared_cloud_batch",
 ]
 
 _lib = None
@@ -379,6 +380,10 @@ def load_library(path: str | None = None):
         lib.tdlo_cloud_assign_visibility.argtypes = [vp, ci, vp, ci, cd, cd, cd, vp, vp, C.POINTER(ci), vp, vp, vp, vp, vp]
         lib.tdlo_cloud_assign_host.argtypes = [vp, ci, vp, ci, cd, vp, vp, vp, C.POINTER(ci)]
         lib.tdlo_tracker_frames_from_shared_cloud_batch.argtypes = [vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "tdlo_cloud_cluster"):
+        lib.tdlo_cloud_cluster.argtypes = [vp, ci, vp, ci, cd, ci, C.POINTER(ci), vp, C.POINTER(ci), vp]
+        lib.tdlo_cloud_cluster_host.argtypes = [vp, ci, ci, cd, ci, vp, C.POINTER(ci), vp, C.POINTER(ci)]
+        lib.tdlo_tracker_initialize_from_shared_cloud_batch.argtypes = [vp, ci, ci, cd, ci, cd, ci, vp, C.POINTER(ci), vp, vp]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -1397,6 +1402,29 @@ class Context:
         out = ([int(v) for v in n_each], un.value) + ((own, d2) if owners else ())
         return out if check else (rc,) + out
 
+    def cluster_route_counts(self):
+        """[calls the cluster launches served, calls the host route served (TDLO_CLUSTER=host, or after a give-up)] (tdlo_debug_route_count 55 / 56)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (55, 56)]
+
+    def cloud_cluster(self, src_slot, dst_slots, tol, min_size, owners=False, check=True):
+        """tdlo_cloud_cluster: the cloud resident in src_slot clustered (points linked within tol, connected components, clusters of fewer than min_size points
+        dropped, numbered by their first point) and cluster c dealt to dst_slots[c].  Returns (n_clusters, n_each [F], n_unowned), with owners=True also
+        owner [n]; check=False: the code in front instead of raising."""
+        dst = np.ascontiguousarray(dst_slots, dtype=np.int32)
+        F = len(dst)
+        assert F >= 1
+        n_each = np.zeros(F, dtype=np.int32); nc = C.c_int(0); un = C.c_int(0)
+        own = None
+        if owners:
+            n = C.c_int(0)
+            self.lib.tdlo_get_cloud(self.h, src_slot, None, 0, C.byref(n))
+            own = np.zeros(n.value, dtype=np.int32)
+        rc = self.lib.tdlo_cloud_cluster(self.h, int(src_slot), _ptr(dst), F, float(tol), int(min_size), C.byref(nc), _ptr(n_each), C.byref(un), _ptr(own))
+        if check:
+            self._chk(rc)
+        out = (nc.value, [int(v) for v in n_each], un.value) + ((own,) if owners else ())
+        return out if check else (rc,) + out
+
     def cloud_assign_visibility(self, src_slot, ropes, d_max, visibility_threshold, d_vis, coords):
         """tdlo_cloud_assign_visibility: cloud_assign, then the visibility pre-pass of every rope against the cloud it was dealt (coords: F arrays of M_f).
         Returns (n_each [F], n_unowned, [node_dist], [visible_nodes], [visible_nodes_extended])."""
@@ -2178,6 +2206,36 @@ def cloud_assign_host(X, ropes, d_max, lib=None):
     if rc:
         raise TdloError(rc, "tdlo_cloud_assign_host refused its arguments")
     return own, d2, [int(v) for v in n_each], un.value
+
+
+def cloud_cluster_host(X, F, tol, min_size, lib=None):
+    """tdlo_cloud_cluster_host: the statement of Context.cloud_cluster on the host, in the plain all-pairs form (no HIP, no context).  X [n x 3].
+    Returns (owner [n], n_clusters, n_each [F], n_unowned)."""
+    lib = lib or load_library()
+    X = _f64(X)
+    assert X.ndim == 2 and X.shape[1] == 3
+    n = X.shape[0]
+    own = np.zeros(n, dtype=np.int32); n_each = np.zeros(max(int(F), 0), dtype=np.int32); nc = C.c_int(0); un = C.c_int(0)
+    rc = lib.tdlo_cloud_cluster_host(_ptr(X), n, int(F), float(tol), int(min_size), _ptr(own), C.byref(nc), _ptr(n_each), C.byref(un))
+    if rc:
+        raise TdloError(rc, "tdlo_cloud_cluster_host refused its arguments")
+    return own, nc.value, [int(v) for v in n_each], un.value
+
+
+def initialize_from_shared_cloud_batch(trackers, src_slot, tol, min_size, mu=0.05, max_iter=100, check=True):
+    """tdlo_tracker_initialize_from_shared_cloud_batch: the cloud resident in src_slot clustered into the trackers' slots (Context.cloud_cluster, cluster c to
+    trackers[c]) and, if it has exactly F clusters, initialize_from_cloud_batch on them.  Returns (codes [F], sigma2 [F], n_clusters, n_each [F]); with
+    check=False the call's own code stands in front (TDLO_E_INVALID with the counts written when the cloud has another number of clusters)."""
+    F = len(trackers)
+    assert F >= 1
+    tab = (C.c_void_p * F)(*[t.h for t in trackers])
+    s2 = np.full(F, np.nan); rcs = np.zeros(F, dtype=np.int32); n_each = np.zeros(F, dtype=np.int32); nc = C.c_int(0)
+    rc = trackers[0].ctx.lib.tdlo_tracker_initialize_from_shared_cloud_batch(C.cast(tab, C.c_void_p), F, int(src_slot), float(tol), int(min_size), float(mu),
+                                                                             int(max_iter), _ptr(s2), C.byref(nc), _ptr(n_each), _ptr(rcs))
+    if rc and check:
+        trackers[0].ctx._chk(rc)
+    out = ([int(r) for r in rcs], s2, nc.value, [int(v) for v in n_each])
+    return out if check else (rc,) + out
 
 
 def frames_from_shared_cloud_batch(trackers, src_slot, d_max, d_vis, check=True):

@@ -10,6 +10,7 @@
 #include "tdlo_rig_host.h"
 #include "tdlo_painter_host.h"
 #include "tdlo_assign_host.h"
+#include "tdlo_cluster_lane.h"
 #include "tdlo_view_batch_plan.h"
 #include "tdlo_rig_batch_plan.h"
 
@@ -280,6 +281,11 @@ struct tdlo_ctx {
     bool asg_armed = false;
     bool assign_ride = getenv("TDLO_ASSIGN_RIDE") && atoi(getenv("TDLO_ASSIGN_RIDE")) != 0;
     long long asg_route[2] = {0, 0};
+    // one cloud clustered into ropes (tdlo_cloud_cluster and the tracker call built on it: tdlo_cluster.hip in front of k_assign_scatter).  Its workspace (parent,
+    // size, rank, the kept-root counts) lies in asg_dev behind the split's own blocks; asg_res carries two more words (give-up, C).  TDLO_CLUSTER=host: the owners
+    // come from the host statement.  clu_route: tdlo_debug_route_count 55 / 56: calls the cluster launches served / calls the host route served (forced, or after a give-up)
+    bool cluster_host = getenv("TDLO_CLUSTER") && std::strcmp(getenv("TDLO_CLUSTER"), "host") == 0;
+    long long clu_route[2] = {0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -5403,7 +5409,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 54) return -1;
+    if (!c || which < 0 || which > 56) return -1;
+    if (which >= 55) return c->clu_route[which - 55];
     if (which >= 53) return c->asg_route[which - 53];
     if (which >= 51) return c->pnt_route[which - 51];
     if (which >= 49) return c->rbatch_route[which - 49];
@@ -6821,6 +6828,67 @@ static const char *assign_refusal(const tdlo_ctx *c, int src_slot, const tdlo_as
 
 static size_t asg_pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
+// the split's growing buffers: dev_bytes of asg_dev, T minima (+ the ticket) of asg_state, armed, res_words of asg_res.  Shared by the split and the clustering
+static int asg_reserve(tdlo_ctx *c, size_t dev_bytes, size_t T, size_t res_words) {
+    if (dev_bytes > c->asg_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_dev) hipFree(c->asg_dev);
+        c->asg_dev = nullptr; c->asg_dev_cap = 0;
+        const size_t cap = (dev_bytes + (dev_bytes >> 2) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipMalloc((void **)&c->asg_dev, cap));
+        c->asg_dev_cap = cap;
+    }
+    if (T > c->asg_state_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_state) hipFree(c->asg_state);
+        c->asg_state = nullptr; c->asg_state_cap = 0;
+        const size_t cap = (T + 1023) & ~(size_t)1023;
+        HIPCHK(c, hipMalloc((void **)&c->asg_state, sizeof(unsigned long long) * (cap + 8)));
+        c->asg_state_cap = cap; c->asg_armed = false;
+    }
+    if (!c->asg_armed) {
+        std::vector<unsigned long long> init(c->asg_state_cap + 8, 0x7ff0000000000000ull);
+        for (size_t i = c->asg_state_cap; i < c->asg_state_cap + 8; ++i) init[i] = 0ull;
+        HIPCHK(c, hipMemcpy(c->asg_state, init.data(), sizeof(unsigned long long) * init.size(), hipMemcpyHostToDevice));
+        c->asg_armed = true;
+    }
+    if (res_words > c->asg_res_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->asg_res) hipHostFree(c->asg_res);
+        c->asg_res = nullptr; c->asg_res_cap = 0;
+        const size_t cap = (res_words + 1023) & ~(size_t)1023;
+        HIPCHK(c, hipHostMalloc((void **)&c->asg_res, sizeof(unsigned long long) * cap, hipHostMallocDefault));
+        std::memset(c->asg_res, 0, sizeof(unsigned long long) * cap);
+        c->asg_res_cap = cap; c->asg_epoch = 0;
+    }
+    return TDLO_OK;
+}
+
+// the ONE host wait of a split: until k_assign_scatter's last workgroup has raised the word to asg_epoch
+static int asg_wait(tdlo_ctx *c) {
+    auto t_chk = std::chrono::steady_clock::now();
+    for (unsigned spins = 1;; ++spins) {
+        if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
+        if ((spins & 255u) == 0) {
+            const auto now = std::chrono::steady_clock::now();
+            if (std::chrono::duration<double, std::micro>(now - t_chk).count() > 500.0) {
+                t_chk = now;
+                const hipError_t e = hipStreamQuery(c->stream);
+                if (e == hipSuccess) {
+                    if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
+                    c->asg_armed = false;
+                    return fail(c, TDLO_E_HIP, "the stream drained, but the cloud split did not report");
+                }
+                if (e != hipErrorNotReady) { c->asg_armed = false; return fail(c, TDLO_E_HIP, std::string("stream: ") + hipGetErrorString(e)); }
+            }
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return TDLO_OK;
+}
+
 // what a split left behind: off[F + 1] of the flat node list, the counts, and -- the pre-pass rode -- the T squared minima in pinned host memory (until the next split)
 struct AssignRun { std::vector<int> off, n_each; int n = 0, n_unowned = 0; const double *mins = nullptr; };
 
@@ -6843,38 +6911,7 @@ static int assign_run(tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, 
     const size_t o_dst = asg_pad16(sizeof(int) * ((size_t)F + 1)), o_Y = o_dst + asg_pad16(sizeof(double *) * (size_t)F), tab = o_Y + sizeof(double) * 3 * (size_t)T;
     const size_t o_own = asg_pad16(tab), o_g = o_own + asg_pad16(sizeof(int) * (size_t)n), o_cnt = o_g + sizeof(double) * (size_t)n;
     const size_t need = o_cnt + asg_pad16(sizeof(int) * (size_t)nwg * F);
-    if (need > c->asg_dev_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->asg_dev) hipFree(c->asg_dev);
-        c->asg_dev = nullptr; c->asg_dev_cap = 0;
-        const size_t cap = (need + (need >> 2) + 4095) & ~(size_t)4095;
-        HIPCHK(c, hipMalloc((void **)&c->asg_dev, cap));
-        c->asg_dev_cap = cap;
-    }
-    if ((size_t)T > c->asg_state_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->asg_state) hipFree(c->asg_state);
-        c->asg_state = nullptr; c->asg_state_cap = 0;
-        const size_t cap = ((size_t)T + 1023) & ~(size_t)1023;
-        HIPCHK(c, hipMalloc((void **)&c->asg_state, sizeof(unsigned long long) * (cap + 8)));
-        c->asg_state_cap = cap; c->asg_armed = false;
-    }
-    if (!c->asg_armed) {
-        std::vector<unsigned long long> init(c->asg_state_cap + 8, 0x7ff0000000000000ull);
-        for (size_t i = c->asg_state_cap; i < c->asg_state_cap + 8; ++i) init[i] = 0ull;
-        HIPCHK(c, hipMemcpy(c->asg_state, init.data(), sizeof(unsigned long long) * init.size(), hipMemcpyHostToDevice));
-        c->asg_armed = true;
-    }
-    const size_t res_words = 1 + (size_t)F + (size_t)T;
-    if (res_words > c->asg_res_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->asg_res) hipHostFree(c->asg_res);
-        c->asg_res = nullptr; c->asg_res_cap = 0;
-        const size_t cap = (res_words + 1023) & ~(size_t)1023;
-        HIPCHK(c, hipHostMalloc((void **)&c->asg_res, sizeof(unsigned long long) * cap, hipHostMallocDefault));
-        std::memset(c->asg_res, 0, sizeof(unsigned long long) * cap);
-        c->asg_res_cap = cap; c->asg_epoch = 0;
-    }
+    if ((rc = asg_reserve(c, need, (size_t)T, 1 + (size_t)F + (size_t)T))) return rc;
     // the pinned staging block: [off | dst | Yx | Yy | Yz], copied up once
     if ((rc = ensure_pin(c, (tab + 7) / 8 + 8))) return rc;
     char *hp = (char *)c->pin;
@@ -6894,26 +6931,7 @@ static int assign_run(tdlo_ctx *c, int src_slot, const tdlo_assign_rope *ropes, 
     HIPCHK(c, launch_assign(c->slots[src_slot].Xraw, n, (const int *)c->asg_dev, (double *const *)(c->asg_dev + o_dst), (const double *)(c->asg_dev + o_Y), F, T,
                             d_max * d_max, d_owner, owner_d2 ? d_g : nullptr, (int *)(c->asg_dev + o_cnt), ride, c->asg_state, c->asg_state + c->asg_state_cap,
                             c->asg_res, c->asg_epoch, st));
-    auto t_chk = std::chrono::steady_clock::now();
-    for (unsigned spins = 1;; ++spins) {
-        if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
-        if ((spins & 255u) == 0) {
-            const auto now = std::chrono::steady_clock::now();
-            if (std::chrono::duration<double, std::micro>(now - t_chk).count() > 500.0) {
-                t_chk = now;
-                const hipError_t e = hipStreamQuery(st);
-                if (e == hipSuccess) {
-                    if ((unsigned)__atomic_load_n(c->asg_res, __ATOMIC_ACQUIRE) == c->asg_epoch) break;
-                    c->asg_armed = false;
-                    return fail(c, TDLO_E_HIP, "the stream drained, but the cloud split did not report");
-                }
-                if (e != hipErrorNotReady) { c->asg_armed = false; return fail(c, TDLO_E_HIP, std::string("stream: ") + hipGetErrorString(e)); }
-            }
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
+    if ((rc = asg_wait(c))) return rc;
     long long owned = 0;
     for (int f = 0; f < F; ++f) {
         const int nf = (int)(unsigned)c->asg_res[1 + f];
@@ -7030,6 +7048,134 @@ int tdlo_tracker_frames_from_shared_cloud_batch(tdlo_tracker *const *trackers, i
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && run.n_each[i] == 0) ? fail(c, TDLO_E_EMPTY, "the rope owns no point of the shared cloud: no cloud for this frame") : rcs[i];
     return TDLO_OK;
+}
+
+// ---- starting ropes of one colour: one cloud clustered into F slots (include/trackdlo_hip.h has the statement; tdlo_cluster.hip the kernels) ---------------------
+// what refuses a call as a whole, nullptr when nothing does
+static const char *cluster_refusal(const tdlo_ctx *c, int src_slot, const int *dst_slots, int F, double tol, int min_size) {
+    const int S = (int)c->slots.size();
+    if (F < 1 || F > S) return "cloud cluster: F < 1 or F > max_frames";
+    if (F > kAssignMaxRopes) return "cloud cluster: more than 2048 destinations";
+    if (!dst_slots) return "cloud cluster: null dst_slots";
+    if (const char *why = cluster_fault(F, tol, min_size)) return why;
+    if (src_slot < 0 || src_slot >= S) return "cloud cluster: the context has no such source slot";
+    for (int f = 0; f < F; ++f) {
+        if (dst_slots[f] < 0 || dst_slots[f] >= S) return "cloud cluster: the context has no such destination slot";
+        if (dst_slots[f] == src_slot) return "cloud cluster: the source slot is among the destinations";
+        for (int j = 0; j < f; ++j) if (dst_slots[j] == dst_slots[f]) return "cloud cluster: the destinations must be distinct";
+    }
+    if (c->slots[src_slot].N0 > kClusterMaxPoints) return "cloud cluster: more than 262 144 points (every pair is tested: a call's time must stay bounded)";
+    return nullptr;
+}
+
+struct ClusterRun { std::vector<int> n_each; int n = 0, n_clusters = 0, n_unowned = 0; };
+
+// the clustering of checked arguments.  Device route: the cluster launches and k_assign_scatter, ONE wait.  Host route (TDLO_CLUSTER=host, or a lane gave up): the
+// cloud comes down, owners and their per-workgroup counts go up, the same k_assign_scatter.  owner (NULL or n entries) is copied out behind it
+static int cluster_run(tdlo_ctx *c, int src_slot, const int *dst_slots, int F, double tol, int min_size, int *owner, ClusterRun &run) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if (c->cloud_pending >= 0 && (rc = flush_pending_cloud(c))) return rc;
+    const int n = c->slots[src_slot].N0;
+    run.n_each.assign(F, 0); run.n = n; run.n_clusters = 0; run.n_unowned = 0;
+    if (n <= 0) {      // nothing to cluster: every destination is the cloud of 0 points
+        for (int f = 0; f < F; ++f) { Slot &d = c->slots[dst_slots[f]]; d.N0 = 0; d.sorted_valid = false; }
+        return TDLO_OK;
+    }
+    for (int f = 0; f < F; ++f) if ((rc = ensure_points(c, c->slots[dst_slots[f]], n))) return rc;      // a cluster may hold every point
+    int nwg, cpb;
+    assign_geometry(n, &nwg, &cpb);
+    const size_t chunks = ((size_t)n + kBlock - 1) / kBlock, ints = asg_pad16(sizeof(int) * (size_t)n);
+    // asg_dev: [dst x F | owner | counts] -- what the host route sends up in one copy -- then [parent | size | rank | kept roots per chunk]
+    const size_t o_own = asg_pad16(sizeof(double *) * (size_t)F), o_cnt = o_own + ints, o_par = o_cnt + asg_pad16(sizeof(int) * (size_t)nwg * F);
+    const size_t o_size = o_par + ints, o_rank = o_size + ints, o_kc = o_rank + ints, need = o_kc + asg_pad16(sizeof(int) * chunks);
+    if ((rc = asg_reserve(c, need, 1, 1 + (size_t)F + 2)) || (rc = ensure_pin(c, o_par / 8 + 8))) return rc;
+    char *hp = (char *)c->pin;
+    double **hdst = (double **)hp;
+    for (int f = 0; f < F; ++f) hdst[f] = c->slots[dst_slots[f]].Xraw;
+    hipStream_t st = c->stream;
+    const double *X = c->slots[src_slot].Xraw;
+    int *d_owner = (int *)(c->asg_dev + o_own), *d_cnt = (int *)(c->asg_dev + o_cnt);
+    unsigned long long *giveup = c->asg_res + 1 + F, *n_clusters = giveup + 1;      // behind the scatter's [word | F counts]
+    auto scatter = [&]() {
+        if (++c->asg_epoch == 0) ++c->asg_epoch;
+        return launch_assign_scatter(X, n, d_owner, d_cnt, nullptr, (double *const *)c->asg_dev, nullptr, F, 0, false, c->asg_state, c->asg_state + c->asg_state_cap,
+                                     c->asg_res, c->asg_epoch, st);
+    };
+    bool host = c->cluster_host;
+    if (!host) {
+        __atomic_store_n(giveup, 0ull, __ATOMIC_RELEASE);
+        HIPCHK(c, hipMemcpyAsync(c->asg_dev, hp, sizeof(double *) * (size_t)F, hipMemcpyHostToDevice, st));
+        HIPCHK(c, launch_cluster(X, n, tol * tol, min_size, F, (int *)(c->asg_dev + o_par), (int *)(c->asg_dev + o_size), (int *)(c->asg_dev + o_rank),
+                                 (int *)(c->asg_dev + o_kc), d_owner, d_cnt, giveup, n_clusters, st));
+        HIPCHK(c, scatter());
+        if ((rc = asg_wait(c))) return rc;
+        if (__atomic_load_n(giveup, __ATOMIC_ACQUIRE)) host = true;      // a lane ran out of attempts: what the launches wrote is overwritten below
+        else { run.n_clusters = (int)(unsigned)*n_clusters; ++c->clu_route[0]; }
+    }
+    if (host) {
+        std::vector<double> Xh(3 * (size_t)n);
+        HIPCHK(c, hipMemcpyAsync(Xh.data(), X, sizeof(double) * Xh.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, wait_stream(st));
+        int *h_owner = (int *)(hp + o_own);
+        if (!cluster_owners_host(Xh.data(), n, F, tol * tol, min_size, h_owner, &run.n_clusters)) return fail(c, TDLO_E_NUMERIC, "cloud cluster: the host statement gave up");
+        cluster_counts_host(h_owner, n, F, kBlock, nwg, cpb, (int *)(hp + o_cnt));
+        HIPCHK(c, hipMemcpyAsync(c->asg_dev, hp, o_par, hipMemcpyHostToDevice, st));
+        HIPCHK(c, scatter());
+        if ((rc = asg_wait(c))) return rc;
+        ++c->clu_route[1];
+    }
+    long long owned = 0;
+    for (int f = 0; f < F; ++f) {
+        const int nf = (int)(unsigned)c->asg_res[1 + f];
+        run.n_each[f] = nf; owned += nf;
+        Slot &d = c->slots[dst_slots[f]];
+        d.N0 = nf; d.sorted_valid = false;      // as tdlo_set_cloud leaves it
+    }
+    run.n_unowned = (int)(n - owned);
+    if (owner) {
+        HIPCHK(c, hipMemcpyAsync(owner, d_owner, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, wait_stream(st));
+    }
+    return TDLO_OK;
+}
+
+int tdlo_cloud_cluster(tdlo_ctx *c, int src_slot, const int *dst_slots, int F, double tol, int min_size, int *n_clusters, int *n_each, int *n_unowned, int *owner) {
+    if (!c) return TDLO_E_INVALID;
+    if (const char *why = cluster_refusal(c, src_slot, dst_slots, F, tol, min_size)) return fail(c, TDLO_E_INVALID, why);
+    ClusterRun run;
+    if (const int rc = cluster_run(c, src_slot, dst_slots, F, tol, min_size, owner, run)) return rc;
+    if (n_clusters) *n_clusters = run.n_clusters;
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    if (n_unowned) *n_unowned = run.n_unowned;
+    return TDLO_OK;
+}
+
+int tdlo_tracker_initialize_from_shared_cloud_batch(tdlo_tracker *const *trackers, int F, int src_slot, double tol, int min_size, double mu, int max_iter,
+                                                    double *sigma2_out, int *n_clusters, int *n_each, int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    const int M = trackers[0]->M;
+    if (F > (int)c->slots.size()) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: more trackers than the context has slots");
+    std::vector<int> slots(F);
+    for (int i = 0; i < F; ++i) {      // (what tdlo_tracker_initialize_from_cloud_batch would refuse behind the split is refused in front of it)
+        const tdlo_tracker *t = trackers[i];
+        if (!t) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: a tracker is null");
+        if (t->ctx != c) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: the trackers of a batch share one context");
+        if (t->M != M) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: the trackers of a batch share num_of_nodes");
+        slots[i] = t->slot;
+    }
+    if (M < 4 || M > reg_max_nodes()) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: a tracker has 4 .. " + std::to_string(reg_max_nodes()) + " nodes (tdlo_reg)");
+    if (max_iter < 0 || !(mu >= 0 && mu < 1)) return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: bad reg arguments");
+    if (const char *why = cluster_refusal(c, src_slot, slots.data(), F, tol, min_size)) return fail(c, TDLO_E_INVALID, why);
+    ClusterRun run;
+    if (const int rc = cluster_run(c, src_slot, slots.data(), F, tol, min_size, nullptr, run)) return rc;
+    if (n_clusters) *n_clusters = run.n_clusters;
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    if (run.n_clusters != F)
+        return fail(c, TDLO_E_INVALID, "initialize_from_shared_cloud_batch: the cloud has " + std::to_string(run.n_clusters) + " clusters for " + std::to_string(F) +
+                                           " trackers (the slots hold the split, no tracker was touched)");
+    return tdlo_tracker_initialize_from_cloud_batch(trackers, F, mu, max_iter, sigma2_out, rc_each);
 }
 
 // The rope tdlo_tracker_render_result draws: the projection matrix it chooses and the reference's not_self_occluded_nodes.  false: no matrix to be had.

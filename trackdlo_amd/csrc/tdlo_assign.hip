@@ -144,12 +144,18 @@ hipError_t launch_assign(const double *X, int n, const int *off, double *const *
     int nwg, cpb;
     assign_geometry(n, &nwg, &cpb);
     const size_t lds_count = sizeof(double) * 3 * kAssignTile + sizeof(int) * (size_t)(((F + 1 + 3) & ~3) + ((F + 3) & ~3));
-    const size_t lds_scatter = sizeof(int) * (size_t)(6 * ((F + 3) & ~3) + 4);
     hipLaunchKernelGGL(k_assign_count, dim3(nwg), dim3(kBlock), lds_count, s, X, n, off, Y, F, T, dmax2, cpb, owner, g, counts);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_assign_scatter, dim3(nwg), dim3(kBlock), lds_scatter, s, X, n, (const int *)owner, (const int *)counts, cpb, off, dst, Y, F, T, ride ? 1 : 0,
-                       state, ticket, res_host, epoch);
+    return launch_assign_scatter(X, n, owner, counts, off, dst, Y, F, T, ride, state, ticket, res_host, epoch, s);
+}
+
+hipError_t launch_assign_scatter(const double *X, int n, const int *owner, const int *counts, const int *off, double *const *dst, const double *Y, int F, int T,
+                                 bool ride, unsigned long long *state, unsigned long long *ticket, unsigned long long *res_host, unsigned epoch, hipStream_t s) {
+    int nwg, cpb;
+    assign_geometry(n, &nwg, &cpb);
+    const size_t lds_scatter = sizeof(int) * (size_t)(6 * ((F + 3) & ~3) + 4);
+    hipLaunchKernelGGL(k_assign_scatter, dim3(nwg), dim3(kBlock), lds_scatter, s, X, n, owner, counts, cpb, off, dst, Y, F, T, ride ? 1 : 0, state, ticket, res_host, epoch);
     return hipGetLastError();
 }
 

@@ -269,6 +269,19 @@ constexpr int kAssignMaxRopes = 2048;     // ropes of one call (the scatter kern
 void assign_geometry(int n, int *nwg, int *cpb);      // workgroups of both kernels, chunks of kBlock points per workgroup
 hipError_t launch_assign(const double *X, int n, const int *off, double *const *dst, const double *Y, int F, int T, double dmax2, int *owner, double *g, int *counts,
                          bool ride, unsigned long long *state, unsigned long long *ticket, unsigned long long *res_host, unsigned epoch, hipStream_t s);
+// (k_assign_scatter alone, for owners and counts somebody else formed: the second launch of launch_assign.  ride off: off and Y are not read)
+hipError_t launch_assign_scatter(const double *X, int n, const int *owner, const int *counts, const int *off, double *const *dst, const double *Y, int F, int T,
+                                 bool ride, unsigned long long *state, unsigned long long *ticket, unsigned long long *res_host, unsigned epoch, hipStream_t s);
+// tdlo_cluster.hip: one cloud clustered into ropes (k_cluster_init / _link / _flatten / _count / _rank / _owner), in front of launch_assign_scatter.  parent, size,
+// rank [n], kcnt [ceil(n / kBlock)]: workspace; owner [n], counts [nwg x F]: what k_assign_scatter reads; giveup_host (zeroed by the caller), n_clusters_host:
+// words in pinned host memory, complete when the scatter reports
+hipError_t launch_cluster(const double *X, int n, double tol2, int min_size, int F, int *parent, int *size, int *rank, int *kcnt, int *owner, int *counts,
+                          unsigned long long *giveup_host, unsigned long long *n_clusters_host, hipStream_t s);
+// tdlo_cluster_host.cpp (no HIP): the statement on the host.  cluster_fault: what refuses F, tol or min_size, or nullptr; cluster_owners_host: owner [n] and C of
+// checked arguments (false: a join gave up); cluster_counts_host: the owners' counts [nwg x F] as k_assign_count lays them out
+const char *cluster_fault(int F, double tol, int min_size);
+bool cluster_owners_host(const double *X, int n, int F, double tol2, int min_size, int *owner, int *n_clusters);
+void cluster_counts_host(const int *owner, int n, int F, int block, int nwg, int cpb, int *counts);
 size_t mstep_lds_bytes(int M);
 // tdlo_mstep_big.hip: M-step for 60 < M <= kMaxNodes without LLE (blocked Gauss-Jordan, tableau in global memory)
 hipError_t launch_mstep_big(const FrameDev *frames_dev, const FrameDev *frames_host, int F, int from_sums, bool f64, hipStream_t s);

@@ -919,6 +919,81 @@ int tdlo_rig_self_occlusion_batch(tdlo_ctx *ctx, int F, const tdlo_rig_painter_f
                                   int *visible_nodes /* F x Mmax */, int *n_vis /* F */, unsigned *seen_words, unsigned *hidden_words);
 int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_cam /* NULL or K x 12 */, int K, int dlo_pixel_width);
 
+/* ---- ropes that hide one another: the painter test over a cell of ropes ----------------------------------------- */
+/* Every test above looks at ONE rope's own edges.  In a harness of cables rope A lying over rope B is the normal case: B's nodes under the crossing stay
+ * "visible", the shared-cloud split gives the crossing's points to whichever rope has the nearer node, and B is pulled towards A's points.  THIS is the painter
+ * test with every rope of the cell painted into the same picture.
+ * A CELL: F ropes in the caller's order, rope f with nodes Y_f (M_f x 3 doubles, column-major), node_dist_f[M_f] and visibility_threshold_f; ONE rig (cams,
+ * rig_to_cam NULL or K x 12, K, rows, cols, exactly as in "self-occlusion under a rig") and ONE dlo_pixel_width w.  The FLAT INDEX of node m of rope f is
+ * n = off_f + m with off_f = M_0 + ... + M_{f-1}; N = sum of the M_f is the number of nodes of the cell.
+ * PER CAMERA k:
+ *   1. Steps 1 and 2 of "self-occlusion under a rig", word for word, for every node of every rope: the camera-frame node without fused multiply-adds, the
+ *      pixel, DRAWABLE and SEEN.
+ *   2. edges: edge (f, i) joins nodes i and i + 1 of rope f and has the flat index off_f + i.  NO edge joins the last node of one rope to the first node of the
+ *      next.  An edge is PAINTED when both of its ends are drawable; its key is that section's key of its camera-frame ends.
+ *   3. order: all painted edges of the cell are ordered together by (key, flat edge index) ascending.
+ *   4. first_k(n): the earlier, in that order, of node n's painted incident edges (edges of its own rope only).  A node without a painted incident edge stands
+ *      after every painted edge -- the only node of a rope with M_f = 1 among them.
+ *   5. node n is HIDDEN in k when it is drawable and some painted edge of ANY rope covers its pixel (within w / 2 of the segment between the edge's end pixels,
+ *      in exact integer arithmetic, unchanged) and stands STRICTLY before first_k(n).
+ * THE VERDICT: node (f, m) is visible when node_dist_f[m] <= visibility_threshold_f (a NaN distance fails) AND at least one camera sees it and does not hide
+ * it.  A camera that does not see a node has no say.  The sets are per rope, ascending, in rope-local indices.
+ * CONSEQUENCES (tests/test_cell_painter_ref.py): (a) F = 1 gives the set and the words of tdlo_rig_self_occlusion_visible, bit for bit.  (b) The ropes of a
+ * cell may be permuted: that changes a verdict only through the tie rule of equal keys (the flat index decides).  Parity against OpenCV's rasteriser stays
+ * UNPINNED, as everywhere.
+ * seen_words / hidden_words (optional): K x ceil(N / 32) words a cell, bit n % 32 of word n / 32 of camera k, n the flat index; in the batch call each of the two
+ * arrays holds its words cell after cell, packed.
+ * "Ordered" is the statement's wording: an implementation may decide "before" by comparing (key, flat index) pairs and never sort; this one does.
+ *
+ * tdlo_cell_occlusion_visible: the host statement (csrc/tdlo_cell_painter_host.cpp through csrc/tdlo_cell_painter_lane.h, the header the kernels compile;
+ * no context, no GPU).  visible_nodes: F pointers, rope f's to M_f entries; n_vis: F counts.
+ * tdlo_cell_occlusion_batch: C cells of one image size -- each its own ropes, rig and width -- in ONE upload, TWO launches and ONE wait
+ * (csrc/tdlo_cell_painter.hip).  Per camera the work is N nodes x N edges, so one workgroup per (camera, cell) would leave the device idle: a job is spread
+ * over node blocks, grid (node blocks of 256 of the largest cell, largest K, cells), lane = flat node; a workgroup beyond its cell's node count or its cell's K
+ * leaves at once; nobody waits for anybody, there is no grid barrier.  k_cell_project writes the (camera, cell) table of 16-byte records (key of the edge that
+ * starts at the node, the pixel as two int16, flags) and the seen words; k_cell_cover keeps its node's pixel and threshold pair (key, flat index of first_k(n))
+ * in registers, streams the cell's table through LDS in tiles of 512 edges (every lane reads the same record: a broadcast), tests per edge painted, "before my
+ * threshold", a pixel box reject, then the exact coverage, and stops testing as soon as no drawable node of the wave is undecided.  The words arrive in pinned
+ * host memory (ballots, stored by lane 0); the host forms union, thresholds and sets.  visible_nodes: sum over the cells of F_c rows of Mmax entries, Mmax the
+ * largest M_f of the call, cell after cell in rope order; n_vis likewise.  Always the kernels: the host statement's sets and words, bit for bit.
+ * REFUSED as a whole with TDLO_E_INVALID, nothing touched: every refusal of the rig test (K outside 1 .. 64; dlo_pixel_width outside 1 .. 255; rows or cols
+ * outside 1 .. 8192; an intrinsic or matrix entry that is not finite, a camera's 12 NaN apart; fx or fy 0; a null Y, cams or node_dist); F < 1; M_f outside
+ * 1 .. 1024; N > 16 384 (kCellPainterMaxNodes: every node meets every edge and a call's time on shared hardware must stay bounded, as for the cluster call);
+ * in the batch call fewer than 1 or more than 1024 cells.
+ *
+ * tdlo_tracker_frames_from_shared_cloud_occluded_batch: tdlo_tracker_frames_from_shared_cloud_batch with the cell's verdict in place of every tracker's
+ * visible set.  (1) the split and the pre-pass as there; (2) the F trackers' ropes, in the call's order, are ONE cell under `view`; every tracker's visible
+ * set is the cell's verdict on its rope -- formed on the trackers' nodes as they stand before the step, with the pre-pass's node_dist and the tracker's own
+ * threshold; (3) the gap fill (tdlo_extend_visible_nodes); (4) tdlo_tracker_tracking_step_batch.  It is the composition tdlo_cloud_assign_visibility,
+ * tdlo_cell_occlusion_visible, tdlo_extend_visible_nodes, tdlo_tracker_tracking_step_batch made by hand, bit for bit.  A tracker with either self-occlusion
+ * switch on (tdlo_tracker_set_self_occlusion, tdlo_tracker_set_rig_self_occlusion) is refused with TDLO_E_INVALID and nothing is touched: the cell test
+ * subsumes both.  So is what the cell test refuses (F M > 16 384 among it).  A tracker that owns no point gets TDLO_E_EMPTY and stays untouched, as in the
+ * existing call; its rope still takes part in the cell as an occluder.  On the kernel route the two launches are enqueued in front of the split, whose wait
+ * they share: the call adds no host wait (the pre-pass's distances are needed on the host alone, for the threshold; nothing on the device depends on them).
+ * ROUTE RULE (set before anything was measured): the tracker call takes the kernels from kCellPainterMin (flat nodes x cameras, N K) on and the host
+ * statement below it; kCellPainterMin is the smallest measured N K at and above which the kernels are faster on every measured line of
+ * profiles/cell_painter_ab.txt (scripts/gpu_cell_painter.py: F = 2, 4, 8, 32 ropes of 45 nodes and 16 ropes of 1024 nodes, each at K = 1 and K = 3), a value
+ * above any cell if they win nowhere.  MEASURED (one cell, kernels against host statement, ms, every compared pair bit-equal): N K = 90: 0.053 / 0.012; 180:
+ * 0.079 / 0.029; 270: 0.053 / 0.025; 360: 0.139 / 0.122; 540: 0.082 / 0.095; 1080: 0.137 / 0.446; 1440: 0.454 / 2.01; 4320: 0.458 / 5.39; 16 384 (16 ropes of
+ * 1024 nodes, K = 1): 4.16 / 180.5; 49 152 (K = 3): 4.19 / 540.2.  kCellPainterMin = 540.  The tracker call (F ropes of 45 nodes, 750 F points, kernels / host
+ * statement / tdlo_tracker_frames_from_shared_cloud_batch without the test): F = 2: 0.29 / 0.26 / 0.25 at K = 1, 0.29 / 0.28 / 0.25 at K = 3; F = 4: 0.37 /
+ * 0.33 / 0.30 and 0.37 / 0.41 / 0.30; F = 8: 0.61 / 0.62 / 0.49 and 0.62 / 0.83 / 0.50; F = 32: 3.28 / 4.31 / 1.32 and 3.67 / 7.64 / 1.28 (the trackers of
+ * the two sides of the last comparison do not see the same visible sets, so they do not run the same registrations).
+ * TDLO_CELL_PAINTER_MIN=n (n >= 0, read when the context is made) overrides; 0: always the kernels.  Both routes give the same bits.
+ * Route counters 57 / 58: (camera, cell) jobs the kernels served / jobs the host statement did inside the tracker call.
+ * OUT OF SCOPE: a joint E-step over all ropes' nodes; parity against OpenCV's rasteriser. */
+typedef struct { const double *Y; int M; const double *node_dist; double visibility_threshold; } tdlo_cell_rope;
+typedef struct { const tdlo_cell_rope *ropes; int F; const tdlo_rig_camera *cams; const double *rig_to_cam; /* NULL or K x 12 */ int K; int dlo_pixel_width; } tdlo_cell;
+typedef struct { const tdlo_rig_camera *cams; const double *rig_to_cam; /* NULL or K x 12 */ int K; int rows, cols; int dlo_pixel_width; } tdlo_cell_view;
+int tdlo_cell_occlusion_visible(const tdlo_cell_rope *ropes, int F, const tdlo_rig_camera *cams, const double *rig_to_cam, int K, int rows, int cols,
+                                int dlo_pixel_width, int *const *visible_nodes /* F rows of M_f */, int *n_vis /* F */,
+                                unsigned *seen_words /* NULL or K x ceil(N / 32) */, unsigned *hidden_words);
+int tdlo_cell_occlusion_batch(tdlo_ctx *ctx, int C, const tdlo_cell *cells, int rows, int cols,
+                              int *visible_nodes /* (sum F_c) x Mmax */, int *n_vis /* sum F_c */, unsigned *seen_words, unsigned *hidden_words);
+int tdlo_tracker_frames_from_shared_cloud_occluded_batch(tdlo_tracker *const *trackers, int F, int src_slot, double d_max, double d_vis,
+                                                         const tdlo_cell_view *view, int *visible_nodes /* F x M or NULL */, int *n_vis,
+                                                         int *visible_nodes_extended, int *n_vis_ext, int *n_each /* F or NULL */, tdlo_stats *stats, int *rc_each);
+
 /* ---- ropes of one colour: one cloud dealt out among F trackers on the device ------------------------------------ */
 /* Every entrance above gives each rope a cloud of its own -- its own mask, its own colour ranges.  A harness of identical cables has ropes no segmentation
  * can tell apart: ONE cloud and F trackers.  These calls deal one resident cloud out among F slots on the device and step the trackers on it.
@@ -963,8 +1038,8 @@ int tdlo_tracker_set_rig_self_occlusion(tdlo_tracker *t, const double *rig_to_ca
  * THE RIDE IS OFF BY DEFAULT, TDLO_ASSIGN_RIDE=1 (read when the context is made) turns it on.  Both routes give the same bits.  A rope of more than 1024
  * nodes, or TDLO_DIRECT_UPLOAD=0 (the pre-pass's own fall-back), takes the two calls.
  * Route counters 53 / 54: calls the split launches served (a source of 0 points launches nothing and is not counted) / calls in which the pre-pass rode.
- * OUT OF SCOPE: one rope hiding ANOTHER in the self-occlusion test; a joint E-step over all ropes' nodes.  (Starting F same-coloured ropes from one cloud:
- * the next section.) */
+ * OUT OF SCOPE: a joint E-step over all ropes' nodes.  (One rope hiding another: "ropes that hide one another" above,
+ * tdlo_tracker_frames_from_shared_cloud_occluded_batch.  Starting F same-coloured ropes from one cloud: the next section.) */
 typedef struct { int slot; const double *Y; int M; } tdlo_assign_rope;
 int tdlo_cloud_assign(tdlo_ctx *ctx, int src_slot, const tdlo_assign_rope *ropes, int F, double d_max,
                       int *n_each /* F or NULL */, int *n_unowned, int *owner /* n or NULL */, double *owner_d2 /* n or NULL */);
@@ -1471,6 +1546,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * k_assign_count / k_assign_scatter / calls of the latter two in which the pre-pass rode in k_assign_scatter (TDLO_ASSIGN_RIDE=1).
  * 55 / 56: calls of tdlo_cloud_cluster and tdlo_tracker_initialize_from_shared_cloud_batch served by the cluster launches (k_cluster_link and what follows it) /
  * served by the host route (TDLO_CLUSTER=host, or after a lane of k_cluster_link gave up).  A source of 0 points counts in neither.
+ * 57 / 58: (camera, cell) jobs of the painter test over a cell of ropes served by k_cell_project / k_cell_cover (tdlo_cell_occlusion_batch, and
+ * tdlo_tracker_frames_from_shared_cloud_occluded_batch from kCellPainterMin flat nodes x cameras on) / done by the host statement inside that tracker call.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -109,6 +109,18 @@ class RigPainterFrameC(C.Structure):               # tdlo_rig_painter_frame: one
                 ("node_dist", C.c_void_p), ("visibility_threshold", C.c_double)]
 
 
+class CellRopeC(C.Structure):                      # tdlo_cell_rope: one rope of a cell -- its nodes (M x 3 column-major), distances and threshold
+    _fields_ = [("Y", C.c_void_p), ("M", C.c_int), ("node_dist", C.c_void_p), ("visibility_threshold", C.c_double)]
+
+
+class CellC(C.Structure):                          # tdlo_cell: F ropes under one rig for the painter test over a cell of ropes
+    _fields_ = [("ropes", C.c_void_p), ("F", C.c_int), ("cams", C.c_void_p), ("rig_to_cam", C.c_void_p), ("K", C.c_int), ("dlo_pixel_width", C.c_int)]
+
+
+class CellViewC(C.Structure):                      # tdlo_cell_view: the rig, image size and width the occluded shared-cloud tracker call looks through
+    _fields_ = [("cams", C.c_void_p), ("rig_to_cam", C.c_void_p), ("K", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("dlo_pixel_width", C.c_int)]
+
+
 class AssignRopeC(C.Structure):                    # tdlo_assign_rope: a destination slot and the rope's nodes (M x 3 column-major)
     _fields_ = [("slot", C.c_int), ("Y", C.c_void_p), ("M", C.c_int)]
 
@@ -160,6 +172,7 @@ SYMBOLS = [
     "tdlo_rig_self_occlusion_visible", "tdlo_rig_self_occlusion_batch", "tdlo_tracker_set_rig_self_occlusion",
     "tdlo_cloud_assign", "tdlo_cloud_assign_visibility", "tdlo_cloud_assign_host", "tdlo_tracker_frames_from_shared_cloud_batch",
     "tdlo_cloud_cluster", "tdlo_cloud_cluster_host", "tdlo_tracker_initialize_from_shared_cloud_batch",
+    "tdlo_cell_occlusion_visible", "tdlo_cell_occlusion_batch", "tdlo_tracker_frames_from_shared_cloud_occluded_batch",
 ]
 
 _lib = None
@@ -384,6 +397,10 @@ def load_library(path: str | None = None):
         lib.tdlo_cloud_cluster.argtypes = [vp, ci, vp, ci, cd, ci, C.POINTER(ci), vp, C.POINTER(ci), vp]
         lib.tdlo_cloud_cluster_host.argtypes = [vp, ci, ci, cd, ci, vp, C.POINTER(ci), vp, C.POINTER(ci)]
         lib.tdlo_tracker_initialize_from_shared_cloud_batch.argtypes = [vp, ci, ci, cd, ci, cd, ci, vp, C.POINTER(ci), vp, vp]
+    if hasattr(lib, "tdlo_cell_occlusion_visible"):
+        lib.tdlo_cell_occlusion_visible.argtypes = [vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
+        lib.tdlo_cell_occlusion_batch.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
+        lib.tdlo_tracker_frames_from_shared_cloud_occluded_batch.argtypes = [vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "tdlo_render_result_batch"):
         lib.tdlo_render_batch_table.argtypes = [vp, ci, ci, vp, vp, ci, C.POINTER(ci), vp]
         lib.tdlo_render_result_batch.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp]
@@ -1108,6 +1125,46 @@ class Context:
         """[(camera, frame) jobs of the self-occlusion test under a rig served by the kernel, jobs done by the host statement inside a rig tracker call]
         (tdlo_debug_route_count 51 / 52)."""
         return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (51, 52)]
+
+    def cell_occlusion_batch(self, cells, rows, cols, words=False):
+        """tdlo_cell_occlusion_batch: the painter test over C cells of ropes in two launches (k_cell_project, k_cell_cover).  cells: tuples
+        (ropes, cams, rig_to_cam, dlo_pixel_width) with ropes a list of (Y [M x 3], node_dist, visibility_threshold) and cams / rig_to_cam as
+        cell_occlusion_visible takes them; cells may differ in everything.  Returns per cell the list of its ropes' visible indices (rope-local); with
+        words=True also the lists of the cells' seen and hidden words, [K_c x ceil(N_c / 32)] uint32 each, bit = flat node index."""
+        cells = list(cells)
+        Cn = len(cells)
+        tab = (CellC * max(Cn, 1))(); keep = []
+        Fs, Ks, Ns, Ms = [], [], [], []
+        for i, (ropes, cams, rig_to_cam, width) in enumerate(cells):
+            rt, F, N, Mx, k2 = _cell_ropes(ropes)
+            ct, K = _painter_cams(cams); T = _painter_matrices(rig_to_cam, K)
+            keep += [rt, k2, ct, T]
+            tab[i].ropes = C.cast(rt, C.c_void_p).value; tab[i].F = F; tab[i].cams = C.cast(ct, C.c_void_p).value
+            tab[i].rig_to_cam = None if T is None else T.ctypes.data; tab[i].K = K; tab[i].dlo_pixel_width = int(width)
+            Fs.append(F); Ks.append(K); Ns.append(N); Ms.append(Mx)
+        Mmax = max([m for mx in Ms for m in mx] + [1])
+        rows_n = max(sum(Fs), 1)
+        nw = [K * ((N + 31) // 32) for K, N in zip(Ks, Ns)]
+        vis = np.zeros((rows_n, Mmax), dtype=np.int32); nv = np.zeros(rows_n, dtype=np.int32)
+        seen = np.zeros(max(sum(nw), 1), dtype=np.uint32); hidden = np.zeros_like(seen)
+        rc = self.lib.tdlo_cell_occlusion_batch(self.h, Cn, C.cast(tab, C.c_void_p), int(rows), int(cols), _ptr(vis), _ptr(nv),
+                                                _ptr(seen) if words else None, _ptr(hidden) if words else None)
+        del keep
+        self._chk(rc)
+        out, r = [], 0
+        for F in Fs:
+            out.append([vis[r + f, :nv[r + f]].copy() for f in range(F)])
+            r += F
+        if not words:
+            return out
+        off = np.concatenate(([0], np.cumsum(nw))).astype(int)
+        cut = lambda a: [a[off[i]:off[i + 1]].reshape(Ks[i], -1).copy() for i in range(Cn)]
+        return out, cut(seen), cut(hidden)
+
+    def cell_painter_route_counts(self):
+        """[(camera, cell) jobs of the painter test over a cell of ropes served by the kernels, jobs done by the host statement inside the occluded shared-cloud
+        tracker call] (tdlo_debug_route_count 57 / 58)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (57, 58)]
 
     def rig_batch_arena(self):
         """(address, bytes) of the rig-batch arena as it stands (tdlo_debug_rig_batch_arena; (0, 0) before the first batch launch)."""
@@ -2251,6 +2308,23 @@ def frames_from_shared_cloud_batch(trackers, src_slot, d_max, d_vis, check=True)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n]
 
 
+def frames_from_shared_cloud_occluded_batch(trackers, src_slot, d_max, d_vis, cams, rig_to_cam, rows, cols, dlo_pixel_width, check=True):
+    """tdlo_tracker_frames_from_shared_cloud_occluded_batch: frames_from_shared_cloud_batch with every tracker's visible set replaced by the verdict of the
+    painter test over the cell of all the trackers' ropes (cell_occlusion_visible) under the rig cams / rig_to_cam, before the gap fill and the step.
+    Returns (codes, [visible_nodes], [visible_nodes_extended], n_each [F])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    M = trackers[0].M
+    ct, K = _painter_cams(cams); T = _painter_matrices(rig_to_cam, K)
+    view = CellViewC(C.cast(ct, C.c_void_p).value, None if T is None else T.ctypes.data, K, int(rows), int(cols), int(dlo_pixel_width))
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_shared_cloud_occluded_batch(C.cast(tab, C.c_void_p), F, int(src_slot), float(d_max), float(d_vis),
+                                                                                  C.cast(C.pointer(view), C.c_void_p), _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne),
+                                                                                  _ptr(n), C.cast(st, C.c_void_p), _ptr(rcs))
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n]
+
+
 def render_result_batch(trackers, images, image_of, proj=None, params=None, corners=True, check=True):
     """tdlo_tracker_render_result_batch: the trackers' current nodes (one context) in one launch -- tracker i over image image_of[i], its vis and matrix as
     trackdlo.render_result forms them; proj / params: None, or F entries of which any may be None.  images as Context.render_result_batch takes them, with a
@@ -2394,6 +2468,43 @@ def rig_self_occlusion_visible(Y, cams, rig_to_cam, rows, cols, dlo_pixel_width,
     if rc:
         raise TdloError(rc, "tdlo_rig_self_occlusion_visible")
     return (v[:nv.value].copy(), seen[:K, :W], hidden[:K, :W]) if words else v[:nv.value].copy()
+
+
+def _cell_ropes(ropes):
+    """The tdlo_cell_rope table of [(Y [M x 3], node_dist, visibility_threshold)].  Returns (table, F, N, [M_f], what must stay alive)."""
+    ropes = list(ropes)
+    F = len(ropes)
+    tab = (CellRopeC * max(F, 1))(); keep = []; Ms = []
+    for f, (Y, node_dist, thr) in enumerate(ropes):
+        Y = _f64(Y); nd = np.ascontiguousarray(node_dist, dtype=np.float64)
+        keep += [Y, nd]
+        tab[f].Y = Y.ctypes.data; tab[f].M = Y.shape[0]; tab[f].node_dist = nd.ctypes.data; tab[f].visibility_threshold = float(thr)
+        Ms.append(Y.shape[0])
+    return tab, F, sum(Ms), Ms, keep
+
+
+def cell_occlusion_visible(ropes, cams, rig_to_cam, rows, cols, dlo_pixel_width, words=False):
+    """tdlo_cell_occlusion_visible, the host statement of the painter test over a cell of ropes (no context, no GPU; parity against OpenCV's rasteriser
+    unpinned): every rope's edges are painted into one picture per camera, so a rope hides the nodes of another that lie under it.  ropes: a list of
+    (Y [M x 3], node_dist, visibility_threshold); cams: (fx, fy, cx, cy) tuples or RigCamera objects; rig_to_cam: None, or per camera a 3 x 4 matrix or None.
+    Returns the list of the ropes' visible indices (rope-local); with words=True also the cameras' seen and hidden bit words, [K x ceil(N / 32)] uint32 each,
+    bit = flat node index."""
+    lib = load_library()
+    rt, F, N, Ms, keep = _cell_ropes(ropes)
+    tab, K = _painter_cams(cams)
+    T = _painter_matrices(rig_to_cam, K)
+    W = (N + 31) // 32
+    v = [np.zeros(max(M, 1), dtype=np.int32) for M in Ms]
+    pv = (C.c_void_p * max(F, 1))(*[x.ctypes.data for x in v])
+    nv = np.zeros(max(F, 1), dtype=np.int32)
+    seen = np.zeros((max(K, 1), max(W, 1)), dtype=np.uint32); hidden = np.zeros_like(seen)
+    rc = lib.tdlo_cell_occlusion_visible(C.cast(rt, C.c_void_p), F, C.cast(tab, C.c_void_p), _ptr(T), K, int(rows), int(cols), int(dlo_pixel_width),
+                                         C.cast(pv, C.c_void_p), _ptr(nv), _ptr(seen) if words else None, _ptr(hidden) if words else None)
+    del keep
+    if rc:
+        raise TdloError(rc, "tdlo_cell_occlusion_visible")
+    out = [v[f][:nv[f]].copy() for f in range(F)]
+    return (out, seen[:K, :W], hidden[:K, :W]) if words else out
 
 
 def extend_visible_nodes(visible_nodes, geodesic_coord, d_vis, M):

@@ -9,6 +9,7 @@
 #include "tdlo_reg_plan.h"
 #include "tdlo_rig_host.h"
 #include "tdlo_painter_host.h"
+#include "tdlo_cell_painter_host.h"
 #include "tdlo_assign_host.h"
 #include "tdlo_cluster_lane.h"
 #include "tdlo_view_batch_plan.h"
@@ -269,6 +270,17 @@ struct tdlo_ctx {
     size_t pnt_pin_cap = 0;
     int rig_painter_min = (getenv("TDLO_RIG_PAINTER_MIN") && atoi(getenv("TDLO_RIG_PAINTER_MIN")) >= 1) ? atoi(getenv("TDLO_RIG_PAINTER_MIN")) : 0;
     long long pnt_route[2] = {0, 0};
+    // the painter test over a cell of ropes (tdlo_cell_occlusion_batch: k_cell_project / k_cell_cover).  cel_pin: [cell table | camera records | nodes | link
+    // words | result words] in pinned host memory -- all but the last go up in ONE copy into cel_dev, whose tail holds the kernels' (camera, cell) tables --,
+    // both grown on demand.  TDLO_CELL_PAINTER_MIN=n: the tracker call runs the host statement on a cell of fewer than n flat nodes x cameras (0: always the kernels).
+    // cel_route: tdlo_debug_route_count 57 / 58: jobs served by the kernels / done by the host statement
+    void *cel_dev = nullptr;
+    size_t cel_dev_cap = 0;
+    char *cel_pin = nullptr;
+    size_t cel_pin_cap = 0;
+    long long cell_painter_min = (getenv("TDLO_CELL_PAINTER_MIN") && *getenv("TDLO_CELL_PAINTER_MIN") && atoll(getenv("TDLO_CELL_PAINTER_MIN")) >= 0)
+                                     ? atoll(getenv("TDLO_CELL_PAINTER_MIN")) : -1;      // (-1: not set)
+    long long cel_route[2] = {0, 0};
     // one cloud dealt out among F slots (tdlo_cloud_assign and the calls built on it: k_assign_count / k_assign_scatter).  asg_dev: [table | owner | g | counts]
     // in device memory, grown on demand; asg_state: [asg_state_cap minima | ticket], armed when allocated or after a launch that did not report, kept armed by
     // the kernel; asg_res: [word | F counts | T minima] in pinned host memory.  TDLO_ASSIGN_RIDE=1: the pre-pass rides in k_assign_scatter (measured slower, profiles/cloud_assign_ab.txt: off by default).
@@ -1848,6 +1860,8 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->rbatch_pin) hipHostFree(c->rbatch_pin);
     if (c->pnt_dev) hipFree(c->pnt_dev);
     if (c->pnt_pin) hipHostFree(c->pnt_pin);
+    if (c->cel_dev) hipFree(c->cel_dev);
+    if (c->cel_pin) hipHostFree(c->cel_pin);
     if (c->asg_dev) hipFree(c->asg_dev);
     if (c->asg_state) hipFree(c->asg_state);
     if (c->asg_res) hipHostFree(c->asg_res);
@@ -5409,7 +5423,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 56) return -1;
+    if (!c || which < 0 || which > 58) return -1;
+    if (which >= 57) return c->cel_route[which - 57];
     if (which >= 55) return c->clu_route[which - 55];
     if (which >= 53) return c->asg_route[which - 53];
     if (which >= 51) return c->pnt_route[which - 51];
@@ -6473,10 +6488,12 @@ int tdlo_tracker_tracking_step_batch(tdlo_tracker *const *trackers, int F, const
     return finish();
 }
 
+// cell_verdict (NULL outside the occluded shared-cloud call): tracker i's visible set from the cell's words, in place of the pre-pass's.
 // rigs (NULL outside the rig calls): tracker i's cameras, for the trackers whose rig switch is on -- the test under a rig replaces the pre-pass's visible set.
 // From rig_painter_min jobs on k_rig_painter_batch is enqueued in front of the pre-pass and its words are read after that call's wait: no wait is added
 static int tracker_frame_batch_impl(tdlo_tracker *const *trackers, int F, double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
-                                    tdlo_stats *stats, int *rc_each, const tdlo_rig_camera *const *rigs, int rows, int cols, const double *pre_min_d2 = nullptr) {
+                                    tdlo_stats *stats, int *rc_each, const tdlo_rig_camera *const *rigs, int rows, int cols, const double *pre_min_d2 = nullptr,
+                                    const std::function<void(int, const tdlo_tracker *, std::vector<int> &)> *cell_verdict = nullptr) {
     if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
     tdlo_ctx *c = trackers[0]->ctx;
     if (const char *why = tracker_batch_refusal(trackers, F)) return fail(c, TDLO_E_INVALID, why);
@@ -6541,6 +6558,13 @@ static int tracker_frame_batch_impl(tdlo_tracker *const *trackers, int F, double
             std::vector<int> qv, qe;
             if (painter_kernel) rig_painter_verdict(pw.seen[pf_of[i]], pw.hidden[pf_of[i]], q.K, M, q.node_dist, q.visibility_threshold, qv);
             else tracker_painter_host(c, q, rows, cols, qv);
+            fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
+            nv[i] = (int)qv.size(); ne[i] = (int)qe.size();
+            std::copy(qv.begin(), qv.end(), v); std::copy(qe.begin(), qe.end(), e);
+        }
+        if (cell_verdict) {      // the cell's verdict on this rope (tdlo_tracker_frames_from_shared_cloud_occluded_batch) with the pre-pass's distances, then the gap fill
+            std::vector<int> qv, qe;
+            (*cell_verdict)(i, t, qv);
             fill_visible_gaps(qv, t->geodesic_coord.data(), d_vis, qe);
             nv[i] = (int)qv.size(); ne[i] = (int)qe.size();
             std::copy(qv.begin(), qv.end(), v); std::copy(qe.begin(), qe.end(), e);
@@ -7028,6 +7052,209 @@ int tdlo_tracker_frames_from_shared_cloud_batch(tdlo_tracker *const *trackers, i
         std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
         const int brc = tracker_frame_batch_impl(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data(), nullptr, 0, 0,
                                                  (ride && run.mins) ? mins.data() : nullptr);
+        bool sany = false;
+        for (int r : src) sany = sany || r != 0;
+        for (int k = 0; k < Fs; ++k) {
+            const int i = who[k];
+            rcs[i] = (brc && !sany) ? brc : src[k];
+            nv[i] = snv[k]; ne[i] = sne[k];
+            std::copy(&svis[(size_t)M * k], &svis[(size_t)M * k] + M, &vis[(size_t)M * i]);
+            std::copy(&sext[(size_t)M * k], &sext[(size_t)M * k] + M, &ext[(size_t)M * i]);
+            st[2 * (size_t)i] = sst[2 * (size_t)k]; st[2 * (size_t)i + 1] = sst[2 * (size_t)k + 1];
+        }
+    }
+    if (visible_nodes) std::copy(vis.begin(), vis.end(), visible_nodes);
+    if (visible_nodes_extended) std::copy(ext.begin(), ext.end(), visible_nodes_extended);
+    if (n_vis) std::copy(nv.begin(), nv.end(), n_vis);
+    if (n_vis_ext) std::copy(ne.begin(), ne.end(), n_vis_ext);
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (rc_each) std::copy(rcs.begin(), rcs.end(), rc_each);
+    for (int i = 0; i < F; ++i)
+        if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && run.n_each[i] == 0) ? fail(c, TDLO_E_EMPTY, "the rope owns no point of the shared cloud: no cloud for this frame") : rcs[i];
+    return TDLO_OK;
+}
+
+// ---- ropes that hide one another: the painter test over a cell of ropes (include/trackdlo_hip.h has the statement; tdlo_cell_painter_lane.h the lane,
+// tdlo_cell_painter_host.cpp the host statement, tdlo_cell_painter.hip the kernels) ------------------------------------------------------------------------
+// From this many flat nodes x cameras on, tdlo_tracker_frames_from_shared_cloud_occluded_batch hands the cell to the kernels; below it, it runs the host
+// statement: the same sets.  MEASURED (scripts/gpu_cell_painter.py, profiles/cell_painter_ab.txt; the rule set beforehand: the smallest measured N K at and above
+// which the kernels are faster on every measured line): the host statement wins at N K = 90, 180, 270 and 360 (0.139 against 0.122 ms at 360), the kernels at
+// 540 (0.082 against 0.095 ms) and on every line above it, up to 4.19 against 540 ms at N K = 49 152.  TDLO_CELL_PAINTER_MIN=n, read when the context is
+// made, overrides.
+constexpr long long kCellPainterMin = 540;
+static long long cell_painter_min(const tdlo_ctx *c) { return c->cell_painter_min >= 0 ? c->cell_painter_min : kCellPainterMin; }
+
+// where the kernels' words of the cells of one call lie in cel_pin (valid until the next enqueue)
+struct CellWords { std::vector<const unsigned *> seen, hidden; };
+
+// One upload of [cell table | camera records | nodes | link words], the two launches; the words are in place once the stream has passed them.  The cells are
+// checked (cell_painter_fault); nothing waits here
+static int cell_painter_enqueue(tdlo_ctx *c, int C, const tdlo_cell *cells, int rows, int cols, CellWords &cw) {
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t sumK = 0, sumN = 0, sumW = 0, sumKW = 0, sumKN = 0;
+    int Kmax = 0, Nmax = 0;
+    std::vector<int> Ns(C);
+    for (int i = 0; i < C; ++i) {
+        const int N = cell_painter_nodes(cells[i].ropes, cells[i].F), K = cells[i].K, W = (N + 31) / 32;
+        Ns[i] = N;
+        sumK += (size_t)K; sumN += (size_t)N; sumW += (size_t)W; sumKW += (size_t)K * W; sumKN += (size_t)K * N;
+        Kmax = std::max(Kmax, K); Nmax = std::max(Nmax, N);
+    }
+    const size_t cams_off = sizeof(CellJob) * (size_t)C, y_off = cams_off + sizeof(PainterCam) * sumK, link_off = y_off + sizeof(double) * 3 * sumN;
+    const size_t up = link_off + sizeof(unsigned) * sumW, recs_off = (up + 15) & ~(size_t)15, dev_bytes = recs_off + sizeof(CellRec) * sumKN;
+    const size_t words_off = (up + 7) & ~(size_t)7, pin_bytes = words_off + sizeof(unsigned) * 2 * sumKW;
+    hipStream_t st = c->stream;
+    if (dev_bytes > c->cel_dev_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cel_dev) hipFree(c->cel_dev);
+        c->cel_dev = nullptr; c->cel_dev_cap = 0;
+        const size_t cap = (dev_bytes + (dev_bytes >> 2) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipMalloc(&c->cel_dev, cap));
+        c->cel_dev_cap = cap;
+    }
+    if (pin_bytes > c->cel_pin_cap) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->cel_pin) hipHostFree(c->cel_pin);
+        c->cel_pin = nullptr; c->cel_pin_cap = 0;
+        const size_t cap = (pin_bytes + (pin_bytes >> 2) + 4095) & ~(size_t)4095;
+        HIPCHK(c, hipHostMalloc((void **)&c->cel_pin, cap, hipHostMallocDefault));
+        std::memset(c->cel_pin, 0, cap);
+        c->cel_pin_cap = cap;
+    }
+    char *pin = c->cel_pin, *dev = (char *)c->cel_dev;
+    CellJob *tab = (CellJob *)pin;
+    PainterCam *cams = (PainterCam *)(pin + cams_off);
+    double *Yp = (double *)(pin + y_off);
+    unsigned *link = (unsigned *)(pin + link_off), *words = (unsigned *)(pin + words_off);
+    cw.seen.assign(C, nullptr); cw.hidden.assign(C, nullptr);
+    size_t ik = 0, iy = 0, il = 0, iw = 0, ir = 0;
+    for (int i = 0; i < C; ++i) {
+        const tdlo_cell &q = cells[i];
+        const int N = Ns[i], K = q.K, W = (N + 31) / 32;
+        for (int k = 0; k < K; ++k) rig_painter_camera(q.cams[k], q.rig_to_cam ? q.rig_to_cam + 12 * (size_t)k : nullptr, cams[ik + k]);
+        cell_painter_flatten(q.ropes, q.F, Yp + iy, Yp + iy + N, Yp + iy + 2 * (size_t)N, link + il);
+        tab[i] = CellJob{(const double *)(dev + y_off) + iy, (const unsigned *)(dev + link_off) + il, (const PainterCam *)(dev + cams_off) + ik,
+                         (CellRec *)(dev + recs_off) + ir, words + iw, words + iw + (size_t)K * W, N, K, q.dlo_pixel_width, 0};
+        cw.seen[i] = words + iw; cw.hidden[i] = words + iw + (size_t)K * W;
+        ik += (size_t)K; iy += 3 * (size_t)N; il += (size_t)W; iw += 2 * (size_t)K * W; ir += (size_t)K * N;
+    }
+    HIPCHK(c, hipMemcpyAsync(dev, pin, up, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_cell_painter((const CellJob *)dev, C, Kmax, Nmax, rows, cols, st));
+    c->cel_route[0] += (long long)sumK;
+    return TDLO_OK;
+}
+
+int tdlo_cell_occlusion_batch(tdlo_ctx *c, int C, const tdlo_cell *cells, int rows, int cols, int *visible_nodes, int *n_vis, unsigned *seen_words,
+                              unsigned *hidden_words) {
+    if (!c) return TDLO_E_INVALID;
+    if (C < 1 || C > kCellPainterMaxCells || !cells || !visible_nodes || !n_vis)
+        return fail(c, TDLO_E_INVALID, "tdlo_cell_occlusion_batch: 1 .. 1024 cells, visible_nodes and n_vis");
+    int Mmax = 0;
+    for (int i = 0; i < C; ++i) {
+        const tdlo_cell &q = cells[i];
+        if (const char *why = cell_painter_fault(q.ropes, q.F, q.cams, q.rig_to_cam, q.K, rows, cols, q.dlo_pixel_width)) return fail(c, TDLO_E_INVALID, why);
+        for (int f = 0; f < q.F; ++f) Mmax = std::max(Mmax, q.ropes[f].M);
+    }
+    CellWords cw;
+    int rc = cell_painter_enqueue(c, C, cells, rows, cols, cw);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int> vis;
+    size_t iw = 0, row = 0;
+    for (int i = 0; i < C; ++i) {
+        const tdlo_cell &q = cells[i];
+        const int N = cell_painter_nodes(q.ropes, q.F);
+        const size_t KW = (size_t)q.K * ((N + 31) / 32);
+        int off = 0;
+        for (int f = 0; f < q.F; ++f, ++row) {
+            const tdlo_cell_rope &r = q.ropes[f];
+            cell_painter_verdict(cw.seen[i], cw.hidden[i], q.K, N, off, r.M, r.node_dist, r.visibility_threshold, vis);
+            n_vis[row] = (int)vis.size();
+            std::copy(vis.begin(), vis.end(), visible_nodes + row * (size_t)Mmax);
+            off += r.M;
+        }
+        if (seen_words) std::copy(cw.seen[i], cw.seen[i] + KW, seen_words + iw);
+        if (hidden_words) std::copy(cw.hidden[i], cw.hidden[i] + KW, hidden_words + iw);
+        iw += KW;
+    }
+    return TDLO_OK;
+}
+
+// The shared-cloud tracker call with the cell's verdict in place of every tracker's visible set.  The cell is the F trackers' ropes in the call's order, the
+// ones that own no point included (they hide others).  Kernel route: the two launches go in front of the split, whose one wait they share; host route: the
+// statement is run on the host while nothing of the device is waited for.  Either way the words stand before the pre-pass's distances are thresholded
+int tdlo_tracker_frames_from_shared_cloud_occluded_batch(tdlo_tracker *const *trackers, int F, int src_slot, double d_max, double d_vis, const tdlo_cell_view *view,
+                                                         int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_each, tdlo_stats *stats,
+                                                         int *rc_each) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (!view) return fail(c, TDLO_E_INVALID, "frames_from_shared_cloud_occluded_batch: null view");
+    const int M = trackers[0]->M;
+    for (int i = 0; i < F; ++i)
+        if (trackers[i]->painter_on || trackers[i]->rig_painter_K)
+            return fail(c, TDLO_E_INVALID, "frames_from_shared_cloud_occluded_batch: a tracker has a self-occlusion switch on (the cell test subsumes both)");
+    std::vector<tdlo_assign_rope> ropes(F);
+    std::vector<tdlo_cell_rope> cr(F);
+    for (int i = 0; i < F; ++i) {
+        ropes[i] = tdlo_assign_rope{trackers[i]->slot, trackers[i]->Y.data(), M};
+        cr[i] = tdlo_cell_rope{trackers[i]->Y.data(), M, nullptr, trackers[i]->visibility_threshold};
+    }
+    if (const char *why = assign_refusal(c, src_slot, ropes.data(), F, d_max)) return fail(c, TDLO_E_INVALID, why);
+    if (const char *why = cell_painter_fault(cr.data(), F, view->cams, view->rig_to_cam, view->K, view->rows, view->cols, view->dlo_pixel_width, false))
+        return fail(c, TDLO_E_INVALID, why);
+    const int K = view->K, N = F * M, W = (N + 31) / 32;
+    const bool kernels = (long long)N * K >= cell_painter_min(c);
+    CellWords cw;
+    std::vector<unsigned> hseen, hhidden;
+    const unsigned *seen = nullptr, *hidden = nullptr;
+    if (kernels) {
+        const tdlo_cell cell{cr.data(), F, view->cams, view->rig_to_cam, K, view->dlo_pixel_width};
+        if (const int rc = cell_painter_enqueue(c, 1, &cell, view->rows, view->cols, cw)) return rc;
+        seen = cw.seen[0]; hidden = cw.hidden[0];
+    }
+    const bool ride = assign_ride_ok(c, ropes.data(), F);
+    AssignRun run;
+    if (const int rc = assign_run(c, src_slot, ropes.data(), F, d_max, ride, nullptr, nullptr, run)) {
+        if (kernels) (void)hipStreamSynchronize(c->stream);      // (the words are not read; nothing of this call stays in flight)
+        return rc;
+    }
+    if (kernels && run.n <= 0) HIPCHK(c, hipStreamSynchronize(c->stream));      // (a source of 0 points: the split launched nothing and waited for nothing)
+    if (n_each) std::copy(run.n_each.begin(), run.n_each.end(), n_each);
+    std::vector<int> rcs(F, 0), who;
+    std::vector<tdlo_tracker *> sub;
+    std::vector<double> mins;
+    for (int i = 0; i < F; ++i) {
+        if (run.n_each[i] == 0) { rcs[i] = TDLO_E_EMPTY; continue; }
+        sub.push_back(trackers[i]); who.push_back(i);
+        if (ride && run.mins) mins.insert(mins.end(), run.mins + run.off[i], run.mins + run.off[i] + M);
+    }
+    std::vector<tdlo_stats> st(2 * (size_t)F);
+    std::memset(st.data(), 0, sizeof(tdlo_stats) * st.size());
+    std::vector<int> nv(F, 0), ne(F, 0), vis((size_t)F * M, 0), ext((size_t)F * M, 0);
+    if (!sub.empty()) {
+        if (!kernels) {      // the host statement, on every rope of the cell
+            std::vector<PainterCam> pc(K);
+            for (int k = 0; k < K; ++k) rig_painter_camera(view->cams[k], view->rig_to_cam ? view->rig_to_cam + 12 * (size_t)k : nullptr, pc[k]);
+            std::vector<double> xyz(3 * (size_t)N);
+            std::vector<unsigned> link(W);
+            hseen.assign((size_t)K * W, 0u); hhidden.assign((size_t)K * W, 0u);
+            cell_painter_flatten(cr.data(), F, xyz.data(), xyz.data() + N, xyz.data() + 2 * (size_t)N, link.data());
+            cell_painter_host(xyz.data(), xyz.data() + N, xyz.data() + 2 * (size_t)N, link.data(), N, pc.data(), K, view->rows, view->cols, view->dlo_pixel_width,
+                              hseen.data(), hhidden.data());
+            seen = hseen.data(); hidden = hhidden.data();
+            c->cel_route[1] += K;
+        }
+        // (kernel route: the split's wait came after the two launches in stream order, so the words are in place)
+        const std::function<void(int, const tdlo_tracker *, std::vector<int> &)> verdict = [&](int k, const tdlo_tracker *t, std::vector<int> &qv) {
+            cell_painter_verdict(seen, hidden, K, N, who[k] * M, M, t->frame_dist.data(), t->visibility_threshold, qv);
+        };
+        const int Fs = (int)sub.size();
+        std::vector<int> snv(Fs, 0), sne(Fs, 0), svis((size_t)Fs * M, 0), sext((size_t)Fs * M, 0), src(Fs, 0);
+        std::vector<tdlo_stats> sst(2 * (size_t)Fs);
+        std::memset(sst.data(), 0, sizeof(tdlo_stats) * sst.size());
+        const int brc = tracker_frame_batch_impl(sub.data(), Fs, d_vis, svis.data(), snv.data(), sext.data(), sne.data(), sst.data(), src.data(), nullptr, 0, 0,
+                                                 (ride && run.mins) ? mins.data() : nullptr, &verdict);
         bool sany = false;
         for (int r : src) sany = sany || r != 0;
         for (int k = 0; k < Fs; ++k) {

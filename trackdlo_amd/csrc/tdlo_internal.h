@@ -263,6 +263,12 @@ hipError_t launch_node_min_dist_batch(const VisBatchFrame *tab, const int *wg0, 
 struct PainterCam;
 struct PainterFrame { const double *Y; const PainterCam *cams; unsigned *seen, *hidden; int M, K, width, pad; };
 hipError_t launch_rig_painter_batch(const PainterFrame *tab_dev, int F, int Kmax, int rows, int cols, hipStream_t s);
+// tdlo_cell_painter.hip: the painter test over a cell of ropes, a (camera, cell) job spread over node blocks (k_cell_project, k_cell_cover).  CellJob: a cell's
+// record of the table in device memory -- X: the flat nodes x | y | z of N doubles each; link: ceil(N / 32) words; cams: K records; recs: K x N records of
+// workspace in device memory; seen / hidden: K x ceil(N / 32) result words each, in pinned host memory
+struct CellRec;
+struct CellJob { const double *X; const unsigned *link; const PainterCam *cams; CellRec *recs; unsigned *seen, *hidden; int N, K, width, pad; };
+hipError_t launch_cell_painter(const CellJob *tab_dev, int C, int Kmax, int Nmax, int rows, int cols, hipStream_t s);
 // tdlo_assign.hip: one cloud dealt out among F slots (k_assign_count, k_assign_scatter).  off / dst / Y: the table in device memory -- off[F + 1], the F destination
 // clouds, the flat node list x | y | z of T = off[F] entries each; owner [n], g [n] (or nullptr), counts [nwg x F]: workspace; state [T] + ticket: kept armed
 constexpr int kAssignMaxRopes = 2048;     // ropes of one call (the scatter kernel's LDS tables)

@@ -1231,6 +1231,66 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
                             double fx, double fy, double cx, double cy, double leaf_size, double d_vis,
                             int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                             int *n_out, int *n_raw_out, tdlo_stats *stats);
+/* ---- depth aligned to the colour camera, in front of every frame call ----------------------------------- */
+/* Every frame call above takes depth and colour (or mask) on ONE pixel grid.  The reference gets that grid from the camera driver: its launch files subscribe
+ * to /camera/aligned_depth_to_color/image_raw (launch/trackdlo.launch:6; realsense_node.launch:13 sets align_depth), an image the driver's align filter forms
+ * on the CPU.  tdlo_align_depth forms it on the device from the sensor's raw depth stream, so a caller with the two raw streams (or a simulator that renders
+ * depth and colour from two cameras) needs no CPU pass over every depth pixel.  The algorithm is the published one of the RealSense SDK's align (depth to
+ * another stream); parity against that library is UNPINNED (it is not part of this project's tests), as for OpenCV everywhere else.  THE STATEMENT
+ * (tests/align_ref.py is its numpy form, csrc/tdlo_align_lane.h its one text for host and device):
+ *   Inputs   a depth image D of rows_d x cols_d (TDLO_IMG_U16C1 millimetres, or TDLO_IMG_F32C1 converted to millimetres by the image views' rule above), the
+ *            depth intrinsics (fx_d, fy_d, cx_d, cy_d), the colour camera's size rows_c x cols_c and intrinsics (fx_c, fy_c, cx_c, cy_c), and depth_to_colour:
+ *            NULL, or a row-major 3 x 4 matrix T in metres.  No distortion coefficients: both streams are taken as rectified.
+ *   Arithmetic   double; every product, quotient and sum is rounded on its own, sums go left to right, NO fused multiply-add anywhere.
+ *   Per depth pixel (u, v) with k = D[v, u] != 0:  z = (double)k / 1000.0; for the two corners s = -0.5, +0.5:
+ *            x = (((u + s) - cx_d) / fx_d) z, y likewise; q = (x, y, z) if T is NULL, else q_i = ((T_i0 x + T_i1 y) + T_i2 z) + T_i3; the corner is BAD if
+ *            q_z <= 0 or any of q is not finite; px = (q_x / q_z) fx_c + cx_c, py likewise; BAD if not |px| < 2^30 or not |py| < 2^30;
+ *            X = floor(px + 0.5), Y = floor(py + 0.5) (floor, not the SDK's truncation: the two differ only for -1.5 < px < -0.5, where truncation would let
+ *            a footprint reach over the left or top border).  (x0, y0) comes from s = -0.5, (x1, y1) from s = +0.5.  Decisions, IN THIS ORDER:
+ *            1 dropped: a corner is bad, or x0 < 0, y0 < 0, x1 >= cols_c, y1 >= rows_c, x1 < x0 or y1 < y0 -- the whole footprint, never clipped;
+ *            2 wide:    x1 - x0 + 1 or y1 - y0 + 1 exceeds max_footprint (0 means 16; legal 1 .. 64): a call's time stays bounded;
+ *            3 used:    the pixel offers k to every pixel of [y0, y1] x [x0, x1].
+ *   Output   A[y, x] = the MINIMUM k offered to the pixel, 0 if none was: a packed rows_c x cols_c uint16 plane.
+ *   Counts   counts[4] = {depth pixels with k != 0, used, dropped, wide}.
+ * What follows from it: a minimum does not depend on order, so A has one right bit pattern whatever the schedule.  A footprint is about fx_c / fx_d + 1 pixels
+ * wide whatever the depth.  Two identical cameras with T = NULL do NOT give D back: the corners land on integers up to rounding, so footprints are 2 - 3
+ * pixels wide (580 of the 768 pixels of a random 24 x 32 image differ) -- the algorithm's nature, and the reason the no-FMA rule matters: a corner within one
+ * rounding of an integer + 1/2 moves to the next pixel when one multiply-add is fused.  A T that is the identity matrix gives NULL's bits.
+ * Out of scope: distortion models, colour aligned to depth, a batch form for F frames or a rig's K cameras. */
+typedef struct {
+    int rows_d, cols_d;
+    double fx_d, fy_d, cx_d, cy_d;
+    int rows_c, cols_c;
+    double fx_c, fy_c, cx_c, cy_c;
+    const double *depth_to_colour;   /* NULL, or 12 doubles: row-major 3 x 4, metres */
+    int max_footprint;               /* 0: 16; else 1 .. 64 */
+} tdlo_align_params;
+/* TDLO_E_INVALID for null params, sizes that tdlo_image_view_check refuses (rows or cols <= 0, rows x cols > 2^26, of either camera), a focal length that is
+ * not finite and positive, a principal point that is not finite, a non-finite matrix entry, max_footprint outside {0, 1 .. 64}.  No context, no GPU. */
+int tdlo_align_check(const tdlo_align_params *p);
+/* The statement on the host (csrc/tdlo_align_host.cpp, no HIP): depth is a HOST view of rows_d x cols_d (tdlo_image_view_check, role depth); aligned_out
+ * takes rows_c x cols_c uint16; counts may be NULL. */
+int tdlo_align_depth_host(const tdlo_image_view *depth /* host */, const tdlo_align_params *p, unsigned short *aligned_out, long long counts[4]);
+/* The statement on the device: k_align_splat (lane = depth pixel; a returnless 32-bit atomic minimum per offered word of a scratch plane) and k_align_pack
+ * (scratch -> uint16, and the scratch armed again), csrc/tdlo_align.hip.  The depth view lies in host or device memory (location and ready_stream as in the
+ * view calls above; a host view goes up once, packed); aligned_out: host memory, device memory (2-byte alignment suffices) or NULL; *device_plane
+ * (device_plane may be NULL) is the context's aligned plane in device memory, valid until the next align call or a change of size, so that a caller can
+ * build a TDLO_MEM_DEVICE depth view on it; counts may be NULL.  One host wait.  TDLO_ALIGN=host, read when the context is made, is the comparator: the plane
+ * comes from tdlo_align_depth_host and is uploaded -- the same bits.  tdlo_debug_route_count 59 / 60 count device / host aligns.  A refused call
+ * (TDLO_E_INVALID: what tdlo_align_check or tdlo_image_view_check refuse, a pointer on another GPU) has touched nothing. */
+int tdlo_align_depth(tdlo_ctx *ctx, const tdlo_image_view *depth, const tdlo_align_params *p, unsigned short *aligned_out,
+                     const unsigned short **device_plane, long long counts[4]);
+/* tdlo_frame_to_cloud_view / tdlo_tracker_frame_view on two raw streams: fv->depth has the DEPTH camera's size (p->rows_d x p->cols_d); colour, occluder and
+ * mask have the colour camera's (p->rows_c x p->cols_c), and the cloud is formed with the colour intrinsics of p.  THE CONTRACT: bit for bit tdlo_align_depth
+ * followed by the view call on a TDLO_MEM_DEVICE view of the aligned plane.  The two align launches are enqueued on the context's stream in front of the
+ * import: they add NO host wait (TDLO_ALIGN=host adds the host's pass), and counts (may be NULL) come back with the frame's own wait.  A refused call -- bad
+ * params, a bad view, a tracker without nodes -- leaves the slot, the tracker, the canonical images and the route counters untouched. */
+int tdlo_frame_to_cloud_view_aligning(tdlo_ctx *ctx, int slot, const tdlo_frame_view *fv, const tdlo_align_params *p, const tdlo_colour_params *colour_params,
+                                      double leaf_size, double *X_out, int x_capacity, int *n_out, int *n_raw_out, long long counts[4]);
+int tdlo_tracker_frame_view_aligning(tdlo_tracker *t, const tdlo_frame_view *fv, const tdlo_align_params *p, const tdlo_colour_params *colour_params,
+                                     double leaf_size, double d_vis,
+                                     int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                     int *n_out, int *n_raw_out, tdlo_stats *stats, long long counts[4]);
 /* ---- image views for many slots in one call ----------------------------------------------------------- */
 /* tdlo_depth_to_cloud_batch for callers who come with image VIEWS: a simulator, renderer or decoder on the same GPU that makes K camera images as one device
  * tensor ([K, H, W, 4] uint8 and [K, H, W] float32) and steps as many trackers.  An IMAGE is a tdlo_frame_view -- depth, and a mask, or a colour view (with
@@ -1548,6 +1608,7 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * served by the host route (TDLO_CLUSTER=host, or after a lane of k_cluster_link gave up).  A source of 0 points counts in neither.
  * 57 / 58: (camera, cell) jobs of the painter test over a cell of ropes served by k_cell_project / k_cell_cover (tdlo_cell_occlusion_batch, and
  * tdlo_tracker_frames_from_shared_cloud_occluded_batch from kCellPainterMin flat nodes x cameras on) / done by the host statement inside that tracker call.
+ * 59 / 60: aligned planes (tdlo_align_depth, and the aligning frame calls) formed by k_align_splat / k_align_pack / by the host statement (TDLO_ALIGN=host).
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

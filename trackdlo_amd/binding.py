@@ -134,6 +134,14 @@ class FrameView(C.Structure):
     _fields_ = [("depth", ImageView), ("colour", ImageView), ("occluder", ImageView), ("mask", ImageView)]
 
 
+class AlignParams(C.Structure):
+    """tdlo_align_params: the depth camera, the colour camera, depth_to_colour (NULL or 12 doubles) and max_footprint.  Built by make_align_params(), which
+    keeps the matrix alive in .owner."""
+    _fields_ = [("rows_d", C.c_int), ("cols_d", C.c_int), ("fx_d", C.c_double), ("fy_d", C.c_double), ("cx_d", C.c_double), ("cy_d", C.c_double),
+                ("rows_c", C.c_int), ("cols_c", C.c_int), ("fx_c", C.c_double), ("fy_c", C.c_double), ("cx_c", C.c_double), ("cy_c", C.c_double),
+                ("depth_to_colour", C.c_void_p), ("max_footprint", C.c_int)]
+
+
 class ViewImage(C.Structure):                      # tdlo_view_image: one image of a view batch -- its views and its camera
     _fields_ = [("fv", FrameView), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
@@ -173,6 +181,7 @@ SYMBOLS = [
     "tdlo_cloud_assign", "tdlo_cloud_assign_visibility", "tdlo_cloud_assign_host", "tdlo_tracker_frames_from_shared_cloud_batch",
     "tdlo_cloud_cluster", "tdlo_cloud_cluster_host", "tdlo_tracker_initialize_from_shared_cloud_batch",
     "tdlo_cell_occlusion_visible", "tdlo_cell_occlusion_batch", "tdlo_tracker_frames_from_shared_cloud_occluded_batch",
+    "tdlo_align_check", "tdlo_align_depth_host", "tdlo_align_depth", "tdlo_frame_to_cloud_view_aligning", "tdlo_tracker_frame_view_aligning",
 ]
 
 _lib = None
@@ -421,6 +430,13 @@ def load_library(path: str | None = None):
         lib.tdlo_tracker_frame_views_batch.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.tdlo_view_batch_images.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         lib.tdlo_debug_slot_cloud.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(ci)]
+    if hasattr(lib, "tdlo_align_depth"):
+        app, ivp, fvp, ll4 = C.POINTER(AlignParams), C.POINTER(ImageView), C.POINTER(FrameView), C.POINTER(C.c_longlong * 4)
+        lib.tdlo_align_check.argtypes = [app]
+        lib.tdlo_align_depth_host.argtypes = [ivp, app, vp, ll4]
+        lib.tdlo_align_depth.argtypes = [vp, ivp, app, vp, C.POINTER(vp), ll4]
+        lib.tdlo_frame_to_cloud_view_aligning.argtypes = [vp, ci, fvp, app, cpp, cd, vp, ci, C.POINTER(ci), C.POINTER(ci), ll4]
+        lib.tdlo_tracker_frame_view_aligning.argtypes = [vp, fvp, app, cpp, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp, ll4]
     if path is None:
         _lib = lib
     return lib
@@ -622,6 +638,45 @@ def image_view_extent(v: ImageView, rows=None, cols=None):
 def image_view_form(v: ImageView, cols=None) -> int:
     """How the import kernel would load this view: 0 element by element, 1 dword loads, 2 one 8- / 16-byte load per four pixels (tdlo_image_view_form)."""
     return int(load_library().tdlo_image_view_form(C.byref(v), int(v.cols if cols is None else cols)))
+
+
+def make_align_params(rows_d, cols_d, fx_d, fy_d, cx_d, cy_d, rows_c, cols_c, fx_c, fy_c, cx_c, cy_c, depth_to_colour=None, max_footprint=0, **_) -> AlignParams:
+    """tdlo_align_params.  depth_to_colour: None, or 12 numbers (row-major 3 x 4, metres); T= is taken for it as well (the scenes of tests/align_ref.py)."""
+    T = depth_to_colour if depth_to_colour is not None else _.get("T")
+    Tm = None if T is None else np.ascontiguousarray(T, dtype=np.float64).reshape(12)
+    p = AlignParams(int(rows_d), int(cols_d), float(fx_d), float(fy_d), float(cx_d), float(cy_d), int(rows_c), int(cols_c), float(fx_c), float(fy_c),
+                    float(cx_c), float(cy_c), Tm.ctypes.data if Tm is not None else None, int(max_footprint))
+    p.owner = Tm
+    return p
+
+
+def align_check(p: AlignParams) -> int:
+    """tdlo_align_check: TDLO_OK or TDLO_E_INVALID.  No context, no GPU."""
+    return int(load_library().tdlo_align_check(C.byref(p) if p is not None else None))
+
+
+def align_depth_host(depth, p: AlignParams, lib=None):
+    """The statement on the host (tdlo_align_depth_host): depth an ImageView in host memory or a numpy array.  Returns (A uint16 [rows_c x cols_c], counts [4])."""
+    v = depth if isinstance(depth, ImageView) else image_view(depth)
+    A = np.zeros((p.rows_c, p.cols_c), dtype=np.uint16)
+    cnt = (C.c_longlong * 4)()
+    rc = (lib or load_library()).tdlo_align_depth_host(C.byref(v), C.byref(p), A.ctypes.data, C.byref(cnt))
+    if rc:
+        raise TdloError(rc, "tdlo_align_depth_host: bad params or not a host depth view")
+    return A, [int(x) for x in cnt]
+
+
+def aligning_frame_view(depth, colour=None, occluder=None, mask=None) -> FrameView:
+    """tdlo_frame_view of two raw streams: depth at the depth camera's size; colour, occluder and mask at the colour camera's (the aligning calls)."""
+    vs = [None if o is None else o if isinstance(o, ImageView) else image_view(o) for o in (depth, colour, occluder, mask)]
+    if vs[0] is None:
+        raise ValueError("aligning_frame_view: a frame has a depth image")
+    rest = [v for v in vs[1:] if v is not None]
+    if any((v.rows, v.cols) != (rest[0].rows, rest[0].cols) for v in rest):
+        raise ValueError("aligning_frame_view: colour, occluder and mask have one shape")
+    fv = FrameView(*[v if v is not None else ImageView() for v in vs])
+    fv.owners = vs
+    return fv
 
 
 def make_params(beta, lambda_, lle_weight, mu, max_iter=30, tol=1e-4, include_lle=True, alpha=0.0, k_vis=0.0,
@@ -1793,6 +1848,41 @@ class Context:
                                                                _ptr(ext), C.byref(ne), C.byref(n), C.byref(nraw)))
         return dist, vis[:nv.value].copy(), ext[:ne.value].copy(), n.value, nraw.value
 
+    def align_route_counts(self):
+        """[aligned planes formed by k_align_splat / k_align_pack, formed by the host statement (TDLO_ALIGN=host)] (tdlo_debug_route_count 59 / 60)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (59, 60)]
+
+    def align_depth(self, depth, p: AlignParams, *, out="host", ready_stream=None):
+        """Depth aligned to the colour camera on the device (tdlo_align_depth).  depth: an ImageView, a numpy array or a device tensor.  out: "host" (a new
+        array), None (nothing is copied out), a numpy uint16 array, or an integer device address that takes rows_c x cols_c uint16.
+        Returns (A or None, counts [4], the address of the context's aligned plane in device memory)."""
+        v = depth if isinstance(depth, ImageView) else image_view(depth, ready_stream=ready_stream)
+        A, addr = None, None
+        if isinstance(out, str):
+            A = np.zeros((p.rows_c, p.cols_c), dtype=np.uint16); addr = A.ctypes.data
+        elif isinstance(out, np.ndarray):
+            if out.dtype != np.uint16 or out.size != p.rows_c * p.cols_c or not out.flags.c_contiguous:
+                raise ValueError("align_depth: out takes rows_c x cols_c packed uint16")
+            A = out; addr = A.ctypes.data
+        elif out is not None:
+            addr = int(out)
+        cnt = (C.c_longlong * 4)(); plane = C.c_void_p(0)
+        self._chk(self.lib.tdlo_align_depth(self.h, C.byref(v), C.byref(p) if p is not None else None, C.c_void_p(addr), C.byref(plane), C.byref(cnt)))
+        return A, [int(x) for x in cnt], int(plane.value or 0)
+
+    def frame_to_cloud_view_aligning(self, slot, fv, p: AlignParams, params: ColourParams, leaf_size, *, fetch=True):
+        """frame_to_cloud_view on two raw streams (tdlo_frame_to_cloud_view_aligning): fv an aligning_frame_view() or its arguments as a tuple or dict.
+        Returns (X [n x 3] or None, n, n_raw, counts [4])."""
+        fv = fv if isinstance(fv, FrameView) else aligning_frame_view(*fv) if isinstance(fv, (tuple, list)) else aligning_frame_view(**fv)
+        cap = p.rows_c * p.cols_c if fetch else 0
+        buf = np.zeros(3 * max(cap, 1)) if fetch else None
+        n = C.c_int(0); nraw = C.c_int(0); cnt = (C.c_longlong * 4)()
+        self._chk(self.lib.tdlo_frame_to_cloud_view_aligning(self.h, slot, C.byref(fv), C.byref(p) if p is not None else None,
+                                                             C.byref(params) if params is not None else None, float(leaf_size), _ptr(buf), cap,
+                                                             C.byref(n), C.byref(nraw), C.byref(cnt)))
+        X = buf[:3 * n.value].reshape(3, n.value).T.copy() if fetch else None
+        return X, n.value, nraw.value, [int(x) for x in cnt]
+
     def debug_read_images(self, rows, cols, depth=False, colour=False, occluder=False, mask=False):
         """The canonical images the last view call left (tdlo_debug_read_images): a dict of those asked for -- depth uint16 [rows x cols], colour uint8
         [rows x cols x 3], occluder / mask uint8 [rows x cols]."""
@@ -2046,6 +2136,22 @@ class trackdlo:
         if rc:
             self.ctx._chk(rc)
         return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
+
+    def frame_view_aligning(self, fv, p: AlignParams, params: ColourParams, leaf_size=0.008, d_vis=0.06):
+        """frame_view on two raw streams (tdlo_tracker_frame_view_aligning): the depth image at the depth camera's size is aligned to the colour camera on the
+        device in front of the frame.  Returns (visible_nodes, visible_nodes_extended, n, n_raw, counts [4])."""
+        fv = fv if isinstance(fv, FrameView) else aligning_frame_view(*fv) if isinstance(fv, (tuple, list)) else aligning_frame_view(**fv)
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        cnt = (C.c_longlong * 4)()
+        rc = self.ctx.lib.tdlo_tracker_frame_view_aligning(self.h, C.byref(fv), C.byref(p) if p is not None else None, C.byref(params) if params is not None else None,
+                                                           leaf_size, d_vis, v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw),
+                                                           self._st_ptr, C.byref(cnt))
+        self._stats_raw = self._st
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value, [int(x) for x in cnt]
 
     def render_result(self, proj=None, params: RenderParams = None, *, out=None, corners=True):
         """The published image of this frame (trackdlo_node.cpp:377-452; tdlo_tracker_render_result): the tracker's current nodes over the last colour frame

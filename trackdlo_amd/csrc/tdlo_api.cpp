@@ -12,6 +12,7 @@
 #include "tdlo_cell_painter_host.h"
 #include "tdlo_assign_host.h"
 #include "tdlo_cluster_lane.h"
+#include "tdlo_align_host.h"
 #include "tdlo_view_batch_plan.h"
 #include "tdlo_rig_batch_plan.h"
 
@@ -298,6 +299,18 @@ struct tdlo_ctx {
     // come from the host statement.  clu_route: tdlo_debug_route_count 55 / 56: calls the cluster launches served / calls the host route served (forced, or after a give-up)
     bool cluster_host = getenv("TDLO_CLUSTER") && std::strcmp(getenv("TDLO_CLUSTER"), "host") == 0;
     long long clu_route[2] = {0, 0};
+    // depth aligned to the colour camera (tdlo_align_depth and the aligning frame calls: k_align_splat / k_align_pack).  aln_dev: [scratch plane of 32-bit words |
+    // aligned uint16 plane | packed depth of a host view | 4 count words], grown on demand; the scratch words and the counts are armed (all ones / zero) when
+    // allocated or after a call that failed between its launches, and kept armed by k_align_pack.  aln_res: 4 count words in pinned host memory; aln_pin: the
+    // pinned staging of a host view's packed depth (and of the host route's plane).  TDLO_ALIGN=host: the plane comes from the host statement and is uploaded
+    // (the comparator).  aln_route: tdlo_debug_route_count 59 / 60: planes formed by the kernels / by the host statement
+    char *aln_dev = nullptr, *aln_pin = nullptr;
+    size_t aln_dev_cap = 0, aln_pin_cap = 0, aln_Pc = 0, aln_Pd = 0;
+    unsigned long long *aln_res = nullptr;
+    bool aln_armed = false;
+    int aln_res_at = 0;                   // where in aln_res the last call's counts lie: 0 (written by k_align_pack) or 4 (the host route's)
+    bool align_host = getenv("TDLO_ALIGN") && std::strcmp(getenv("TDLO_ALIGN"), "host") == 0;
+    long long aln_route[2] = {0, 0};
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1865,6 +1878,9 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->asg_dev) hipFree(c->asg_dev);
     if (c->asg_state) hipFree(c->asg_state);
     if (c->asg_res) hipHostFree(c->asg_res);
+    if (c->aln_dev) hipFree(c->aln_dev);
+    if (c->aln_pin) hipHostFree(c->aln_pin);
+    if (c->aln_res) hipHostFree(c->aln_res);
     for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
@@ -4899,6 +4915,18 @@ static int frame_view_refusal(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, 
     return TDLO_OK;
 }
 
+// Where a checked image view lies (pointer_location), and the one thing a host view must not do
+static int image_view_where(tdlo_ctx *c, const tdlo_image_view *v, int rows, int cols, bool *device) {
+    if (int rc = pointer_location(c, v->data, v->location, "image view", device)) return rc;
+    if (*device) return TDLO_OK;
+    long long lo, hi;
+    image_view_span(v, rows, cols, &lo, &hi);
+    const char *a = (const char *)v->data + lo, *b = (const char *)v->data + hi;
+    if ((c->img_pin && a < c->img_pin + c->img_pin_cap && b > c->img_pin) || (c->col_pin && a < c->col_pin + c->col_pin_cap && b > c->col_pin))
+        return fail(c, TDLO_E_INVALID, "image view: a host view inside the context's pinned image buffers (hand those to the packed calls)");
+    return TDLO_OK;
+}
+
 // A checked frame view -> its canonical images.  Device sources: one launch of k_image_import into the device image buffers (cloud_ws: depth | mask,
 // col_dev: colour | occluder), which depth_to_cloud_impl / colour_stage recognise by their addresses.  Host sources: packed and converted by the host
 // into the pinned buffers of tdlo_image_buffers / tdlo_colour_buffers, i.e. the in-place route; in a frame that has device sources too they are
@@ -4911,14 +4939,8 @@ static int stage_frame_view(tdlo_ctx *c, const tdlo_frame_view *fv, const tdlo_c
     bool dev[4] = {false, false, false, false}, any_dev = false, any_host = false;
     for (int r = 0; r < 4; ++r) {
         if (!iv[r]->data) continue;
-        if (int rc = pointer_location(c, iv[r]->data, iv[r]->location, "image view", &dev[r])) return rc;
-        if (dev[r]) { any_dev = true; continue; }
-        any_host = true;
-        long long lo, hi;
-        image_view_span(iv[r], rows, cols, &lo, &hi);
-        const char *a = (const char *)iv[r]->data + lo, *b = (const char *)iv[r]->data + hi;
-        if ((c->img_pin && a < c->img_pin + c->img_pin_cap && b > c->img_pin) || (c->col_pin && a < c->col_pin + c->col_pin_cap && b > c->col_pin))
-            return fail(c, TDLO_E_INVALID, "image view: a host view inside the context's pinned image buffers (hand those to the packed calls)");
+        if (int rc = image_view_where(c, iv[r], rows, cols, &dev[r])) return rc;
+        if (dev[r]) any_dev = true; else any_host = true;
     }
     sf.colour = fv->colour.data != nullptr;
     const bool want_col = sf.colour;
@@ -4996,6 +5018,160 @@ int tdlo_frame_to_cloud_visibility_view(tdlo_ctx *c, int slot, const tdlo_frame_
     if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
     return depth_to_cloud_visibility_impl(c, slot, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, rows, cols, fx, fy, cx, cy, leaf_size, Y, M, visibility_threshold,
                                           d_vis, geodesic_coord, node_dist, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out);
+}
+
+// ---- depth aligned to the colour camera (include/trackdlo_hip.h: tdlo_align_depth; tdlo_align.hip, tdlo_align_host.cpp) ------------------------------------
+// aln_dev = [4 count words (256 bytes) | scratch: cap_c words | aligned plane: cap_c uint16 | packed depth of a host view: cap_d uint16], every block 256-byte
+// aligned; aln_pin = [packed depth: cap_d uint16 | the host route's plane: cap_c uint16].  Grown together when either camera's size passes its capacity.
+static size_t aln_round(size_t b) { return (b + 255) & ~(size_t)255; }
+static unsigned long long *aln_counts(tdlo_ctx *c) { return (unsigned long long *)c->aln_dev; }
+static unsigned *aln_scratch(tdlo_ctx *c) { return (unsigned *)(c->aln_dev + 256); }
+static unsigned short *aln_plane(tdlo_ctx *c) { return (unsigned short *)(c->aln_dev + 256 + aln_round(4 * c->aln_Pc)); }
+static unsigned short *aln_depth(tdlo_ctx *c) { return (unsigned short *)(c->aln_dev + 256 + aln_round(4 * c->aln_Pc) + aln_round(2 * c->aln_Pc)); }
+static unsigned short *aln_pin_plane(tdlo_ctx *c) { return (unsigned short *)(c->aln_pin + aln_round(2 * c->aln_Pd)); }
+
+static int align_reserve(tdlo_ctx *c, size_t Pc, size_t Pd) {
+    if (!c->aln_res) {
+        HIPCHK(c, hipHostMalloc((void **)&c->aln_res, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+        std::memset(c->aln_res, 0, 8 * sizeof(unsigned long long));
+    }
+    if (Pc <= c->aln_Pc && Pd <= c->aln_Pd && c->aln_dev && c->aln_pin) return TDLO_OK;
+    HIPCHK(c, drain_for_realloc(c));
+    if (c->aln_dev) hipFree(c->aln_dev);
+    if (c->aln_pin) hipHostFree(c->aln_pin);
+    c->aln_dev = c->aln_pin = nullptr; c->aln_dev_cap = c->aln_pin_cap = 0; c->aln_armed = false;
+    const size_t cap_c = std::max(Pc, c->aln_Pc), cap_d = std::max(Pd, c->aln_Pd);
+    c->aln_Pc = c->aln_Pd = 0;
+    const size_t dev_bytes = 256 + aln_round(4 * cap_c) + aln_round(2 * cap_c) + aln_round(2 * cap_d), pin_bytes = aln_round(2 * cap_d) + aln_round(2 * cap_c);
+    HIPCHK(c, hipMalloc((void **)&c->aln_dev, dev_bytes));
+    c->aln_dev_cap = dev_bytes;
+    HIPCHK(c, hipHostMalloc((void **)&c->aln_pin, pin_bytes, hipHostMallocDefault));
+    c->aln_pin_cap = pin_bytes; c->aln_Pc = cap_c; c->aln_Pd = cap_d;
+    return TDLO_OK;
+}
+
+// What an align call refuses before it looks at the context's GPU: the params, the depth view
+static int align_refusal(tdlo_ctx *c, const tdlo_image_view *depth, const tdlo_align_params *p) {
+    if (const char *why = align_fault(p)) return fail(c, TDLO_E_INVALID, why);
+    if (const char *why = image_view_fault(depth, p->rows_d, p->cols_d, kRoleDepth)) return fail(c, TDLO_E_INVALID, why);
+    return TDLO_OK;
+}
+
+// The aligned plane of a checked (depth view, params), enqueued on the context's stream WITHOUT a host wait on the device route: *plane is the context's
+// aligned plane.  The counts are the caller's after the stream's next wait (align_counts_fetch).  dev: where the depth view lies (image_view_where)
+static int align_enqueue(tdlo_ctx *c, const tdlo_image_view *depth, bool dev, const tdlo_align_params *p, const unsigned short **plane) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t Pc = (size_t)p->rows_c * p->cols_c, Pd = (size_t)p->rows_d * p->cols_d;
+    if (int rc = align_reserve(c, Pc, Pd)) return rc;
+    if (dev && depth->ready_stream) {
+        if (!c->ev_view) HIPCHK(c, hipEventCreateWithFlags(&c->ev_view, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_view, (hipStream_t)depth->ready_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_view, 0));
+    }
+    *plane = aln_plane(c);
+    if (c->align_host) {
+        // the comparator: the host statement's plane, uploaded.  A device view comes down as its packed canonical depth (k_image_import, one copy, one wait)
+        tdlo_image_view hv = *depth;
+        if (dev) {
+            ImageJob job{};
+            job.P = (int)Pd; job.cols = p->cols_d;
+            job.src[kRoleDepth] = ImageSrc{(const unsigned char *)depth->data, depth->row_stride, depth->format, image_import_form(depth->data, depth->row_stride, p->cols_d, depth->format)};
+            job.dst[kRoleDepth] = (unsigned char *)aln_depth(c);
+            HIPCHK(c, launch_image_import(job, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->aln_pin, aln_depth(c), 2 * Pd, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, wait_stream(c->stream));
+            hv = tdlo_image_view{c->aln_pin, TDLO_IMG_U16C1, TDLO_MEM_HOST, 2ll * p->cols_d, nullptr};
+        }
+        long long n[4];
+        if (tdlo_align_depth_host(&hv, p, aln_pin_plane(c), n)) return fail(c, TDLO_E_INVALID, "align: the host statement refused the call");
+        for (int i = 0; i < 4; ++i) c->aln_res[4 + i] = (unsigned long long)n[i];
+        HIPCHK(c, hipMemcpyAsync(aln_plane(c), aln_pin_plane(c), 2 * Pc, hipMemcpyHostToDevice, c->stream));
+        c->aln_res_at = 4;
+        ++c->aln_route[1];
+        return TDLO_OK;
+    }
+    AlignJob job;
+    align_job(depth, p, job);
+    if (!dev) {                                             // a host view goes up once, packed
+        image_pack_host(depth, p->rows_d, p->cols_d, c->aln_pin);
+        HIPCHK(c, hipMemcpyAsync(aln_depth(c), c->aln_pin, 2 * Pd, hipMemcpyHostToDevice, c->stream));
+        job.depth = (const unsigned char *)aln_depth(c); job.row_stride = 2ll * p->cols_d; job.format = TDLO_IMG_U16C1;
+    }
+    if (!c->aln_armed) {                                    // the first use of an allocation (or after a call that failed between its launches): filled once
+        HIPCHK(c, hipMemsetAsync(c->aln_dev, 0, 256, c->stream));
+        HIPCHK(c, hipMemsetAsync(aln_scratch(c), 0xff, 4 * c->aln_Pc, c->stream));
+    }
+    c->aln_armed = false;
+    HIPCHK(c, launch_align(job, aln_scratch(c), aln_plane(c), aln_counts(c), c->aln_res, c->stream));
+    c->aln_armed = true;                                    // k_align_pack leaves every word it read, and the counts, armed
+    c->aln_res_at = 0;
+    ++c->aln_route[0];
+    return TDLO_OK;
+}
+
+// after a wait of the context's stream that followed align_enqueue
+static void align_counts_fetch(tdlo_ctx *c, long long counts[4]) {
+    if (counts) for (int i = 0; i < 4; ++i) counts[i] = (long long)c->aln_res[c->aln_res_at + i];
+}
+
+int tdlo_align_depth(tdlo_ctx *c, const tdlo_image_view *depth, const tdlo_align_params *p, unsigned short *aligned_out,
+                     const unsigned short **device_plane, long long counts[4]) {
+    if (!c) return TDLO_E_INVALID;
+    int rc = align_refusal(c, depth, p);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    bool dev = false, out_dev = false;
+    if ((rc = image_view_where(c, depth, p->rows_d, p->cols_d, &dev))) return rc;
+    if (aligned_out && (rc = pointer_location(c, aligned_out, TDLO_MEM_AUTO, "align: aligned_out", &out_dev))) return rc;
+    const unsigned short *plane = nullptr;
+    if ((rc = align_enqueue(c, depth, dev, p, &plane))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    const size_t bytes = 2 * (size_t)p->rows_c * p->cols_c;
+    if (aligned_out) HIPCHK(c, hipMemcpyAsync(aligned_out, plane, bytes, out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, wait_stream(c->stream));
+    align_counts_fetch(c, counts);
+    if (device_plane) *device_plane = plane;
+    return TDLO_OK;
+}
+
+// The checks of an aligning frame call, in front of everything it touches: the params and the depth view at the depth camera's size, the rest of the frame
+// at the colour camera's (fv2: the frame the view call behind it will see, its depth a device view of the aligned plane), where every view lies
+static int align_frame_refusal(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, const tdlo_align_params *p, const tdlo_colour_params *cp, double leaf_size,
+                               tdlo_frame_view &fv2, bool *depth_dev) {
+    if (!fv) return fail(c, TDLO_E_INVALID, "frame view: null");
+    int rc = align_refusal(c, &fv->depth, p);
+    if (rc) return rc;
+    alignas(8) static const unsigned short placeholder[4] = {0, 0, 0, 0};      // stands for the aligned plane until it exists
+    fv2 = *fv;
+    fv2.depth = tdlo_image_view{placeholder, TDLO_IMG_U16C1, TDLO_MEM_DEVICE, 2ll * p->cols_c, nullptr};
+    if ((rc = frame_view_refusal(c, slot, &fv2, cp, p->rows_c, p->cols_c, p->fx_c, p->fy_c, leaf_size))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = image_view_where(c, &fv->depth, p->rows_d, p->cols_d, depth_dev))) return rc;
+    const tdlo_image_view *iv[3] = {&fv->colour, &fv->occluder, &fv->mask};
+    for (int r = 0; r < 3; ++r) {
+        bool d;
+        if (iv[r]->data && (rc = image_view_where(c, iv[r], p->rows_c, p->cols_c, &d))) return rc;
+    }
+    return TDLO_OK;
+}
+
+int tdlo_frame_to_cloud_view_aligning(tdlo_ctx *c, int slot, const tdlo_frame_view *fv, const tdlo_align_params *p, const tdlo_colour_params *colour_params,
+                                      double leaf_size, double *X_out, int x_capacity, int *n_out, int *n_raw_out, long long counts[4]) {
+    if (!c) return TDLO_E_INVALID;
+    tdlo_frame_view fv2;
+    bool dev = false;
+    int rc = align_frame_refusal(c, slot, fv, p, colour_params, leaf_size, fv2, &dev);
+    if (rc) return rc;
+    const unsigned short *plane = nullptr;
+    StagedFrame sf;
+    if ((rc = align_enqueue(c, &fv->depth, dev, p, &plane)) || (fv2.depth.data = plane, rc = stage_frame_view(c, &fv2, colour_params, p->rows_c, p->cols_c, sf))) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    rc = depth_to_cloud_impl(c, slot, sf.depth, sf.mask, p->rows_c, p->cols_c, p->fx_c, p->fy_c, p->cx_c, p->cy_c, leaf_size, X_out, x_capacity, n_out, n_raw_out,
+                             nullptr, 0, nullptr, sf.colour ? &sf.ci : nullptr);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    align_counts_fetch(c, counts);
+    return rc;
 }
 
 // ---- image views for F slots in one call (include/trackdlo_hip.h: tdlo_frame_views_to_cloud_batch) ------------------------------------------------
@@ -5423,7 +5599,8 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 58) return -1;
+    if (!c || which < 0 || which > 60) return -1;
+    if (which >= 59) return c->aln_route[which - 59];
     if (which >= 57) return c->cel_route[which - 57];
     if (which >= 55) return c->clu_route[which - 55];
     if (which >= 53) return c->asg_route[which - 53];
@@ -6110,6 +6287,31 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
     if ((rc = stage_frame_view(c, fv, colour_params, rows, cols, sf))) return rc;
     return tracker_frame_impl(t, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, rows, cols, fx, fy, cx, cy, leaf_size, d_vis, visible_nodes, n_vis,
                               visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
+}
+
+// tdlo_tracker_frame_view on two raw streams: the align launches in front of the import, on the same stream -- no host wait of their own
+int tdlo_tracker_frame_view_aligning(tdlo_tracker *t, const tdlo_frame_view *fv, const tdlo_align_params *p, const tdlo_colour_params *colour_params,
+                                     double leaf_size, double d_vis,
+                                     int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                     int *n_out, int *n_raw_out, tdlo_stats *stats, long long counts[4]) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    if (t->geodesic_coord.size() != (size_t)t->M) return fail(c, TDLO_E_INVALID, "the tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)");
+    tdlo_frame_view fv2;
+    bool dev = false;
+    int rc = align_frame_refusal(c, t->slot, fv, p, colour_params, leaf_size, fv2, &dev);
+    if (rc) return rc;
+    const unsigned short *plane = nullptr;
+    StagedFrame sf;
+    if ((rc = align_enqueue(c, &fv->depth, dev, p, &plane)) || (fv2.depth.data = plane, rc = stage_frame_view(c, &fv2, colour_params, p->rows_c, p->cols_c, sf))) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    rc = tracker_frame_impl(t, sf.depth, sf.mask, sf.colour ? &sf.ci : nullptr, p->rows_c, p->cols_c, p->fx_c, p->fy_c, p->cx_c, p->cy_c, leaf_size, d_vis,
+                            visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    align_counts_fetch(c, counts);
+    return rc;
 }
 
 // The same from a cloud view: the voxel grid on the view into the tracker's slot and the visibility pre-pass (tdlo_cloud_view_voxel_grid_visibility: in one

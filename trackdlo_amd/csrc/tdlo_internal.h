@@ -432,5 +432,10 @@ hipError_t launch_image_import(const ImageJob &job, hipStream_t s);
 // jobs: the table on the host, checked per job as launch_image_import checks its argument; table_dev: the same J x sizeof(ImageJob) bytes in device memory,
 // which the caller has enqueued on s ahead of this call (it travels with the call's descriptor table)
 hipError_t launch_image_import_batch(const ImageJob *jobs, int J, const void *table_dev, hipStream_t s);
+// tdlo_align.hip: depth aligned to the colour camera (k_align_splat, k_align_pack; tdlo_align_lane.h).  scratch: rows_c x cols_c words, all ones (the pack arms
+// them again), 16-byte aligned; out: the uint16 plane, 8-byte aligned; counts: 4 zeroed device words (the pack zeroes them again); counts_out: 4 words of
+// pinned host memory, valid after the stream's next wait
+struct AlignJob;
+hipError_t launch_align(const AlignJob &job, unsigned *scratch, unsigned short *out, unsigned long long *counts, unsigned long long *counts_out, hipStream_t s);
 
 }  // namespace tdlo

@@ -1256,7 +1256,7 @@ int tdlo_tracker_frame_view(tdlo_tracker *t, const tdlo_frame_view *fv, const td
  * wide whatever the depth.  Two identical cameras with T = NULL do NOT give D back: the corners land on integers up to rounding, so footprints are 2 - 3
  * pixels wide (580 of the 768 pixels of a random 24 x 32 image differ) -- the algorithm's nature, and the reason the no-FMA rule matters: a corner within one
  * rounding of an integer + 1/2 moves to the next pixel when one multiply-add is fused.  A T that is the identity matrix gives NULL's bits.
- * Out of scope: distortion models, colour aligned to depth, a batch form for F frames or a rig's K cameras. */
+ * Out of scope: distortion models, colour aligned to depth.  The form for many cameras in one call -- a rig's K cameras, F frames -- is tdlo_align_depth_batch, below. */
 typedef struct {
     int rows_d, cols_d;
     double fx_d, fy_d, cx_d, cy_d;
@@ -1291,6 +1291,79 @@ int tdlo_tracker_frame_view_aligning(tdlo_tracker *t, const tdlo_frame_view *fv,
                                      double leaf_size, double d_vis,
                                      int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
                                      int *n_out, int *n_raw_out, tdlo_stats *stats, long long counts[4]);
+/* ---- raw depth for many cameras in one call: rigs and batches ------------------------------------------------- */
+/* Every RGB-D camera has its depth sensor and its colour sensor on different pixel grids, so a rig of K cameras arrives as 2 K raw streams.  tdlo_align_depth
+ * serves one camera: K calls are 2 K small launches and K host waits, and each call overwrites the context's one aligned plane.  tdlo_align_depth_batch aligns J
+ * JOBS -- a depth view and its params each -- in two launches, the job as the second dimension of the single call's grids (csrc/tdlo_align_batch.hip:
+ * k_align_splat_batch, grid (blocks of the job with the most depth pixels, J), and k_align_pack_batch, grid (blocks of the job with the most colour pixels / 4, J);
+ * workgroup row j fetches record j of a job table in device memory and runs the single kernels' lanes, csrc/tdlo_align_lane.h unchanged; a workgroup beyond its own
+ * job's pixels leaves at once; no grid barrier, no workgroup waits for another), into planes of an ARENA of the context that all stay valid together.
+ *   JOBS are independent: each has its own sizes, format (U16 / F32), pitch (positive, negative, padded), location (host / device / auto), ready_stream, transform
+ * and max_footprint.  Two jobs may name the same depth view under different params.  A host view goes up once, packed: all host views of a call go into ONE pinned
+ * block and ONE copy (a view named by several jobs once).  All device views share one event per distinct ready_stream.
+ *   BITS: plane j and counts[4 j .. 4 j + 3] are those of tdlo_align_depth on job j alone, i.e. THE STATEMENT above (tests/align_ref.py: align, counts_of); they
+ * depend neither on what else shares the call nor on the order of the jobs.
+ *   OUTPUTS: aligned_out: NULL, or J entries, each NULL, host memory or device memory (2-byte alignment suffices) that receives a copy of plane j;
+ * device_planes: NULL, or J entries out: plane j in the arena (256-byte aligned, packed rows_c x cols_c uint16); counts: NULL or 4 J; rc_each: NULL or J (a job
+ * cannot fail on its own once the call is accepted: zeros).
+ *   WAITS: ONE host wait when something must reach the host -- counts non-NULL, or a host aligned_out[j].  Otherwise NO HOST WAIT: the planes are produced on the
+ * context's stream (tdlo_stream), and the library guarantees the order by enqueueing on that one stream everything a later call of THIS context does with
+ * device_planes[j] -- the rig calls copy a device depth plane on it, the view calls import a TDLO_MEM_DEVICE view on it (ready_stream NULL; a consumer on another
+ * stream or context passes ready_stream = tdlo_stream(ctx)), the render batch reads on it.  (A call waits on the host only for the PREVIOUS batch call's uploads to
+ * have left the pinned block it is about to rewrite -- long done as a rule; a call that grows the arena drains the stream first.)
+ *   LIFETIME: device_planes stay valid, all J together, until the next tdlo_align_depth_batch of the context or one of the aligning rig calls below.  The single
+ * call's plane and this arena are independent of each other.
+ *   THE ARENA (csrc/tdlo_align_batch_plan.h; tdlo_debug_align_batch_plan): [scratch region | uint16 planes | count words | job table]; scratch planes 16-byte,
+ * uint16 planes 256-byte aligned.  Every word of the scratch region is armed (all ones) between calls -- filled when the arena is allocated or the region grows,
+ * re-armed by the pack for every plane of the current layout -- so a call whose sizes, order or J differ from the call before needs no fill launch and cannot see
+ * a stale word.  J is 1 .. 1024; an arena beyond 1 GiB (kAlignBatchBudget; 64 cameras of 1280 x 720 need about 0.35 GiB) refuses the call.
+ *   REFUSED AS A WHOLE with TDLO_E_INVALID before anything is touched, no counter moved: J outside 1 .. 1024; a job that tdlo_align_check or tdlo_image_view_check
+ * (role depth, the depth camera's size) refuses; a pointer on another GPU; a device aligned_out[j] or a device view that overlaps the arena; the budget exceeded.
+ *   ROUTES (the same bits on each).  kAlignBatchMin (csrc/tdlo_api.cpp) is the smallest J from which a call takes the batch launches; below it the call loops the
+ * single launches into the arena's planes -- no host wait either.  NOT MEASURED YET (scripts/gpu_align_batch.py writes profiles/align_batch_ab.txt; the rule, set
+ * beforehand: the smallest J from which every batch value lies below every looped value on all four lines -- 640 x 480 -> 640 x 480 and 848 x 480 -> 1280 x 720,
+ * device and pageable host depth --, 1025 if no J up to 32 qualifies): until it is, kAlignBatchMin is 1025 and BY DEFAULT THE CALL LOOPS THE SINGLE LAUNCHES.
+ * TDLO_ALIGN_BATCH_MIN=n, read when the context is made, overrides it.  TDLO_ALIGN=host forms every plane with tdlo_align_depth_host and uploads it.
+ * tdlo_debug_route_count 61 counts the jobs the batch launches served, 62 the jobs the looped single launches served; 59 / 60 keep counting what the single
+ * launches / the host statement did (a looped job moves 59 and 62); 63 counts the DISTINCT jobs formed inside the aligning rig calls below.
+ * Out of scope: an aligning form of tdlo_tracker_frame_views_batch -- the no-wait call and TDLO_MEM_DEVICE views of device_planes compose it by hand --, the pack
+ * writing straight into the rig arena. */
+typedef struct { tdlo_image_view depth; tdlo_align_params p; } tdlo_align_job;
+int tdlo_align_depth_batch(tdlo_ctx *ctx, const tdlo_align_job *jobs, int J,
+                           unsigned short *const *aligned_out   /* NULL, or J entries: NULL / host / device memory */,
+                           const unsigned short **device_planes /* NULL, or J entries out: the arena's planes */,
+                           long long *counts /* NULL or 4 J */, int *rc_each /* NULL or J */);
+/* The rig calls from raw streams.  cams[k].depth must be NULL; raw[k] is camera k's raw depth view and its align params, whose colour size is the rig's
+ * rows x cols.  THE CONTRACT: bit for bit the composition by hand -- tdlo_align_depth per camera, each plane kept, then the existing rig call (tdlo_rig_to_cloud,
+ * tdlo_tracker_frame_from_rig, tdlo_tracker_frames_from_rig_batch) with those planes as device depth planes: the cloud, n, n_raw, the visible sets, the nodes and
+ * sigma2, under the existing calls' own conditions.  These entrances CALL the existing calls, so the routes and the rig self-occlusion switch behave as there.
+ *   DISTINCT JOBS: two (camera, frame) entries with equal view fields (data, format, row_stride, location, ready_stream) and bytewise-equal params (the matrix
+ * compared by value) are ONE job: F ropes under one rig align K planes, not F K (tdlo_debug_route_count 63 counts them; at most 1024 a call).  counts (NULL, or
+ * four per (frame, camera) entry, frame after frame) still has one row per entry.
+ *   WAITS: the align launches go in front of the rig call's copies on the context's stream and add no host wait; counts come back with the rig call's own wait.
+ *   A REFUSED call leaves slots, trackers, the arena's planes and all counters untouched: a camera with depth non-NULL, a raw[k].p whose colour size is not
+ * rows x cols, and everything tdlo_align_depth_batch and the existing rig call refuse. */
+int tdlo_rig_to_cloud_aligning(tdlo_ctx *ctx, int slot, const tdlo_rig_camera *cams, const tdlo_align_job *raw, int K, int rows, int cols,
+                               double leaf_size, double *X_out, int x_capacity, int *n_out, int *n_raw_out, long long *counts /* NULL or 4 K */);
+int tdlo_tracker_frame_from_rig_aligning(tdlo_tracker *t, const tdlo_rig_camera *cams, const tdlo_align_job *raw, int K, int rows, int cols,
+                                         double leaf_size, double d_vis,
+                                         int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                         int *n_out, int *n_raw_out, tdlo_stats *stats, long long *counts /* NULL or 4 K */);
+typedef struct { int slot; const tdlo_rig_camera *cams; const tdlo_align_job *raw; int K; } tdlo_rig_raw_frame;
+int tdlo_tracker_frames_from_rig_aligning_batch(tdlo_tracker *const *trackers, int F, const tdlo_rig_raw_frame *frames /* .slot not read */,
+                                                int rows, int cols, double leaf_size, double d_vis,
+                                                int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext,
+                                                int *n_out, int *n_raw_out, tdlo_stats *stats /* 2 F */, int *rc_each, long long *counts /* NULL or 4 sum K_f */);
+/* The arena layout of csrc/tdlo_align_batch_plan.h (no context, no GPU), shaped like tdlo_debug_rig_batch_plan: J jobs of rows_c[j] x cols_c[j] colour pixels;
+ * budget: the bytes the arena may take (<= 0: the library's 1 GiB).  Outputs in bytes from the arena's start, any may be NULL: scratch_off / plane_off / counts_off:
+ * J entries (job j's scratch plane, uint16 plane, four count words); *table_off; *scratch_bytes: the scratch region is [0, scratch_bytes); *total.
+ * TDLO_E_INVALID: J outside 1 .. 1024, a size below 1 or beyond 2^26 pixels, a total beyond the budget.  tdlo_debug_align_batch_arena: where the context's
+ * align-batch arena lies at present (a test aid for the overlap refusal; NULL / 0 before the first batch).  tdlo_debug_align_distinct_jobs: the distinct-job rule
+ * on n (view, params) entries -- job_of[e] is the index of entry e's job in order of first appearance; returns the number of distinct jobs, or a negative code. */
+int tdlo_debug_align_batch_plan(const int *rows_c, const int *cols_c, int J, long long budget, long long *scratch_off, long long *plane_off,
+                                long long *counts_off, long long *table_off, long long *scratch_bytes, long long *total);
+int tdlo_debug_align_batch_arena(tdlo_ctx *ctx, const void **base, long long *bytes);
+int tdlo_debug_align_distinct_jobs(const tdlo_align_job *entries, int n, int *job_of);
 /* ---- image views for many slots in one call ----------------------------------------------------------- */
 /* tdlo_depth_to_cloud_batch for callers who come with image VIEWS: a simulator, renderer or decoder on the same GPU that makes K camera images as one device
  * tensor ([K, H, W, 4] uint8 and [K, H, W] float32) and steps as many trackers.  An IMAGE is a tdlo_frame_view -- depth, and a mask, or a colour view (with
@@ -1609,6 +1682,8 @@ int tdlo_debug_lle_band_device(tdlo_ctx *ctx, const double *Y, int M, double *Hb
  * 57 / 58: (camera, cell) jobs of the painter test over a cell of ropes served by k_cell_project / k_cell_cover (tdlo_cell_occlusion_batch, and
  * tdlo_tracker_frames_from_shared_cloud_occluded_batch from kCellPainterMin flat nodes x cameras on) / done by the host statement inside that tracker call.
  * 59 / 60: aligned planes (tdlo_align_depth, and the aligning frame calls) formed by k_align_splat / k_align_pack / by the host statement (TDLO_ALIGN=host).
+ * 61 / 62 / 63: jobs of tdlo_align_depth_batch (the aligning rig calls' among them) served by k_align_splat_batch / k_align_pack_batch / by the single launches in
+ * a loop (below kAlignBatchMin; these move 59 as well); the distinct jobs formed inside the aligning rig calls.
  * -1 for a null context or an unknown counter. */
 long long tdlo_debug_route_count(tdlo_ctx *ctx, int which);
 /* Phase stamps (s_memtime) of the last depth -> cloud launch's finishing workgroup; only a -DTDLO_CLOUD_STAMPS build writes them. */

@@ -23,6 +23,7 @@ cd $S
 /opt/rocm/bin/hipcc $F -c tdlo_import.hip -o $B/tdlo_import.o &
 /opt/rocm/bin/hipcc $F -c tdlo_batch.hip -o $B/tdlo_batch.o &
 /opt/rocm/bin/hipcc $F -c tdlo_image.hip -o $B/tdlo_image.o &
+/opt/rocm/bin/hipcc $F -ffp-contract=off -c tdlo_align_batch.hip -o $B/tdlo_align_batch.o &
 /opt/rocm/bin/hipcc $F -c tdlo_render.hip -o $B/tdlo_render.o &
 /opt/rocm/bin/hipcc $F -c tdlo_render_batch.hip -o $B/tdlo_render_batch.o &
 /opt/rocm/bin/hipcc $F -x hip -c tdlo_api.cpp -o $B/tdlo_api.o &

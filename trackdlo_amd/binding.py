@@ -142,6 +142,16 @@ class AlignParams(C.Structure):
                 ("depth_to_colour", C.c_void_p), ("max_footprint", C.c_int)]
 
 
+class AlignJobC(C.Structure):
+    """tdlo_align_job: one job of tdlo_align_depth_batch and the aligning rig calls -- a raw depth view and its align params.  Built by make_align_job(), which
+    keeps the image and the matrix alive in .owner."""
+    _fields_ = [("depth", ImageView), ("p", AlignParams)]
+
+
+class RigRawFrameC(C.Structure):                   # tdlo_rig_raw_frame: a slot, a rig's cameras (depth NULL) and their K raw depth jobs
+    _fields_ = [("slot", C.c_int), ("cams", C.c_void_p), ("raw", C.c_void_p), ("K", C.c_int)]
+
+
 class ViewImage(C.Structure):                      # tdlo_view_image: one image of a view batch -- its views and its camera
     _fields_ = [("fv", FrameView), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
@@ -182,6 +192,8 @@ SYMBOLS = [
     "tdlo_cloud_cluster", "tdlo_cloud_cluster_host", "tdlo_tracker_initialize_from_shared_cloud_batch",
     "tdlo_cell_occlusion_visible", "tdlo_cell_occlusion_batch", "tdlo_tracker_frames_from_shared_cloud_occluded_batch",
     "tdlo_align_check", "tdlo_align_depth_host", "tdlo_align_depth", "tdlo_frame_to_cloud_view_aligning", "tdlo_tracker_frame_view_aligning",
+    "tdlo_align_depth_batch", "tdlo_rig_to_cloud_aligning", "tdlo_tracker_frame_from_rig_aligning", "tdlo_tracker_frames_from_rig_aligning_batch",
+    "tdlo_debug_align_batch_plan", "tdlo_debug_align_batch_arena", "tdlo_debug_align_distinct_jobs",
 ]
 
 _lib = None
@@ -437,6 +449,15 @@ def load_library(path: str | None = None):
         lib.tdlo_align_depth.argtypes = [vp, ivp, app, vp, C.POINTER(vp), ll4]
         lib.tdlo_frame_to_cloud_view_aligning.argtypes = [vp, ci, fvp, app, cpp, cd, vp, ci, C.POINTER(ci), C.POINTER(ci), ll4]
         lib.tdlo_tracker_frame_view_aligning.argtypes = [vp, fvp, app, cpp, cd, cd, vp, C.POINTER(ci), vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp, ll4]
+    if hasattr(lib, "tdlo_align_depth_batch"):
+        pi = C.POINTER(ci)
+        lib.tdlo_align_depth_batch.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        lib.tdlo_rig_to_cloud_aligning.argtypes = [vp, ci, vp, vp, ci, ci, ci, cd, vp, ci, pi, pi, vp]
+        lib.tdlo_tracker_frame_from_rig_aligning.argtypes = [vp, vp, vp, ci, ci, ci, cd, cd, vp, pi, vp, pi, pi, pi, vp, vp]
+        lib.tdlo_tracker_frames_from_rig_aligning_batch.argtypes = [vp, ci, vp, ci, ci, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.tdlo_debug_align_batch_plan.argtypes = [vp, vp, ci, C.c_longlong, vp, vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        lib.tdlo_debug_align_batch_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_longlong)]
+        lib.tdlo_debug_align_distinct_jobs.argtypes = [vp, ci, vp]
     if path is None:
         _lib = lib
     return lib
@@ -664,6 +685,74 @@ def align_depth_host(depth, p: AlignParams, lib=None):
     if rc:
         raise TdloError(rc, "tdlo_align_depth_host: bad params or not a host depth view")
     return A, [int(x) for x in cnt]
+
+
+def make_align_job(depth, p: AlignParams, ready_stream=None) -> AlignJobC:
+    """tdlo_align_job: depth an ImageView or anything image_view() takes (a numpy array, a device tensor), p the job's AlignParams."""
+    v = depth if isinstance(depth, ImageView) else image_view(depth, ready_stream=ready_stream)
+    j = AlignJobC()
+    C.memmove(C.addressof(j), C.addressof(v), C.sizeof(ImageView))
+    C.memmove(C.addressof(j) + AlignJobC.p.offset, C.addressof(p), C.sizeof(AlignParams))
+    j.owner = (v, getattr(v, "owner", None), p, getattr(p, "owner", None))
+    return j
+
+
+def _align_jobs(jobs):
+    """The tdlo_align_job table of a list of AlignJobC (or (depth, params) pairs).  Returns (table, J, owners)."""
+    jobs = [j if isinstance(j, AlignJobC) else make_align_job(*j) for j in jobs]
+    J = len(jobs)
+    tab = (AlignJobC * max(J, 1))()
+    for i, j in enumerate(jobs):
+        C.memmove(C.addressof(tab[i]), C.addressof(j), C.sizeof(AlignJobC))
+    return tab, J, jobs
+
+
+def align_batch_plan(rows_c, cols_c, budget=0):
+    """tdlo_debug_align_batch_plan: where the align batch keeps the blocks of J jobs of rows_c[j] x cols_c[j] colour pixels (bytes from the arena's start; budget
+    0: the library's 1 GiB).  Returns dict(scratch, plane, counts: J entries each; table, scratch_bytes, total), or None where the library refuses."""
+    r = np.ascontiguousarray(rows_c, dtype=np.int32); c = np.ascontiguousarray(cols_c, dtype=np.int32)
+    J = len(r)
+    if len(c) != J:
+        return None
+    so = np.zeros(max(J, 1), dtype=np.int64); po = np.zeros(max(J, 1), dtype=np.int64); co = np.zeros(max(J, 1), dtype=np.int64)
+    tab = C.c_longlong(0); sb = C.c_longlong(0); tot = C.c_longlong(0)
+    if load_library().tdlo_debug_align_batch_plan(_ptr(r), _ptr(c), J, int(budget), _ptr(so), _ptr(po), _ptr(co), C.byref(tab), C.byref(sb), C.byref(tot)):
+        return None
+    return dict(scratch=so[:J].tolist(), plane=po[:J].tolist(), counts=co[:J].tolist(), table=tab.value, scratch_bytes=sb.value, total=tot.value)
+
+
+def align_distinct_jobs(entries):
+    """tdlo_debug_align_distinct_jobs: the distinct-job rule of the aligning rig calls on a list of AlignJobC.  Returns job_of [n] (the job of every entry, jobs
+    numbered in order of first appearance)."""
+    tab, n, keep = _align_jobs(entries)
+    job_of = np.zeros(max(n, 1), dtype=np.int32)
+    rc = load_library().tdlo_debug_align_distinct_jobs(C.cast(tab, C.c_void_p), n, _ptr(job_of))
+    if rc < 0:
+        raise TdloError(rc, "tdlo_debug_align_distinct_jobs")
+    del keep
+    return [int(v) for v in job_of[:n]]
+
+
+def _rig_cameras_raw(cams, raw):
+    """The tables of an aligning rig call: cams RigCamera objects whose depth is None, raw their K align jobs.  Returns (cameras, jobs, K, rows, cols, owners)."""
+    cams = list(cams)
+    jtab, K, jkeep = _align_jobs(raw)
+    if K < 1 or len(cams) != K:
+        raise ValueError("an aligning rig has at least one camera and one raw depth job per camera")
+    rows, cols = int(jtab[0].p.rows_c), int(jtab[0].p.cols_c)
+    tab = (RigCameraC * K)(); keep = [jkeep]
+    for k, cm in enumerate(cams):
+        if cm.depth is not None:
+            raise ValueError(f"camera {k}: an aligning rig's cameras bring no depth plane (the plane comes from the raw job)")
+        for name, dt, shape in (("mask", np.uint8, (rows, cols)), ("colour", np.uint8, (rows, cols, 3)), ("occluder", np.uint8, (rows, cols))):
+            adr, owner = _batch_plane(getattr(cm, name), dt, shape, f"camera {k}: {name}")
+            setattr(tab[k], name, adr); keep.append(owner)
+        tab[k].depth = None
+        tab[k].colour_params = _params_address(cm.params)
+        tab[k].fx, tab[k].fy, tab[k].cx, tab[k].cy = cm.cam
+        tab[k].cam_to_rig = None if cm.cam_to_rig is None else cm.cam_to_rig.ctypes.data
+        keep.append(cm)
+    return tab, jtab, K, rows, cols, keep
 
 
 def aligning_frame_view(depth, colour=None, occluder=None, mask=None) -> FrameView:
@@ -1870,6 +1959,58 @@ class Context:
         self._chk(self.lib.tdlo_align_depth(self.h, C.byref(v), C.byref(p) if p is not None else None, C.c_void_p(addr), C.byref(plane), C.byref(cnt)))
         return A, [int(x) for x in cnt], int(plane.value or 0)
 
+    def align_batch_route_counts(self):
+        """[jobs the batch launches served, jobs the looped single launches served, distinct jobs formed inside the aligning rig calls]
+        (tdlo_debug_route_count 61 / 62 / 63)."""
+        return [int(self.lib.tdlo_debug_route_count(self.h, k)) for k in (61, 62, 63)]
+
+    def align_batch_arena(self):
+        """(address, bytes) of the context's align-batch arena (tdlo_debug_align_batch_arena); (0, 0) before the first batch."""
+        base = C.c_void_p(0); n = C.c_longlong(0)
+        self._chk(self.lib.tdlo_debug_align_batch_arena(self.h, C.byref(base), C.byref(n)))
+        return int(base.value or 0), int(n.value)
+
+    def align_depth_batch(self, jobs, *, out="host", counts=True):
+        """Raw depth aligned for J cameras in one call (tdlo_align_depth_batch).  jobs: AlignJobC objects (make_align_job) or (depth, params) pairs.  out: "host"
+        (new arrays), None (nothing is copied out), or a list of J entries, each None, a numpy uint16 array or an integer device address.  counts=False together
+        with no host output makes the call return without a host wait.
+        Returns ([A_j or None] or None, [counts_j [4]] or None, [the address of plane j in the context's arena])."""
+        tab, J, keep = _align_jobs(jobs)
+        arrs, optr = None, None
+        if out is not None:
+            outs = [out] * J if isinstance(out, str) else list(out)
+            if len(outs) != J:
+                raise ValueError("align_depth_batch: out has one entry per job")
+            arrs = []; optr = (C.c_void_p * max(J, 1))()
+            for j, o in enumerate(outs):
+                rc_, cc_ = int(tab[j].p.rows_c), int(tab[j].p.cols_c)
+                if isinstance(o, str):
+                    o = np.zeros((max(rc_, 0), max(cc_, 0)), dtype=np.uint16)
+                if isinstance(o, np.ndarray):
+                    if o.dtype != np.uint16 or o.size != rc_ * cc_ or not o.flags.c_contiguous:
+                        raise ValueError("align_depth_batch: an output takes rows_c x cols_c packed uint16")
+                    arrs.append(o); optr[j] = o.ctypes.data
+                else:
+                    arrs.append(None); optr[j] = None if o is None else int(o)
+        planes = (C.c_void_p * max(J, 1))()
+        cnt = np.zeros(4 * max(J, 1), dtype=np.int64) if counts else None
+        rcs = np.zeros(max(J, 1), dtype=np.int32)
+        self._chk(self.lib.tdlo_align_depth_batch(self.h, C.cast(tab, C.c_void_p), J, C.cast(optr, C.c_void_p) if optr is not None else None,
+                                                  C.cast(planes, C.c_void_p), _ptr(cnt), _ptr(rcs)))
+        del keep
+        return arrs, (cnt.reshape(-1, 4)[:J].tolist() if counts else None), [int(planes[j] or 0) for j in range(J)]
+
+    def rig_to_cloud_aligning(self, slot, cams, raw, leaf_size, *, fetch=True, counts=True):
+        """rig_to_cloud from raw streams (tdlo_rig_to_cloud_aligning): cams RigCamera objects whose depth is None, raw their K align jobs (make_align_job),
+        whose colour size is the rig's image size.  Returns (X [n x 3] or None, n, n_raw, [counts_k [4]] or None)."""
+        tab, jtab, K, rows, cols, keep = _rig_cameras_raw(cams, raw)
+        n = C.c_int(0); nraw = C.c_int(0)
+        cnt = np.zeros(4 * K, dtype=np.int64) if counts else None
+        self._chk(self.lib.tdlo_rig_to_cloud_aligning(self.h, slot, C.cast(tab, C.c_void_p), C.cast(jtab, C.c_void_p), K, rows, cols, float(leaf_size), None, 0,
+                                                      C.byref(n), C.byref(nraw), _ptr(cnt)))
+        del keep
+        return (self.get_cloud(slot) if fetch else None), n.value, nraw.value, (cnt.reshape(K, 4).tolist() if counts else None)
+
     def frame_to_cloud_view_aligning(self, slot, fv, p: AlignParams, params: ColourParams, leaf_size, *, fetch=True):
         """frame_to_cloud_view on two raw streams (tdlo_frame_to_cloud_view_aligning): fv an aligning_frame_view() or its arguments as a tuple or dict.
         Returns (X [n x 3] or None, n, n_raw, counts [4])."""
@@ -2122,6 +2263,22 @@ class trackdlo:
             self.ctx._chk(rc)
         return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value
 
+    def frame_from_rig_aligning(self, cams, raw, leaf_size=0.008, d_vis=0.06):
+        """frame_from_rig from raw streams (tdlo_tracker_frame_from_rig_aligning): cams RigCamera objects whose depth is None, raw their K align jobs.
+        Returns (visible_nodes, visible_nodes_extended, n, n_raw, [counts_k [4]]); the nodes: get_tracking_result()."""
+        tab, jtab, K, rows, cols, keep = _rig_cameras_raw(cams, raw)
+        if self._fv is None:
+            self._fv = (np.zeros(self.M, dtype=np.int32), np.zeros(self.M, dtype=np.int32), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0))
+        v, e, nv, ne, n, nraw = self._fv
+        cnt = np.zeros(4 * K, dtype=np.int64)
+        rc = self.ctx.lib.tdlo_tracker_frame_from_rig_aligning(self.h, C.cast(tab, C.c_void_p), C.cast(jtab, C.c_void_p), K, rows, cols, leaf_size, d_vis,
+                                                               v.ctypes.data, C.byref(nv), e.ctypes.data, C.byref(ne), C.byref(n), C.byref(nraw), self._st_ptr, _ptr(cnt))
+        self._stats_raw = self._st
+        del keep
+        if rc:
+            self.ctx._chk(rc)
+        return v[:nv.value].copy(), e[:ne.value].copy(), n.value, nraw.value, cnt.reshape(K, 4).tolist()
+
     def frame_view(self, fv, params: ColourParams, fx, fy, cx, cy, leaf_size=0.008, d_vis=0.06):
         """frame_from_depth (fv has a mask) / frame_from_colour (fv has a colour image) from images where they lie -- device tensors, pitched, 4-channel,
         float-metre or flipped images (tdlo_tracker_frame_view).  fv: a FrameView, or the arguments of frame_view() as a tuple or dict.
@@ -2342,6 +2499,32 @@ def frames_from_rig_batch(trackers, rigs, leaf_size, d_vis, check=True):
     del keep
     codes = _batch_done(trackers, st, rcs, rc, check)
     return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw]
+
+
+def frames_from_rig_aligning_batch(trackers, rigs, raws, leaf_size, d_vis, check=True):
+    """tdlo_tracker_frames_from_rig_aligning_batch: frames_from_rig_batch from raw streams -- tracker i: the cameras rigs[i] (depth None) and their align jobs
+    raws[i].  Entries with equal views and params are one job: F ropes under one rig align K planes.
+    Returns (codes, [visible_nodes], [visible_nodes_extended], n [F], n_raw [F], counts [sum K_f][4])."""
+    F, tab, st, rcs = _tracker_table(trackers)
+    assert len(rigs) == F and len(raws) == F
+    ftab = (RigRawFrameC * F)(); keep = []
+    rows = cols = 0; E = 0
+    for f in range(F):
+        ctab, jtab, K, r, c, owners = _rig_cameras_raw(rigs[f], raws[f])
+        if f and (r, c) != (rows, cols):
+            raise ValueError(f"frame {f}: the rigs of a batch share one image size")
+        rows, cols = r, c
+        ftab[f].slot, ftab[f].cams, ftab[f].raw, ftab[f].K = 0, C.addressof(ctab), C.addressof(jtab), K
+        keep.append((ctab, jtab, owners)); E += K
+    M = trackers[0].M
+    vis = np.zeros((F, M), dtype=np.int32); ext = np.zeros((F, M), dtype=np.int32)
+    nv = np.zeros(F, dtype=np.int32); ne = np.zeros(F, dtype=np.int32); n = np.zeros(F, dtype=np.int32); nraw = np.zeros(F, dtype=np.int32)
+    cnt = np.zeros(4 * E, dtype=np.int64)
+    rc = trackers[0].ctx.lib.tdlo_tracker_frames_from_rig_aligning_batch(C.cast(tab, C.c_void_p), F, C.cast(ftab, C.c_void_p), rows, cols, float(leaf_size), float(d_vis),
+                                                                         _ptr(vis), _ptr(nv), _ptr(ext), _ptr(ne), _ptr(n), _ptr(nraw), C.cast(st, C.c_void_p), _ptr(rcs), _ptr(cnt))
+    del keep
+    codes = _batch_done(trackers, st, rcs, rc, check)
+    return codes, [vis[i, :nv[i]].copy() for i in range(F)], [ext[i, :ne[i]].copy() for i in range(F)], [int(v) for v in n], [int(v) for v in nraw], cnt.reshape(E, 4).tolist()
 
 
 def _assign_ropes(ropes):

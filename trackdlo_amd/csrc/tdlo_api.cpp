@@ -13,6 +13,7 @@
 #include "tdlo_assign_host.h"
 #include "tdlo_cluster_lane.h"
 #include "tdlo_align_host.h"
+#include "tdlo_align_batch_plan.h"
 #include "tdlo_view_batch_plan.h"
 #include "tdlo_rig_batch_plan.h"
 
@@ -310,7 +311,21 @@ struct tdlo_ctx {
     bool aln_armed = false;
     int aln_res_at = 0;                   // where in aln_res the last call's counts lie: 0 (written by k_align_pack) or 4 (the host route's)
     bool align_host = getenv("TDLO_ALIGN") && std::strcmp(getenv("TDLO_ALIGN"), "host") == 0;
-    long long aln_route[2] = {0, 0};
+    long long aln_route[5] = {0, 0, 0, 0, 0};
+    // ... for many cameras in one call (tdlo_align_depth_batch and the aligning rig calls: k_align_splat_batch / k_align_pack_batch).  alnb_dev: the arena of
+    // tdlo_align_batch_plan.h, [scratch region | uint16 planes | count words | job table], grown on demand; alnb_armed: the bytes of the scratch region filled with
+    // all ones and kept so by k_align_pack_batch (the header's invariant).  alnb_up: the packed depth of the call's host views in device memory.  alnb_pin: pinned,
+    // [4 x 1024 count words the pack kernel writes | zeroed count words and the job table, copied up in one piece | the host views' packed depth, one copy (the host
+    // route: its depth images and planes)].  alnb_ev_up: recorded behind a call's uploads -- the next call waits for it before it writes alnb_pin again.  alnb_ev: one
+    // event per distinct ready_stream of a call.  alnb_host_counts: the host route's counts.  aln_route[2 ..]: tdlo_debug_route_count 61 / 62 / 63: jobs the batch
+    // launches served / jobs the single launches served in a loop / distinct jobs formed inside the aligning rig calls
+    char *alnb_dev = nullptr, *alnb_up = nullptr, *alnb_pin = nullptr;
+    size_t alnb_cap = 0, alnb_armed = 0, alnb_up_cap = 0, alnb_pin_cap = 0;
+    hipEvent_t alnb_ev_up = nullptr;
+    bool alnb_up_pending = false;
+    std::vector<hipEvent_t> alnb_ev;
+    std::vector<long long> alnb_host_counts;
+    int align_batch_min = (getenv("TDLO_ALIGN_BATCH_MIN") && atoi(getenv("TDLO_ALIGN_BATCH_MIN")) >= 1) ? atoi(getenv("TDLO_ALIGN_BATCH_MIN")) : 0;
     long long view_team_route[3] = {0, 0, 0};   // tdlo_debug_route_count 27 / 28 / 29: voxel-grid view calls served by the one-launch kernel / passed on by it / whose pre-pass rode in it
     // colour segmentation in front of depth -> cloud (tdlo_colour_*): pinned colour + occluder images a caller may fill directly (tdlo_colour_buffers: read in
     // place over PCIe), the device copies of images handed over elsewhere (colour | occluder | HSV image of tdlo_colour_mask).  TDLO_COLOUR_FUSED=0: the mask
@@ -1881,6 +1896,11 @@ void tdlo_destroy(tdlo_ctx *c) {
     if (c->aln_dev) hipFree(c->aln_dev);
     if (c->aln_pin) hipHostFree(c->aln_pin);
     if (c->aln_res) hipHostFree(c->aln_res);
+    if (c->alnb_dev) hipFree(c->alnb_dev);
+    if (c->alnb_up) hipFree(c->alnb_up);
+    if (c->alnb_pin) hipHostFree(c->alnb_pin);
+    if (c->alnb_ev_up) hipEventDestroy(c->alnb_ev_up);
+    for (hipEvent_t e : c->alnb_ev) hipEventDestroy(e);
     for (hipEvent_t e : c->wbat_ev) hipEventDestroy(e);
     if (c->vis_state) hipFree(c->vis_state);
     if (c->vis_res) hipHostFree(c->vis_res);
@@ -5599,7 +5619,7 @@ int tdlo_debug_mstep_lle_dense(int on) { return mstep_set_lle_dense(on); }
 long long tdlo_debug_band_retries(tdlo_ctx *c) { return c ? c->band_retries : -1; }
 
 long long tdlo_debug_route_count(tdlo_ctx *c, int which) {
-    if (!c || which < 0 || which > 60) return -1;
+    if (!c || which < 0 || which > 63) return -1;
     if (which >= 59) return c->aln_route[which - 59];
     if (which >= 57) return c->cel_route[which - 57];
     if (which >= 55) return c->clu_route[which - 55];
@@ -7034,6 +7054,383 @@ int tdlo_tracker_frames_from_rig_batch(tdlo_tracker *const *trackers, int F, con
     for (int i = 0; i < F; ++i)
         if (rcs[i]) return (rcs[i] == TDLO_E_EMPTY && n[i] == 0) ? fail(c, TDLO_E_EMPTY, "no pixel of the rig is kept: no cloud for this frame") : rcs[i];
     return TDLO_OK;
+}
+
+// ---- raw depth for many cameras in one call (include/trackdlo_hip.h: tdlo_align_depth_batch and the aligning rig calls; tdlo_align_batch.hip the kernels,
+// tdlo_align_batch_plan.h the arena) ---------------------------------------------------------------------------------------------------------------------
+// From this many jobs on a call takes the batch launches; below it it loops launch_align into the arena's planes (the same bits, no host wait either).  The rule,
+// set beforehand (scripts/gpu_align_batch.py -> profiles/align_batch_ab.txt): the smallest J from which every batch value lies below every looped value on all
+// four lines (640 x 480 -> 640 x 480 and 848 x 480 -> 1280 x 720, device and pageable host depth), 1025 where no J up to 32 qualifies.  NOT MEASURED YET: 1025,
+// the call loops by default; TDLO_ALIGN_BATCH_MIN=n (read when the context is made) overrides.
+constexpr int kAlignBatchMin = 1025;
+static int align_batch_min(const tdlo_ctx *c) { return c->align_batch_min ? c->align_batch_min : kAlignBatchMin; }
+constexpr size_t kAlnbPinCounts = 32 * (size_t)kAlignBatchMaxJobs;                                      // the pack kernel's 4 x 1024 result words
+constexpr size_t kAlnbPinHead = kAlnbPinCounts + 32 * (size_t)kAlignBatchMaxJobs + sizeof(AlignBatchRec) * (size_t)kAlignBatchMaxJobs;
+
+int tdlo_debug_align_batch_plan(const int *rows_c, const int *cols_c, int J, long long budget, long long *scratch_off, long long *plane_off,
+                                long long *counts_off, long long *table_off, long long *scratch_bytes, long long *total) {
+    return align_batch_plan(rows_c, cols_c, J, budget > 0 ? budget : kAlignBatchBudget, scratch_off, plane_off, counts_off, table_off, scratch_bytes, total) ? TDLO_E_INVALID : TDLO_OK;
+}
+
+int tdlo_debug_align_batch_arena(tdlo_ctx *c, const void **base, long long *bytes) {
+    if (!c || !base || !bytes) return TDLO_E_INVALID;
+    *base = c->alnb_dev; *bytes = (long long)c->alnb_cap;
+    return TDLO_OK;
+}
+
+int tdlo_debug_align_distinct_jobs(const tdlo_align_job *entries, int n, int *job_of) {
+    if (!entries || !job_of || n < 1) return TDLO_E_INVALID;
+    std::vector<tdlo_image_view> v(n);
+    std::vector<tdlo_align_params> p(n);
+    for (int e = 0; e < n; ++e) { v[e] = entries[e].depth; p[e] = entries[e].p; }
+    return align_distinct_jobs(v.data(), p.data(), n, job_of);
+}
+
+// A checked batch as the enqueue takes it: where every view lies, the plan, which jobs share an uploaded host view
+struct AlignBatchWork {
+    int J = 0;
+    std::vector<char> dev;                                  // job j's depth view lies in device memory
+    std::vector<long long> scratch_off, plane_off, counts_off;
+    long long table_off = 0, scratch_bytes = 0, total = 0;
+    std::vector<int> up_of;                                 // a host view's upload (-1: a device view); jobs that name one view share it
+    std::vector<size_t> up_at;                              // per upload: bytes from the start of the packed block
+    size_t up_bytes = 0;
+    int most_Pd = 0, most_Pc = 0;
+};
+
+static bool alnb_overlaps(const tdlo_ctx *c, const char *a, const char *b) {      // [a, b) against the arena and the upload block
+    return (c->alnb_dev && a < c->alnb_dev + c->alnb_cap && b > c->alnb_dev) || (c->alnb_up && a < c->alnb_up + c->alnb_up_cap && b > c->alnb_up);
+}
+
+// Everything that refuses a batch as a whole; nothing of the context is touched.  aligned_out may be null; out_dev (may be null): which outputs are device memory
+static int align_batch_refusal(tdlo_ctx *c, const tdlo_align_job *jobs, int J, unsigned short *const *aligned_out, AlignBatchWork &w, std::vector<char> *out_dev) {
+    if (!jobs || J < 1 || J > kAlignBatchMaxJobs) return fail(c, TDLO_E_INVALID, "align batch: 1 .. 1024 jobs");
+    for (int j = 0; j < J; ++j)
+        if (int rc = align_refusal(c, &jobs[j].depth, &jobs[j].p)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    w.J = J;
+    w.dev.assign(J, 0); w.up_of.assign(J, -1); w.up_at.clear(); w.up_bytes = 0; w.most_Pd = w.most_Pc = 0;
+    if (out_dev) out_dev->assign(J, 0);
+    std::vector<int> rows(J), cols(J);
+    for (int j = 0; j < J; ++j) {
+        const tdlo_align_params &p = jobs[j].p;
+        bool dev = false;
+        if (int rc = image_view_where(c, &jobs[j].depth, p.rows_d, p.cols_d, &dev)) return rc;
+        w.dev[j] = dev;
+        if (dev) {
+            long long lo, hi;
+            image_view_span(&jobs[j].depth, p.rows_d, p.cols_d, &lo, &hi);
+            if (alnb_overlaps(c, (const char *)jobs[j].depth.data + lo, (const char *)jobs[j].depth.data + hi))
+                return fail(c, TDLO_E_INVALID, "align batch: a device view overlaps the arena");
+        }
+        if (aligned_out && aligned_out[j]) {
+            bool od = false;
+            if (int rc = pointer_location(c, aligned_out[j], TDLO_MEM_AUTO, "align batch: aligned_out", &od)) return rc;
+            if (od && alnb_overlaps(c, (const char *)aligned_out[j], (const char *)aligned_out[j] + 2 * (size_t)p.rows_c * p.cols_c))
+                return fail(c, TDLO_E_INVALID, "align batch: a device aligned_out overlaps the arena");
+            if (out_dev) (*out_dev)[j] = od;
+        }
+        rows[j] = p.rows_c; cols[j] = p.cols_c;
+        w.most_Pd = std::max(w.most_Pd, p.rows_d * p.cols_d); w.most_Pc = std::max(w.most_Pc, p.rows_c * p.cols_c);
+    }
+    w.scratch_off.assign(J, 0); w.plane_off.assign(J, 0); w.counts_off.assign(J, 0);
+    if (align_batch_plan(rows.data(), cols.data(), J, kAlignBatchBudget, w.scratch_off.data(), w.plane_off.data(), w.counts_off.data(), &w.table_off, &w.scratch_bytes, &w.total))
+        return fail(c, TDLO_E_INVALID, "align batch: the arena of these jobs would pass 1 GiB");
+    // the packed block: every depth image the host has to hold -- on the device route the host views (one named by several jobs once), on the host route all
+    for (int j = 0; j < J; ++j) {
+        if (w.dev[j] && !c->align_host) continue;
+        const tdlo_image_view &v = jobs[j].depth;
+        for (int i = 0; i < j && w.up_of[j] < 0; ++i) {
+            const tdlo_image_view &u = jobs[i].depth;
+            if (w.up_of[i] >= 0 && u.data == v.data && u.format == v.format && u.row_stride == v.row_stride && u.location == v.location && u.ready_stream == v.ready_stream &&
+                jobs[i].p.rows_d == jobs[j].p.rows_d && jobs[i].p.cols_d == jobs[j].p.cols_d) w.up_of[j] = w.up_of[i];
+        }
+        if (w.up_of[j] >= 0) continue;
+        w.up_of[j] = (int)w.up_at.size();
+        w.up_at.push_back(w.up_bytes);
+        w.up_bytes += aln_round(2 * (size_t)jobs[j].p.rows_d * jobs[j].p.cols_d);
+    }
+    return TDLO_OK;
+}
+
+// The planes of a checked batch, enqueued on the context's stream WITHOUT a host wait on the device routes: planes[j] (J entries) are the arena's.  The counts
+// are the caller's after the stream's next wait (align_batch_counts_fetch)
+static int align_batch_enqueue(tdlo_ctx *c, const tdlo_align_job *jobs, AlignBatchWork &w, const unsigned short **planes) {
+    const int J = w.J;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->alnb_up_pending) { HIPCHK(c, hipEventSynchronize(c->alnb_ev_up)); c->alnb_up_pending = false; }      // the pinned block is about to be rewritten
+    // ---- room: the arena (a new one is filled where its scratch region lies), the upload block, the pinned block
+    const size_t plane_bytes = (size_t)(w.counts_off[0] - w.plane_off[0]);
+    const size_t pin_need = kAlnbPinHead + w.up_bytes + (c->align_host ? plane_bytes : 0);
+    if ((size_t)w.total > c->alnb_cap || w.up_bytes > c->alnb_up_cap || pin_need > c->alnb_pin_cap) HIPCHK(c, drain_for_realloc(c));
+    if ((size_t)w.total > c->alnb_cap) {
+        if (c->alnb_dev) hipFree(c->alnb_dev);
+        c->alnb_dev = nullptr; c->alnb_cap = 0; c->alnb_armed = 0;
+        HIPCHK(c, hipMalloc((void **)&c->alnb_dev, (size_t)w.total));
+        c->alnb_cap = (size_t)w.total;
+    }
+    if (w.up_bytes > c->alnb_up_cap) {
+        if (c->alnb_up) hipFree(c->alnb_up);
+        c->alnb_up = nullptr; c->alnb_up_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->alnb_up, w.up_bytes));
+        c->alnb_up_cap = w.up_bytes;
+    }
+    if (pin_need > c->alnb_pin_cap) {
+        if (c->alnb_pin) hipHostFree(c->alnb_pin);
+        c->alnb_pin = nullptr; c->alnb_pin_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **)&c->alnb_pin, pin_need, hipHostMallocDefault));
+        c->alnb_pin_cap = pin_need;
+        std::memset(c->alnb_pin, 0, kAlnbPinCounts);
+    }
+    if (!c->alnb_ev_up) HIPCHK(c, hipEventCreateWithFlags(&c->alnb_ev_up, hipEventDisableTiming));
+    char *arena = c->alnb_dev, *pin_up = c->alnb_pin + kAlnbPinHead;
+    for (int j = 0; j < J; ++j) planes[j] = (const unsigned short *)(arena + w.plane_off[j]);
+    // ---- one event per distinct ready_stream of the device views
+    {
+        std::vector<void *> seen;
+        for (int j = 0; j < J; ++j) {
+            void *rs = jobs[j].depth.ready_stream;
+            if (!w.dev[j] || !rs || std::find(seen.begin(), seen.end(), rs) != seen.end()) continue;
+            if (seen.size() == c->alnb_ev.size()) {
+                hipEvent_t e = nullptr;
+                HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                c->alnb_ev.push_back(e);
+            }
+            HIPCHK(c, hipEventRecord(c->alnb_ev[seen.size()], (hipStream_t)rs));
+            HIPCHK(c, hipStreamWaitEvent(st, c->alnb_ev[seen.size()], 0));
+            seen.push_back(rs);
+        }
+    }
+    if (c->align_host) {
+        // the comparator: every plane from the host statement, uploaded in one copy.  Device views come down as their packed canonical depth (k_image_import)
+        bool any_dev = false;
+        std::vector<char> done(w.up_at.size(), 0);
+        for (int j = 0; j < J; ++j) {
+            const int u = w.up_of[j];
+            if (done[u]) continue;
+            done[u] = 1;
+            const tdlo_align_params &p = jobs[j].p;
+            const size_t Pd = (size_t)p.rows_d * p.cols_d;
+            if (!w.dev[j]) { image_pack_host(&jobs[j].depth, p.rows_d, p.cols_d, pin_up + w.up_at[u]); continue; }
+            ImageJob ij{};
+            ij.P = (int)Pd; ij.cols = p.cols_d;
+            ij.src[kRoleDepth] = ImageSrc{(const unsigned char *)jobs[j].depth.data, jobs[j].depth.row_stride, jobs[j].depth.format,
+                                          image_import_form(jobs[j].depth.data, jobs[j].depth.row_stride, p.cols_d, jobs[j].depth.format)};
+            ij.dst[kRoleDepth] = (unsigned char *)(c->alnb_up + w.up_at[u]);
+            HIPCHK(c, launch_image_import(ij, st));
+            HIPCHK(c, hipMemcpyAsync(pin_up + w.up_at[u], c->alnb_up + w.up_at[u], 2 * Pd, hipMemcpyDeviceToHost, st));
+            any_dev = true;
+        }
+        if (any_dev) HIPCHK(c, wait_stream(st));
+        char *pin_planes = pin_up + w.up_bytes;
+        c->alnb_host_counts.assign(4 * (size_t)J, 0);
+        for (int j = 0; j < J; ++j) {
+            const tdlo_align_params &p = jobs[j].p;
+            const tdlo_image_view hv{pin_up + w.up_at[w.up_of[j]], TDLO_IMG_U16C1, TDLO_MEM_HOST, 2ll * p.cols_d, nullptr};
+            if (tdlo_align_depth_host(&hv, &p, (unsigned short *)(pin_planes + (w.plane_off[j] - w.plane_off[0])), &c->alnb_host_counts[4 * (size_t)j]))
+                return fail(c, TDLO_E_INVALID, "align batch: the host statement refused a job");
+        }
+        HIPCHK(c, hipMemcpyAsync(arena + w.plane_off[0], pin_planes, plane_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(c->alnb_ev_up, st));
+        c->alnb_up_pending = true;
+        if ((size_t)w.scratch_bytes < c->alnb_armed) c->alnb_armed = (size_t)w.scratch_bytes;      // (planes of this layout may lie over words that were armed)
+        c->aln_route[1] += J;
+        return TDLO_OK;
+    }
+    c->alnb_host_counts.clear();
+    // ---- the host views: packed into the pinned block, ONE copy
+    {
+        std::vector<char> done(w.up_at.size(), 0);
+        for (int j = 0; j < J; ++j) {
+            const int u = w.up_of[j];
+            if (u < 0 || done[u]) continue;
+            done[u] = 1;
+            image_pack_host(&jobs[j].depth, jobs[j].p.rows_d, jobs[j].p.cols_d, pin_up + w.up_at[u]);
+        }
+        if (w.up_bytes) HIPCHK(c, hipMemcpyAsync(c->alnb_up, pin_up, w.up_bytes, hipMemcpyHostToDevice, st));
+    }
+    // ---- the table and the zeroed count words: one copy
+    char *pin_tab = c->alnb_pin + kAlnbPinCounts;
+    const size_t cnt_bytes = (size_t)(w.table_off - w.counts_off[0]);
+    std::memset(pin_tab, 0, cnt_bytes);
+    AlignBatchRec *h_tab = (AlignBatchRec *)(pin_tab + cnt_bytes);
+    for (int j = 0; j < J; ++j) {
+        AlignBatchRec &r = h_tab[j];
+        std::memset(&r, 0, sizeof r);
+        align_job(&jobs[j].depth, &jobs[j].p, r.job);
+        if (!w.dev[j]) { r.job.depth = (const unsigned char *)(c->alnb_up + w.up_at[w.up_of[j]]); r.job.row_stride = 2ll * jobs[j].p.cols_d; r.job.format = TDLO_IMG_U16C1; }
+        r.scratch = (unsigned *)(arena + w.scratch_off[j]);
+        r.plane = (unsigned short *)(arena + w.plane_off[j]);
+        r.counts = (unsigned long long *)(arena + w.counts_off[j]);
+    }
+    HIPCHK(c, hipMemcpyAsync(arena + w.counts_off[0], pin_tab, cnt_bytes + sizeof(AlignBatchRec) * (size_t)J, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->alnb_ev_up, st));
+    c->alnb_up_pending = true;
+    // ---- the scratch region: filled where it was not yet (a new arena, a region that grows); everything else of it is armed (the plan's invariant)
+    const size_t armed = std::min(c->alnb_armed, (size_t)w.scratch_bytes);
+    if (armed < (size_t)w.scratch_bytes) HIPCHK(c, hipMemsetAsync(arena + armed, 0xff, (size_t)w.scratch_bytes - armed, st));
+    c->alnb_armed = 0;                                      // (a call that fails between its launches leaves offered words behind: filled again next time)
+    unsigned long long *res = (unsigned long long *)c->alnb_pin;
+    if (J >= align_batch_min(c)) {
+        HIPCHK(c, launch_align_batch((const AlignBatchRec *)(arena + w.table_off), J, w.most_Pd, w.most_Pc, res, st));
+        c->aln_route[2] += J;
+    } else {
+        for (int j = 0; j < J; ++j) HIPCHK(c, launch_align(h_tab[j].job, h_tab[j].scratch, h_tab[j].plane, h_tab[j].counts, res + 4 * j, st));
+        c->aln_route[0] += J; c->aln_route[3] += J;
+    }
+    c->alnb_armed = (size_t)w.scratch_bytes;
+    return TDLO_OK;
+}
+
+// after a wait of the context's stream that followed align_batch_enqueue: job j's four counts
+static void align_batch_counts_fetch(const tdlo_ctx *c, int j, long long counts[4]) {
+    for (int i = 0; i < 4; ++i)
+        counts[i] = c->alnb_host_counts.empty() ? (long long)((const unsigned long long *)c->alnb_pin)[4 * j + i] : c->alnb_host_counts[4 * (size_t)j + i];
+}
+
+int tdlo_align_depth_batch(tdlo_ctx *c, const tdlo_align_job *jobs, int J, unsigned short *const *aligned_out, const unsigned short **device_planes,
+                           long long *counts, int *rc_each) {
+    if (!c) return TDLO_E_INVALID;
+    AlignBatchWork w;
+    std::vector<char> out_dev;
+    int rc = align_batch_refusal(c, jobs, J, aligned_out, w, &out_dev);
+    if (rc) return rc;
+    std::vector<const unsigned short *> planes(J, nullptr);
+    if ((rc = align_batch_enqueue(c, jobs, w, planes.data()))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    bool to_host = counts != nullptr;
+    if (aligned_out)
+        for (int j = 0; j < J; ++j) {
+            if (!aligned_out[j]) continue;
+            HIPCHK(c, hipMemcpyAsync(aligned_out[j], planes[j], 2 * (size_t)jobs[j].p.rows_c * jobs[j].p.cols_c, out_dev[j] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+            to_host = to_host || !out_dev[j];
+        }
+    if (to_host) HIPCHK(c, wait_stream(c->stream));
+    if (counts) for (int j = 0; j < J; ++j) align_batch_counts_fetch(c, j, counts + 4 * j);
+    if (device_planes) std::copy(planes.begin(), planes.end(), device_planes);
+    if (rc_each) std::fill(rc_each, rc_each + J, 0);
+    return TDLO_OK;
+}
+
+// The (camera, frame) entries of an aligning rig call: what refuses them on their own, the cameras with a placeholder depth plane (what the rig call's own
+// checks see before the planes exist), the distinct jobs
+struct RigAlignWork {
+    std::vector<tdlo_rig_camera> cams;                      // every entry's camera, its depth the placeholder, later the arena's plane
+    std::vector<int> job_of;                                // entry -> distinct job
+    std::vector<tdlo_align_job> jobs;                       // the distinct jobs
+    AlignBatchWork w;
+};
+alignas(8) static const unsigned short kRigAlignPlaceholder[4] = {0, 0, 0, 0};
+
+static int rig_align_entries(tdlo_ctx *c, const tdlo_rig_camera *cams, const tdlo_align_job *raw, int K, int rows, int cols, RigAlignWork &ra) {
+    if (!cams || !raw || K < 1 || K > 64) return fail(c, TDLO_E_INVALID, "aligning rig: 1 .. 64 cameras and their raw depth");
+    for (int k = 0; k < K; ++k) {
+        if (cams[k].depth) return fail(c, TDLO_E_INVALID, "aligning rig: a camera brings a depth plane (cams[k].depth must be NULL: the plane comes from raw[k])");
+        if (int rc = align_refusal(c, &raw[k].depth, &raw[k].p)) return rc;
+        if (raw[k].p.rows_c != rows || raw[k].p.cols_c != cols) return fail(c, TDLO_E_INVALID, "aligning rig: the colour size of raw[k].p is not the rig's rows x cols");
+        ra.cams.push_back(cams[k]);
+        ra.cams.back().depth = kRigAlignPlaceholder;
+    }
+    return TDLO_OK;
+}
+
+// the distinct jobs of all entries (raw: one pointer per entry), checked as a batch
+static int rig_align_jobs(tdlo_ctx *c, const std::vector<const tdlo_align_job *> &raw, RigAlignWork &ra) {
+    const int E = (int)raw.size();
+    std::vector<tdlo_image_view> v(E);
+    std::vector<tdlo_align_params> p(E);
+    for (int e = 0; e < E; ++e) { v[e] = raw[e]->depth; p[e] = raw[e]->p; }
+    ra.job_of.assign(E, 0);
+    const int Jd = align_distinct_jobs(v.data(), p.data(), E, ra.job_of.data());
+    if (Jd > kAlignBatchMaxJobs) return fail(c, TDLO_E_INVALID, "aligning rig: more than 1024 distinct jobs");
+    ra.jobs.resize(Jd);
+    for (int e = E - 1; e >= 0; --e) ra.jobs[ra.job_of[e]] = *raw[e];
+    return align_batch_refusal(c, ra.jobs.data(), Jd, nullptr, ra.w, nullptr);
+}
+
+// the planes enqueued, every entry's camera pointed at its job's plane
+static int rig_align_enqueue(tdlo_ctx *c, RigAlignWork &ra) {
+    std::vector<const unsigned short *> planes(ra.jobs.size(), nullptr);
+    if (int rc = align_batch_enqueue(c, ra.jobs.data(), ra.w, planes.data())) { (void)hipStreamSynchronize(c->stream); return rc; }
+    for (size_t e = 0; e < ra.cams.size(); ++e) ra.cams[e].depth = planes[ra.job_of[e]];
+    c->aln_route[4] += (long long)ra.jobs.size();
+    return TDLO_OK;
+}
+
+// after the rig call's own wait: one row per entry
+static void rig_align_counts(tdlo_ctx *c, const RigAlignWork &ra, long long *counts) {
+    if (!counts) return;
+    (void)hipStreamSynchronize(c->stream);                  // (idle after a rig call that reached its kernels; a rig call that failed early may not have waited)
+    for (size_t e = 0; e < ra.job_of.size(); ++e) align_batch_counts_fetch(c, ra.job_of[e], counts + 4 * e);
+}
+
+int tdlo_rig_to_cloud_aligning(tdlo_ctx *c, int slot, const tdlo_rig_camera *cams, const tdlo_align_job *raw, int K, int rows, int cols, double leaf_size,
+                               double *X_out, int x_capacity, int *n_out, int *n_raw_out, long long *counts) {
+    if (!c) return TDLO_E_INVALID;
+    RigAlignWork ra;
+    int rc = rig_align_entries(c, cams, raw, K, rows, cols, ra);
+    if (rc) return rc;
+    std::vector<BatchPlanes> where;
+    if ((rc = rig_refusal(c, slot, ra.cams.data(), K, rows, cols, leaf_size, where))) return rc;
+    std::vector<const tdlo_align_job *> entries(K);
+    for (int k = 0; k < K; ++k) entries[k] = raw + k;
+    if ((rc = rig_align_jobs(c, entries, ra)) || (rc = rig_align_enqueue(c, ra))) return rc;
+    rc = tdlo_rig_to_cloud(c, slot, ra.cams.data(), K, rows, cols, leaf_size, X_out, x_capacity, n_out, n_raw_out);
+    rig_align_counts(c, ra, counts);
+    return rc;
+}
+
+int tdlo_tracker_frame_from_rig_aligning(tdlo_tracker *t, const tdlo_rig_camera *cams, const tdlo_align_job *raw, int K, int rows, int cols, double leaf_size,
+                                         double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out,
+                                         tdlo_stats *stats, long long *counts) {
+    if (!t) return TDLO_E_INVALID;
+    tdlo_ctx *c = t->ctx;
+    if (t->geodesic_coord.size() != (size_t)t->M) return fail(c, TDLO_E_INVALID, "the tracker has no nodes / geodesic coordinates yet (tdlo_tracker_initialize_*)");
+    if (t->painter_on) return fail(c, TDLO_E_INVALID, "a rig frame with the self-occlusion switch on: that test is one camera's");
+    RigAlignWork ra;
+    int rc = rig_align_entries(c, cams, raw, K, rows, cols, ra);
+    if (rc) return rc;
+    std::vector<BatchPlanes> where;
+    if ((rc = rig_refusal(c, t->slot, ra.cams.data(), K, rows, cols, leaf_size, where))) return rc;
+    if (const char *why = tracker_rig_painter_refusal(t, ra.cams.data(), K, rows, cols)) return fail(c, TDLO_E_INVALID, why);
+    std::vector<const tdlo_align_job *> entries(K);
+    for (int k = 0; k < K; ++k) entries[k] = raw + k;
+    if ((rc = rig_align_jobs(c, entries, ra)) || (rc = rig_align_enqueue(c, ra))) return rc;
+    rc = tdlo_tracker_frame_from_rig(t, ra.cams.data(), K, rows, cols, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out, n_raw_out, stats);
+    rig_align_counts(c, ra, counts);
+    return rc;
+}
+
+int tdlo_tracker_frames_from_rig_aligning_batch(tdlo_tracker *const *trackers, int F, const tdlo_rig_raw_frame *frames, int rows, int cols, double leaf_size,
+                                                double d_vis, int *visible_nodes, int *n_vis, int *visible_nodes_extended, int *n_vis_ext, int *n_out, int *n_raw_out,
+                                                tdlo_stats *stats, int *rc_each, long long *counts) {
+    if (!trackers || F < 1 || !trackers[0]) return TDLO_E_INVALID;
+    tdlo_ctx *c = trackers[0]->ctx;
+    if (const char *why = tracker_batch_refusal(trackers, F, false)) return fail(c, TDLO_E_INVALID, why);
+    if (!frames) return fail(c, TDLO_E_INVALID, "null frames");
+    for (int i = 0; i < F; ++i)
+        if (trackers[i]->painter_on) return fail(c, TDLO_E_INVALID, "a rig frame with the self-occlusion switch on: that test is one camera's");
+    RigAlignWork ra;
+    std::vector<const tdlo_align_job *> entries;
+    std::vector<size_t> first(F, 0);
+    for (int i = 0; i < F; ++i) {
+        first[i] = ra.cams.size();
+        if (int rc = rig_align_entries(c, frames[i].cams, frames[i].raw, frames[i].K, rows, cols, ra)) return rc;
+        for (int k = 0; k < frames[i].K; ++k) entries.push_back(frames[i].raw + k);
+    }
+    std::vector<tdlo_rig_frame> fr(F);
+    for (int i = 0; i < F; ++i) fr[i] = tdlo_rig_frame{trackers[i]->slot, ra.cams.data() + first[i], frames[i].K};
+    for (int i = 0; i < F; ++i)
+        if (trackers[i]->rig_painter_K)
+            if (const char *why = tracker_rig_painter_refusal(trackers[i], fr[i].cams, fr[i].K, rows, cols)) return fail(c, TDLO_E_INVALID, why);
+    std::vector<std::vector<BatchPlanes>> where;
+    int rc = rig_batch_refusal(c, fr.data(), F, rows, cols, leaf_size, where);
+    if (rc) return rc;
+    if ((rc = rig_align_jobs(c, entries, ra)) || (rc = rig_align_enqueue(c, ra))) return rc;
+    rc = tdlo_tracker_frames_from_rig_batch(trackers, F, fr.data(), rows, cols, leaf_size, d_vis, visible_nodes, n_vis, visible_nodes_extended, n_vis_ext, n_out,
+                                            n_raw_out, stats, rc_each);
+    rig_align_counts(c, ra, counts);
+    return rc;
 }
 
 // ---- ropes of one colour: one cloud dealt out among F slots (include/trackdlo_hip.h has the statement; tdlo_assign.hip the kernels) -------------------------

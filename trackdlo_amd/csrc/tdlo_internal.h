@@ -437,5 +437,9 @@ hipError_t launch_image_import_batch(const ImageJob *jobs, int J, const void *ta
 // pinned host memory, valid after the stream's next wait
 struct AlignJob;
 hipError_t launch_align(const AlignJob &job, unsigned *scratch, unsigned short *out, unsigned long long *counts, unsigned long long *counts_out, hipStream_t s);
+// tdlo_align_batch.hip: the same for J jobs in two launches (k_align_splat_batch / k_align_pack_batch; grid row j takes record j of `table`, whose blocks follow
+// tdlo_align_batch_plan.h); most_Pd / most_Pc: the most depth / colour pixels of a job; counts_out: 4 J words in pinned host memory
+struct AlignBatchRec;
+hipError_t launch_align_batch(const AlignBatchRec *table, int J, int most_Pd, int most_Pc, unsigned long long *counts_out, hipStream_t s);
 
 }  // namespace tdlo
